@@ -18,6 +18,11 @@ Weak scaling: every rank brings its own 10k samples, so N ranks compare (N*10k)^
 Rank 0 prints ONE JSON line.  `value` = samples sketched-and-compared per second over the whole job.
 The pairwise rate of the same step is reported beside it as cells_per_s (cells = ordered (i, j) pairs, full
 N x N matrix, as the reference computes them).
+
+A plain run sets up, warms up, times the K steps and prints that line.  `--full` adds everything else the benchmark
+measures or checks: probe steps for the comparison kernels' times, the norms' host check, the configs[2] / streamed /
+density / search legs, the strong-scaled legs, the C++ step and the CPU baseline.  `--dump-outputs DIR` writes what
+the last timed step computed as DIR/<name>.npy (the inputs are seeded: the same arguments give the same arrays).
 """
 import argparse
 import json
@@ -125,6 +130,25 @@ def fast_norm_sq(sumsq, d):
             y[i] = float("%g" % x[idx[i]])
     out[nz] = y
     return out * out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays, seed=20261016):
+    """--dump-outputs: name -> tensor or array (rows on the first axis) -> out_dir/<name>.npy in float64.  The budget is
+    split evenly between the arrays; one larger than its share is written as a sample of its rows, drawn with a fixed seed
+    and kept in order, and <name>_rows.npy holds the indices of the rows written.  Integer outputs stay exact (|x| < 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - (1 << 20)) // len(arrays)          # 1 MiB left for the .npy headers
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        row_bytes = 8 * max(1, int(np.prod(a.shape[1:])))
+        if a.shape[0] * row_bytes > share:
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], share // (row_bytes + 8), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def launch_workers(n, argv, script=None, python=None, env=None, poll_s=0.05, grace_s=20.0, deadline_s=None):
@@ -246,6 +270,14 @@ def main():
     ap.add_argument("--host-input", action="store_true",
                     help="also time the step with the hash lists handed over as host buffers (PCIe inclusive; "
                          "reported as pcie_inclusive, never as value)")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: everything beside the headline as well -- the probe steps behind the timed region "
+                         "(comparison kernel times, roofline_pairwise_step), the host check of the norms' text round trip, the "
+                         "pairwise / streamed / density / search legs, the strong-scaled legs, strong_cpp and the CPU baseline.  "
+                         "Without it the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, 64 MB at "
+                         "most; a fixed seeded sample where an output is larger).  Rank 0 writes its own rows")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -357,7 +389,8 @@ def main():
             coll = parallel.TorchCollectives(dist, rank, world, stream=side)
 
     if args.config != 2:
-        res = strong_run(args, ctx, dev, rank, world, dist if world > 1 else None, coll, args.config, args.steps, args.warmup)
+        res = strong_run(args, ctx, dev, rank, world, dist if world > 1 else None, coll, args.config, args.steps, args.warmup,
+                         dump_dir=args.dump_outputs if rank == 0 else None)
         res["config"]["collectives_note"] = coll_note
         if rank == 0:
             print(json.dumps(res))
@@ -435,23 +468,28 @@ def main():
             gather_ms.append(sc.last_gather_ms())    # events recorded before the comparison's end: already complete
     sync_all()
     elapsed = time.perf_counter() - t0
-    # probe steps behind the timed region: the comparison kernels of the rank's block plan (filter launches + re-check + exact
-    # kernel on flagged tiles) from the plan's own events, which the timed steps do without
-    state["probe"] = True
-    for _ in range(3):
-        step()
-        ps = ctx.plan_stats()
-        k2_ms.append(ps["filter_ms"] + ps["recheck_ms"] + ps["tiles_ms"])
-        state["plan"] = ps
-    sync_all()
-    ctx.set_timing(True)
-    ps = state["plan"]
-    state["candidates"] = ps["candidates"]
-    state["filter_ms"] = ps["filter_ms"] if not ps["exact_mode"] else None
-    state["filter_info"] = None if ps["exact_mode"] else (8, 256, ps["filter_tiles"], ps["d_pad"])
-    # outside the timed region: the device's text round trip against the host's (printf / strtod semantics)
-    if not np.array_equal(n2_local.cpu().numpy(), fast_norm_sq(sumsq.cpu().numpy(), D)):
-        raise SystemExit("device norm text round trip differs from the host's")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from the last timed one: sketches, squared norms as parsed back from their text,
+        # kept cells (row, col, dot, q) sorted by (row, col)
+        write_outputs(args.dump_outputs, {"sketches": sketches, "norms_sq": n2_local, "cells": cells[:state["cnt"]]})
+    if args.full:
+        # probe steps behind the timed region: the comparison kernels of the rank's block plan (filter launches + re-check +
+        # exact kernel on flagged tiles) from the plan's own events, which the timed steps do without
+        state["probe"] = True
+        for _ in range(3):
+            step()
+            ps = ctx.plan_stats()
+            k2_ms.append(ps["filter_ms"] + ps["recheck_ms"] + ps["tiles_ms"])
+            state["plan"] = ps
+        sync_all()
+        ctx.set_timing(True)
+        ps = state["plan"]
+        state["candidates"] = ps["candidates"]
+        state["filter_ms"] = ps["filter_ms"] if not ps["exact_mode"] else None
+        state["filter_info"] = None if ps["exact_mode"] else (8, 256, ps["filter_tiles"], ps["d_pad"])
+        # outside the timed region: the device's text round trip against the host's (printf / strtod semantics)
+        if not np.array_equal(n2_local.cpu().numpy(), fast_norm_sq(sumsq.cpu().numpy(), D)):
+            raise SystemExit("device norm text round trip differs from the host's")
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -513,7 +551,7 @@ def main():
         return out
 
     strong = {}
-    if args.strong_steps > 0 and world > 1 and rank != 0:  # every rank takes part (rank 0: below, once its headline is assembled)
+    if args.full and args.strong_steps > 0 and world > 1 and rank != 0:  # every rank takes part (rank 0: below, once its headline is assembled)
         del hashes, sketches, cells, sc
         run_strong_guarded(None)
 
@@ -525,7 +563,7 @@ def main():
     samples_per_s = N_total / (elapsed / args.steps)
     cells_per_step = float(N_total) * float(N_total)
     k1 = float(np.mean(k1_ms))
-    k2 = float(np.mean(k2_ms))
+    k2 = float(np.mean(k2_ms)) if args.full else None
     limbs = state["limbs"]
 
     # roofline of the dominant kernel (K1, projection): algorithmic bytes = 8*n_i + 4*d per sample
@@ -563,12 +601,14 @@ def main():
                    "collectives": (coll.kind if coll is not None else "none"), "collectives_note": coll_note,
                    **comm_facts(coll, world)},
         "cells_per_s": cells_per_step / (elapsed / args.steps),
+        # the comparison kernels' times come from the probe steps of --full
         "stages": {"projection_kernel_ms": k1, "projection_samples_per_s_per_gpu": S / (k1 * 1e-3),
-                   "pairwise_kernel_ms": k2, "pairwise_cells_per_s_per_gpu": S * float(N_total) / (k2 * 1e-3),
+                   **({"pairwise_kernel_ms": k2, "pairwise_cells_per_s_per_gpu": S * float(N_total) / (k2 * 1e-3)}
+                      if args.full else {}),
                    "allgather_ms": float(np.mean(gather_ms)) if world > 1 else 0.0,
                    "allgather_bytes_per_rank": state.get("allgather_bytes_per_rank", 0),
                    "allgather_bytes_received_per_rank": state.get("allgather_bytes_per_rank", 0) * (world - 1),
-                   "other_ms": ms_per_step - k1 - k2},
+                   **({"other_ms": ms_per_step - k1 - k2} if args.full else {})},
         # the dominant kernel of the step.  The contract prices it against HBM (algorithmic bytes = 8 n_i + 4 d per
         # sample); the +-1 matrix is generated from the hashes, so the kernel's binding bound is integer-VALU issue:
         # `binding` says so and roofline_valu_issue carries that fraction.
@@ -589,25 +629,26 @@ def main():
                                 # NOT a roofline fraction: bit-slicing does 64 sign-accumulations in ~4.4 instructions
                                 "sign_accumulations_per_s_T": k1_intops / (k1 * 1e-3) / 1e12,
                                 "int32_lane_op_peak_T": VALU_INT_PEAK_TOPS},
-        "roofline_pairwise_step": step_pairwise_roofline(state, S, N_total, D, k2, k2_flops, traffic),
     }
+    if args.full:
+        res["roofline_pairwise_step"] = step_pairwise_roofline(state, S, N_total, D, k2, k2_flops, traffic)
 
-    if args.strong_steps > 0 and world > 1:
+    if args.full and args.strong_steps > 0 and world > 1:
         del sketches, cells, sc
         strong = run_strong_guarded(res)
 
-    if args.pairwise_samples and world == 1:
+    if args.full and args.pairwise_samples and world == 1:
         pw = pairwise_leg(ctx, dev, args.pairwise_samples, args.pairwise_dim, NH, args.pairwise_reps)
         res["config"]["workload_pairwise"] = pw.pop("workload")
         res["pairwise"] = pw.pop("leg")
         res["roofline_pairwise"] = pw.pop("roofline")
 
-    if args.stream_samples and world == 1:
+    if args.full and args.stream_samples and world == 1:
         res["streamed_dense"] = stream_leg(ctx, dev, args.stream_samples, args.pairwise_dim, NH)
 
-    if args.density_samples and world == 1:
+    if args.full and args.density_samples and world == 1:
         res["density"] = density_leg(ctx, dev, args.density_samples, args.pairwise_dim, NH)
-    if args.search_samples and world == 1:
+    if args.full and args.search_samples and world == 1:
         res["search"] = search_leg(ctx, dev, args.search_samples, args.pairwise_dim, NH)
 
     if args.host_input and world == 1:
@@ -638,15 +679,15 @@ def main():
 
     # (the GPU legs first: the CPU baseline's thread teams keep the host cores busy for a while after they return, and a
     # strong-scaled step has two host round trips in it -- measured once behind the baseline: 11.05 ms instead of 10.25)
-    if args.strong_steps > 0 and world == 1:
+    if args.full and args.strong_steps > 0 and world == 1:
         del sketches, cells, sc
         strong = run_strong()
     if strong:
         res["strong"] = strong
-    if args.cpp_step_ranks > 1 and args.strong_steps > 0 and world == 1:
+    if args.full and args.cpp_step_ranks > 1 and args.strong_steps > 0 and world == 1:
         res["strong_cpp"] = cpp_step_leg(dev, args.cpp_step_ranks, args.hashes)
 
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"] = cpu_baseline(hashes, offsets, S, NH, D, dev)
         if "pairwise" in res:
             res["pairwise"]["vs_cpu_port_all_cores"] = res["pairwise"]["cells_per_s"] / res["cpu_baseline"]["pairwise_cells_per_s"]
@@ -758,7 +799,7 @@ def comm_facts(coll, world):
 STRONG = {3: (100_000, 2048, 2345), 4: (100_000, 4096, 3456), 5: (1_000_000, 2048, 4567)}   # --config -> (N, d, seed)
 
 
-def strong_run(args, ctx, dev, rank, world, dist, coll, config, steps, warmup):
+def strong_run(args, ctx, dev, rank, world, dist, coll, config, steps, warmup, dump_dir=None):
     """BASELINE.json configs[2] / [3] / [4] -- pairwise only, a FIXED number of synthesised sketches split over the ranks by
     the reference's shard formula (src/pairwise_comp_optimized.cpp:937-940).  One step = parallel.ShardedComparison.run():
     re-code this rank's rows (limb planes + the filter's coarse plane and row statistics, OWN rows only) -> all-gather of
@@ -806,6 +847,8 @@ def strong_run(args, ctx, dev, rank, world, dist, coll, config, steps, warmup):
         step()
     sync_all()
     elapsed = time.perf_counter() - t0
+    if dump_dir:
+        write_outputs(dump_dir, {"cells": cells[:state["cnt"]]})      # this rank's kept cells (row, col, dot, q), sorted
     ctx.set_timing(timing_was)
     sc.time_gather, sc.trace = True, []
     acc = {k: [] for k in ("filter", "recheck", "tiles", "prepare", "plan_span", "cells", "gather")}

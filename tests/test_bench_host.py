@@ -120,3 +120,25 @@ def test_search_index_subcommand_checks_the_folder(tmp_path, capsys):
     with pytest.raises(ValueError):
         search.main(["index", str(d)])
     assert search.main(["-v", "index", str(d)]) == 0 and capsys.readouterr().out.startswith("Version: ")
+
+
+def test_write_outputs_float64_within_budget_and_seeded(tmp_path):
+    """--dump-outputs: every array lands as float64 .npy, integers exactly; an array larger than its share of the 64 MB is
+    written as the same seeded, ordered sample of rows on every call, with the indices of those rows beside it"""
+    import bench
+    big = np.arange(20_000 * 2048, dtype=np.int64).reshape(20_000, 2048) % 50_001 - 25_000   # 328 MB as float64
+    small = np.array([1.5, 2.0 ** 40, 3.0])
+    cells = np.arange(40, dtype=np.int32).reshape(10, 4)
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), {"sketches": big, "norms_sq": small, "cells": cells})
+    total = sum(os.path.getsize(str(p)) for p in (tmp_path / "a").iterdir())
+    assert total <= bench.DUMP_BUDGET_BYTES
+    for name in ("sketches", "sketches_rows", "norms_sq", "cells"):
+        a, b = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy")))
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+    rows = np.load(str(tmp_path / "a" / "sketches_rows.npy")).astype(np.int64)
+    assert len(rows) > 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "sketches.npy")), big[rows].astype(np.float64))
+    assert np.array_equal(np.load(str(tmp_path / "a" / "norms_sq.npy")), small)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "cells.npy")), cells.astype(np.float64))
+    assert not (tmp_path / "a" / "cells_rows.npy").exists()

@@ -61,18 +61,52 @@ def test_standalone_projection_usage():
     assert r.returncode == 1 and "Error opening file: /nonexistent/file" in r.stderr
 
 
+def _toy_sig_zip(path, name, k31):
+    """a sourmash .sig.zip in the layout of the reference's toy archives: stored members signatures/<md5>.sig.gz (gzip of the
+    JSON list of one signature) for k = 15 / 31 / 33 and SOURMASH-MANIFEST.csv; k = 15 and 33 carry other hashes"""
+    import gzip
+    import hashlib
+    import json
+    import zipfile
+    import numpy as np
+    mask = np.uint64(0x5DEECE66D5DEECE6)
+    members, manifest = [], ["# SOURMASH-MANIFEST-VERSION: 1.0",
+                             "internal_location,md5,md5short,ksize,moltype,num,scaled,n_hashes,with_abundance,name,filename"]
+    for k, mins in ((15, np.unique(k31 // np.uint64(3))), (31, k31), (33, np.unique(k31 ^ mask))):
+        md5 = hashlib.md5(("%s %d %d" % (name, k, len(mins))).encode()).hexdigest()
+        sig = [{"class": "sourmash_signature", "email": "", "hash_function": "0.murmur64", "filename": name + ".unitigs.fa",
+                "name": name, "license": "CC0", "signatures": [{"num": 0, "ksize": k, "seed": 42, "max_hash": 18446744073709552,
+                                                                "mins": [int(x) for x in mins], "md5sum": md5, "molecule": "DNA"}],
+                "version": 0.4}]
+        members.append(("signatures/%s.sig.gz" % md5, gzip.compress(json.dumps(sig).encode(), mtime=0)))
+        manifest.append("signatures/%s.sig.gz,%s,%s,%d,DNA,0,1000,%d,0,%s,%s.unitigs.fa" % (md5, md5, md5[:8], k, len(mins), name, name))
+    members.append(("SOURMASH-MANIFEST.csv", ("\n".join(manifest) + "\n").encode()))
+    with zipfile.ZipFile(str(path), "w", zipfile.ZIP_STORED) as z:
+        for n, data in members:
+            z.writestr(n, data)
+
+
 def test_convert_matches_reference_fixture(tmp_path):
     """`project_everything convert` on the reference's toy .sig.zip set: every sample's k=31 hash set equals
     the fixture (tests/golden/toy_hashes.npz, cross-checked against the reference's own convert by
-    make_golden.py).  Needs the reference's test data, which exists only in the dev container."""
+    make_golden.py).  tests/golden/toy_sigs/ holds 58 of the 61 archives of the reference's test/toy, unchanged; the three
+    largest (4.5 MB) are rebuilt here in the same layout from their k=31 hashes in the fixture."""
     import json
+    import shutil
     import numpy as np
-    import pytest
-    toy = "/root/reference/test/toy"
-    if not os.path.isdir(toy):
-        pytest.skip("reference test data not present on this machine")
+    h = np.load(os.path.join(ROOT, "tests", "golden", "toy_hashes.npz"))
+    names = [str(x) for x in h["names"]]
+    offs = h["offsets"]
+    deltas = h["deltas"].astype(np.uint64)
+    want = {n: np.cumsum(deltas[offs[i]:offs[i + 1]], dtype=np.uint64) for i, n in enumerate(names)}
+    toy = tmp_path / "toy"
+    shutil.copytree(os.path.join(ROOT, "tests", "golden", "toy_sigs"), str(toy))
+    stored = {f.split(".")[0] for f in os.listdir(str(toy))}
+    assert len(stored) == 58 and stored <= set(names)
+    for n in sorted(set(names) - stored):
+        _toy_sig_zip(toy / (n + ".unitigs.fa.sig.zip"), n, want[n])
     out = tmp_path / "toy_hashes.txt"
-    r = run(os.path.join(BIN, "project_everything"), "convert", toy, str(out), "-t", "4")
+    r = run(os.path.join(BIN, "project_everything"), "convert", str(toy), str(out), "-t", "4")
     assert r.returncode == 0, r.stderr
     assert r.stdout.count("Processed ") == 61 and "Time to convert all signatures: " in r.stdout
     got = {}
@@ -80,14 +114,9 @@ def test_convert_matches_reference_fixture(tmp_path):
         if ":" in line:
             name, rest = line.split(":", 1)
             got[name] = np.array([int(t) for t in rest.split()], dtype=np.uint64)
-    h = np.load(os.path.join(ROOT, "tests", "golden", "toy_hashes.npz"))
-    names = [str(x) for x in h["names"]]
-    offs = h["offsets"]
-    deltas = h["deltas"].astype(np.uint64)
     assert sorted(got) == names
-    for i, n in enumerate(names):
-        want = np.cumsum(deltas[offs[i]:offs[i + 1]], dtype=np.uint64)
-        assert np.array_equal(got[n], want), n
+    for n in names:
+        assert np.array_equal(got[n], want[n]), n
     with open(os.path.join(ROOT, "tests", "golden", "toy_sketch_digests.json")) as f:
         dg = json.load(f)
     assert all(len(got[n]) == dg[n]["n_hashes"] for n in names)

@@ -617,55 +617,98 @@ def test_executables_on_the_references_malformed_input_fixtures(tmp_path):
 
 
 REF = os.path.join(ROOT, "oracle", "_ref")
+CLI_RANDOM_GOLD = os.path.join(ROOT, "tests", "golden", "ref_cli_random.json")
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "project_everything")),
-                    reason="oracle/_ref is built only where /root/reference exists")
-def test_sketch_cli_vs_reference_binary_random(tmp_path):
-    """the reference's own executables (oracle/_ref, compiled from its sources) and ours on fresh random
-    input: ragged sizes, an empty sample, duplicates, hashes near 2^64; vectors.bin must be identical."""
-    import json
-    import time
-    rng = np.random.default_rng(20251226)
-    n = int(os.environ.get("MVS_CLI_COMPARE_N", "400"))            # scale up by hand for an end-to-end timing
-    sizes = rng.integers(1, int(os.environ.get("MVS_CLI_COMPARE_MAXH", "30000")), n)
+def _random_hash_file(path, n, maxh, seed=20251226):
+    """fresh random input: ragged sizes, an empty sample, duplicates, hashes near 2^64 (tests/golden/make_golden_cli_random.py
+    writes the same file for the reference's executables)"""
+    rng = np.random.default_rng(seed)
+    sizes = rng.integers(1, maxh, n)
     sizes[7] = 0
     sizes[11] = 1
-    hf = tmp_path / "h.txt"
-    with open(hf, "w") as f:
+    with open(str(path), "w") as f:
         for i, s in enumerate(sizes):
             h = rng.integers(0, 2 ** 64, int(s), dtype=np.uint64)
             if i % 5 == 0 and s > 4:
                 h[:4] = np.array([0, 2 ** 64 - 1, 2 ** 63, h[4]], dtype=np.uint64)
             f.write("s%d:" % i + "".join(" %d" % int(x) for x in h) + "\n")
-    t = {}
-    threads = os.cpu_count() or 16
-    for tag, exe in (("ref", os.path.join(REF, "project_everything")), ("ours", os.path.join(BIN, "project_everything"))):
-        t0 = time.time()
-        r = run(exe, "sketch", str(hf), str(tmp_path / tag), "-t", str(threads), "-d", "1024")
-        t[tag] = time.time() - t0
-        assert r.returncode == 0, r.stderr
-    a = np.fromfile(str(tmp_path / "ref" / "vectors.bin"), dtype="<i4")
-    b = np.fromfile(str(tmp_path / "ours" / "vectors.bin"), dtype="<i4")
-    assert a.size == n * 1024 and np.array_equal(a, b)
-    for name in ("dimension.txt", "dtype.txt"):
-        assert open(str(tmp_path / "ref" / name)).read() == open(str(tmp_path / "ours" / name)).read()
-    ra = open(str(tmp_path / "ref" / "vector_norms.txt")).read().strip().split("\n")
-    rb = open(str(tmp_path / "ours" / "vector_norms.txt")).read().strip().split("\n")
-    assert len(ra) == len(rb) == n
+    return sizes
+
+
+def _sha256(path):
+    import hashlib
+    h = hashlib.sha256()
+    with open(str(path), "rb") as f:
+        for block in iter(lambda: f.read(1 << 20), b""):
+            h.update(block)
+    return h.hexdigest()
+
+
+def _same_norms(ra, rb):
+    assert len(ra) == len(rb)
     for x, y in zip(ra, rb):
         (xn, xv), (yn, yv) = x.split(" "), y.split(" ")
         assert xn == yn and abs(float(xv) - float(yv)) <= 1e-5 * abs(float(xv)) + 1e-12
+
+
+def test_sketch_cli_vs_reference_binary_random(tmp_path):
+    """the reference's own executables (oracle/_ref, compiled from its sources) and ours on fresh random
+    input: ragged sizes, an empty sample, duplicates, hashes near 2^64; vectors.bin must be identical.  What the reference
+    wrote for the default input is recorded in tests/golden/ref_cli_random.json (make_golden_cli_random.py); where
+    oracle/_ref is built, the reference runs beside ours as well (and MVS_CLI_COMPARE_N / _MAXH scale the input up by hand
+    for an end-to-end timing)."""
+    import json
+    import time
+    with open(CLI_RANDOM_GOLD) as f:
+        gold = json.load(f)
+    n = int(os.environ.get("MVS_CLI_COMPARE_N", gold["n"]))
+    maxh = int(os.environ.get("MVS_CLI_COMPARE_MAXH", gold["maxh"]))
+    live = os.path.exists(os.path.join(REF, "project_everything"))
+    recorded = (n, maxh) == (gold["n"], gold["maxh"])
+    if not recorded and not live:
+        pytest.skip("MVS_CLI_COMPARE_N / _MAXH: only the reference binaries under oracle/_ref know that input")
+    hf = tmp_path / "h.txt"
+    sizes = _random_hash_file(hf, n, maxh)
+    if recorded:
+        assert _sha256(hf) == gold["input_sha256"], "the seeded input differs from the one the fixture was recorded on"
+    t = {}
+    threads = os.cpu_count() or 16
+    for tag, exe in (("ref", os.path.join(REF, "project_everything")), ("ours", os.path.join(BIN, "project_everything"))):
+        if tag == "ref" and not live:
+            continue
+        t0 = time.time()
+        r = run(exe, "sketch", str(hf), str(tmp_path / tag), "-t", str(threads), "-d", str(gold["d"]))
+        t[tag] = time.time() - t0
+        assert r.returncode == 0, r.stderr
+    b = np.fromfile(str(tmp_path / "ours" / "vectors.bin"), dtype="<i4")
+    assert b.size == n * gold["d"]
+    rb = open(str(tmp_path / "ours" / "vector_norms.txt")).read().strip().split("\n")
+    assert len(rb) == n
+    if recorded:
+        assert _sha256(tmp_path / "ours" / "vectors.bin") == gold["vectors_sha256"]
+        for name in ("dimension.txt", "dtype.txt"):
+            assert open(str(tmp_path / "ours" / name)).read() == gold[name]
+        _same_norms(gold["vector_norms"], rb)
+    if live:
+        a = np.fromfile(str(tmp_path / "ref" / "vectors.bin"), dtype="<i4")
+        assert np.array_equal(a, b)
+        for name in ("dimension.txt", "dtype.txt"):
+            assert open(str(tmp_path / "ref" / name)).read() == open(str(tmp_path / "ours" / name)).read()
+        _same_norms(open(str(tmp_path / "ref" / "vector_norms.txt")).read().strip().split("\n"), rb)
     # query-side protocol on the same file
     q = tmp_path / "q.txt"
-    q.write_text("".join(open(hf).readlines()[:40]))
-    ra = run(os.path.join(REF, "standalone_projection"), str(q), "512")
-    rb = run(os.path.join(BIN, "standalone_projection"), str(q), "512")
-    assert ra.returncode == 0 and rb.returncode == 0 and ra.stdout == rb.stdout
-    out = os.path.join(ROOT, "gpurun_out")
-    os.makedirs(out, exist_ok=True)
-    json.dump({"samples": n, "hashes": int(sizes.sum()), "d": 1024, "threads": threads, "seconds": t},
-              open(os.path.join(out, "cli_vs_reference.json"), "w"))
+    q.write_text("".join(open(str(hf)).readlines()[:gold["q_rows"]]))
+    ours = run(os.path.join(BIN, "standalone_projection"), str(q), str(gold["q_d"]))
+    assert ours.returncode == 0
+    if recorded:
+        import hashlib
+        assert hashlib.sha256(ours.stdout.encode()).hexdigest() == gold["standalone_stdout_sha256"]
+    if live:
+        ref = run(os.path.join(REF, "standalone_projection"), str(q), str(gold["q_d"]))
+        assert ref.returncode == 0 and ref.stdout == ours.stdout
+    print("cli_vs_reference", json.dumps({"samples": n, "hashes": int(sizes.sum()), "d": gold["d"], "threads": threads,
+                                          "seconds": t}))
 
 
 def test_pairwise_db_that_needs_more_limbs(tmp_path):

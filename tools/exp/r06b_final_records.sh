@@ -18,5 +18,5 @@ for rep in 1 2 3 4 5; do
 done
 python3 tools/strong_model.py --from-cpp $OUT/step_bench/step_bench_G*_run*.json > $OUT/strong_model_cpp_configs2.json 2> $OUT/strong_model.err || { tail -5 $OUT/strong_model.err; exit 1; }
 tail -c 1500 $OUT/strong_model_cpp_configs2.json; echo
-timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 echo "bench done"

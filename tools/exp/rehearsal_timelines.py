@@ -25,7 +25,7 @@ for path in sys.argv[1:]:
     if rec.get("scaling") == "strong":
         show("MVS_BENCH_REHEARSAL=1 python bench.py --gpus %d --config 3 --steps 3 --warmup 1" % g, rec)
     else:
-        print("== MVS_BENCH_REHEARSAL=1 python bench.py --gpus %d --steps 5 --warmup 2 --no-cpu-baseline   (default line; its `strong` record)" % g)
+        print("== MVS_BENCH_REHEARSAL=1 python bench.py --gpus %d --steps 5 --warmup 2 --no-cpu-baseline --full   (default line; its `strong` record)" % g)
         print("   configs[1] value %.0f samples/s over %d ranks sharing one card (not a scaling number); collectives %s" %
               (rec["value"], g, rec["config"].get("collectives")))
         for k, v in rec.get("strong", {}).items():
