@@ -128,6 +128,9 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *                         mvs_pairwise_rows / _stream -- take a balanced tile order: every XCD the same number of tiles of every
  *                         16 x 16-tile super-patch; 0 the static super-patch map (a triangle's static sub-patches hold 32, 26, 10
  *                         or 0 tiles: launches of a few rounds waited for their fullest XCD)
+ *   topk_dots, topk_block_rows
+ *                         mvs_pairwise_topk: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds
+ *                         the rows of a block (0: by the device budget)
  *   stream_block_rows, encode_stage_words, pairwise_map, coarse_radix, cand_regions, recheck_mode, recheck_blocks
  *                         test / experiment switches (DESIGN.md, appendix "switches"; encode_stage_words below 64 also keeps
  *                         every row on the device encoder's general loop)
@@ -390,6 +393,31 @@ int mvs_pairwise_block(mvs_ctx* ctx, const mvs_sketch_set* set, const double* no
 int mvs_search_block(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, double jaccard_min,
                      int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, mvs_cell* cells,
                      int64_t capacity, int64_t* n_cells);
+
+/* Exact k nearest neighbours: for every row of [row_begin, row_end), the k columns of [col_begin, col_end) whose Jaccard
+ * estimate is highest -- the question `query_pc_mat --top` and read_pc_mat.py ask of a thresholded matrix
+ * (src/pairwise_comp_optimized.cpp:135-147 keeps a cell only when dot/d > 0.05 (n2_i + n2_j)), answered for every row
+ * whatever its neighbours' Jaccard.
+ *   score : J = inter / (n2_row + n2_col - inter), inter = (double)dot / d, in fp64 in that order -- the writer's Jaccard
+ *           before its clamp (:654-672); `dot` is the int32 dot, wrapped as mvs_pairwise_dots returns it.  The same for
+ *           int32 and int16 DBs.
+ *   order : J descending, equal J by the smaller column; a cell whose J is NaN is never selected, +-inf are ordinary values.
+ *           MVS_TOPK_EXCLUDE_SELF in `flags` skips the cell col == row.
+ *   k     : 1..256 (MVS_E_INVALID otherwise).
+ *   cells : (row_end - row_begin) * k entries (`mem_cells`); on return *n_cells cells sorted by (row, col): per row its best
+ *           min(k, eligible columns), in ASCENDING column order (what the shard writer needs, :718-722), with `dot` and
+ *           `q` exactly as mvs_pairwise_rows reports them (q = the writer's quantised Jaccard, :658-665).
+ *   norms_sq : n doubles (`mem_norms`), as for mvs_pairwise_rows.
+ * Exact and deterministic: bit-identical to a brute-force evaluation of the rule above, whatever the device, the blocking or
+ * the options.  Rows go in blocks whose dots fit a quarter of the free device memory (option topk_block_rows bounds them,
+ * option topk_dots = 1 computes the dots on the vector ALUs instead of the matrix cores); no N x N buffer exists.  Synchronous.
+ * mvs_ctx_topk_stats: what the last call did -- dots and selection kernel times summed over its row blocks (0 unless
+ * mvs_ctx_set_timing is on), the number of row blocks and the rows per block.  Any pointer may be NULL. */
+#define MVS_TOPK_EXCLUDE_SELF 1
+int mvs_pairwise_topk(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, int k,
+                      int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int flags,
+                      mvs_cell* cells, int mem_cells, int64_t* n_cells);
+int mvs_ctx_topk_stats(const mvs_ctx* ctx, double* dots_ms, double* select_ms, int64_t* row_blocks, int64_t* block_rows);
 
 /* ---- block plans: one rank's share of the symmetric multi-rank schedule, compared in few launches ----------------
  * The reference shards by rows and lets every shard process compute its rows against ALL columns

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("MVS_HIP_LIBRARY") or os.path.join(_HERE, "libmvs_hip.
 MVS_OK, MVS_E_INVALID, MVS_E_HIP, MVS_E_CAPACITY, MVS_E_NOMEM, MVS_E_RANGE, MVS_E_ABORTED = 0, 1, 2, 3, 4, 5, 6
 MEM_HOST, MEM_DEVICE = 0, 1
 KEEP_INT32, KEEP_INT16 = 0, 1
+TOPK_EXCLUDE_SELF = 1
 LIMBS_K3 = 0x103
 BLOCK_SYMMETRIC, BLOCK_MIRROR_ALL = 1, 2
 
@@ -96,6 +97,10 @@ SYMBOLS = [
     ("mvs_cells_sort", _c.c_int, [_P, _P, _c.c_int64, _P]),
     ("mvs_search_block", _c.c_int, [_P, _P, _P, _c.c_double, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P,
                                      _c.c_int64, _c.POINTER(_c.c_int64)]),
+    ("mvs_pairwise_topk", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                      _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_int64)]),
+    ("mvs_ctx_topk_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
+                                       _c.POINTER(_c.c_int64)]),
     ("mvs_pairwise_dots", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int,
                                       _c.c_int]),
     ("mvs_sketch_set_planes", _c.c_int, [_P, _c.POINTER(_P)]),
@@ -838,6 +843,37 @@ class Context:
         if im != MEM_DEVICE or om != MEM_DEVICE:
             raise ValueError("device buffers required")
         _check(self.lib.mvs_cells_sort(self._h, ip, int(n), op))
+
+    def pairwise_topk(self, sset, norms_sq, k, row_begin=0, row_end=None, col_begin=0, col_end=None, exclude_self=True,
+                      cells_out=None):
+        """mvs_pairwise_topk: per row of [row_begin, row_end) the k columns of [col_begin, col_end) with the highest Jaccard
+        estimate (ties: the smaller column; NaN never), each row's cells in ascending column order.  Returns a structured
+        CELL_DTYPE array sorted by (row, col), or -- with a device buffer `cells_out` (torch int32 tensor [rows * k, 4]) --
+        (cells_out, n_cells)."""
+        if row_end is None:
+            row_end = sset.n
+        if col_end is None:
+            col_end = sset.n
+        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        flags = TOPK_EXCLUDE_SELF if exclude_self else 0
+        count = _c.c_int64()
+        if cells_out is not None:
+            cp, cm, ck = _buf(cells_out)
+            _check(self.lib.mvs_pairwise_topk(self._h, sset._h, np_, nm, int(k), int(row_begin), int(row_end), int(col_begin),
+                                              int(col_end), flags, cp, cm, ctypes.byref(count)))
+            return cells_out, count.value
+        cells = np.empty(max(1, (row_end - row_begin) * max(int(k), 0)), dtype=CELL_DTYPE)
+        _check(self.lib.mvs_pairwise_topk(self._h, sset._h, np_, nm, int(k), int(row_begin), int(row_end), int(col_begin),
+                                          int(col_end), flags, cells.ctypes.data, MEM_HOST, ctypes.byref(count)))
+        return cells[:count.value]
+
+    def topk_stats(self):
+        """-> dict of the last pairwise_topk: dots_ms / select_ms (kernel times over its row blocks, timing on), row_blocks,
+        block_rows"""
+        a, b = _c.c_double(), _c.c_double()
+        n, r = _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_topk_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)))
+        return {"dots_ms": a.value, "select_ms": b.value, "row_blocks": n.value, "block_rows": r.value}
 
     def pairwise_dots(self, sset, r0, r1, c0, c1, algo=0, out=None):
         if out is None:

@@ -5,6 +5,10 @@
 //   pairwise_comp_optimized --db D/ --max_memory_gb G --num_threads T --output_folder O
 //                           --num_shards S --shard_idx k [--start_shard a] [--end_shard b] [--help]
 //   (extension: --shard_idx -1 computes ALL S shards from this one process on all visible GPUs)
+//   (extension: --top_k K, 1 <= K <= 256, writes every row's K nearest neighbours -- the K columns with the highest Jaccard
+//    estimate, self excluded, ties to the smaller column -- instead of the cells that pass the keep test; same folders, files
+//    and stdout lines.  Each shard is its rows x all columns (mvs_pairwise_topk): no exchange, so MVS_COLLECTIVE opens no
+//    communicator and every shard process reads the whole vectors.bin; --shard_idx -1 deals whole shards to the contexts.)
 //
 // Multi-GPU: the reference runs one process per shard and every process re-reads the whole vectors.bin and compares
 // its rows against ALL columns (src/pairwise_comp_optimized.cpp:937-982).  Started the same way -- one process per shard,
@@ -38,6 +42,8 @@ struct Options {
     double max_memory_gb = 0.0;
     int num_threads = 1, num_shards = 1, shard_idx = 0, start_shard = 0, end_shard = 1;
     bool show_help = false;
+    int top_k = 0;             // --top_k K (0: not given -- the threshold output)
+    bool top_k_bad = false;    // --top_k given without a value in 1..256
 };
 
 static void print_usage(const char* argv0) {
@@ -69,6 +75,12 @@ static bool parse(int argc, char* argv[], Options& o) {
             o.max_memory_gb = strtod(v.c_str(), &end);
             if (end == v.c_str() || *end) return false;
             have[1] = true;
+        } else if (a == "--top_k") {
+            // checked here, reported by main() before any file or device is touched
+            long x = 0;
+            if (value(v)) x = strtol(v.c_str(), &end, 10);
+            if (end == nullptr || end == v.c_str() || *end || x < 1 || x > 256) o.top_k_bad = true;
+            else o.top_k = (int)x;
         } else if (a == "--output_folder") {
             if (!value(o.output_folder)) return false;
             have[3] = true;
@@ -374,6 +386,107 @@ static int stream_shard(Gpu& g, const std::vector<double>& norms_sq, int keep_mo
     return 0;
 }
 
+// --top_k: one shard's rows x all columns, every row's k nearest neighbours (mvs_pairwise_topk, cells on the device in (row, col)
+// order) -> the same writer as a threshold shard (mvs_cells_stream_encoded, or the host encoder under MVS_SHARD_ENCODER=host)
+static int topk_shard(Gpu& g, const std::vector<double>& norms_sq, int k, int64_t begin_row, int64_t end_row, int64_t n_total,
+                      const std::string& shard_folder, bool stage_timing, int64_t* n_cells, ShardStats* stats) {
+    *n_cells = 0;
+    void* cells = nullptr;
+    const size_t bytes = (size_t)std::max<int64_t>(1, (end_row - begin_row) * (int64_t)k) * sizeof(mvs_cell);
+    if (mvs_device_alloc(g.ctx, bytes, 0, &cells) != MVS_OK) return gpu_fail("top-k cell buffer");
+    struct Free {
+        mvs_ctx* c;
+        void* p;
+        ~Free() { mvs_device_free(c, p); }
+    } release{g.ctx, cells};
+    if (mvs_pairwise_topk(g.ctx, g.set, norms_sq.data(), MVS_MEM_HOST, k, begin_row, end_row, 0, n_total, MVS_TOPK_EXCLUDE_SELF,
+                          (mvs_cell*)cells, MVS_MEM_DEVICE, n_cells) != MVS_OK)
+        return gpu_fail("top-k comparison");
+    if (stage_timing) {
+        double dots_ms = 0.0, select_ms = 0.0;
+        int64_t blocks = 0, block_rows = 0;
+        mvs_ctx_topk_stats(g.ctx, &dots_ms, &select_ms, &blocks, &block_rows);
+        std::cerr << "[top-k] rows " << begin_row << ".." << end_row << ": dots " << dots_ms << " ms, selection " << select_ms
+                  << " ms in " << blocks << " row block(s) of " << block_rows << ", " << *n_cells << " cells" << std::endl;
+    }
+    ShardSink sink(shard_folder);
+    int64_t delivered = 0;
+    const int src = host_encoder_wanted()
+                        ? mvs_cells_stream(g.ctx, (const mvs_cell*)cells, *n_cells, begin_row, end_row, &ShardSink::on_block, &sink,
+                                           &delivered)
+                        : mvs_cells_stream_encoded(g.ctx, (const mvs_cell*)cells, *n_cells, begin_row, end_row, &ShardSink::on_encoded,
+                                                   &sink, &delivered);
+    if (src != MVS_OK) {
+        if (!sink.error.empty()) std::cerr << "pairwise_comp_optimized: " << sink.error << std::endl;
+        return gpu_fail("writing a shard's rows");
+    }
+    try {
+        *stats = sink.writer.finish();                                                              // :990
+    } catch (const std::exception& e) {
+        std::cerr << "pairwise_comp_optimized: " << e.what() << std::endl;
+        return 2;
+    }
+    return 0;
+}
+
+// --top_k with --shard_idx -1: whole shards dealt to the contexts (shard s on context s mod G, MVS_PAIRWISE_CONTEXTS / MVS_DEVICE
+// as for the threshold run), the whole vectors.bin resident on each -- top-k needs no exchange
+static int run_all_shards_topk(const Options& o, const std::string& output_folder, const std::string& matrix_file, int elem_bytes,
+                               int64_t total_vectors, int dimension, const std::vector<double>& norms_sq, bool stage_timing) {
+    std::vector<int> devices;
+    {
+        int ndev = 0;
+        if (getenv("MVS_DEVICE") || mvs_device_count(&ndev) != MVS_OK || ndev <= 0) {
+            devices.push_back(pick_device());
+        } else {
+            int want = std::min(ndev, std::max(1, o.num_shards));
+            if (const char* e = getenv("MVS_PAIRWISE_CONTEXTS")) want = std::max(1, std::min(64, atoi(e)));
+            for (int i = 0; i < want; ++i) devices.push_back(i % ndev);
+        }
+    }
+    for (int shard = 0; shard < o.num_shards; ++shard) {
+        const std::string folder = output_folder + "shard_" + std::to_string(shard) + "/";
+        if (!fs::exists(folder)) fs::create_directories(folder);
+    }
+    std::mutex out_mu;
+    const size_t n_ctx = devices.size();
+    std::vector<int> status(n_ctx, 0);
+    auto work = [&](size_t gi) {
+        Gpu g;
+        if (mvs_ctx_create(devices[gi], &g.ctx) != MVS_OK) {
+            std::lock_guard<std::mutex> lk(out_mu);
+            status[gi] = gpu_fail("creating context");
+            return;
+        }
+        if (stage_timing) mvs_ctx_set_timing(g.ctx, 1);
+        int rc = load_db(g, matrix_file, elem_bytes, total_vectors, dimension);
+        for (int shard = (int)gi; shard < o.num_shards && !rc; shard += (int)n_ctx) {
+            const std::string shard_folder = output_folder + "shard_" + std::to_string(shard) + "/";
+            int64_t b = 0, e = 0, n = 0;
+            mvs_shard_rows(total_vectors, o.num_shards, shard, &b, &e);
+            {
+                std::lock_guard<std::mutex> lk(out_mu);
+                std::cout << "Shard " << shard << " processing rows " << b << " to " << e << std::endl;   // :941
+            }
+            ShardStats st;
+            rc = topk_shard(g, norms_sq, o.top_k, b, e, total_vectors, shard_folder, stage_timing, &n, &st);
+            std::lock_guard<std::mutex> lk(out_mu);
+            if (!rc) std::cout << "Jac space: " << st.jac_space << " ngh space: " << st.ngh_space << std::endl;   // :808
+        }
+        status[gi] = rc;
+    };
+    if (n_ctx == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (size_t gi = 0; gi < n_ctx; ++gi) pool.emplace_back(work, gi);
+        for (auto& th : pool) th.join();
+    }
+    if (stage_timing) std::cerr << "[stage] " << o.num_shards << " top-k shards on " << n_ctx << " context(s)" << std::endl;
+    for (int rc : status)
+        if (rc) return rc;
+    return 0;
+}
 
 // -------------------------------------------------------------------------------------------------------------------
 // the strong-scaled step under the reference's command line (mvs_step.hpp)
@@ -702,7 +815,17 @@ static int run_all_shards(const Options& o, const std::string& output_folder, co
 
 int main(int argc, char* argv[]) {
     Options o;
-    if (!parse(argc, argv, o) || o.show_help) {                                   // :846-850
+    const bool parsed = parse(argc, argv, o);
+    if (o.top_k_bad) {
+        std::cerr << "pairwise_comp_optimized: --top_k takes an integer in the range 1..256" << std::endl;
+        return 1;
+    }
+    if (o.top_k && legacy16_output()) {
+        std::cerr << "pairwise_comp_optimized: --top_k cannot be combined with MVS_INT16_LEGACY_OUTPUT=1 (that writer is "
+                     "threshold-only)" << std::endl;
+        return 1;
+    }
+    if (!parsed || o.show_help) {                                                 // :846-850
         print_usage(argv[0]);
         return o.show_help ? 0 : 1;
     }
@@ -761,6 +884,16 @@ int main(int argc, char* argv[]) {
     }
     auto start_time = std::chrono::high_resolution_clock::now();                  // :918
 
+    if (o.shard_idx == -1 && o.top_k) {
+        db.norms_sq.resize((size_t)total_vectors);
+        const int rc_all = run_all_shards_topk(o, output_folder, matrix_file, elem_bytes, total_vectors, dimension, db.norms_sq,
+                                               getenv("MVS_STAGE_TIMING") != nullptr);
+        if (rc_all) return rc_all;
+        auto end_time = std::chrono::high_resolution_clock::now();
+        auto duration = std::chrono::duration_cast<std::chrono::milliseconds>(end_time - start_time);
+        std::cout << "Total computation time: " << duration.count() << " ms" << std::endl;
+        return 0;
+    }
     if (o.shard_idx == -1) {
         if (int16 && legacy16_output()) {
             std::cerr << "pairwise_comp_optimized: --shard_idx -1 (all shards) writes the active shard format only" << std::endl;
@@ -801,6 +934,11 @@ int main(int argc, char* argv[]) {
     // the whole file
     const char* coll = getenv("MVS_COLLECTIVE");
     int rc = 0;
+    if (coll && *coll && o.num_shards > 1 && o.top_k) {
+        std::cerr << "pairwise_comp_optimized: --top_k needs no exchange: MVS_COLLECTIVE is ignored, this shard process reads the "
+                     "whole vectors.bin and computes its shard alone" << std::endl;
+        coll = nullptr;
+    }
     if (coll && *coll && o.num_shards > 1) {
         if (std::string(coll) != "rccl" && std::string(coll) != "files") {
             std::cerr << "pairwise_comp_optimized: MVS_COLLECTIVE must be rccl or files" << std::endl;
@@ -879,8 +1017,14 @@ int main(int argc, char* argv[]) {
     }
     int64_t n_kept = 0;
     ShardStats st;
-    rc = stream_shard(g, db.norms_sq, keep_mode, begin_row, end_row, shard_folder, stage_timing, &n_kept, &st, lap);
-    if (rc) return rc;
+    if (o.top_k) {
+        rc = topk_shard(g, db.norms_sq, o.top_k, begin_row, end_row, total_vectors, shard_folder, stage_timing, &n_kept, &st);
+        if (rc) return rc;
+        lap("top-k comparison + shard files");
+    } else {
+        rc = stream_shard(g, db.norms_sq, keep_mode, begin_row, end_row, shard_folder, stage_timing, &n_kept, &st, lap);
+        if (rc) return rc;
+    }
     if (int16) {                                                                  // _16bits.cpp:419-423
         auto end_time = std::chrono::high_resolution_clock::now();
         auto duration = std::chrono::duration_cast<std::chrono::milliseconds>(end_time - start_time);

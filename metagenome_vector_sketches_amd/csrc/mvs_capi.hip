@@ -195,6 +195,8 @@ const OptionSpec kOptions[] = {
     {"stream_piece_mib", &mvs::Options::stream_piece_mib, nullptr, 1, 1024},
     {"stream_spec", &mvs::Options::stream_spec, nullptr, 0, 1},
     {"stream_copy", &mvs::Options::stream_copy, nullptr, 0, 1},
+    {"topk_dots", &mvs::Options::topk_dots, nullptr, 0, 1},
+    {"topk_block_rows", &mvs::Options::topk_block_rows, nullptr, 0, 1 << 30},
     {"pairwise_block_cells", nullptr, &mvs::Options::pairwise_block_cells, 1, (1LL << 62)},
 };
 

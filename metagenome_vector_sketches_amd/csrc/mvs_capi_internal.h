@@ -143,6 +143,9 @@ struct mvs_ctx {
     struct PlanState* plan = nullptr;
     void* plan_tmp = nullptr;   size_t plan_tmp_bytes = 0;
     const void* rows_max_done = nullptr;   // state block whose widest row mvs_cells_sort_rows_ahead has already computed
+    // what the last mvs_pairwise_topk did (mvs_ctx_topk_stats): kernel times summed over its row blocks (timing enabled)
+    double tk_dots_ms = 0.0, tk_select_ms = 0.0;
+    long long tk_blocks = 0, tk_block_rows = 0;
 };
 
 struct mvs_sketch_set {

@@ -100,8 +100,13 @@ struct Options {
     int plan_strip_wgs = 1 << 22;   // block plans: a rectangle whose padded grid holds more workgroups than this is cut into column
                                     // strips (a dispatch holds 2^32 work-items per dimension = 2^23 workgroups; tests lower it)
     int comm_timeout_s = 600;       // file transport: how long a rank waits for a peer's block before it gives up
+    int topk_dots = 0;              // mvs_pairwise_topk: dots of a row block from 0 = the matrix-core kernels (launch_pairwise algo 0),
+                                    // 1 = the vector-ALU kernel (A/B, tests); same selection, same result
+    int topk_block_rows = 0;        // mvs_pairwise_topk: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
     double pairwise_block_cells = 1099511627776.0;   // row-chunk bound of mvs_pairwise_rows (2^40 cells)
 };
+
+constexpr int kMaxTopk = 256;   // largest k of mvs_pairwise_topk
 
 constexpr int kCandRegion = 8;   // candidate entries a filter wave can leave in its own region (one 64-byte line)
 
@@ -248,6 +253,13 @@ int launch_cand_thr(hipStream_t stream, const double* d_norms_sq, int64_t n, int
                     double coeff, int32_t* d_thr);
 // mode 0: comparison (kept cells), mode 1: dense dots.  algo 0: MFMA, 1: vector ALU.
 int launch_pairwise(hipStream_t stream, const PairwiseArgs& a, int mode, int algo, const Options& opt);
+// top-k selection over a block of dense dots (mvs_topk.hip): rows [row0, row0 + rows) x columns [c0, c0 + ld) -> k padded cells
+// per row at (row - out_row0) * k of d_pad, their number in d_counts[row - out_row0]; then the padded lists -> consecutive cells
+int launch_topk_select(hipStream_t stream, const int32_t* d_dots, int64_t rows, int64_t ld, int64_t row0, int64_t c0,
+                       const double* d_norms_sq, int d, int k, int exclude_self, mvs_cell* d_pad, int* d_counts,
+                       int64_t out_row0);
+int launch_topk_compact(hipStream_t stream, const mvs_cell* d_pad, const int* d_counts, const int64_t* d_offs, int64_t rows,
+                        int k, mvs_cell* d_out);
 // two-stage comparison for two base-256 limbs: coarse plane + row statistics from the limb planes,
 // per-call filter constants, the one-pass filter
 // that appends candidate pairs, and the exact re-check of the candidates that appends kept cells

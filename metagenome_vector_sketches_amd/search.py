@@ -124,12 +124,26 @@ class SearchIndex:
             out += self._search_lists(lists[q0:q0 + self.max_queries], q0, j, verbose)
         return out
 
-    def _search_lists(self, lists, q_first, j, verbose):
+    def search_topk(self, query_file, k, verbose=False):
+        """-> one list per query (file order): its k best database samples as (name, jaccard), best first (ties: the
+        earlier sample), exactly what FAISS's index.search(q, k) ranks in src/jaccard.py:117-131 -- but exact, with the
+        estimate jaccard = (dot/d) / (nn^2 + qn^2 - dot/d) of :199 in float64 and no threshold.  A query with norm 0 gets
+        an empty list (:184)."""
+        k = int(k)
+        if not 1 <= k <= 256:
+            raise ValueError("k must be in 1..256")
+        qnames, lists = read_queries(query_file)
+        out = []
+        for q0 in range(0, len(lists), self.max_queries):
+            out += self._topk_lists(lists[q0:q0 + self.max_queries], q0, k, verbose)
+        return out
+
+    def _queries_in_set(self, lists):
+        """project the queries into rows [n, n + len(lists)) of the set -> (their squared norms, all rows' squared norms
+        on the device)"""
         import torch
-        ctx, n, d, names, norms, dev = self.ctx, self.n, self.d, self.names, self.norms, self.dev
+        ctx, n, d, norms, dev = self.ctx, self.n, self.d, self.norms, self.dev
         nq = len(lists)
-        if nq == 0:
-            return []
         offs = np.zeros(nq + 1, dtype=np.int64)
         offs[1:] = np.cumsum([len(x) for x in lists])
         flat = np.concatenate(lists) if offs[-1] else np.zeros(0, dtype=np.uint64)
@@ -141,6 +155,45 @@ class SearchIndex:
         self.sset.fill(q_sk, n)
         qn2 = q_ss.cpu().numpy().astype(np.float64) / d             # query_norm^2 (:120-121, exact here)
         n2 = torch.from_numpy(np.concatenate([norms * norms, qn2, np.zeros(self.max_queries - nq)])).to(dev)
+        return qn2, n2
+
+    def _topk_lists(self, lists, q_first, k, verbose):
+        n, d, names, norms = self.n, self.d, self.names, self.norms
+        nq = len(lists)
+        if nq == 0:
+            return []
+        qn2, n2 = self._queries_in_set(lists)
+        cells = self.ctx.pairwise_topk(self.sset, n2, k, n, n + nq, 0, n, exclude_self=True)
+        out = []
+        for qi in range(nq):
+            if verbose:
+                print("Query %d:" % (q_first + qi))
+            if qn2[qi] == 0:                                        # :184 query_norm == 0 -> nothing
+                out.append([])
+                continue
+            mine = cells[cells["row"] == n + qi]
+            inter = mine["dot"].astype(np.float64) / d
+            nn2 = norms[mine["col"]] * norms[mine["col"]]
+            jac = inter / (nn2 + qn2[qi] - inter)                   # the kernel's score, bit for bit
+            order = np.lexsort((mine["col"], -jac))
+            res = []
+            for rank, t in enumerate(order):
+                c = int(mine["col"][t])
+                if verbose:
+                    ip = inter[t] / (np.sqrt(qn2[qi]) * norms[c])
+                    print("  Neighbor %d: %s (jaccard: %.4f), inner_product: %.4f %s %s"
+                          % (rank, names[c], jac[t], ip, norms[c], np.sqrt(qn2[qi])))
+                res.append((names[c], float(jac[t])))
+            out.append(res)
+        return out
+
+    def _search_lists(self, lists, q_first, j, verbose):
+        import torch
+        ctx, n, d, names, norms, dev = self.ctx, self.n, self.d, self.names, self.norms, self.dev
+        nq = len(lists)
+        if nq == 0:
+            return []
+        qn2, n2 = self._queries_in_set(lists)
         # hits land in a grow-only buffer; if it is too small the library says how many there are and the block is
         # compared ONCE more with exactly that room (the reference re-queries FAISS with 3x the neighbours, :131-170)
         cap = max(1 << 16, 256 * nq) if self._hits is None else self._hits.shape[0]
@@ -190,6 +243,15 @@ def search_index(index_folder, query_file, j, ctx=None, verbose=True):
         return idx.search(query_file, j, verbose=verbose)
 
 
+def search_index_topk(index_folder, query_file, k, ctx=None, verbose=True):
+    """search_index's top-k form: per query its k best database samples [(name, jaccard)], best first, no threshold."""
+    nq = sum(1 for line in open(query_file) if line.strip())
+    with SearchIndex(index_folder, ctx=ctx, max_queries=max(1, min(nq, 4096))) as idx:
+        if ctx is not None:
+            idx._own = False
+        return idx.search_topk(query_file, k, verbose=verbose)
+
+
 def index_vectors(output_dir, verbose=True):
     """The reference's `index` step (src/jaccard.py:18-61) reads vectors.bin, L2-normalises a float copy and writes
     faiss.index.  Nothing of that is needed here -- the search runs on the integer sketches -- so this only checks that
@@ -224,6 +286,8 @@ def build_parser():
                                help="Path to query file. Formatted as ID: space_separated_hashes, one ID per line per line")
     parser_search.add_argument("-j", type=float, default=0.1, help="Retrieve all datasets with higher Jaccard index")
     parser_search.add_argument("-t", "--threads", type=int, default=1, help="Number of threads [1] (accepted, unused)")
+    parser_search.add_argument("--top", type=int, default=None, metavar="K",
+                               help="Report every query's K nearest datasets (1..256) instead of those above -j (extension)")
     parser.add_argument("-v", "--version", action="store_true", help="Show version and date")
     return parser
 
@@ -241,8 +305,14 @@ def main(argv=None):
         index_vectors(args.output_index)
     elif args.command == "search":
         folder = args.index_folder if args.index_folder.endswith("/") else args.index_folder + "/"
+        if args.top is not None and not 1 <= args.top <= 256:
+            print("--top takes an integer in the range 1..256")
+            return 2
         try:
-            search_index(folder, args.query_file, args.j)
+            if args.top is not None:
+                search_index_topk(folder, args.query_file, args.top)
+            else:
+                search_index(folder, args.query_file, args.j)
         except ValueError as e:
             if str(e).startswith("ERROR 332"):                     # the reference prints the line and exits 332 (:82-84)
                 print(e)
