@@ -103,9 +103,10 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   pairwise_block_cells  row-chunk bound of mvs_pairwise_rows, in cells (default 2^40)
  *   sort                  kept-cell sort: 0 (default) by list length, 1 merge sort, 2 radix sort
  *   enable_k3             1: mvs_sketch_set_create codes sets with 127 < max|v| <= 8127 as MVS_LIMBS_K3
- *   project_variant       projection kernel: 0 (default) by dimension -- 14 = four 64-dim blocks per wave sharing the
- *                         first splitmix64 round when d is a multiple of 256 (>= 512), else 2 or 1 blocks per wave;
- *                         1 / 2 / 12 / 14 force a variant
+ *   project_variant       projection kernel: 0 (default) by dimension -- 24 = four 64-dim blocks per wave sharing the
+ *                         first splitmix64 round, deep carry-save tree, VALU-only epilogue, when d is a multiple of 256
+ *                         (>= 512), else 2 or 1 blocks per wave; 1 / 2 / 12 / 14 / 24 force a variant (14 = 24 with
+ *                         the ripple every 32 hashes and the ds_bpermute epilogue)
  *   stream_dense          mvs_pairwise_stream, dense results: 1 (default) one byte per cell in a matrix, a row block turned
  *                         into CSR / encoded rows on a side stream beside the next block's launch where the exact kernel
  *                         does whole row blocks, on the context's stream where the two-stage comparison feeds the matrix;

@@ -170,7 +170,7 @@ const OptionSpec kOptions[] = {
     {"sort", &mvs::Options::sort, nullptr, 0, 2},
     {"enable_k3", &mvs::Options::enable_k3, nullptr, 0, 1},
     {"markers", &mvs::Options::markers, nullptr, 0, 1},
-    {"project_variant", &mvs::Options::project_variant, nullptr, 0, 14},
+    {"project_variant", &mvs::Options::project_variant, nullptr, 0, 24},
     {"comm_timeout_s", &mvs::Options::comm_timeout_s, nullptr, 1, 86400},
     {"pairwise_map", &mvs::Options::pairwise_map, nullptr, 0, 2},
     {"coarse_radix", &mvs::Options::coarse_radix, nullptr, 0, 1},

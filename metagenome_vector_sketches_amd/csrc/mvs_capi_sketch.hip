@@ -101,10 +101,11 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
     }
     if (c->timing) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     const int nblk = (d + 63) / 64;
-    // kernel variant (launch_project): four blocks per wave sharing the first splitmix64 round where the dimension
-    // fills them (8.97 vs 9.44 ms on 10k x 50k hashes, d = 2048), else two or one block per wave; option
-    // project_variant forces one
-    int bpw = (nblk % 4 == 0 && nblk >= 8) ? 14 : (nblk >= 2 ? 2 : 1);
+    // kernel variant (launch_project): four blocks per wave sharing the first splitmix64 round, with the deep carry-save
+    // tree and the VALU epilogue, where the dimension fills them (variant 24; 14 measured 8.97 vs 9.44 ms for 2 on 10k x
+    // 50k hashes, d = 2048), else two or one block per wave; option project_variant forces one
+    int bpw = (nblk % 4 == 0 && nblk >= 8) ? 24 : (nblk >= 2 ? 2 : 1);
+    if (c->opt.project_variant == 24 && nblk >= 4) bpw = 24;
     if (c->opt.project_variant == 14 && nblk >= 4) bpw = 14;
     if (c->opt.project_variant == 12 && nblk >= 2) bpw = 12;
     if (c->opt.project_variant == 2 && nblk >= 2) bpw = 2;

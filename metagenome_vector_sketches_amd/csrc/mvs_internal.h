@@ -46,7 +46,8 @@ struct Options {
     int pairwise_debug = 0;         // profiling ablations; only honoured by a -DMVS_ABLATIONS build
     int sort = 0;                   // kept-cell sort: 0 by list length, 1 merge, 2 radix
     int project_variant = 0;        // projection kernel: 0 by dimension; 1 / 2 blocks per wave; 12 / 14 = 2 / 4 blocks per
-                                    // wave sharing the first splitmix64 round
+                                    // wave sharing the first splitmix64 round; 24 = 14 with the deep carry-save tree and
+                                    // the VALU epilogue
     int markers = 0;                // 1: roctx ranges around the main entry points (rocprofv3 --marker-trace)
     int enable_k3 = 0;              // 1: mvs_sketch_set_create picks the three-plane Karatsuba code for |v| <= 8127
     int pairwise_map = 0;           // sub-patch an XCD takes in k_pairwise_pp: 0 = 4 rows x 8 cols, 1 = 8 x 4, 2 = 2 x 16

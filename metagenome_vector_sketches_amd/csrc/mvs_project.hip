@@ -214,6 +214,96 @@ __device__ __forceinline__ int32_t reduce_counts(const uint32_t (&lo_in)[kLV], c
     return cnt;
 }
 
+// The same sums without LDS: every cross-lane move is a DPP move or a v_permlane*_swap, all inside the VALU.  Lane k only
+// needs the digits of its own word (lo for k < 32, hi for k >= 32), so the first step adds the two 32-lane halves AND
+// merges lo with hi: v_permlane32_swap(lo, hi) hands lanes 0-31 the pair (lo[k], lo[k + 32]) and lanes 32-63 the pair
+// (hi[k - 32], hi[k]).  From there on one word per digit is reduced instead of two, over the 32 lanes of each half:
+// quad_perm [1,0,3,2] / [2,3,0,1] (pairs within a quad), row_half_mirror (lane i <-> 7 - i: quad 0 <-> quad 1),
+// row_mirror (i <-> 15 - i: half-rows), v_permlane16_swap (rows 0 <-> 1 and 2 <-> 3).  A swap leaves {own, partner}
+// in its two outputs in some order, and the sum of the two is the same either way.  Every lane ends up with its half's
+// total.  6 stages, (LV0 + 1) + ... + (LV0 + 5) digit additions of one word each.
+__device__ __forceinline__ void add_digit(uint32_t& w, uint32_t a, uint32_t b, uint32_t& c) {
+    w = xor3(a, b, c);
+    c = maj3(a, b, c);
+}
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_mov(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
+}
+
+// one stage on the LIVE low digits of w; the carry out becomes digit LIVE
+template <int CTRL, int LIVE, int N>
+__device__ __forceinline__ void reduce_stage_dpp(uint32_t (&w)[N]) {
+    static_assert(LIVE < N, "room for the carry");
+    uint32_t c = 0;
+#pragma unroll
+    for (int l = 0; l < LIVE; ++l) {
+        add_digit(w[l], w[l], dpp_mov<CTRL>(w[l]), c);
+    }
+    w[LIVE] = c;
+}
+
+template <int LV0>
+__device__ __forceinline__ int32_t reduce_counts_valu(const uint32_t (&lo_in)[kLV], const uint32_t (&hi_in)[kLV],
+                                                      int lane) {
+    static_assert(LV0 >= 1 && LV0 <= kLV, "live digits");
+    constexpr int kOut = LV0 + 6;
+    uint32_t w[kOut];
+    uint32_t c = 0;
+#pragma unroll
+    for (int l = 0; l < LV0; ++l) {
+        const auto r = __builtin_amdgcn_permlane32_swap(lo_in[l], hi_in[l], false, false);
+        add_digit(w[l], r[0], r[1], c);
+    }
+    w[LV0] = c;
+#pragma unroll
+    for (int l = LV0 + 1; l < kOut; ++l) w[l] = 0u;
+    reduce_stage_dpp<0xb1, LV0 + 1>(w);     // quad_perm [1,0,3,2]
+    reduce_stage_dpp<0x4e, LV0 + 2>(w);     // quad_perm [2,3,0,1]
+    reduce_stage_dpp<0x141, LV0 + 3>(w);    // row_half_mirror
+    reduce_stage_dpp<0x140, LV0 + 4>(w);    // row_mirror
+    c = 0;
+#pragma unroll
+    for (int l = 0; l < LV0 + 5; ++l) {
+        const auto r = __builtin_amdgcn_permlane16_swap(w[l], w[l], false, false);
+        add_digit(w[l], r[0], r[1], c);
+    }
+    w[LV0 + 5] = c;
+    int32_t cnt = 0;
+    const int sh = lane & 31;
+#pragma unroll
+    for (int l = 0; l < kOut; ++l) cnt += (int32_t)((w[l] >> sh) & 1u) << l;
+    return cnt;
+}
+
+// the STATS all-reduce (sum of squares, max |v|) over the wave with the same moves: every lane gets the totals
+template <int CTRL>
+__device__ __forceinline__ void sum_max_stage_dpp(unsigned long long& ss, uint32_t& mx) {
+    ss += ((unsigned long long)dpp_mov<CTRL>((uint32_t)(ss >> 32)) << 32) | dpp_mov<CTRL>((uint32_t)ss);
+    const uint32_t o = dpp_mov<CTRL>(mx);
+    mx = o > mx ? o : mx;
+}
+
+template <bool SWAP32>
+__device__ __forceinline__ void sum_max_stage_swap(unsigned long long& ss, uint32_t& mx) {
+    const uint32_t l = (uint32_t)ss, h = (uint32_t)(ss >> 32);
+    const auto rl = SWAP32 ? __builtin_amdgcn_permlane32_swap(l, l, false, false) : __builtin_amdgcn_permlane16_swap(l, l, false, false);
+    const auto rh = SWAP32 ? __builtin_amdgcn_permlane32_swap(h, h, false, false) : __builtin_amdgcn_permlane16_swap(h, h, false, false);
+    const auto rm = SWAP32 ? __builtin_amdgcn_permlane32_swap(mx, mx, false, false) : __builtin_amdgcn_permlane16_swap(mx, mx, false, false);
+    ss = (((unsigned long long)rh[0] << 32) | rl[0]) + (((unsigned long long)rh[1] << 32) | rl[1]);
+    mx = rm[0] > rm[1] ? rm[0] : rm[1];
+}
+
+__device__ __forceinline__ void wave_sum_max_valu(unsigned long long& ss, uint32_t& mx) {
+    sum_max_stage_dpp<0xb1>(ss, mx);
+    sum_max_stage_dpp<0x4e>(ss, mx);
+    sum_max_stage_dpp<0x141>(ss, mx);
+    sum_max_stage_dpp<0x140>(ss, mx);
+    sum_max_stage_swap<false>(ss, mx);
+    sum_max_stage_swap<true>(ss, mx);
+}
+
 // 256 threads = 4 waves, each wave owns BPW consecutive 64-dim blocks and streams over all hashes of
 // one unit; a unit needs ny = ceil(nblk / (4*BPW)) workgroups.  1-D grid, XCD aware: workgroups are
 // dealt round-robin over the 8 XCDs, so the ny workgroups of one unit are given linear ids 8 apart
@@ -222,7 +312,14 @@ __device__ __forceinline__ int32_t reduce_counts(const uint32_t (&lo_in)[kLV], c
 // STATS: also accumulate each sample's exact sum of squares (int64 atomics, one per wave) and the largest |v|
 // of the launch -- valid only when every sample is a single unit (the host checks), because a multi-unit
 // sample's entries are only final once all its units have been added.
-template <int BPW, bool STATS, bool SHARED = false>
+//
+// DEEP (variant 24): the carry-save tree reaches 128 hashes per lane before anything ripples.  The loop still hashes four
+// batches per iteration and gets one weight-32 carry out of them; carries of weight 32 and 64 wait in p32 / p64 until a
+// second one of the same weight exists, and the two are full-added into digit 5 / 6 at once.  A ripple (half adders through
+// digits 7..10) follows once per 128 hashes instead of through 5..10 once per 32, so counting costs ~2.05 bitop3 per
+// input word instead of ~2.45.  The branches on the iteration number are wave-uniform.  The epilogue is
+// reduce_counts_valu.
+template <int BPW, bool STATS, bool SHARED = false, bool DEEP = false>
 __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ hashes,
                                                  const ProjUnit* __restrict__ units, long long n_units, int ny,
                                                  int d, int nblk, int32_t* __restrict__ out,
@@ -258,8 +355,10 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
         uint64_t hv[8], hn[8];
         load_batch<true>(hv, base, 0, lane, last);
         int64_t b = 0;
-        // four batches = 32 hashes per lane: Harley-Seal tree of depth 5, then one ripple.  The loop
+        // four batches = 32 hashes per lane: Harley-Seal tree of depth 5, then one ripple (DEEP: see above).  The loop
         // runs while the NEXT four batches are full too, so its prefetches need no bounds handling.
+        uint32_t p32lo[BPW], p32hi[BPW], p64lo[BPW], p64hi[BPW];
+        int grp4 = 0;   // DEEP: iterations done; bit 0 / 1 = a weight-32 / weight-64 carry is pending
         for (; b + 4 < nfull; b += 4) {
             uint32_t c8lo[4][BPW], c8hi[4][BPW];
 #pragma unroll
@@ -295,7 +394,44 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
                 s.lo[q][4] = xor3(tl, c16lo[0][q], c16lo[1][q]);
                 s.hi[q][4] = xor3(th, c16hi[0][q], c16hi[1][q]);
             }
-            ripple<5, BPW>(s, c32lo, c32hi);
+            if constexpr (DEEP) {
+                if (grp4 & 1) {
+                    uint32_t c64lo[BPW], c64hi[BPW];
+#pragma unroll
+                    for (int q = 0; q < BPW; ++q) {
+                        const uint32_t tl = s.lo[q][5], th = s.hi[q][5];
+                        c64lo[q] = maj3(tl, p32lo[q], c32lo[q]);
+                        c64hi[q] = maj3(th, p32hi[q], c32hi[q]);
+                        s.lo[q][5] = xor3(tl, p32lo[q], c32lo[q]);
+                        s.hi[q][5] = xor3(th, p32hi[q], c32hi[q]);
+                    }
+                    if (grp4 & 2) {
+                        uint32_t c128lo[BPW], c128hi[BPW];
+#pragma unroll
+                        for (int q = 0; q < BPW; ++q) {
+                            const uint32_t tl = s.lo[q][6], th = s.hi[q][6];
+                            c128lo[q] = maj3(tl, p64lo[q], c64lo[q]);
+                            c128hi[q] = maj3(th, p64hi[q], c64hi[q]);
+                            s.lo[q][6] = xor3(tl, p64lo[q], c64lo[q]);
+                            s.hi[q][6] = xor3(th, p64hi[q], c64hi[q]);
+                        }
+                        ripple<7, BPW>(s, c128lo, c128hi);
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < BPW; ++q) p64lo[q] = c64lo[q], p64hi[q] = c64hi[q];
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < BPW; ++q) p32lo[q] = c32lo[q], p32hi[q] = c32hi[q];
+                }
+                ++grp4;
+            } else {
+                ripple<5, BPW>(s, c32lo, c32hi);
+            }
+        }
+        if constexpr (DEEP) {   // the pending carries go in before anything of weight 1 is added again
+            if (grp4 & 1) ripple<5, BPW>(s, p32lo, p32hi);
+            if (grp4 & 2) ripple<6, BPW>(s, p64lo, p64hi);
         }
         // leftover full batches
         for (; b < nfull; ++b) {
@@ -335,7 +471,14 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
     for (int b = 0; b < BPW; ++b) {
         if (b0 + b >= nblk) break;
         int32_t cnt;   // a lane absorbed at most ceil(count / 64) hashes
-        if (count <= 64) cnt = reduce_counts<1>(s.lo[b], s.hi[b], lane);
+        if constexpr (DEEP) {
+            if (count <= 64) cnt = reduce_counts_valu<1>(s.lo[b], s.hi[b], lane);
+            else if (count <= 64 * 15) cnt = reduce_counts_valu<4>(s.lo[b], s.hi[b], lane);
+            else if (count <= 64 * 127) cnt = reduce_counts_valu<7>(s.lo[b], s.hi[b], lane);
+            else if (count <= 64 * 511) cnt = reduce_counts_valu<9>(s.lo[b], s.hi[b], lane);
+            else if (count <= 64 * 1023) cnt = reduce_counts_valu<10>(s.lo[b], s.hi[b], lane);
+            else cnt = reduce_counts_valu<kLV>(s.lo[b], s.hi[b], lane);
+        } else if (count <= 64) cnt = reduce_counts<1>(s.lo[b], s.hi[b], lane);
         else if (count <= 64 * 15) cnt = reduce_counts<4>(s.lo[b], s.hi[b], lane);
         else if (count <= 64 * 127) cnt = reduce_counts<7>(s.lo[b], s.hi[b], lane);
         else if (count <= 64 * 511) cnt = reduce_counts<9>(s.lo[b], s.hi[b], lane);
@@ -356,11 +499,19 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
         }
     }
     if (STATS) {
+        if constexpr (DEEP) {
+            unsigned long long uss = (unsigned long long)ss;   // two's complement: the wrapped sum is the same
+            uint32_t umx = mx;
+            wave_sum_max_valu(uss, umx);
+            ss = (long long)uss;
+            mx = umx;
+        } else {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            ss += __shfl_xor(ss, o, 64);
-            const unsigned int other = (unsigned int)__shfl_xor((int)mx, o, 64);
-            mx = other > mx ? other : mx;
+            for (int o = 32; o > 0; o >>= 1) {
+                ss += __shfl_xor(ss, o, 64);
+                const unsigned int other = (unsigned int)__shfl_xor((int)mx, o, 64);
+                mx = other > mx ? other : mx;
+            }
         }
         if (lane == 0) {
             atomicAdd(sumsq + u.sample, (unsigned long long)ss);
@@ -437,16 +588,17 @@ __global__ __launch_bounds__(256) void k_saturate_i16(const int32_t* __restrict_
 }  // namespace
 
 // variant: 1 / 2 = that many 64-dim blocks per wave, every block hashed on its own; 12 / 14 = two / four blocks per wave
-// with the shared first splitmix64 round (BatchGenShared)
-template <int BPW, bool SHARED>
+// with the shared first splitmix64 round (BatchGenShared); 24 = 14 with the deeper carry-save tree and the VALU epilogue
+// (DEEP)
+template <int BPW, bool SHARED, bool DEEP = false>
 static void launch_project_as(hipStream_t stream, unsigned grid, bool stats, const uint64_t* d_hashes, const ProjUnit* d_units,
                               long long nu, int ny, int d, int nblk, int32_t* d_out, unsigned long long* d_sumsq,
                               unsigned long long* d_max_abs) {
     if (stats)
-        hipLaunchKernelGGL((k_project<BPW, true, SHARED>), dim3(grid), dim3(256), 0, stream, d_hashes, d_units, nu, ny, d, nblk,
+        hipLaunchKernelGGL((k_project<BPW, true, SHARED, DEEP>), dim3(grid), dim3(256), 0, stream, d_hashes, d_units, nu, ny, d, nblk,
                            d_out, d_sumsq, d_max_abs);
     else
-        hipLaunchKernelGGL((k_project<BPW, false, SHARED>), dim3(grid), dim3(256), 0, stream, d_hashes, d_units, nu, ny, d, nblk,
+        hipLaunchKernelGGL((k_project<BPW, false, SHARED, DEEP>), dim3(grid), dim3(256), 0, stream, d_hashes, d_units, nu, ny, d, nblk,
                            d_out, d_sumsq, d_max_abs);
 }
 
@@ -465,6 +617,7 @@ int launch_project(hipStream_t stream, const uint64_t* d_hashes, const ProjUnit*
         switch (variant) {
             case 1: launch_project_as<1, false>(stream, grid, stats, d_hashes, d_units + u0, (long long)nu, ny, d, nblk, d_out, d_sumsq, d_max_abs); break;
             case 12: launch_project_as<2, true>(stream, grid, stats, d_hashes, d_units + u0, (long long)nu, ny, d, nblk, d_out, d_sumsq, d_max_abs); break;
+            case 24: launch_project_as<4, true, true>(stream, grid, stats, d_hashes, d_units + u0, (long long)nu, ny, d, nblk, d_out, d_sumsq, d_max_abs); break;
             case 14: launch_project_as<4, true>(stream, grid, stats, d_hashes, d_units + u0, (long long)nu, ny, d, nblk, d_out, d_sumsq, d_max_abs); break;
             default: launch_project_as<2, false>(stream, grid, stats, d_hashes, d_units + u0, (long long)nu, ny, d, nblk, d_out, d_sumsq, d_max_abs); break;
         }

@@ -40,8 +40,8 @@ def run(cmd):
     return subprocess.run(cmd, check=True, capture_output=True)
 
 
-def disassemble(path, is_dis=False):
-    """-> disassembly text of the gfx950 code object(s) inside `path` that hold k_pairwise_pp kernels"""
+def disassemble(path, is_dis=False, want="k_pairwise_pp"):
+    """-> disassembly text of the gfx950 code object(s) inside `path` that hold `want` kernels"""
     if is_dis:
         with open(path) as f:
             return f.read()
@@ -65,11 +65,11 @@ def disassemble(path, is_dis=False):
             if r.returncode != 0 or not os.path.exists(co) or os.path.getsize(co) == 0:
                 continue
             syms = run([os.path.join(LLVM, "llvm-readelf"), "-s", "-W", co]).stdout.decode()
-            if "k_pairwise_pp" not in syms:
+            if want not in syms:
                 continue
             out.append(run([os.path.join(LLVM, "llvm-objdump"), "-d", co]).stdout.decode())
     if not out:
-        raise SystemExit("check_isa: no gfx950 code object with k_pairwise_pp kernels in %s" % path)
+        raise SystemExit("check_isa: no gfx950 code object with %s kernels in %s" % (want, path))
     return "\n".join(out)
 
 
