@@ -132,6 +132,10 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   topk_dots, topk_block_rows
  *                         mvs_pairwise_topk: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds
  *                         the rows of a block (0: by the device budget)
+ *   cluster_cells, cluster_block_rows
+ *                         mvs_pairwise_cluster: cells the staging buffer of a row block holds (0, default: a quarter of the free
+ *                         device memory) and an upper bound on the rows of a block (0: by pairwise_block_cells); a block that
+ *                         overflows the buffer is halved and redone, so neither changes a result
  *   stream_block_rows, encode_stage_words, pairwise_map, coarse_radix, cand_regions, recheck_mode, recheck_blocks
  *                         test / experiment switches (DESIGN.md, appendix "switches"; encode_stage_words below 64 also keeps
  *                         every row on the device encoder's general loop)
@@ -419,6 +423,55 @@ int mvs_pairwise_topk(mvs_ctx* ctx, const mvs_sketch_set* set, const double* nor
                       int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int flags,
                       mvs_cell* cells, int mem_cells, int64_t* n_cells);
 int mvs_ctx_topk_stats(const mvs_ctx* ctx, double* dots_ms, double* select_ms, int64_t* row_blocks, int64_t* block_rows);
+
+/* Single-linkage clustering of the samples at a Jaccard level, on the device: samples i != j are LINKED iff
+ *   (double)dot / (double)d > (t / (1.0 + t)) * (n2[i] + n2[j])        (fp64, in that order; t = min_jaccard, 0 < t < 1)
+ * -- "the Jaccard estimate of src/pairwise_comp_optimized.cpp:661-662 exceeds t", the rule and the kernels of mvs_search_block
+ * (the floating keep test with the coefficient t/(1+t) in place of 0.05); `dot` is the wrapped int32 dot every path reports.
+ * A sample whose norm is NaN or +inf is linked to nothing.  A CLUSTER is a connected component of that graph.  The reference
+ * has no clustering: it writes the thresholded matrix (:645-817) and leaves the grouping to its readers; here the kept cells
+ * never leave the device and the answer is four int32 arrays:
+ *   labels[i]          cluster of sample i; clusters are numbered 0 .. C-1 by ascending smallest member
+ *   sizes[c]           members of cluster c
+ *   representatives[c] the member with the largest norms_sq (the largest estimated hash set), equal values: the smaller index;
+ *                      a NaN norm ranks below every number
+ *   degree[i]          samples linked to i (self excluded)
+ * Exact and deterministic: everything is a function of the edge set, so the arrays equal a brute force over all pairs bit
+ * for bit, whatever the blocking, the options or the comparison path (mvs_cluster.hip states the argument).
+ *
+ * mvs_cluster_create    a forest of n singletons on the context's device (parent[i] = i, degree 0); resets the statistics
+ *                       mvs_ctx_cluster_stats reports.
+ * mvs_cluster_add_cells unions row ~ col of every cell of a DEVICE list (cells with row == col are ignored; dot and q are not
+ *                       read) and adds 1 to degree[row] per cell with row != col -- so degree is the graph's only if every
+ *                       ordered pair is fed exactly once; feeding a list twice changes degree and nothing else.  Any producer
+ *                       may feed it (mvs_search_block, mvs_pairwise_block, a multi-rank step's own cells).  The list is
+ *                       consumed when the call returns.  MVS_E_RANGE: a cell named a sample outside [0, n) (ignored).
+ * mvs_pairwise_cluster  the one-call producer: compares `set` (n samples, the cluster's n) with itself at level min_jaccard,
+ *                       row block by row block -- the launch mvs_pairwise_rows makes, with the other coefficient: every ordered
+ *                       pair of linked samples arrives exactly once -- and feeds each block's unsorted list to add_cells.  No
+ *                       sort, no download.  min_jaccard outside (0, 1), NaN included: MVS_E_INVALID.  Never fails because the
+ *                       result is dense: the staging buffer holds option cluster_cells cells (default: a quarter of the free
+ *                       device memory, at most 2^30 cells or what the block can produce); a block that reports more is halved
+ *                       on a multiple of 256 rows and redone, a block of 256 rows grows the buffer instead.  Option
+ *                       cluster_block_rows bounds the rows of a block (default: pairwise_block_cells / n).
+ * mvs_cluster_finish    flattens the forest and writes the arrays (`mem_out` says where all four live; any pointer may be NULL;
+ *                       representatives and sizes need room for n entries, *n_clusters of them are written).  norms_sq: n
+ *                       doubles, read for the representatives.  More cells may be added afterwards and finish called again.
+ * mvs_ctx_cluster_stats since the context's last mvs_cluster_create: time of the comparison kernels and of the union-find
+ *                       kernels (hook + flatten + verify + finish; both 0 unless mvs_ctx_set_timing is on), cells with
+ *                       row != col consumed, row blocks of mvs_pairwise_cluster, the most hook -> flatten -> verify rounds any
+ *                       list needed.  Any pointer may be NULL.
+ * All synchronous. */
+typedef struct mvs_cluster mvs_cluster;
+int mvs_cluster_create(mvs_ctx* ctx, int64_t n, mvs_cluster** cluster);
+int mvs_cluster_add_cells(mvs_cluster* cluster, const mvs_cell* d_cells, int64_t n_cells);
+int mvs_pairwise_cluster(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double min_jaccard,
+                         mvs_cluster* cluster);
+int mvs_cluster_finish(mvs_cluster* cluster, const double* norms_sq, int mem_norms, int32_t* labels, int32_t* degree,
+                       int32_t* representatives, int32_t* sizes, int mem_out, int64_t* n_clusters);
+int mvs_cluster_destroy(mvs_cluster* cluster);
+int mvs_ctx_cluster_stats(const mvs_ctx* ctx, double* compare_ms, double* union_ms, int64_t* edges, int64_t* row_blocks,
+                          int64_t* rounds);
 
 /* ---- block plans: one rank's share of the symmetric multi-rank schedule, compared in few launches ----------------
  * The reference shards by rows and lets every shard process compute its rows against ALL columns

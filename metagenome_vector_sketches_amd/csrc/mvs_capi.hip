@@ -197,6 +197,8 @@ const OptionSpec kOptions[] = {
     {"stream_copy", &mvs::Options::stream_copy, nullptr, 0, 1},
     {"topk_dots", &mvs::Options::topk_dots, nullptr, 0, 1},
     {"topk_block_rows", &mvs::Options::topk_block_rows, nullptr, 0, 1 << 30},
+    {"cluster_cells", &mvs::Options::cluster_cells, nullptr, 0, 1 << 30},
+    {"cluster_block_rows", &mvs::Options::cluster_block_rows, nullptr, 0, 1 << 30},
     {"pairwise_block_cells", nullptr, &mvs::Options::pairwise_block_cells, 1, (1LL << 62)},
 };
 

@@ -1,0 +1,285 @@
+// mvs_capi_cluster.hip -- C ABI of the single-linkage clustering: mvs_cluster_create / _add_cells / _finish / _destroy (a
+// consumer of DEVICE cell lists, whoever produced them), mvs_pairwise_cluster (the one-call producer: the threshold comparison
+// of a sketch set, row block by row block, each block's unsorted cells fed straight into the consumer) and
+// mvs_ctx_cluster_stats.  The kernels and the argument for their exactness are in mvs_cluster.hip.  No cell crosses the link:
+// what comes back is four int32 arrays.
+#include "mvs_capi_internal.h"
+
+#include <hip/hip_runtime.h>
+
+using namespace mvs_capi;
+
+struct mvs_cluster {
+    mvs_ctx* ctx = nullptr;
+    int64_t n = 0;
+    int32_t* parent = nullptr;              // the forest: parent[x] <= x
+    int32_t* degree = nullptr;
+    unsigned long long* counters = nullptr;  // mvs_cluster.hip: edges, cells out of range, cells whose endpoints are apart
+};
+
+namespace {
+
+constexpr int kMaxRounds = 64;   // hook -> flatten -> verify rounds per list before the call gives up (one is the normal case)
+
+struct EventPair {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~EventPair() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
+// the union-find rounds over one device list; the list is consumed when this returns
+int consume_cells(mvs_cluster* k, const mvs_cell* d_cells, int64_t n_cells) {
+    mvs_ctx* c = k->ctx;
+    if (n_cells == 0) return MVS_OK;
+    EventPair ev;
+    if (c->timing) {
+        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    }
+    HIP_TRY(hipMemsetAsync(k->counters, 0, 3 * sizeof(unsigned long long), c->stream));
+    unsigned long long back[3] = {0, 0, 0};
+    int round = 0;
+    for (;;) {
+        ++round;
+        int rc = mvs::launch_cluster_hook(c->stream, d_cells, n_cells, k->parent, k->degree, k->n, round == 1, k->counters);
+        if (!rc) rc = check_kernel("k_cluster_hook");
+        if (rc) return rc;
+        rc = mvs::launch_cluster_flatten(c->stream, k->parent, k->n);
+        if (!rc) rc = check_kernel("k_cluster_flatten");
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(k->counters + 2, 0, sizeof(unsigned long long), c->stream));
+        rc = mvs::launch_cluster_verify(c->stream, d_cells, n_cells, k->parent, k->n, k->counters);
+        if (!rc) rc = check_kernel("k_cluster_verify");
+        if (rc) return rc;
+        rc = read_back(c, c->stream, {{back, k->counters, sizeof(back)}});
+        if (rc) return rc;
+        if (back[1] != 0) break;
+        if (back[2] == 0) break;
+        if (round >= kMaxRounds)
+            return fail(MVS_E_HIP, "internal: %llu cells still join different trees after %d union-find rounds", back[2], round);
+    }
+    if (c->timing) {
+        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+        HIP_TRY(hipEventSynchronize(ev.e[1]));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        c->cl_union_ms += ms;
+    }
+    c->cl_edges += (long long)back[0];
+    c->cl_rounds = std::max<long long>(c->cl_rounds, round);
+    if (back[1] != 0)
+        return fail(MVS_E_RANGE, "%llu cells name a sample outside [0, %lld): they were ignored", back[1], (long long)k->n);
+    return MVS_OK;
+}
+
+template <typename T>
+int give_out(mvs_ctx* c, T* dst, const void* d_src, int64_t count, int mem_out) {
+    if (!dst || count <= 0) return MVS_OK;
+    HIP_TRY(hipMemcpyAsync(dst, d_src, (size_t)count * sizeof(T), mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                           c->stream));
+    return MVS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvs_cluster_create(mvs_ctx* c, int64_t n, mvs_cluster** out) {
+    if (!c || !out) return fail(MVS_E_INVALID, "NULL argument");
+    *out = nullptr;
+    if (n < 0) return fail(MVS_E_INVALID, "n = %lld is negative", (long long)n);
+    if (n >= (1LL << 31) - 256) return fail(MVS_E_RANGE, "n too large for int32 sample indices");
+    HIP_TRY(hipSetDevice(c->device));
+    mvs_cluster* k = new (std::nothrow) mvs_cluster();
+    if (!k) return fail(MVS_E_NOMEM, "out of host memory");
+    k->ctx = c;
+    k->n = n;
+    const size_t words = (size_t)std::max<int64_t>(n, 1);
+    if (hipMalloc((void**)&k->parent, words * 4) != hipSuccess || hipMalloc((void**)&k->degree, words * 4) != hipSuccess ||
+        hipMalloc((void**)&k->counters, 64) != hipSuccess) {
+        mvs_cluster_destroy(k);
+        return fail(MVS_E_NOMEM, "hipMalloc of the forest of %lld samples failed", (long long)n);
+    }
+    int rc = mvs::launch_cluster_init(c->stream, k->parent, k->degree, n);
+    if (!rc) rc = check_kernel("k_cluster_init");
+    if (rc) {
+        mvs_cluster_destroy(k);
+        return rc;
+    }
+    c->cl_compare_ms = c->cl_union_ms = 0.0;
+    c->cl_edges = c->cl_blocks = c->cl_rounds = 0;
+    *out = k;
+    return MVS_OK;
+}
+
+int mvs_cluster_add_cells(mvs_cluster* k, const mvs_cell* d_cells, int64_t n_cells) {
+    if (!k) return fail(MVS_E_INVALID, "NULL cluster");
+    if (n_cells < 0 || (n_cells > 0 && !d_cells)) return fail(MVS_E_INVALID, "bad cell list");
+    HIP_TRY(hipSetDevice(k->ctx->device));
+    const Range range(k->ctx, "mvs_cluster_add_cells");
+    return consume_cells(k, d_cells, n_cells);
+}
+
+int mvs_pairwise_cluster(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int mem_norms, double min_jaccard,
+                         mvs_cluster* k) {
+    if (!c || !s || !k) return fail(MVS_E_INVALID, "NULL argument");
+    if (!(min_jaccard > 0.0) || !(min_jaccard < 1.0)) return fail(MVS_E_INVALID, "min_jaccard = %g outside (0, 1)", min_jaccard);
+    if (!mem_ok(mem_norms)) return fail(MVS_E_INVALID, "bad argument");
+    if (k->ctx != c) return fail(MVS_E_INVALID, "the cluster belongs to another context");
+    if (k->n != s->n) return fail(MVS_E_INVALID, "the cluster holds %lld samples, the sketch set %lld", (long long)k->n, (long long)s->n);
+    const int64_t n = s->n;
+    if (n == 0) return MVS_OK;
+    if (!norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
+    const Range range(c, "mvs_pairwise_cluster");
+    HIP_TRY(hipSetDevice(c->device));
+
+    DevBuf dn;
+    const double* d_n2 = norms_sq;
+    if (mem_norms == MVS_MEM_HOST) {
+        HIP_TRY(dn.alloc((size_t)n * 8));
+        HIP_TRY(hipMemcpyAsync(dn.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        d_n2 = (const double*)dn.p;
+    }
+    // J > t  <=>  double(P)/d > t/(1+t) * (n2r + n2c): mvs_search_block's coefficient
+    const double coeff = min_jaccard / (1.0 + min_jaccard);
+    // rows per block: the bound mvs_pairwise_rows puts on its chunks (borders on multiples of 256 rows: the symmetric schedule)
+    int64_t R = (int64_t)(c->opt.pairwise_block_cells / (double)n);
+    R = std::max<int64_t>(256, R / 256 * 256);
+    if (c->opt.cluster_block_rows > 0) R = std::min<int64_t>(R, std::max<int64_t>(256, (int64_t)c->opt.cluster_block_rows / 256 * 256));
+    // the staging buffer: a fixed share of the free memory, never more than the first block can produce
+    int64_t capacity = c->opt.cluster_cells;
+    if (capacity <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const size_t have = free_b + c->pw_tmp_bytes;               // (the buffer below is the context's own, counted as free)
+        capacity = (int64_t)std::min<size_t>(std::max<size_t>(4096, have / 4 / sizeof(mvs_cell)), (size_t)1 << 30);   // (the option's range)
+        const double block = (double)std::min(R, n) * (double)n;
+        if (block < (double)capacity) capacity = (int64_t)block;
+    }
+    capacity = std::max<int64_t>(capacity, 1);
+    int rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)capacity * sizeof(mvs_cell));
+    if (rc) return rc;
+    for (int64_t rb = 0; rb < n;) {
+        const int64_t re = std::min(n, rb + R);
+        unsigned long long count = 0;
+        rc = pairwise_launch(c, s, d_n2, MVS_KEEP_INT16, rb, re, 0, n, true, false, (mvs_cell*)c->pw_tmp, capacity, 0, &count, coeff);
+        if (rc) return rc;
+        if (count == ~0ULL) {
+            rc = read_back(c, c->stream, {{&count, c->d_counter, 8}});
+            if (rc) return rc;
+        }
+        if (c->timing && c->ev_valid[1]) {
+            float ms = 0.f;
+            if (mvs_ctx_kernel_ms(c, 1, &ms) == MVS_OK) c->cl_compare_ms += ms;
+        }
+        if ((int64_t)count > capacity) {
+            // a dense block: the list was cut off at the buffer's end.  Half the rows and again; a block of 256 rows cannot
+            // shrink (the symmetric schedule's granule), so there the buffer takes what the block was seen to need.
+            if (re - rb > 256) {
+                R = std::max<int64_t>(256, ((re - rb) / 2 + 255) / 256 * 256);
+                continue;
+            }
+            capacity = (int64_t)count;
+            rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)capacity * sizeof(mvs_cell));
+            if (rc) return rc;
+            continue;
+        }
+        rc = consume_cells(k, (const mvs_cell*)c->pw_tmp, (int64_t)count);
+        if (rc) return rc;
+        ++c->cl_blocks;
+        rb = re;
+    }
+    return MVS_OK;
+}
+
+int mvs_cluster_finish(mvs_cluster* k, const double* norms_sq, int mem_norms, int32_t* labels, int32_t* degree,
+                       int32_t* representatives, int32_t* sizes, int mem_out, int64_t* n_clusters) {
+    if (!k) return fail(MVS_E_INVALID, "NULL cluster");
+    if (!mem_ok(mem_norms) || !mem_ok(mem_out)) return fail(MVS_E_INVALID, "bad argument");
+    if (n_clusters) *n_clusters = 0;
+    mvs_ctx* c = k->ctx;
+    const int64_t n = k->n;
+    if (n == 0) return MVS_OK;
+    if (!norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    const Range range(c, "mvs_cluster_finish");
+    DevBuf dn, dwork, dbest, dscan;
+    const double* d_n2 = norms_sq;
+    if (mem_norms == MVS_MEM_HOST) {
+        HIP_TRY(dn.alloc((size_t)n * 8));
+        HIP_TRY(hipMemcpyAsync(dn.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        d_n2 = (const double*)dn.p;
+    }
+    // is_root, ids (n + 1 each), labels, sizes, representatives (n each)
+    const size_t np1 = ((size_t)n + 1 + 63) / 64 * 64;
+    HIP_TRY(dwork.alloc(5 * np1 * 4));
+    HIP_TRY(dbest.alloc((size_t)n * 8));
+    int32_t* d_is_root = (int32_t*)dwork.p;
+    int32_t* d_ids = d_is_root + np1;
+    int32_t* d_labels = d_ids + np1;
+    int32_t* d_sizes = d_labels + np1;
+    int32_t* d_rep = d_sizes + np1;
+    size_t need = 0;
+    int rc = mvs::cluster_finish(c->stream, k->parent, d_n2, n, d_is_root, d_ids, d_labels, d_sizes, d_rep, (unsigned long long*)dbest.p,
+                                 nullptr, 0, &need);
+    if (rc) return fail(rc, "cluster finish: scan sizing failed");
+    HIP_TRY(dscan.alloc(need));
+    EventPair ev;
+    if (c->timing) {
+        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    }
+    rc = mvs::launch_cluster_flatten(c->stream, k->parent, n);
+    if (!rc) rc = check_kernel("k_cluster_flatten");
+    if (rc) return rc;
+    rc = mvs::cluster_finish(c->stream, k->parent, d_n2, n, d_is_root, d_ids, d_labels, d_sizes, d_rep, (unsigned long long*)dbest.p,
+                             dscan.p, need, nullptr);
+    if (rc) return fail(rc, "cluster finish failed");
+    rc = check_kernel("k_cluster_label");
+    if (rc) return rc;
+    if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    int32_t total = 0;
+    rc = read_back(c, c->stream, {{&total, d_ids + n, 4}});
+    if (rc) return rc;
+    if (c->timing) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        c->cl_union_ms += ms;
+    }
+    if (n_clusters) *n_clusters = total;
+    rc = give_out(c, labels, d_labels, n, mem_out);
+    if (!rc) rc = give_out(c, degree, k->degree, n, mem_out);
+    if (!rc) rc = give_out(c, representatives, d_rep, total, mem_out);
+    if (!rc) rc = give_out(c, sizes, d_sizes, total, mem_out);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (also before the DevBufs free the scratch)
+    return MVS_OK;
+}
+
+int mvs_cluster_destroy(mvs_cluster* k) {
+    if (!k) return MVS_OK;
+    if (k->ctx) {
+        (void)hipSetDevice(k->ctx->device);
+        (void)hipStreamSynchronize(k->ctx->stream);
+    }
+    if (k->parent) (void)hipFree(k->parent);
+    if (k->degree) (void)hipFree(k->degree);
+    if (k->counters) (void)hipFree(k->counters);
+    delete k;
+    return MVS_OK;
+}
+
+int mvs_ctx_cluster_stats(const mvs_ctx* c, double* compare_ms, double* union_ms, int64_t* edges, int64_t* row_blocks,
+                          int64_t* rounds) {
+    if (!c) return fail(MVS_E_INVALID, "NULL context");
+    if (compare_ms) *compare_ms = c->cl_compare_ms;
+    if (union_ms) *union_ms = c->cl_union_ms;
+    if (edges) *edges = c->cl_edges;
+    if (row_blocks) *row_blocks = c->cl_blocks;
+    if (rounds) *rounds = c->cl_rounds;
+    return MVS_OK;
+}
+
+}  // extern "C"

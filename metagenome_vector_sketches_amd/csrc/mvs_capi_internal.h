@@ -146,6 +146,9 @@ struct mvs_ctx {
     // what the last mvs_pairwise_topk did (mvs_ctx_topk_stats): kernel times summed over its row blocks (timing enabled)
     double tk_dots_ms = 0.0, tk_select_ms = 0.0;
     long long tk_blocks = 0, tk_block_rows = 0;
+    // what the clustering calls did since the last mvs_cluster_create on this context (mvs_ctx_cluster_stats)
+    double cl_compare_ms = 0.0, cl_union_ms = 0.0;
+    long long cl_edges = 0, cl_blocks = 0, cl_rounds = 0;
 };
 
 struct mvs_sketch_set {

@@ -104,6 +104,9 @@ struct Options {
     int topk_dots = 0;              // mvs_pairwise_topk: dots of a row block from 0 = the matrix-core kernels (launch_pairwise algo 0),
                                     // 1 = the vector-ALU kernel (A/B, tests); same selection, same result
     int topk_block_rows = 0;        // mvs_pairwise_topk: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
+    int cluster_cells = 0;          // mvs_pairwise_cluster: cells the staging buffer of a row block holds; 0 = a quarter of the free
+                                    // device memory (never more than the block can produce); tests lower it
+    int cluster_block_rows = 0;     // mvs_pairwise_cluster: > 0 = upper bound on the rows of a block (tests); 0 = by pairwise_block_cells
     double pairwise_block_cells = 1099511627776.0;   // row-chunk bound of mvs_pairwise_rows (2^40 cells)
 };
 
@@ -261,6 +264,18 @@ int launch_topk_select(hipStream_t stream, const int32_t* d_dots, int64_t rows, 
                        int64_t out_row0);
 int launch_topk_compact(hipStream_t stream, const mvs_cell* d_pad, const int* d_counts, const int64_t* d_offs, int64_t rows,
                         int k, mvs_cell* d_out);
+// single-linkage clustering over device cell lists (mvs_cluster.hip): union-find rounds over parent[n] -- d_counters: [0] cells
+// with row != col, [1] cells with an index outside [0, n), [2] cells whose endpoints still have different roots -- and the
+// finish passes (cluster ids by ascending root, sizes, representatives)
+int launch_cluster_init(hipStream_t stream, int32_t* d_parent, int32_t* d_degree, int64_t n);
+int launch_cluster_hook(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, int32_t* d_parent, int32_t* d_degree, int64_t n,
+                        bool first, unsigned long long* d_counters);
+int launch_cluster_flatten(hipStream_t stream, int32_t* d_parent, int64_t n);
+int launch_cluster_verify(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_parent, int64_t n,
+                          unsigned long long* d_counters);
+int cluster_finish(hipStream_t stream, const int32_t* d_parent, const double* d_norms_sq, int64_t n, int32_t* d_is_root, int32_t* d_ids,
+                   int32_t* d_labels, int32_t* d_sizes, int32_t* d_rep, unsigned long long* d_best, void* d_scratch,
+                   size_t scratch_bytes, size_t* scratch_needed);
 // two-stage comparison for two base-256 limbs: coarse plane + row statistics from the limb planes,
 // per-call filter constants, the one-pass filter
 // that appends candidate pairs, and the exact re-check of the candidates that appends kept cells
