@@ -107,6 +107,10 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *                         first splitmix64 round, deep carry-save tree, VALU-only epilogue, when d is a multiple of 256
  *                         (>= 512), else 2 or 1 blocks per wave; 1 / 2 / 12 / 14 / 24 force a variant (14 = 24 with
  *                         the ripple every 32 hashes and the ds_bpermute epilogue)
+ *   project_balance       1 (default): the projection cuts the units of work that would end behind the launch's ideal end
+ *                         -- the last partial round of workgroups, a long sample late in the list, every sample of a launch
+ *                         too small to fill the device -- into pieces that fill the idle workgroup slots
+ *                         (mvs_project_plan); 0: samples are cut at 65536 hashes only
  *   stream_dense          mvs_pairwise_stream, dense results: 1 (default) one byte per cell in a matrix, a row block turned
  *                         into CSR / encoded rows on a side stream beside the next block's launch where the exact kernel
  *                         does whole row blocks, on the context's stream where the two-stage comparison feeds the matrix;
@@ -201,14 +205,44 @@ int mvs_event_destroy(mvs_event* event);
 int mvs_project_csr(mvs_ctx* ctx, const uint64_t* hashes, int mem_hashes, const int64_t* offsets,
                     int64_t n_samples, int d, int32_t* out, int mem_out);
 
-/* mvs_project_csr plus the two statistics the next stages need, produced by the same kernel when every
- * sample holds <= 65536 hashes (otherwise by one extra pass): sumsq[s] = exact sum of squares of sketch s
+/* mvs_project_csr plus the two statistics the next stages need, produced by the same kernel for every sample
+ * that is one unit of work (the others -- longer than 65536 hashes, or cut by the planner below -- by one extra pass
+ * over their rows alone): sumsq[s] = exact sum of squares of sketch s
  * (int64[n_samples], in the same memory space as `out`: device array for device sketches, host array for host
  * sketches) and *max_abs = largest |v| (host; decides the limb code).  Synchronous.
  * Host hash lists beyond 32 MiB travel through two pinned staging buffers: the host-side copy, the DMA and the
  * projection of the samples already complete overlap (measured: 1.07 x the bare PCIe time of the same bytes). */
 int mvs_project_csr_stats(mvs_ctx* ctx, const uint64_t* hashes, int mem_hashes, const int64_t* offsets,
                           int64_t n_samples, int d, int32_t* out, int mem_out, int64_t* sumsq, int64_t* max_abs);
+
+/* The units of work a projection launch consists of, without a device: how mvs_project_csr would lay out the samples of
+ * `offsets` (n_samples + 1 entries) for a kernel variant that takes `ny` workgroups per unit on a device that holds
+ * `slots` of its workgroups at a time (compute units x occupancy; the library asks the runtime).  A unit is a run of
+ * at most 65536 hashes of one sample; `single` = 1: it is the whole sample (plain stores, statistics inside the
+ * kernel), 0: its sample consists of several units that combine with int32 atomics.  The units of a sample tile it
+ * in order; an empty sample has one unit of zero hashes.  balance != 0: units that would end behind the ideal end of
+ * the launch (total work / slots) under in-order dispatch are cut into pieces that fill the slots which would idle.
+ * Each piece is sized when its turn comes, from what still fits in front of the ideal end: a multiple of 2048 hashes,
+ * at least 4096, so the pieces of a unit need not be equal; the last piece takes what is left of the unit (any
+ * remainder of 2048 hashes or more; a smaller one is added to the piece before it).  A workgroup is taken to cost its
+ * hashes + `overhead` hash-times (< 0: the library's constant).  The model is described where it is implemented
+ * (csrc/mvs_capi_sketch.hip, "projection units").  balance == 0 or slots <= 0: samples are cut at 65536 hashes only.
+ * flags bit 0: the 512 hashes behind the unit's last full batch of 512 are not all inside [0, offsets[n_samples]).
+ * Writes at most `capacity` units and returns the number the plan has in *n_units (units may be NULL when capacity is 0).
+ * Pure host code. */
+typedef struct mvs_proj_unit {
+    int64_t begin;   /* index of the unit's first hash */
+    int32_t count;   /* hashes in the unit */
+    int32_t sample;  /* output row */
+    int32_t single;
+    int32_t flags;
+} mvs_proj_unit;
+int mvs_project_plan(const int64_t* offsets, int64_t n_samples, int ny, int slots, int overhead, int balance,
+                     mvs_proj_unit* units, int64_t capacity, int64_t* n_units);
+/* What the context's most recent mvs_project_csr[_stats] launched: the units of its list, the samples among them that
+ * consist of several units, and the `slots` and `ny` its plan was made with (slots = 0: no balancing -- option
+ * project_balance 0, or the pipelined upload of a large host hash list).  Any pointer may be NULL. */
+int mvs_ctx_project_stats(const mvs_ctx* ctx, int64_t* n_units, int64_t* cut_samples, int* slots, int* ny);
 
 /* Sum of squares of each sketch (exact int64): the integer the norm of
  * src/project_everything.cpp:328-329 is derived from (norm = sqrt(sumsq / d)). */

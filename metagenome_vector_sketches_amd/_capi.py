@@ -65,6 +65,10 @@ SYMBOLS = [
     ("mvs_project_csr", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int64, _c.c_int, _P, _c.c_int]),
     ("mvs_project_csr_stats", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int64, _c.c_int, _P, _c.c_int, _P,
                                           _c.POINTER(_c.c_int64)]),
+    ("mvs_project_plan", _c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int64,
+                                     _c.POINTER(_c.c_int64)]),
+    ("mvs_ctx_project_stats", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int),
+                                          _c.POINTER(_c.c_int)]),
     ("mvs_sketch_sumsq", _c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_int]),
     ("mvs_sketch_stats", _c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_int64)]),
     ("mvs_norms_sq_text", _c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P]),
@@ -515,6 +519,13 @@ class Context:
         return a.value, b.value, t.value
 
     # ---- projection ----
+    def project_stats(self):
+        """(units, cut_samples, slots, ny) of the last projection: the units of work it launched, the samples that consist of
+        several of them, and the resident workgroups / workgroups per unit its plan was made with (slots 0: not balanced)"""
+        u, k, s, y = _c.c_int64(), _c.c_int64(), _c.c_int(), _c.c_int()
+        _check(self.lib.mvs_ctx_project_stats(self._h, ctypes.byref(u), ctypes.byref(k), ctypes.byref(s), ctypes.byref(y)))
+        return u.value, k.value, s.value, y.value
+
     def project_csr(self, hashes, offsets, d, out=None):
         """hashes: uint64 numpy array or torch CUDA tensor (int64 view of the bits is accepted);
         offsets: host int64 array (n_samples+1).  Returns out (numpy unless `out` is given)."""
@@ -532,8 +543,8 @@ class Context:
 
     def project_csr_stats(self, hashes, offsets, d, out, sumsq):
         """project_csr into the device tensor `out`, filling the device int64 tensor `sumsq` with the exact
-        sums of squares; returns the largest |v| (fused into the projection kernel when every sample is
-        a single unit)."""
+        sums of squares; returns the largest |v| (fused into the projection kernel for every sample that is
+        a single unit of work; one pass over the rows of the others)."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(offsets) - 1
         hp, hm, hk = _buf(hashes) if _is_torch(hashes) else _buf(hashes, np.uint64)
@@ -998,6 +1009,20 @@ def shard_layout(n_total, world):
     a, b = _c.c_int64(), _c.c_int64()
     _check(load_library().mvs_shard_layout(int(n_total), int(world), ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
+
+
+PROJ_UNIT_DTYPE = np.dtype([("begin", "<i8"), ("count", "<i4"), ("sample", "<i4"), ("single", "<i4"), ("flags", "<i4")])
+
+
+def project_plan(offsets, ny, slots, balance=True, overhead=-1):
+    """mvs_project_plan: the projection's units of work for the samples of `offsets` (structured array, PROJ_UNIT_DTYPE)"""
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    lib, n = load_library(), _c.c_int64()
+    args = (off.ctypes.data, len(off) - 1, int(ny), int(slots), int(overhead), int(bool(balance)))
+    _check(lib.mvs_project_plan(*args, None, 0, ctypes.byref(n)))
+    units = np.empty(n.value, dtype=PROJ_UNIT_DTYPE)
+    _check(lib.mvs_project_plan(*args, units.ctypes.data, len(units), ctypes.byref(n)))
+    return units
 
 
 def shard_rows(n, num_shards, shard_idx):

@@ -171,6 +171,7 @@ const OptionSpec kOptions[] = {
     {"enable_k3", &mvs::Options::enable_k3, nullptr, 0, 1},
     {"markers", &mvs::Options::markers, nullptr, 0, 1},
     {"project_variant", &mvs::Options::project_variant, nullptr, 0, 24},
+    {"project_balance", &mvs::Options::project_balance, nullptr, 0, 1},
     {"comm_timeout_s", &mvs::Options::comm_timeout_s, nullptr, 1, 86400},
     {"pairwise_map", &mvs::Options::pairwise_map, nullptr, 0, 2},
     {"coarse_radix", &mvs::Options::coarse_radix, nullptr, 0, 1},
@@ -306,6 +307,7 @@ int mvs_ctx_create(int device, mvs_ctx** out) {
     mvs_ctx* c = new (std::nothrow) mvs_ctx();
     if (!c) return fail(MVS_E_NOMEM, "out of host memory");
     c->device = device;
+    c->cu_count = prop.multiProcessorCount;
 #ifdef MVS_ABLATIONS
     // The profiling build compiles the ping-pong kernels with extra code (time stamps, injected candidates), and with it
     // hipcc no longer keeps the fragment registers of the direct-B loop's hand-counted loads untouched: measured in round 5,

@@ -130,6 +130,13 @@ struct mvs_ctx {
     size_t up_bytes = 0;
     hipStream_t up_stream = nullptr;
     hipEvent_t up_done[2] = {nullptr, nullptr};   // DMA out of staging buffer i has completed
+    // workgroups of k_project the device holds at a time, by [variant][statistics]: CUs x the occupancy of that instantiation,
+    // asked for once (0: not yet) -- what mvs_project_plan balances a launch's last round against
+    int cu_count = 0;
+    int proj_slots[25][2] = {};
+    // what the last projection launched (mvs_ctx_project_stats)
+    long long pj_units = 0, pj_cut_samples = 0;
+    int pj_slots = 0, pj_ny = 0;
     // pinned host staging for small metadata uploads (projection unit lists)
     void* pinned = nullptr;
     size_t pinned_bytes = 0;

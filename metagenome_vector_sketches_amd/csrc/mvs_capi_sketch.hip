@@ -3,7 +3,211 @@
 
 using namespace mvs_capi;
 
+namespace mvs_capi {
+
+// -------------------------------------------------------------------------------------------------
+// projection units
+// -------------------------------------------------------------------------------------------------
+// k_project runs one workgroup per (unit, group of 4 * BPW blocks), all of a launch's workgroups about equally long when the
+// samples are, and the device holds `slots` of them at a time: 20 000 workgroups on 512 slots are 39.06 rounds, 40 are paid,
+// and in the last one 480 slots idle.  The planner cuts the units that would end behind the launch's ideal end -- the last
+// partial round, a long sample late in a ragged list, every unit of a launch too small to fill the slots -- into pieces
+// that fit in front of it.
+//
+// Model: a workgroup of a unit of `count` hashes costs count + kProjOverhead hash-times (the overhead is the counters'
+// cross-lane reduction, the masked tail batch and the start of the workgroup), and workgroups start in list order, each on
+// the slot that frees first.  That greedy dispatch is followed exactly but in time quanta, so that the free times of the
+// slots are a histogram and the earliest one a cursor that only moves forward: O(workgroups + buckets), no heap.  Before
+// a unit is placed, the ideal end of the launch is (work placed so far + parent cost of the rest) / slots; a unit
+// whose last workgroup starts at `start` and would end more than one overhead behind the ideal end is cut into pieces of
+// at most ideal end - start each, in multiples of one main-loop iteration of the kernel and never below kProjPieceMin.
+constexpr int kProjOverhead = 2000;    // hash-times per workgroup that do not depend on its hashes (LABNOTES, round 8)
+constexpr int kProjPieceStep = 2048;   // one iteration of the kernel's main loop: 4 batches of 512 hashes
+constexpr int kProjPieceMin = 4096;    // shortest piece: below two iterations the overhead passes a third of a piece's time
+constexpr int64_t kProjBuckets = 1 << 16;
+
+struct RowRange {
+    int64_t lo, hi;
+};
+
+// Writes the unit list of (offsets, n_samples) to dst[0 .. cap) and returns in *n_units how many units it has -- when that
+// is more than cap, the caller repeats the call with room for all.  cut_rows (may be NULL) receives the ranges of samples
+// that consist of several units, in order.
+int plan_project_units(const int64_t* offsets, int64_t n_samples, int ny, int slots, int overhead, bool balance,
+                       mvs::ProjUnit* dst, size_t cap, size_t* n_units, std::vector<RowRange>* cut_rows) {
+    constexpr int64_t kMax = mvs::kProjUnitMax;
+    const int64_t E = overhead;
+    const int64_t total_end = offsets[n_samples];
+    balance = balance && slots > 0 && ny > 0 && total_end >= offsets[0];
+    // greedy list scheduling makes a launch at most (work / slots + longest workgroup) long; twice that leaves room for the
+    // overheads of the pieces.  Free times that would still pass the last bucket stay in it.
+    int qs = 0;                                  // the time quantum is 2^qs hash-times
+    int64_t nb = 0;
+    if (balance) {
+        const int64_t span = total_end - offsets[0], most_units = n_samples + span / kMax;
+        const int64_t horizon = 2 * ((span + most_units * E) / slots * ny + ny * (kMax + E) + 1);
+        while ((horizon >> qs) > kProjBuckets) ++qs;
+        nb = (horizon >> qs) + 2;
+    }
+    const int64_t round_up = ((int64_t)1 << qs) - 1;
+    auto cost = [&](int64_t count) { return (count + E + round_up) >> qs; };
+    int64_t rest = 0;                            // parent cost of the units not yet placed: quanta x workgroups
+    for (int64_t s = 0; s < n_samples; ++s) {
+        const int64_t b = offsets[s], e = offsets[s + 1], len = e - b;
+        if (e < b) return fail(MVS_E_INVALID, "offsets not monotone at sample %lld", (long long)s);
+        if (len >= (1LL << 31)) return fail(MVS_E_RANGE, "sample %lld has >= 2^31 hashes", (long long)s);
+        // (an empty sample gets one unit of zero hashes: the kernel then stores its row of zeros itself)
+        rest += len <= kMax ? cost(len) : (len / kMax) * cost(kMax) + (len % kMax ? cost(len % kMax) : 0);
+    }
+    rest *= ny;
+    if (cut_rows) cut_rows->clear();
+    size_t w = 0;
+    auto put = [&](int64_t begin, int64_t count, int64_t s, bool single) {
+        if (w < cap) {
+            mvs::ProjUnit u{begin, (int32_t)count, (int32_t)s, single ? 1 : 0, 0};
+            if (begin + (((count >> 9) + 1) << 9) > total_end) u.flags = mvs::kProjTailGuard;
+            dst[w] = u;
+        }
+        ++w;
+    };
+    auto note_cut = [&](int64_t s) {
+        if (!cut_rows) return;
+        if (!cut_rows->empty() && cut_rows->back().hi == s) cut_rows->back().hi = s + 1;
+        else cut_rows->push_back(RowRange{s, s + 1});
+    };
+    if (!balance) {   // samples cut at kProjUnitMax only
+        for (int64_t s = 0; s < n_samples; ++s) {
+            const int64_t b = offsets[s], e = offsets[s + 1];
+            const bool single = (e - b) <= kMax;
+            if (e == b) put(b, 0, s, true);
+            for (int64_t p = b; p < e; p += kMax) put(p, std::min<int64_t>(kMax, e - p), s, single);
+            if (!single) note_cut(s);
+        }
+        *n_units = w;
+        return MVS_OK;
+    }
+
+    thread_local std::vector<int32_t> free_buckets;
+    free_buckets.assign((size_t)nb, 0);
+    int32_t* const free_at = free_buckets.data();   // slots that become free in each time bucket
+    free_at[0] = slots;
+    int64_t placed = 0, cur = 0;                 // work placed; no slot becomes free before bucket `cur`
+    auto place = [&](int64_t c, int64_t m) {     // m workgroups of c quanta each, every one on the slot that frees first
+        placed += c * m;
+        while (m > 0) {
+            while (free_at[cur] == 0) ++cur;     // some slot is free at or after `cur`: the loop ends inside the array
+            const int64_t t = std::min<int64_t>(m, free_at[cur]);
+            free_at[cur] -= (int32_t)t;
+            free_at[std::min(cur + c, nb - 1)] += (int32_t)t;
+            m -= t;
+        }
+    };
+    // when the last of a unit's ny workgroups starts: the time the ny-th slot becomes free
+    const int need = std::min(ny, slots);
+    auto start_of_unit = [&]() {
+        while (free_at[cur] == 0) ++cur;
+        int64_t i = cur;
+        for (int have = free_at[i]; have < need; have += free_at[i]) ++i;
+        return i;
+    };
+    // the ideal end of the launch as it stands is `work` / slots, work = placed + parent cost of all that is not (`rest`
+    // does not change it while units go in whole): does a unit of c quanta that starts at `start` end within one overhead of it?
+    const int64_t slack = E >> qs;
+    auto fits = [&](int64_t start, int64_t c, int64_t work) { return (start + c - slack) * slots <= work; };
+    auto one_unit = [&](int64_t p, int64_t n, int64_t s, bool single) {
+        const int64_t c = cost(n);
+        if (n == 0 || fits(start_of_unit(), c, placed + rest)) {
+            put(p, n, s, single);
+            rest -= c * ny;
+            place(c, ny);
+            return;
+        }
+        // the unit would end behind the ideal end: pieces of what still fits in front of it, looked at again for every
+        // piece because each one takes slots the next finds gone
+        rest -= c * ny;
+        for (int64_t left = n; left > 0;) {
+            const int64_t ideal = (placed + rest + cost(left) * ny) / slots;
+            const int64_t room = ((ideal - start_of_unit()) << qs) - E;
+            const int64_t g = std::max<int64_t>(kProjPieceMin, room / kProjPieceStep * kProjPieceStep);
+            const int64_t pn = left - g < kProjPieceMin / 2 ? left : g;   // no crumb of a last piece
+            put(p, pn, s, single && pn == n);
+            place(cost(pn), ny);
+            if (single && pn != n && left == n) note_cut(s);
+            p += pn;
+            left -= pn;
+        }
+    };
+    for (int64_t s = 0; s < n_samples;) {
+        const int64_t b = offsets[s], len = offsets[s + 1] - b;
+        if (len > kMax) {
+            for (int64_t p = b; p < b + len; p += kMax) one_unit(p, std::min<int64_t>(kMax, b + len - p), s, false);
+            note_cut(s++);
+            continue;
+        }
+        // a run of samples of one length: those whose workgroups all start in the same bucket go in together
+        int64_t run = 1;
+        while (s + run < n_samples && offsets[s + run + 1] - offsets[s + run] == len) ++run;
+        const int64_t c = cost(len);
+        while (run > 0) {
+            while (free_at[cur] == 0) ++cur;
+            const int64_t m = std::min<int64_t>(free_at[cur] / ny, run);
+            if (m >= 1 && fits(cur, c, placed + rest)) {
+                for (int64_t i = 0; i < m; ++i) put(offsets[s + i], len, s + i, true);
+                rest -= c * ny * m;
+                place(c, ny * m);
+                s += m;
+                run -= m;
+            } else {
+                one_unit(offsets[s], len, s, true);
+                ++s;
+                --run;
+            }
+        }
+    }
+    *n_units = w;
+    return MVS_OK;
+}
+
+// workgroups of the projection kernel `variant` the device holds at a time; an error if the runtime will not say
+static int project_slots(mvs_ctx* c, int variant, bool stats, int* slots) {
+    int& have = c->proj_slots[variant][stats ? 1 : 0];
+    if (have == 0) {
+        const int per_cu = mvs::project_blocks_per_cu(variant, stats);
+        if (per_cu <= 0 || c->cu_count <= 0)
+            return fail(MVS_E_HIP, "occupancy query of k_project variant %d failed (%d workgroups per CU, %d CUs)", variant, per_cu,
+                        c->cu_count);
+        have = per_cu * c->cu_count;
+    }
+    *slots = have;
+    return MVS_OK;
+}
+
+}  // namespace mvs_capi
+
 extern "C" {
+
+int mvs_project_plan(const int64_t* offsets, int64_t n_samples, int ny, int slots, int overhead, int balance,
+                     mvs_proj_unit* units, int64_t capacity, int64_t* n_units) {
+    static_assert(sizeof(mvs_proj_unit) == sizeof(mvs::ProjUnit), "one layout");
+    if (!offsets || !n_units || n_samples < 0 || capacity < 0 || (capacity > 0 && !units) || ny < 1 || overhead > (1 << 20))
+        return fail(MVS_E_INVALID, "bad argument");
+    if (n_samples >= (1LL << 31)) return fail(MVS_E_RANGE, "too many samples");
+    size_t n = 0;
+    const int rc = plan_project_units(offsets, n_samples, ny, slots, overhead < 0 ? kProjOverhead : overhead, balance != 0,
+                                      reinterpret_cast<mvs::ProjUnit*>(units), (size_t)capacity, &n, nullptr);
+    if (rc) return rc;
+    *n_units = (int64_t)n;
+    return MVS_OK;
+}
+
+int mvs_ctx_project_stats(const mvs_ctx* c, int64_t* n_units, int64_t* cut_samples, int* slots, int* ny) {
+    if (!c) return fail(MVS_E_INVALID, "ctx is NULL");
+    if (n_units) *n_units = c->pj_units;
+    if (cut_samples) *cut_samples = c->pj_cut_samples;
+    if (slots) *slots = c->pj_slots;
+    if (ny) *ny = c->pj_ny;
+    return MVS_OK;
+}
 
 // -------------------------------------------------------------------------------------------------
 // projection
@@ -27,47 +231,59 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
     if (n_samples == 0) return MVS_OK;
     if (!offsets || !out) return fail(MVS_E_INVALID, "offsets/out is NULL");
     HIP_TRY(hipSetDevice(c->device));
-
-    // units: runs of <= kProjUnitMax hashes, written straight into pinned memory
     if (n_samples >= (1LL << 31)) return fail(MVS_E_RANGE, "too many samples");
-    size_t n_units = 0;
-    bool all_single = true;
-    for (int64_t s = 0; s < n_samples; ++s) {
-        const int64_t b = offsets[s], e = offsets[s + 1];
-        if (e < b) return fail(MVS_E_INVALID, "offsets not monotone at sample %lld", (long long)s);
-        if (e - b >= (1LL << 31)) return fail(MVS_E_RANGE, "sample %lld has >= 2^31 hashes", (long long)s);
-        // an empty sample gets one unit of zero hashes: the kernel then stores its row of zeros itself
-        n_units += e == b ? 1 : (size_t)((e - b + mvs::kProjUnitMax - 1) / mvs::kProjUnitMax);
-        all_single = all_single && (e - b) <= mvs::kProjUnitMax;
-    }
-    int rc = acquire_pinned(c, std::max<size_t>(n_units * sizeof(mvs::ProjUnit), 256));
+
+    const int nblk = (d + 63) / 64;
+    // kernel variant (launch_project): four blocks per wave sharing the first splitmix64 round, with the deep carry-save tree and
+    // the VALU epilogue, where the dimension fills them (variant 24; 14 measured 8.97 vs 9.44 ms for 2 on 10k x
+    // 50k hashes, d = 2048), else two or one block per wave; option project_variant forces one
+    int bpw = (nblk % 4 == 0 && nblk >= 8) ? 24 : (nblk >= 2 ? 2 : 1);
+    if (c->opt.project_variant == 24 && nblk >= 4) bpw = 24;
+    if (c->opt.project_variant == 14 && nblk >= 4) bpw = 14;
+    if (c->opt.project_variant == 12 && nblk >= 2) bpw = 12;
+    if (c->opt.project_variant == 2 && nblk >= 2) bpw = 2;
+    if (c->opt.project_variant == 1) bpw = 1;
+    const int ny = mvs::project_ny(bpw, d);
+
+    // Host hash lists larger than one staging piece go up through the two-buffer pipeline: while piece k is on the
+    // link, piece k+1 is being copied into pinned memory and the samples that piece k-1 completed are being projected.
+    // Its launches take the units in hash order as the pieces arrive, each far from filling the device's last round
+    // alone: that path keeps the list cut at kProjUnitMax only.
+    const bool pipelined = mem_hashes == MVS_MEM_HOST && offsets[n_samples] > 0 && (size_t)offsets[n_samples] * 8 > kUploadPiece;
+    const bool balance = c->opt.project_balance != 0 && !pipelined;
+    int slots = 0;
+    int rc = balance ? project_slots(c, bpw, sumsq != nullptr, &slots) : MVS_OK;
     if (rc) return rc;
-    mvs::ProjUnit* units = (mvs::ProjUnit*)c->pinned;
-    {
-        size_t w = 0;
-        for (int64_t s = 0; s < n_samples; ++s) {
-            const int64_t b = offsets[s], e = offsets[s + 1];
-            const bool single = (e - b) <= mvs::kProjUnitMax;
-            if (e == b) units[w++] = mvs::ProjUnit{b, 0, (int32_t)s, 1, 0};
-            for (int64_t p = b; p < e; p += mvs::kProjUnitMax) {
-                mvs::ProjUnit u;
-                u.begin = p;
-                u.count = (int32_t)std::min<int64_t>(mvs::kProjUnitMax, e - p);
-                u.sample = (int32_t)s;
-                u.single = single ? 1 : 0;
-                u.pad = 0;
-                units[w++] = u;
-            }
-        }
+
+    // units, written straight into pinned memory: the buffer as it stands holds the list of all but the first call of a size
+    rc = acquire_pinned(c, 256);
+    if (rc) return rc;
+    size_t n_units = 0;
+    thread_local std::vector<RowRange> cut_rows;   // samples of several units: combined with atomics, statistics afterwards
+    rc = plan_project_units(offsets, n_samples, ny, slots, kProjOverhead, balance, (mvs::ProjUnit*)c->pinned,
+                            c->pinned_bytes / sizeof(mvs::ProjUnit), &n_units, &cut_rows);
+    if (rc) return rc;
+    if (n_units * sizeof(mvs::ProjUnit) > c->pinned_bytes) {
+        rc = acquire_pinned(c, n_units * sizeof(mvs::ProjUnit));
+        if (rc) return rc;
+        rc = plan_project_units(offsets, n_samples, ny, slots, kProjOverhead, balance, (mvs::ProjUnit*)c->pinned,
+                                c->pinned_bytes / sizeof(mvs::ProjUnit), &n_units, &cut_rows);
+        if (rc) return rc;
     }
+    mvs::ProjUnit* units = (mvs::ProjUnit*)c->pinned;
+    // many scattered ranges (long samples all over a ragged list) are not worth a memset and a launch each: rows between
+    // them may be cleared before and measured again after the projection without changing anything
+    c->pj_units = (long long)n_units;
+    c->pj_cut_samples = 0;
+    for (const RowRange& r : cut_rows) c->pj_cut_samples += r.hi - r.lo;
+    c->pj_slots = slots;
+    c->pj_ny = ny;
+    if (cut_rows.size() > 16) cut_rows.assign(1, RowRange{cut_rows.front().lo, cut_rows.back().hi});
     const int64_t total = offsets[n_samples];
     if (total > 0 && !hashes) return fail(MVS_E_INVALID, "hashes is NULL");
 
     DevBuf dh, dout;
     const uint64_t* d_hashes = hashes;
-    // Host hash lists larger than one staging piece go up through the two-buffer pipeline: while piece k is on the
-    // link, piece k+1 is being copied into pinned memory and the samples that piece k-1 completed are being projected.
-    const bool pipelined = mem_hashes == MVS_MEM_HOST && (size_t)total * 8 > kUploadPiece;
     if (mem_hashes == MVS_MEM_HOST) {
         HIP_TRY(dh.alloc((size_t)total * 8));
         if (!pipelined) HIP_TRY(hipMemcpyAsync(dh.p, hashes, (size_t)total * 8, hipMemcpyHostToDevice, c->stream));
@@ -93,23 +309,16 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
     }
 
     // samples cut into several units are combined with atomics and start from zero; single units store
-    if (!all_single) HIP_TRY(hipMemsetAsync(d_out, 0, out_bytes, c->stream));
-    const bool fused = sumsq != nullptr && all_single;         // statistics inside the projection kernel
+    for (const RowRange& r : cut_rows)
+        HIP_TRY(hipMemsetAsync(d_out + r.lo * (int64_t)d, 0, (size_t)(r.hi - r.lo) * (size_t)d * 4, c->stream));
+    // statistics: inside the projection kernel for the samples that are one unit, by k_stats over the rows of the others
+    // once the kernel is through; both feed the same sumsq array and the same running maximum
+    const bool fused = sumsq != nullptr;
     if (fused) {
         HIP_TRY(hipMemsetAsync(sumsq, 0, (size_t)n_samples * 8, c->stream));
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 8, c->stream));
     }
     if (c->timing) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    const int nblk = (d + 63) / 64;
-    // kernel variant (launch_project): four blocks per wave sharing the first splitmix64 round, with the deep carry-save
-    // tree and the VALU epilogue, where the dimension fills them (variant 24; 14 measured 8.97 vs 9.44 ms for 2 on 10k x
-    // 50k hashes, d = 2048), else two or one block per wave; option project_variant forces one
-    int bpw = (nblk % 4 == 0 && nblk >= 8) ? 24 : (nblk >= 2 ? 2 : 1);
-    if (c->opt.project_variant == 24 && nblk >= 4) bpw = 24;
-    if (c->opt.project_variant == 14 && nblk >= 4) bpw = 14;
-    if (c->opt.project_variant == 12 && nblk >= 2) bpw = 12;
-    if (c->opt.project_variant == 2 && nblk >= 2) bpw = 2;
-    if (c->opt.project_variant == 1) bpw = 1;
     if (!pipelined) {
         mvs::launch_project(c->stream, d_hashes, (const mvs::ProjUnit*)c->scratch, (int64_t)n_units, d, d_out, bpw,
                             fused ? (unsigned long long*)sumsq : nullptr, fused ? c->d_counter : nullptr);
@@ -147,18 +356,18 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
         HIP_TRY(hipEventRecord(c->ev[1], c->stream));
         c->ev_valid[0] = true;
     }
-    if (sumsq) {
-        if (fused) {
-            unsigned long long m = 0;
-            {
-                const int rb_rc = read_back(c, c->stream, {{&m, c->d_counter, 8}});
-                if (rb_rc) return rb_rc;
-            }
-            *max_abs = (int64_t)m;
-        } else {   // some sample spans several units: its entries are final only now
-            rc = mvs_sketch_stats(c, d_out, MVS_MEM_DEVICE, n_samples, d, sumsq, MVS_MEM_DEVICE, max_abs);
+    if (fused) {
+        for (const RowRange& r : cut_rows) {   // their entries are final only now
+            mvs::launch_stats(c->stream, d_out + r.lo * (int64_t)d, r.hi - r.lo, d, sumsq + r.lo, c->d_counter);
+            rc = check_kernel("k_stats");
             if (rc) return rc;
         }
+        unsigned long long m = 0;
+        {
+            const int rb_rc = read_back(c, c->stream, {{&m, c->d_counter, 8}});
+            if (rb_rc) return rb_rc;
+        }
+        *max_abs = (int64_t)m;
     }
     if (mem_out == MVS_MEM_HOST) {
         HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));

@@ -11,15 +11,18 @@
 
 namespace mvs {
 
-// One unit of projection work: a run of <= 65536 hashes of one sample.
+// One unit of projection work: a run of <= 65536 hashes of one sample (the layout of mvs_proj_unit, include/mvs_hip.h).
 struct ProjUnit {
     int64_t begin;    // index of the unit's first hash in the CSR value array
     int32_t count;    // hashes in the unit
     int32_t sample;   // output row
-    int32_t single;   // 1: the unit is the whole sample -> plain store; 0: combine with atomics
-    int32_t pad;
+    int32_t single;   // 1: the unit is the whole sample -> plain store, fused statistics; 0: combine with atomics
+    int32_t flags;    // kProjTailGuard
 };
 constexpr int kProjUnitMax = 65536;
+// the 512 hashes behind the unit's last full batch are not all inside the hash array: the main loop of k_project, whose
+// look-ahead load is unclamped, leaves the unit's last group of four batches to the clamped leftover path
+constexpr int kProjTailGuard = 1;
 
 // ---- geometry of the pairwise kernel (mvs_pairwise.hip) ----
 constexpr int kTile = 128;      // samples per workgroup tile edge (rows and cols)
@@ -48,6 +51,8 @@ struct Options {
     int project_variant = 0;        // projection kernel: 0 by dimension; 1 / 2 blocks per wave; 12 / 14 = 2 / 4 blocks per
                                     // wave sharing the first splitmix64 round; 24 = 14 with the deep carry-save tree and
                                     // the VALU epilogue
+    int project_balance = 1;        // 1: units that would end behind the launch's ideal end are cut into pieces that fill the idle
+                                    // workgroup slots (mvs_project_plan); 0: samples are cut at 65536 hashes only
     int markers = 0;                // 1: roctx ranges around the main entry points (rocprofv3 --marker-trace)
     int enable_k3 = 0;              // 1: mvs_sketch_set_create picks the three-plane Karatsuba code for |v| <= 8127
     int pairwise_map = 0;           // sub-patch an XCD takes in k_pairwise_pp: 0 = 4 rows x 8 cols, 1 = 8 x 4, 2 = 2 x 16
@@ -241,9 +246,14 @@ struct CoarseRow {
     int32_t big;
 };
 
-// d_sumsq / d_max_abs non-NULL: fused statistics (all samples must be single units; d_sumsq zeroed by the caller)
+// d_sumsq / d_max_abs non-NULL: fused statistics of the samples that are one unit (d_sumsq zeroed by the caller); the rows
+// of samples cut into several units are final only after the launch and get theirs from launch_stats
 int launch_project(hipStream_t stream, const uint64_t* d_hashes, const ProjUnit* d_units, int64_t n_units,
                    int d, int32_t* d_out, int variant, unsigned long long* d_sumsq, unsigned long long* d_max_abs);
+// workgroups of the k_project instantiation `variant` (with / without statistics) that one CU holds at a time; <= 0 on error
+int project_blocks_per_cu(int variant, bool stats);
+// 64-dim blocks per wave of a variant, and the workgroups one unit takes at dimension d
+inline int project_ny(int variant, int d) { return ((d + 63) / 64 + 4 * (variant % 10) - 1) / (4 * (variant % 10)); }
 int launch_sumsq(hipStream_t stream, const int32_t* d_sk, int64_t n, int d, int64_t* d_out);
 int launch_saturate_i16(hipStream_t stream, const int32_t* d_in, int64_t n, int16_t* d_out);
 int launch_stats(hipStream_t stream, const int32_t* d_sk, int64_t n, int d, int64_t* d_sumsq,

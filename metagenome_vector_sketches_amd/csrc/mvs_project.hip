@@ -15,7 +15,8 @@
 //     bit-sliced counters are summed by a butterfly of bit-sliced ripple adders (ds_bpermute) and
 //     lane k extracts count_k;
 //   * samples are cut into units of <= 65536 hashes so that long samples spread over many
-//     workgroups; units of one sample combine with int32 atomics (order independent => exact).
+//     workgroups, and the units that would run past the launch's ideal end into smaller pieces
+//     (mvs_project_plan); units of one sample combine with int32 atomics (order independent => exact).
 #include "mvs_internal.h"
 
 namespace mvs {
@@ -310,8 +311,8 @@ __device__ __forceinline__ void wave_sum_max_valu(unsigned long long& ss, uint32
 // (same XCD, dispatched together) and share the unit's hashes through that XCD's L2:
 //   id = (unit/8) * 8*ny + y*8 + unit%8.   Placement only affects HBM traffic, never results.
 // STATS: also accumulate each sample's exact sum of squares (int64 atomics, one per wave) and the largest |v|
-// of the launch -- valid only when every sample is a single unit (the host checks), because a multi-unit
-// sample's entries are only final once all its units have been added.
+// of the launch -- for the units that are a whole sample (single) only, because a multi-unit sample's entries
+// are only final once all its units have been added: the host runs k_stats over those rows afterwards.
 //
 // DEEP (variant 24): the carry-save tree reaches 128 hashes per lane before anything ripples.  The loop still hashes four
 // batches per iteration and gets one weight-32 carry out of them; carries of weight 32 and 64 wait in p32 / p64 until a
@@ -356,10 +357,13 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
         load_batch<true>(hv, base, 0, lane, last);
         int64_t b = 0;
         // four batches = 32 hashes per lane: Harley-Seal tree of depth 5, then one ripple (DEEP: see above).  The loop
-        // runs while the NEXT four batches are full too, so its prefetches need no bounds handling.
+        // takes every full group of four batches.  Its prefetches have no bounds handling: the last one of the unit's last
+        // group reads the 512 hashes behind the unit -- the next unit's, which the masked tail ignores -- unless the host
+        // saw that they end outside the hash array (kProjTailGuard): then that group is left to the clamped path below.
         uint32_t p32lo[BPW], p32hi[BPW], p64lo[BPW], p64hi[BPW];
         int grp4 = 0;   // DEEP: iterations done; bit 0 / 1 = a weight-32 / weight-64 carry is pending
-        for (; b + 4 < nfull; b += 4) {
+        const int64_t nloop = (u.flags & kProjTailGuard) ? nfull - 1 : nfull;
+        for (; b + 4 <= nloop; b += 4) {
             uint32_t c8lo[4][BPW], c8hi[4][BPW];
 #pragma unroll
             for (int sb = 0; sb < 4; ++sb) {
@@ -491,14 +495,14 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
                 *dst = v;
             else
                 atomicAdd(dst, v);
-            if (STATS) {
+            if (STATS) {   // (of a unit that is not single: never used)
                 ss += (long long)v * v;
                 const unsigned int av = (unsigned int)(v < 0 ? -v : v);
                 mx = av > mx ? av : mx;
             }
         }
     }
-    if (STATS) {
+    if (STATS && u.single) {
         if constexpr (DEEP) {
             unsigned long long uss = (unsigned long long)ss;   // two's complement: the wrapped sum is the same
             uint32_t umx = mx;
@@ -600,6 +604,24 @@ static void launch_project_as(hipStream_t stream, unsigned grid, bool stats, con
     else
         hipLaunchKernelGGL((k_project<BPW, false, SHARED, DEEP>), dim3(grid), dim3(256), 0, stream, d_hashes, d_units, nu, ny, d, nblk,
                            d_out, d_sumsq, d_max_abs);
+}
+
+template <int BPW, bool SHARED, bool DEEP = false>
+static int project_blocks_as(bool stats) {
+    int nb = 0;
+    const hipError_t e = stats ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_project<BPW, true, SHARED, DEEP>, 256, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_project<BPW, false, SHARED, DEEP>, 256, 0);
+    return e == hipSuccess ? nb : -1;
+}
+
+int project_blocks_per_cu(int variant, bool stats) {
+    switch (variant) {
+        case 1: return project_blocks_as<1, false>(stats);
+        case 12: return project_blocks_as<2, true>(stats);
+        case 24: return project_blocks_as<4, true, true>(stats);
+        case 14: return project_blocks_as<4, true>(stats);
+        default: return project_blocks_as<2, false>(stats);
+    }
 }
 
 int launch_project(hipStream_t stream, const uint64_t* d_hashes, const ProjUnit* d_units, int64_t n_units,
