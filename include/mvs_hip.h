@@ -140,6 +140,8 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *                         mvs_pairwise_cluster: cells the staging buffer of a row block holds (0, default: a quarter of the free
  *                         device memory) and an upper bound on the rows of a block (0: by pairwise_block_cells); a block that
  *                         overflows the buffer is halved and redone, so neither changes a result
+ *   intersect_unit        mvs_intersect_cells: elements of a pair's SHORTER hash list that one unit of work (one wave) covers,
+ *                         64 .. 2^30 (default 2048); a pair with a longer one is cut into several units
  *   stream_block_rows, encode_stage_words, pairwise_map, coarse_radix, cand_regions, recheck_mode, recheck_blocks
  *                         test / experiment switches (DESIGN.md, appendix "switches"; encode_stage_words below 64 also keeps
  *                         every row on the device encoder's general loop)
@@ -506,6 +508,54 @@ int mvs_cluster_finish(mvs_cluster* cluster, const double* norms_sq, int mem_nor
 int mvs_cluster_destroy(mvs_cluster* cluster);
 int mvs_ctx_cluster_stats(const mvs_ctx* ctx, double* compare_ms, double* union_ms, int64_t* edges, int64_t* row_blocks,
                           int64_t* rounds);
+
+/* ---- exact hash-set intersections for kept pairs --------------------------------------------------------------------------
+ * Everything above reports the ESTIMATE of a pair: dot, q, the top-k lists and the clusters are exact with respect to the
+ * reference's arithmetic, which estimates |A n B| from two +-1 random projections.  These calls compute the quantity itself
+ * from the hash lists the sketches were made of, for the pairs a comparison kept ("filter on sketches, verify on sets").
+ * They would replace nothing on the reference's hot path: the closest reference code is its offline error study on simulated
+ * vectors (src/compute_error_of_random_projections.py, jaccard_exact() and the RMSE studies); nothing there says which kept
+ * pairs of real data are above the level.
+ *
+ * For hash lists H(s) (set semantics: a value that occurs several times in a sample counts once) and cells (row, col):
+ *     inter[i] = | H_rows(cells[i].row) n H_cols(cells[i].col) |        (int32, exact)
+ * `dot` and `q` of a cell are not read; row == col on the same set gives the sample's size; an empty sample intersects to 0; a
+ * cell that appears several times is answered every time.  Hash values are arbitrary 64-bit words (0 and 2^64 - 1 are
+ * ordinary values; the implementation has no sentinel).  Exact and deterministic: equal to the size of the intersection of
+ * the two sorted, de-duplicated lists whatever the blocking, the options or the order of the cells.  Derived quantities
+ * (Jaccard = inter / (|A| + |B| - inter), containment = inter / |A|) are the caller's, in fp64.
+ *
+ * mvs_hash_set_create   a resident copy of the lists in HBM, per sample sorted and de-duplicated.  hashes / offsets as for
+ *                       mvs_project_csr (offsets: n_samples + 1 HOST int64, non-decreasing -- MVS_E_INVALID otherwise; each
+ *                       sample < 2^31 hashes, the total may pass 2^32: positions are 64-bit).  One pass checks "strictly
+ *                       increasing inside every sample"; where that holds (the <hash_file>.csr cache, sorted inputs) the
+ *                       data is used as uploaded, otherwise a segmented radix sort and a unique compaction run on the
+ *                       device (which then holds input + sorted copy + result for the duration of the call).  Host lists
+ *                       are uploaded with ONE plain copy of the whole list, not through the pinned staging pipeline of
+ *                       mvs_project_csr_stats: a set is built once and then serves many calls.  Synchronous.
+ * mvs_hash_set_info     samples, distinct hashes in total, whether the input was already sorted and unique.  Any pointer may be NULL.
+ * mvs_hash_set_sizes    distinct hashes per sample: n_samples int32 (`mem_out` says where).  Synchronous.
+ * mvs_intersect_cells   the contract above for n_cells cells (`mem_cells`) into inter (`mem_out`); hs_cols == NULL: columns
+ *                       index hs_rows too.  With device cells and device inter nothing but counters crosses the link: the
+ *                       lists of mvs_pairwise_rows, mvs_search_block and mvs_pairwise_topk with mem_cells = MVS_MEM_DEVICE
+ *                       feed it as they stand.  A cell that names a sample outside its set: MVS_E_RANGE, nothing is written
+ *                       for that cell, every other cell is answered (the rule of mvs_cluster_add_cells).  NULL buffers,
+ *                       negative n_cells, sets of another context: MVS_E_INVALID.  Synchronous.
+ *                       Work is laid out in units of option intersect_unit (default 2048) elements of a pair's shorter list
+ *                       against the window of the longer one they can match, one wave per unit, in cell order (a list
+ *                       sorted by row reuses the row's hashes from the caches); the option never changes a result.
+ * mvs_ctx_intersect_stats  the context's last mvs_intersect_cells: time of its kernels (0 unless mvs_ctx_set_timing is on),
+ *                       units launched, pairs cut into several units, and the bytes the contract implies: the sum of
+ *                       8 (|A| + |B|) over the cells in range.  Any pointer may be NULL. */
+typedef struct mvs_hash_set mvs_hash_set;
+int mvs_hash_set_create(mvs_ctx* ctx, const uint64_t* hashes, int mem_hashes, const int64_t* offsets, int64_t n_samples,
+                        mvs_hash_set** set);
+int mvs_hash_set_info(const mvs_hash_set* set, int64_t* n_samples, int64_t* n_hashes, int* was_sorted);
+int mvs_hash_set_sizes(const mvs_hash_set* set, int32_t* sizes, int mem_out);
+int mvs_hash_set_destroy(mvs_hash_set* set);
+int mvs_intersect_cells(mvs_ctx* ctx, const mvs_hash_set* hs_rows, const mvs_hash_set* hs_cols, const mvs_cell* cells,
+                        int mem_cells, int64_t n_cells, int32_t* inter, int mem_out);
+int mvs_ctx_intersect_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* units, int64_t* cut_pairs, int64_t* bytes);
 
 /* ---- block plans: one rank's share of the symmetric multi-rank schedule, compared in few launches ----------------
  * The reference shards by rows and lets every shard process compute its rows against ALL columns

@@ -112,6 +112,13 @@ SYMBOLS = [
     ("mvs_cluster_destroy", _c.c_int, [_P]),
     ("mvs_ctx_cluster_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                           _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_hash_set_create", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int64, _c.POINTER(_P)]),
+    ("mvs_hash_set_info", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int)]),
+    ("mvs_hash_set_sizes", _c.c_int, [_P, _P, _c.c_int]),
+    ("mvs_hash_set_destroy", _c.c_int, [_P]),
+    ("mvs_intersect_cells", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _P, _c.c_int]),
+    ("mvs_ctx_intersect_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
+                                            _c.POINTER(_c.c_int64)]),
     ("mvs_pairwise_dots", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int,
                                       _c.c_int]),
     ("mvs_sketch_set_planes", _c.c_int, [_P, _c.POINTER(_P)]),
@@ -334,6 +341,45 @@ class Cluster:
             pass
 
 
+class HashSet:
+    """Hash lists of n samples resident in HBM, per sample sorted and de-duplicated (mvs_hash_set): what
+    Context.intersect_cells intersects.  `n` samples, `total` distinct hashes, `was_sorted`: the input was already strictly
+    increasing inside every sample (it is then used as uploaded)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+        ctx._hash_sets.add(self)
+        n, total, ws = _c.c_int64(), _c.c_int64(), _c.c_int()
+        _check(ctx.lib.mvs_hash_set_info(handle, ctypes.byref(n), ctypes.byref(total), ctypes.byref(ws)))
+        self.n, self.total, self.was_sorted = n.value, total.value, bool(ws.value)
+
+    def sizes(self, out=None):
+        """distinct hashes per sample: numpy int32 [n], or written into `out` (numpy or a torch device tensor)"""
+        if out is None:
+            out = np.empty(self.n, dtype=np.int32)
+        op, om, ok = _buf(out, np.int32, writable=True) if not _is_torch(out) else _buf(out)
+        _check(self.ctx.lib.mvs_hash_set_sizes(self._h, op, om))
+        return out
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.mvs_hash_set_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 COMM_ID_BYTES = 128
 PLAN_MIRROR_OUTSIDE = 1
 CELLS_HEADER_BYTES = 64
@@ -422,6 +468,7 @@ class Context:
         self._sets = weakref.WeakSet()   # sketch sets hold a pointer to the context: close them first
         self._comms = weakref.WeakSet()  # communicators likewise
         self._clusters = weakref.WeakSet()
+        self._hash_sets = weakref.WeakSet()
         if stream is not None:
             self.set_stream(stream)
 
@@ -432,6 +479,8 @@ class Context:
             for m in list(self._comms):
                 m.close()
             for k in list(self._clusters):
+                k.close()
+            for k in list(self._hash_sets):
                 k.close()
             self.lib.mvs_ctx_destroy(self._h)
             self._h = None
@@ -991,6 +1040,77 @@ class Context:
         _check(self.lib.mvs_ctx_cluster_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n),
                                               ctypes.byref(r)))
         return {"compare_ms": a.value, "union_ms": b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
+
+    # ---- exact hash-set intersections (include/mvs_hip.h "exact hash-set intersections") ----
+    def hash_set(self, hashes, offsets):
+        """mvs_hash_set_create: hashes = uint64 numpy array or torch tensor (host or device; an int64 view of the bits is
+        accepted), offsets = host int64 [n + 1] -> HashSet"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        hp, hm, hk = _buf(hashes) if _is_torch(hashes) else _buf(hashes, np.uint64)
+        h = _P()
+        _check(self.lib.mvs_hash_set_create(self._h, hp, hm, offsets.ctypes.data, n, ctypes.byref(h)))
+        return HashSet(self, h)
+
+    def intersect_cells(self, hs, cells, n_cells=None, hs_cols=None, out=None):
+        """inter[i] = |H_rows(cells[i].row) n H_cols(cells[i].col)|, exact (mvs_intersect_cells).  cells: numpy structured
+        array (CELL_DTYPE) or int32 [m, 4] / [m, 2+] rows of (row, col, ...), or a torch device tensor int32 [m, 4] (the first
+        n_cells rows, default all).  hs_cols: the columns' set (default: hs).  Returns int32 counts: a numpy array for host
+        cells, a torch device tensor for device cells, or `out`."""
+        if _is_torch(cells):
+            cp, cm, ck = _buf(cells)
+            m = cells.shape[0]
+        else:
+            a = np.asarray(cells)
+            if a.dtype != CELL_DTYPE:
+                a = np.asarray(a, dtype=np.int32)
+                if a.ndim != 2 or a.shape[1] < 2:
+                    raise ValueError("cells must be CELL_DTYPE records or an int32 array [m, >= 2]")
+                full = np.zeros((a.shape[0], 4), dtype=np.int32)
+                full[:, :min(4, a.shape[1])] = a[:, :4]
+                a = full
+            ck = np.ascontiguousarray(a)
+            cp, cm = ck.ctypes.data, MEM_HOST
+            m = ck.shape[0]
+        if n_cells is None:
+            n_cells = m
+        elif n_cells > m:
+            raise ValueError("n_cells beyond the cell list")
+        if out is None:
+            if cm == MEM_DEVICE:
+                import torch
+                out = torch.empty(max(int(n_cells), 0), dtype=torch.int32, device=cells.device)
+            else:
+                out = np.empty(max(int(n_cells), 0), dtype=np.int32)
+        op, om, ok = _buf(out) if _is_torch(out) else _buf(out, np.int32, writable=True)
+        _check(self.lib.mvs_intersect_cells(self._h, hs._h, hs_cols._h if hs_cols is not None else None, cp, cm, int(n_cells),
+                                            op, om))
+        return out
+
+    def exact_jaccard(self, hs, cells, hs_cols=None):
+        """-> (inter int32, jaccard, contain_row, contain_col) as numpy arrays, the last three float64 computed above the
+        library in this order: J = inter / (|A| + |B| - inter), C_row = inter / |A|, C_col = inter / |B|; 0 / 0 is NaN"""
+        inter = self.intersect_cells(hs, cells, hs_cols=hs_cols)
+        if _is_torch(inter):
+            inter = inter.cpu().numpy()
+        if _is_torch(cells):
+            rc = cells[:, :2].cpu().numpy()
+            rows, cols = rc[:, 0], rc[:, 1]
+        else:
+            a = np.asarray(cells)
+            rows, cols = (a["row"], a["col"]) if a.dtype == CELL_DTYPE else (a[:, 0], a[:, 1])
+        sa = hs.sizes()[rows].astype(np.float64)
+        sb = (hs_cols if hs_cols is not None else hs).sizes()[cols].astype(np.float64)
+        fi = inter.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return inter, fi / (sa + sb - fi), fi / sa, fi / sb
+
+    def intersect_stats(self):
+        """-> dict of this context's last intersect_cells: kernel_ms (timing on), units of work launched, cut_pairs (cells
+        that consisted of several units) and bytes = the sum of 8 (|A| + |B|) over its cells"""
+        ms, u, k, b = _c.c_double(), _c.c_int64(), _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_intersect_stats(self._h, ctypes.byref(ms), ctypes.byref(u), ctypes.byref(k), ctypes.byref(b)))
+        return {"kernel_ms": ms.value, "units": u.value, "cut_pairs": k.value, "bytes": b.value}
 
     def pairwise_dots(self, sset, r0, r1, c0, c1, algo=0, out=None):
         if out is None:

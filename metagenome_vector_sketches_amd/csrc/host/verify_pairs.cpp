@@ -1,0 +1,385 @@
+// verify_pairs -- the pairs of a sketch DB whose Jaccard ESTIMATE exceeds a level, each with its EXACT Jaccard and containments
+// computed from the hash lists the DB was sketched from, on the MI355X: filter on sketches, verify on sets.  The reference has
+// no such tool: it measures its estimator offline on simulated vectors (src/compute_error_of_random_projections.py); here the
+// kept cells of the comparison stay on the device and go straight into mvs_intersect_cells.
+//
+//   verify_pairs --db <folder>/ --hashes <file> --min_jaccard <t> --output <pairs.tsv> [--exact_min <u>] [--report <file>]
+//                [--device <i>] [--help]
+//
+// Reads the DB the way pairwise_comp_optimized does (dimension.txt, dtype.txt, vector_norms.txt :893-901, vectors.bin) and the
+// hash file the way `project_everything sketch` does (its <file>.csr cache when valid, else the text).  The hash file's sample
+// names must be the DB's names in the DB's order.  Pairs are kept by the rule of mvs_search_block: Jaccard estimate
+// (:661-662) > t, 0 < t < 1.  The output is tab-separated, written under <pairs.tsv>.part and renamed when complete, one line
+// per kept pair with row < col in ascending (row, col):
+//   row_name  col_name  est_jaccard  exact_jaccard  inter  size_row  size_col  contain_row  contain_col
+// est_jaccard is the unclamped fp64 estimate (inter_est = dot / d; inter_est / (n2r + n2c - inter_est)); exact_jaccard =
+// inter / (size_row + size_col - inter), contain_row = inter / size_row, contain_col = inter / size_col, all fp64 in that
+// order, 0/0 printed as nan; floats as %.9g.  --exact_min u (0 <= u < 1) drops the lines whose exact Jaccard is <= u: the
+// verified edge list.  --report writes counts (pairs kept by the estimate, pairs with exact J > t, pairs with exact J <= t),
+// the RMSE and the largest absolute error of the estimate over the kept pairs, and kernel and wall times.
+// Exit codes: 1 bad arguments, DB or hash file, 2 device errors.  One GPU (--device, else MVS_DEVICE, else 0).
+#include "mvs_host.hpp"
+
+namespace fs = std::filesystem;
+using namespace mvs_host;
+
+namespace {
+
+struct Options {
+    std::string db_folder, hash_file, output, report, bad_flag;
+    double min_jaccard = 0.0, exact_min = -1.0;
+    int device = -1;
+    bool show_help = false, have_db = false, have_t = false, have_out = false, have_hashes = false, unknown = false;
+};
+
+void print_usage(const char* argv0) {
+    std::cout << "Usage:\n"
+              << "        " << argv0
+              << " --db <folder> --hashes <file> --min_jaccard <float in (0,1)> --output <file> [--exact_min <float in [0,1)>]"
+                 " [--report <file>] [--device <int>] [--help]"
+              << std::endl;
+}
+
+// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
+void parse(int argc, char* argv[], Options& o) {
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        const bool has_value = i + 1 < argc;
+        auto bad = [&](const char* flag) {
+            if (o.bad_flag.empty()) o.bad_flag = flag;
+        };
+        char* end = nullptr;
+        if (a == "--help") {
+            o.show_help = true;
+        } else if (a == "--db" || a == "--output" || a == "--report") {
+            if (!has_value) {
+                o.unknown = true;
+                continue;
+            }
+            (a == "--db" ? o.db_folder : a == "--output" ? o.output : o.report) = argv[++i];
+            if (a == "--db") o.have_db = true;
+            if (a == "--output") o.have_out = true;
+        } else if (a == "--hashes") {
+            o.have_hashes = true;
+            const std::string v = has_value ? argv[++i] : "";
+            if (v.empty()) bad("--hashes");
+            else o.hash_file = v;
+        } else if (a == "--min_jaccard") {
+            o.have_t = true;
+            const std::string v = has_value ? argv[++i] : "";
+            const double t = strtod(v.c_str(), &end);
+            if (v.empty() || end == v.c_str() || *end || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
+            else o.min_jaccard = t;
+        } else if (a == "--exact_min") {
+            const std::string v = has_value ? argv[++i] : "";
+            const double u = strtod(v.c_str(), &end);
+            if (v.empty() || end == v.c_str() || *end || !(u >= 0.0) || !(u < 1.0)) bad("--exact_min");
+            else o.exact_min = u;
+        } else if (a == "--device") {
+            const std::string v = has_value ? argv[++i] : "";
+            const long m = strtol(v.c_str(), &end, 10);
+            if (v.empty() || end == v.c_str() || *end || m < 0 || m > 1023) bad("--device");
+            else o.device = (int)m;
+        } else {
+            o.unknown = true;
+        }
+    }
+}
+
+struct Gpu {
+    mvs_ctx* ctx = nullptr;
+    mvs_sketch_set* set = nullptr;
+    mvs_hash_set* hs = nullptr;
+    void* d_norms = nullptr;
+    void* d_cells = nullptr;
+    void* d_inter = nullptr;
+    ~Gpu() {
+        if (ctx) {
+            if (d_norms) mvs_device_free(ctx, d_norms);
+            if (d_cells) mvs_device_free(ctx, d_cells);
+            if (d_inter) mvs_device_free(ctx, d_inter);
+        }
+        if (hs) mvs_hash_set_destroy(hs);
+        if (set) mvs_sketch_set_destroy(set);
+        if (ctx) mvs_ctx_destroy(ctx);
+    }
+};
+
+int gpu_fail(const char* what) {
+    std::cerr << "verify_pairs: " << what << ": " << mvs_last_error() << std::endl;
+    return 2;
+}
+
+// vectors.bin -> limb planes, in row chunks straight from the mapping; two limbs unless a chunk's largest |v| asks for more
+// (as cluster_sketches loads it)
+int load_db(Gpu& g, const std::string& matrix_file, int elem_bytes, int64_t n, int d) {
+    const int64_t row_bytes = (int64_t)d * elem_bytes;
+    const int64_t chunk_rows = std::max<int64_t>(1, (1LL << 30) / row_bytes);
+    const int fd = ::open(matrix_file.c_str(), O_RDONLY);
+    if (fd < 0) {
+        std::cerr << "Error opening file: " << matrix_file << std::endl;       // :35-38
+        return 1;
+    }
+    const size_t bytes = (size_t)(n * row_bytes);
+    const char* base = nullptr;
+    if (bytes) {
+        void* m = ::mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m == MAP_FAILED) {
+            ::close(fd);
+            std::cerr << "Error reading file: " << matrix_file << std::endl;
+            return 1;
+        }
+        ::madvise(m, bytes, MADV_SEQUENTIAL);
+        base = (const char*)m;
+    }
+    ::close(fd);
+    int rc = 0;
+    for (int limbs = 2, attempt = 0; attempt < 4 && !rc; ++attempt) {
+        if (g.set) {
+            mvs_sketch_set_destroy(g.set);
+            g.set = nullptr;
+        }
+        if (mvs_sketch_set_alloc(g.ctx, n, d, limbs, &g.set) != MVS_OK) {
+            rc = gpu_fail("allocating sketch set");
+            break;
+        }
+        int64_t max_abs = 0;
+        for (int64_t r0 = 0; r0 < n && !rc && mvs_limbs_for_max_abs(max_abs) <= limbs; r0 += chunk_rows) {
+            int64_t m = 0;
+            if (mvs_sketch_set_fill_stats(g.set, base + r0 * row_bytes, elem_bytes, MVS_MEM_HOST, r0, std::min(chunk_rows, n - r0), &m) != MVS_OK)
+                rc = gpu_fail("re-coding vectors.bin");
+            max_abs = std::max(max_abs, m);
+        }
+        if (mvs_limbs_for_max_abs(max_abs) <= limbs) break;
+        limbs = mvs_limbs_for_max_abs(max_abs);
+    }
+    if (bytes) ::munmap((void*)base, bytes);
+    return rc;
+}
+
+struct Pair {
+    int32_t row, col, dot, inter;
+};
+
+std::string fmt(double v) {
+    if (v != v) return "nan";
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.9g", v);
+    return buf;
+}
+
+double ratio(double num, double den) { return den == 0.0 ? std::nan("") : num / den; }
+
+bool write_atomically(const std::string& path, const std::string& text) {
+    const std::string part = path + ".part";
+    {
+        std::ofstream out(part, std::ios::binary | std::ios::trunc);
+        out << text;
+        out.flush();
+        if (!out) {
+            std::cerr << "verify_pairs: cannot write " << part << std::endl;
+            ::unlink(part.c_str());
+            return false;
+        }
+    }
+    if (::rename(part.c_str(), path.c_str()) != 0) {
+        std::cerr << "verify_pairs: cannot rename " << part << " to " << path << std::endl;
+        ::unlink(part.c_str());
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+int main(int argc, char* argv[]) {
+    const auto wall_begin = std::chrono::steady_clock::now();
+    Options o;
+    parse(argc, argv, o);
+    if (o.show_help) {
+        print_usage(argv[0]);
+        return 0;
+    }
+    if (!o.have_t && o.bad_flag.empty()) o.bad_flag = "--min_jaccard";
+    if (!o.have_hashes && o.bad_flag.empty()) o.bad_flag = "--hashes";
+    if (!o.bad_flag.empty()) {
+        if (o.bad_flag == "--min_jaccard") std::cerr << "verify_pairs: --min_jaccard takes a number in the open range (0,1)" << std::endl;
+        else if (o.bad_flag == "--hashes") std::cerr << "verify_pairs: --hashes takes the hash file the DB was sketched from" << std::endl;
+        else if (o.bad_flag == "--exact_min") std::cerr << "verify_pairs: --exact_min takes a number in the range [0,1)" << std::endl;
+        else std::cerr << "verify_pairs: --device takes a device index" << std::endl;
+        return 1;
+    }
+    if (o.unknown || !o.have_db || !o.have_out) {
+        print_usage(argv[0]);
+        return 1;
+    }
+    const std::string db_folder = o.db_folder;
+    const std::string norms_file = db_folder + "vector_norms.txt";                // raw concatenation, as :853-891
+    if (!fs::exists(norms_file)) {                                                // :855-858
+        std::cerr << "Error: Required file 'vector_norms.txt' not found in output folder: " << db_folder << std::endl;
+        return 1;
+    }
+    std::string dtype = "int32";
+    {
+        std::ifstream dtype_in(db_folder + "dtype.txt");                          // :859-865
+        if (dtype_in) std::getline(dtype_in, dtype);
+    }
+    int dimension = 0;
+    {
+        std::ifstream dim_in(db_folder + "dimension.txt");                        // :866-873
+        if (dim_in) dim_in >> dimension;
+    }
+    if (dimension <= 0) {
+        std::cerr << "Error: could not read a positive dimension from " << db_folder << "dimension.txt" << std::endl;
+        return 1;
+    }
+    const int elem_bytes = dtype == "int16" ? 2 : 4;
+    const std::string matrix_file = db_folder + "vectors.bin";                    // :891
+    DbInfo db;
+    read_norms(norms_file, db);                                                   // :893-901
+    int64_t file_size = 0;
+    {
+        std::ifstream file(matrix_file, std::ios::ate | std::ios::binary);        // :911-914
+        file_size = file ? (int64_t)file.tellg() : 0;
+    }
+    const int64_t n = file_size / ((int64_t)dimension * elem_bytes);
+    if ((int64_t)db.norms_sq.size() < n) {
+        std::cerr << "Error: vector_norms.txt has " << db.norms_sq.size() << " entries for " << n << " vectors" << std::endl;
+        return 1;
+    }
+    db.norms_sq.resize((size_t)n);
+    db.names.resize((size_t)n);
+
+    // the hash lists: the parsed form `project_everything sketch` left next to the text when it is valid, else the text
+    HashSets sets;
+    bool parsed = load_csr_cache(o.hash_file, sets);
+    if (!parsed) {
+        try {
+            parsed = read_hash_file(o.hash_file, true, sets);
+        } catch (const std::exception& e) {
+            std::cerr << "verify_pairs: reading " << o.hash_file << ": " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if (!parsed) {
+        std::cerr << "Error opening " << o.hash_file << " for reading." << std::endl;
+        return 1;
+    }
+    if ((int64_t)sets.names.size() != n || !std::equal(sets.names.begin(), sets.names.end(), db.names.begin())) {
+        size_t at = 0;
+        while (at < sets.names.size() && at < (size_t)n && sets.names[at] == db.names[at]) ++at;
+        std::cerr << "verify_pairs: the samples of " << o.hash_file << " (" << sets.names.size() << ") are not those of " << norms_file << " ("
+                  << n << ") in the same order: first difference at sample " << at << std::endl;
+        return 1;
+    }
+
+    std::vector<Pair> pairs;
+    std::vector<int32_t> sizes((size_t)n);
+    double compare_ms = 0.0, intersect_ms = 0.0;
+    if (n > 0) {
+        Gpu g;
+        const int device = o.device >= 0 ? o.device : pick_device();
+        if (mvs_ctx_create(device, &g.ctx) != MVS_OK) return gpu_fail("creating context");
+        mvs_ctx_set_timing(g.ctx, 1);
+        const int rc = load_db(g, matrix_file, elem_bytes, n, dimension);
+        if (rc) return rc;
+        if (mvs_hash_set_create(g.ctx, sets.hashes.data(), MVS_MEM_HOST, sets.offsets.data(), n, &g.hs) != MVS_OK)
+            return gpu_fail("uploading the hash lists");
+        if (mvs_hash_set_sizes(g.hs, sizes.data(), MVS_MEM_HOST) != MVS_OK) return gpu_fail("reading the set sizes");
+        if (mvs_device_alloc(g.ctx, (size_t)n * 8, 0, &g.d_norms) != MVS_OK ||
+            mvs_device_copy(g.ctx, g.d_norms, MVS_MEM_DEVICE, db.norms_sq.data(), MVS_MEM_HOST, (size_t)n * 8) != MVS_OK)
+            return gpu_fail("uploading the norms");
+        // row blocks of the search comparison; a block that keeps more than the buffer holds reports what it needs
+        const int64_t block_rows = std::max<int64_t>(256, std::min<int64_t>(n, (1LL << 28) / std::max<int64_t>(n, 1) / 256 * 256));
+        int64_t capacity = 0;
+        std::vector<mvs_cell> cells;
+        std::vector<int32_t> inter;
+        for (int64_t rb = 0; rb < n;) {
+            const int64_t re = std::min(n, rb + block_rows);
+            if (capacity == 0) {
+                capacity = 1 << 20;
+                if (mvs_device_alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK ||
+                    mvs_device_alloc(g.ctx, (size_t)capacity * 4, 0, &g.d_inter) != MVS_OK)
+                    return gpu_fail("allocating the cell buffers");
+            }
+            int64_t count = 0;
+            const int src = mvs_search_block(g.ctx, g.set, (const double*)g.d_norms, o.min_jaccard, rb, re, 0, n, (mvs_cell*)g.d_cells,
+                                             capacity, &count);
+            float ms = 0.f;
+            if (mvs_ctx_kernel_ms(g.ctx, 1, &ms) == MVS_OK) compare_ms += ms;
+            if (src == MVS_E_CAPACITY) {
+                mvs_device_free(g.ctx, g.d_cells);
+                mvs_device_free(g.ctx, g.d_inter);
+                g.d_cells = g.d_inter = nullptr;
+                capacity = count + count / 8 + 1024;
+                if (mvs_device_alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK ||
+                    mvs_device_alloc(g.ctx, (size_t)capacity * 4, 0, &g.d_inter) != MVS_OK)
+                    return gpu_fail("allocating the cell buffers");
+                continue;
+            }
+            if (src != MVS_OK) return gpu_fail("comparing");
+            if (count > 0) {
+                if (mvs_intersect_cells(g.ctx, g.hs, nullptr, (const mvs_cell*)g.d_cells, MVS_MEM_DEVICE, count, (int32_t*)g.d_inter,
+                                        MVS_MEM_DEVICE) != MVS_OK)
+                    return gpu_fail("intersecting");
+                double kms = 0.0;
+                mvs_ctx_intersect_stats(g.ctx, &kms, nullptr, nullptr, nullptr);
+                intersect_ms += kms;
+                cells.resize((size_t)count);
+                inter.resize((size_t)count);
+                if (mvs_device_copy(g.ctx, cells.data(), MVS_MEM_HOST, g.d_cells, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_cell)) != MVS_OK ||
+                    mvs_device_copy(g.ctx, inter.data(), MVS_MEM_HOST, g.d_inter, MVS_MEM_DEVICE, (size_t)count * 4) != MVS_OK)
+                    return gpu_fail("downloading");
+                for (int64_t i = 0; i < count; ++i)                    // sorted by (row, col) inside a block, blocks ascend
+                    if (cells[(size_t)i].row < cells[(size_t)i].col)
+                        pairs.push_back({cells[(size_t)i].row, cells[(size_t)i].col, cells[(size_t)i].dot, inter[(size_t)i]});
+            }
+            rb = re;
+        }
+    }
+
+    std::string text;
+    int64_t above = 0, below = 0, written = 0;
+    double err_sq = 0.0, err_max = 0.0;
+    int64_t err_n = 0;
+    for (const Pair& p : pairs) {
+        const double n2r = db.norms_sq[(size_t)p.row], n2c = db.norms_sq[(size_t)p.col];
+        const double inter_est = (double)p.dot / (double)dimension;
+        const double est = inter_est / (n2r + n2c - inter_est);
+        const double sa = (double)sizes[(size_t)p.row], sb = (double)sizes[(size_t)p.col], in = (double)p.inter;
+        const double exact = ratio(in, sa + sb - in);
+        if (exact > o.min_jaccard) ++above;
+        else ++below;
+        if (exact == exact && est == est) {
+            const double e = std::fabs(est - exact);
+            err_sq += e * e;
+            err_max = std::max(err_max, e);
+            ++err_n;
+        }
+        if (o.exact_min >= 0.0 && exact <= o.exact_min) continue;
+        text += db.names[(size_t)p.row] + '\t' + db.names[(size_t)p.col] + '\t' + fmt(est) + '\t' + fmt(exact) + '\t' + std::to_string(p.inter) +
+                '\t' + std::to_string(sizes[(size_t)p.row]) + '\t' + std::to_string(sizes[(size_t)p.col]) + '\t' + fmt(ratio(in, sa)) + '\t' +
+                fmt(ratio(in, sb)) + '\n';
+        ++written;
+    }
+    if (!write_atomically(o.output, text)) return 1;
+    const double wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall_begin).count();
+    if (!o.report.empty()) {
+        std::string rep;
+        rep += "samples\t" + std::to_string(n) + "\n";
+        rep += "min_jaccard\t" + fmt(o.min_jaccard) + "\n";
+        rep += "pairs_kept_by_estimate\t" + std::to_string((int64_t)pairs.size()) + "\n";
+        rep += "pairs_exact_above\t" + std::to_string(above) + "\n";
+        rep += "false_positives\t" + std::to_string(below) + "\n";
+        rep += "pairs_written\t" + std::to_string(written) + "\n";
+        rep += "estimate_rmse\t" + fmt(err_n ? std::sqrt(err_sq / (double)err_n) : 0.0) + "\n";
+        rep += "estimate_max_abs_error\t" + fmt(err_max) + "\n";
+        rep += "compare_kernel_ms\t" + fmt(compare_ms) + "\n";
+        rep += "intersect_kernel_ms\t" + fmt(intersect_ms) + "\n";
+        rep += "wall_s\t" + fmt(wall_s) + "\n";
+        if (!write_atomically(o.report, rep)) return 1;
+    }
+    std::cout << "Verified " << pairs.size() << " pairs of " << n << " samples kept at Jaccard > " << o.min_jaccard << ": " << above
+              << " above exactly, " << below << " at or below; " << written << " written" << std::endl;
+    return 0;
+}

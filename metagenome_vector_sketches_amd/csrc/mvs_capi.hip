@@ -200,6 +200,7 @@ const OptionSpec kOptions[] = {
     {"topk_block_rows", &mvs::Options::topk_block_rows, nullptr, 0, 1 << 30},
     {"cluster_cells", &mvs::Options::cluster_cells, nullptr, 0, 1 << 30},
     {"cluster_block_rows", &mvs::Options::cluster_block_rows, nullptr, 0, 1 << 30},
+    {"intersect_unit", &mvs::Options::intersect_unit, nullptr, 64, 1 << 30},
     {"pairwise_block_cells", nullptr, &mvs::Options::pairwise_block_cells, 1, (1LL << 62)},
 };
 
@@ -356,6 +357,7 @@ int mvs_ctx_destroy(mvs_ctx* c) {
     if (c->pw_coarse_fm) (void)hipFree(c->pw_coarse_fm);
     if (c->pw_planes_fm) (void)hipFree(c->pw_planes_fm);
     if (c->pw_need) (void)hipFree(c->pw_need);
+    if (c->ix_work) (void)hipFree(c->ix_work);
     if (c->st_tlist) (void)hipFree(c->st_tlist);
     if (c->st_tlist_n) (void)hipFree(c->st_tlist_n);
     if (c->st_ends) (void)hipFree(c->st_ends);

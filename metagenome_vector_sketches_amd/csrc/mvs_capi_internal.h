@@ -156,6 +156,11 @@ struct mvs_ctx {
     // what the clustering calls did since the last mvs_cluster_create on this context (mvs_ctx_cluster_stats)
     double cl_compare_ms = 0.0, cl_union_ms = 0.0;
     long long cl_edges = 0, cl_blocks = 0, cl_rounds = 0;
+    // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
+    // did (mvs_ctx_intersect_stats)
+    void* ix_work = nullptr;    size_t ix_work_bytes = 0;
+    double ix_kernel_ms = 0.0;
+    long long ix_units = 0, ix_cut = 0, ix_bytes = 0;
 };
 
 struct mvs_sketch_set {

@@ -1,0 +1,304 @@
+// mvs_capi_intersect.hip -- C ABI of the exact hash-set intersections: mvs_hash_set_create / _info / _sizes / _destroy (a
+// resident, per-sample sorted and de-duplicated copy of hash lists), mvs_intersect_cells (|H(row) n H(col)| for every cell of a
+// list, whoever produced it) and mvs_ctx_intersect_stats.  The kernels and the layout of the units of work are in
+// mvs_intersect.hip.  With device cells and device counts nothing but a few counters crosses the link.
+#include "mvs_capi_internal.h"
+
+#include <hip/hip_runtime.h>
+
+using namespace mvs_capi;
+
+struct mvs_hash_set {
+    mvs_ctx* ctx = nullptr;
+    int64_t n = 0, total = 0;
+    int was_sorted = 0;
+    unsigned long long* hashes = nullptr;   // per sample strictly increasing
+    long long* offsets = nullptr;           // n + 1
+    int32_t* sizes = nullptr;               // n
+};
+
+namespace {
+
+constexpr int64_t kSortBatch = 1LL << 30;   // keys per segmented sort (rocprim counts them in 32 bits; a sample holds < 2^31)
+
+struct EventQuad {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~EventQuad() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
+struct SetGuard {
+    mvs_hash_set* h;
+    ~SetGuard() {
+        if (h) mvs_hash_set_destroy(h);
+    }
+};
+
+// lists that are not sorted and unique: segmented sort in batches of whole samples, then the distinct values of every sample
+// move together.  On return h->hashes / offsets / sizes / total describe the compacted lists.
+int sort_and_compact(mvs_ctx* c, mvs_hash_set* h, const std::vector<long long>& off) {
+    const int64_t n = h->n;
+    const long long total_in = off[(size_t)n];
+    DevBuf sorted;
+    if (sorted.alloc((size_t)total_in * 8) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %lld hashes for the sort failed", total_in);
+    std::vector<unsigned int> seg;
+    for (int64_t s0 = 0; s0 < n;) {
+        int64_t s1 = s0 + 1;
+        while (s1 < n && off[(size_t)s1 + 1] - off[(size_t)s0] <= kSortBatch && s1 - s0 < (1LL << 30)) ++s1;
+        const long long base = off[(size_t)s0];
+        const unsigned int count = (unsigned int)(off[(size_t)s1] - base);
+        const unsigned int segments = (unsigned int)(s1 - s0);
+        if (count > 0) {
+            seg.resize((size_t)segments + 1);
+            for (int64_t s = s0; s <= s1; ++s) seg[(size_t)(s - s0)] = (unsigned int)(off[(size_t)s] - base);
+            DevBuf dseg, dtmp;
+            HIP_TRY(dseg.alloc(seg.size() * 4));
+            HIP_TRY(hipMemcpyAsync(dseg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, c->stream));
+            const unsigned int* d_begin = (const unsigned int*)dseg.p;
+            size_t need = 0;
+            int rc = mvs::hs_sort_segments(c->stream, h->hashes + base, (unsigned long long*)sorted.p + base, count, segments, d_begin,
+                                           d_begin + 1, nullptr, 0, &need);
+            if (rc) return fail(rc, "hash set: sort sizing failed");
+            HIP_TRY(dtmp.alloc(need));
+            rc = mvs::hs_sort_segments(c->stream, h->hashes + base, (unsigned long long*)sorted.p + base, count, segments, d_begin,
+                                       d_begin + 1, dtmp.p, need, nullptr);
+            if (rc) return fail(rc, "hash set: segmented sort failed");
+            HIP_TRY(hipStreamSynchronize(c->stream));   // (before seg is rewritten and the DevBufs free their memory)
+        }
+        s0 = s1;
+    }
+    int rc = mvs::launch_hs_count(c->stream, (const unsigned long long*)sorted.p, h->offsets, n, h->sizes);
+    if (!rc) rc = check_kernel("k_hs_count");
+    if (rc) return rc;
+    std::vector<int32_t> sizes((size_t)n);
+    HIP_TRY(hipMemcpyAsync(sizes.data(), h->sizes, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<long long> noff((size_t)n + 1);
+    noff[0] = 0;
+    for (int64_t s = 0; s < n; ++s) noff[(size_t)s + 1] = noff[(size_t)s] + sizes[(size_t)s];
+    DevBuf dnoff;
+    HIP_TRY(dnoff.alloc(noff.size() * 8));
+    HIP_TRY(hipMemcpyAsync(dnoff.p, noff.data(), noff.size() * 8, hipMemcpyHostToDevice, c->stream));
+    unsigned long long* out = nullptr;
+    if (hipMalloc((void**)&out, (size_t)std::max<long long>(noff[(size_t)n], 1) * 8) != hipSuccess)
+        return fail(MVS_E_NOMEM, "hipMalloc of %lld distinct hashes failed", noff[(size_t)n]);
+    rc = mvs::launch_hs_compact(c->stream, (const unsigned long long*)sorted.p, h->offsets, (const long long*)dnoff.p, n, out);
+    if (!rc) rc = check_kernel("k_hs_compact");
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc || e != hipSuccess) {
+        (void)hipFree(out);
+        return rc ? rc : fail(MVS_E_HIP, "hash set: compaction failed: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(h->hashes);
+    h->hashes = out;
+    h->total = noff[(size_t)n];
+    void* old_offsets = h->offsets;                     // the set keeps the new offsets, the DevBuf frees the old ones
+    h->offsets = (long long*)dnoff.p;
+    dnoff.p = old_offsets;
+    return MVS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvs_hash_set_create(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, const int64_t* offsets, int64_t n_samples,
+                        mvs_hash_set** out) {
+    if (!c || !out) return fail(MVS_E_INVALID, "NULL argument");
+    *out = nullptr;
+    if (n_samples < 0) return fail(MVS_E_INVALID, "n_samples = %lld is negative", (long long)n_samples);
+    if (n_samples >= (1LL << 31) - 256) return fail(MVS_E_RANGE, "n_samples too large for int32 sample indices");
+    if (!mem_ok(mem_hashes)) return fail(MVS_E_INVALID, "bad argument");
+    if (n_samples > 0 && !offsets) return fail(MVS_E_INVALID, "offsets is NULL");
+    const int64_t n = n_samples;
+    std::vector<long long> off((size_t)n + 1, 0);
+    const int64_t base = n > 0 ? offsets[0] : 0;
+    if (base < 0) return fail(MVS_E_INVALID, "offsets[0] = %lld is negative", (long long)base);
+    for (int64_t s = 0; s < n; ++s) {
+        const int64_t len = offsets[s + 1] - offsets[s];
+        if (len < 0) return fail(MVS_E_INVALID, "offsets are not non-decreasing at sample %lld", (long long)s);
+        if (len >= (1LL << 31)) return fail(MVS_E_RANGE, "sample %lld holds 2^31 hashes or more", (long long)s);
+        off[(size_t)s + 1] = offsets[s + 1] - base;
+    }
+    const long long total_in = off[(size_t)n];
+    if (total_in > 0 && !hashes) return fail(MVS_E_INVALID, "hashes is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    const Range range(c, "mvs_hash_set_create");
+    mvs_hash_set* h = new (std::nothrow) mvs_hash_set();
+    if (!h) return fail(MVS_E_NOMEM, "out of host memory");
+    SetGuard guard{h};
+    h->ctx = c;
+    h->n = n;
+    h->total = total_in;
+    if (hipMalloc((void**)&h->hashes, (size_t)std::max<long long>(total_in, 1) * 8) != hipSuccess ||
+        hipMalloc((void**)&h->offsets, ((size_t)n + 1) * 8) != hipSuccess ||
+        hipMalloc((void**)&h->sizes, (size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess)
+        return fail(MVS_E_NOMEM, "hipMalloc of a hash set of %lld hashes failed", total_in);
+    if (total_in > 0)
+        HIP_TRY(hipMemcpyAsync(h->hashes, hashes + base, (size_t)total_in * 8,
+                               mem_hashes == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(h->offsets, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    unsigned int unsorted = 0;
+    if (n > 0) {
+        unsigned int* d_flag = (unsigned int*)c->d_counter;
+        HIP_TRY(hipMemsetAsync(d_flag, 0, 8, c->stream));
+        int rc = mvs::launch_hs_check(c->stream, h->hashes, h->offsets, n, d_flag);
+        if (!rc) rc = check_kernel("k_hs_check");
+        if (rc) return rc;
+        rc = read_back(c, c->stream, {{&unsorted, d_flag, 4}});
+        if (rc) return rc;
+    }
+    h->was_sorted = unsorted ? 0 : 1;
+    if (unsorted) {
+        const int rc = sort_and_compact(c, h, off);
+        if (rc) return rc;
+    } else if (n > 0) {
+        std::vector<int32_t> sizes((size_t)n);
+        for (int64_t s = 0; s < n; ++s) sizes[(size_t)s] = (int32_t)(off[(size_t)s + 1] - off[(size_t)s]);
+        HIP_TRY(hipMemcpyAsync(h->sizes, sizes.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    guard.h = nullptr;
+    *out = h;
+    return MVS_OK;
+}
+
+int mvs_hash_set_info(const mvs_hash_set* h, int64_t* n_samples, int64_t* n_hashes, int* was_sorted) {
+    if (!h) return fail(MVS_E_INVALID, "NULL hash set");
+    if (n_samples) *n_samples = h->n;
+    if (n_hashes) *n_hashes = h->total;
+    if (was_sorted) *was_sorted = h->was_sorted;
+    return MVS_OK;
+}
+
+int mvs_hash_set_sizes(const mvs_hash_set* h, int32_t* sizes, int mem_out) {
+    if (!h) return fail(MVS_E_INVALID, "NULL hash set");
+    if (!mem_ok(mem_out)) return fail(MVS_E_INVALID, "bad argument");
+    if (h->n == 0) return MVS_OK;
+    if (!sizes) return fail(MVS_E_INVALID, "sizes is NULL");
+    mvs_ctx* c = h->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(sizes, h->sizes, (size_t)h->n * 4, mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MVS_OK;
+}
+
+int mvs_hash_set_destroy(mvs_hash_set* h) {
+    if (!h) return MVS_OK;
+    if (h->ctx) {
+        (void)hipSetDevice(h->ctx->device);
+        (void)hipStreamSynchronize(h->ctx->stream);
+    }
+    if (h->hashes) (void)hipFree(h->hashes);
+    if (h->offsets) (void)hipFree(h->offsets);
+    if (h->sizes) (void)hipFree(h->sizes);
+    delete h;
+    return MVS_OK;
+}
+
+int mvs_intersect_cells(mvs_ctx* c, const mvs_hash_set* hs_rows, const mvs_hash_set* hs_cols, const mvs_cell* cells, int mem_cells,
+                        int64_t n_cells, int32_t* inter, int mem_out) {
+    if (!c || !hs_rows) return fail(MVS_E_INVALID, "NULL argument");
+    if (!hs_cols) hs_cols = hs_rows;
+    if (!mem_ok(mem_cells) || !mem_ok(mem_out)) return fail(MVS_E_INVALID, "bad argument");
+    if (n_cells < 0) return fail(MVS_E_INVALID, "n_cells = %lld is negative", (long long)n_cells);
+    if (n_cells >= (1LL << 40)) return fail(MVS_E_RANGE, "n_cells too large");
+    if (hs_rows->ctx != c || hs_cols->ctx != c) return fail(MVS_E_INVALID, "a hash set belongs to another context");
+    c->ix_kernel_ms = 0.0;
+    c->ix_units = c->ix_cut = c->ix_bytes = 0;
+    if (n_cells == 0) return MVS_OK;
+    if (!cells || !inter) return fail(MVS_E_INVALID, "cells or inter is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    const Range range(c, "mvs_intersect_cells");
+
+    DevBuf dcells, dinter;
+    const mvs_cell* d_cells = cells;
+    if (mem_cells == MVS_MEM_HOST) {
+        if (dcells.alloc((size_t)n_cells * sizeof(mvs_cell)) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %lld cells failed", (long long)n_cells);
+        HIP_TRY(hipMemcpyAsync(dcells.p, cells, (size_t)n_cells * sizeof(mvs_cell), hipMemcpyHostToDevice, c->stream));
+        d_cells = (const mvs_cell*)dcells.p;
+    }
+    int32_t* d_inter = inter;
+    if (mem_out == MVS_MEM_HOST) {
+        if (dinter.alloc((size_t)n_cells * 4) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %lld counts failed", (long long)n_cells);
+        d_inter = (int32_t*)dinter.p;
+    }
+    // work space: counters | units per cell | their scan | the scan's scratch
+    const size_t arr = (((size_t)n_cells + 1) * 8 + 255) & ~(size_t)255;
+    size_t need = 0;
+    int rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes, hs_rows->n, hs_cols->sizes, hs_cols->n, c->opt.intersect_unit,
+                             nullptr, nullptr, d_inter, false, nullptr, nullptr, 0, &need);
+    if (rc) return fail(rc, "intersect: scan sizing failed");
+    rc = ensure_buf(c, &c->ix_work, &c->ix_work_bytes, 256 + 2 * arr + need);
+    if (rc) return rc;
+    unsigned long long* d_counters = (unsigned long long*)c->ix_work;
+    long long* d_units = (long long*)((char*)c->ix_work + 256);
+    long long* d_start = (long long*)((char*)c->ix_work + 256 + arr);
+    void* d_scan = (char*)c->ix_work + 256 + 2 * arr;
+
+    EventQuad ev;
+    if (c->timing) {
+        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    }
+    HIP_TRY(hipMemsetAsync(d_counters, 0, 32, c->stream));
+    rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes, hs_rows->n, hs_cols->sizes, hs_cols->n, c->opt.intersect_unit,
+                         d_units, d_start, d_inter, mem_out == MVS_MEM_HOST, d_counters, d_scan, need, nullptr);
+    if (rc) return fail(rc, "intersect: planning the units failed");
+    rc = check_kernel("k_isect_count");
+    if (rc) return rc;
+    if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    unsigned long long back[3] = {0, 0, 0};
+    long long n_units = 0;
+    rc = read_back(c, c->stream, {{back, d_counters, sizeof(back)}, {&n_units, d_start + n_cells, 8}});
+    if (rc) return rc;
+    if (c->timing) HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+    rc = mvs::launch_isect_units(c->stream, d_cells, n_cells, d_start, n_units, hs_rows->hashes, hs_rows->offsets, hs_rows->sizes,
+                                 hs_cols->hashes, hs_cols->offsets, hs_cols->sizes, c->opt.intersect_unit, d_inter);
+    if (!rc) rc = check_kernel("k_isect_units");
+    if (rc) return rc;
+    if (c->timing) HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    if (mem_out == MVS_MEM_HOST) {
+        if (back[0] == 0) {
+            HIP_TRY(hipMemcpyAsync(inter, d_inter, (size_t)n_cells * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        } else {
+            // the entries of the cells out of range (marked -1 on the device) stay what the caller had there
+            std::vector<int32_t> tmp((size_t)n_cells);
+            HIP_TRY(hipMemcpyAsync(tmp.data(), d_inter, (size_t)n_cells * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (int64_t i = 0; i < n_cells; ++i)
+                if (tmp[(size_t)i] >= 0) inter[i] = tmp[(size_t)i];
+        }
+    } else {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (c->timing) {
+        float a = 0.f, b = 0.f;
+        HIP_TRY(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+        HIP_TRY(hipEventElapsedTime(&b, ev.e[2], ev.e[3]));
+        c->ix_kernel_ms = (double)a + (double)b;
+    }
+    c->ix_units = n_units;
+    c->ix_cut = (long long)back[1];
+    c->ix_bytes = (long long)back[2];
+    if (back[0] != 0)
+        return fail(MVS_E_RANGE, "%llu cells name a sample outside the sets (%lld rows, %lld columns): they were not answered", back[0],
+                    (long long)hs_rows->n, (long long)hs_cols->n);
+    return MVS_OK;
+}
+
+int mvs_ctx_intersect_stats(const mvs_ctx* c, double* kernel_ms, int64_t* units, int64_t* cut_pairs, int64_t* bytes) {
+    if (!c) return fail(MVS_E_INVALID, "NULL context");
+    if (kernel_ms) *kernel_ms = c->ix_kernel_ms;
+    if (units) *units = c->ix_units;
+    if (cut_pairs) *cut_pairs = c->ix_cut;
+    if (bytes) *bytes = c->ix_bytes;
+    return MVS_OK;
+}
+
+}  // extern "C"

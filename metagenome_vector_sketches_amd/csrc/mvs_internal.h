@@ -112,6 +112,7 @@ struct Options {
     int cluster_cells = 0;          // mvs_pairwise_cluster: cells the staging buffer of a row block holds; 0 = a quarter of the free
                                     // device memory (never more than the block can produce); tests lower it
     int cluster_block_rows = 0;     // mvs_pairwise_cluster: > 0 = upper bound on the rows of a block (tests); 0 = by pairwise_block_cells
+    int intersect_unit = 2048;      // mvs_intersect_cells: elements of a pair's shorter hash list that one unit of work (one wave) covers
     double pairwise_block_cells = 1099511627776.0;   // row-chunk bound of mvs_pairwise_rows (2^40 cells)
 };
 
@@ -341,6 +342,26 @@ int launch_exact_tiles(hipStream_t stream, const PairwiseArgs& a, const int* d_l
 constexpr unsigned long long kPlanStale = 1ULL << 62;
 int launch_plan_verdict(hipStream_t stream, unsigned long long* d_counter, unsigned long long cand_capacity, const int* d_tile_total,
                         int tile_cap, bool tiles_skipped);
+// exact hash-set intersections (mvs_intersect.hip).  Building a set: is every sample's list strictly increasing (*d_flag = 1
+// if not), a segmented sort of up to 2^32 - 1 keys (offsets relative to d_in), distinct values per sample of sorted lists, and
+// their compaction.  Intersecting: isect_plan zeroes inter[] for the cells in range (mark_bad: writes -1 for the others),
+// counts the units of every cell and scans them (d_units, d_unit_start: n_cells + 1 entries; d_counters: [0] cells out of
+// range, [1] cells cut into several units, [2] sum of 8 (|A| + |B|)); launch_isect_units gives every unit to one wave.
+int launch_hs_check(hipStream_t stream, const unsigned long long* d_hashes, const long long* d_offsets, int64_t n,
+                    unsigned int* d_flag);
+int hs_sort_segments(hipStream_t stream, const unsigned long long* d_in, unsigned long long* d_out, unsigned int count,
+                     unsigned int segments, const unsigned int* d_begin, const unsigned int* d_end, void* d_scratch,
+                     size_t scratch_bytes, size_t* scratch_needed);
+int launch_hs_count(hipStream_t stream, const unsigned long long* d_sorted, const long long* d_offsets, int64_t n, int32_t* d_sizes);
+int launch_hs_compact(hipStream_t stream, const unsigned long long* d_sorted, const long long* d_offsets, const long long* d_new_offsets,
+                      int64_t n, unsigned long long* d_out);
+int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
+               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, int32_t* d_inter,
+               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed);
+int launch_isect_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const long long* d_unit_start, long long n_units,
+                       const unsigned long long* d_hash_r, const long long* d_off_r, const int32_t* d_size_r,
+                       const unsigned long long* d_hash_c, const long long* d_off_c, const int32_t* d_size_c, int unit,
+                       int32_t* d_inter);
 // packed cells of the streamed output: radix sort on the (row, col) bits, then CSR arrays (row_ptr over `rows` rows,
 // col, q as 8 bits -- *d_wide set if some q needs 16 -- or as 16 bits when d_q16 is given)
 int sort_packed(hipStream_t stream, unsigned long long* d_in, unsigned long long* d_out, int64_t n, int begin_bit, int end_bit,

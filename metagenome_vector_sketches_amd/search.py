@@ -12,6 +12,11 @@ counterpart because the comparison kernel works on the integer sketches of vecto
   jaccard = ip*qn*nn/(nn^2+qn^2-ip*qn*nn)     the same formula with ip*qn*nn = dot/d exactly (:199)
 
 Estimates agree with the float32 reference path to ~1e-6 relative (its inner products are float32).
+
+Extension: `search ... --hashes_db FILE` (FILE = the hash file the DB was sketched from, same samples in the same order)
+verifies every reported hit on the hash sets themselves: each hit also carries its EXACT Jaccard and the containment of the
+query in the hit, |Q n H| / |Q| (Context.intersect_cells on the hits while they are still on the device).  Without the flag
+nothing changes.
 """
 import os
 
@@ -65,7 +70,7 @@ class SearchIndex:
     reference keeps in faiss.index (L2-normalised float copies, src/jaccard.py:18-61) is here the integer sketches
     themselves, re-coded as limb planes; rows [n, n + max_queries) of the set are scratch for the queries' sketches."""
 
-    def __init__(self, index_folder, ctx=None, max_queries=1024):
+    def __init__(self, index_folder, ctx=None, max_queries=1024, hashes_db=None):
         import torch
         self._own = ctx is None
         self.ctx = _capi.Context(0) if ctx is None else ctx
@@ -79,7 +84,17 @@ class SearchIndex:
         self.sset = None
         self.limbs = 0
         self._hits = None                                            # grow-only hit buffer
+        self.hs = None                                               # the DB's hash lists on the device (hashes_db)
         self._load(2)
+        if hashes_db is not None:
+            hnames, hlists = read_queries(hashes_db)
+            if hnames != list(self.names):
+                raise ValueError("%s does not list the samples of %svector_norms.txt in the same order"
+                                 % (hashes_db, index_folder if index_folder.endswith("/") else index_folder + "/"))
+            offs = np.zeros(len(hlists) + 1, dtype=np.int64)
+            offs[1:] = np.cumsum([len(x) for x in hlists])
+            self.hs = self.ctx.hash_set(np.concatenate(hlists) if offs[-1] else np.zeros(0, dtype=np.uint64), offs)
+            self._hs_sizes = self.hs.sizes().astype(np.float64)
 
     def _load(self, limbs):
         """the database goes up once, in row chunks, re-coded for `limbs` limbs; a chunk reports its largest |v| with the
@@ -102,6 +117,9 @@ class SearchIndex:
         self.limbs = limbs
 
     def close(self):
+        if self.hs is not None:
+            self.hs.close()
+            self.hs = None
         if self.sset is not None:
             self.sset.close()
             self.sset = None
@@ -157,6 +175,29 @@ class SearchIndex:
         n2 = torch.from_numpy(np.concatenate([norms * norms, qn2, np.zeros(self.max_queries - nq)])).to(dev)
         return qn2, n2
 
+    def _exact(self, lists, cells):
+        """cells: device tensor int32 [m, 4] or structured host array whose rows are n + query index -> (exact Jaccard,
+        containment of the query in the hit) float64 [m], from the exact intersections of the queries' hash lists with the
+        DB's (J = inter / (|Q| + |H| - inter), C = inter / |Q|, fp64 in that order)"""
+        offs = np.zeros(len(lists) + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([len(x) for x in lists])
+        flat = np.concatenate(lists) if offs[-1] else np.zeros(0, dtype=np.uint64)
+        if _capi._is_torch(cells):
+            local = cells.clone()
+            local[:, 0] -= self.n
+            rc = local[:, :2].cpu().numpy()                         # (also orders torch's stream before the context's)
+        else:
+            local = np.zeros((len(cells), 4), dtype=np.int32)
+            local[:, 0], local[:, 1] = cells["row"] - self.n, cells["col"]
+            rc = local[:, :2]
+        with self.ctx.hash_set(flat, offs) as hq:
+            inter = self.ctx.intersect_cells(hq, local, hs_cols=self.hs)
+            qs = hq.sizes().astype(np.float64)
+        inter = (inter.cpu().numpy() if _capi._is_torch(inter) else inter).astype(np.float64)
+        sa, sb = qs[rc[:, 0]], self._hs_sizes[rc[:, 1]]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return inter / (sa + sb - inter), inter / sa
+
     def _topk_lists(self, lists, q_first, k, verbose):
         n, d, names, norms = self.n, self.d, self.names, self.norms
         nq = len(lists)
@@ -164,6 +205,7 @@ class SearchIndex:
             return []
         qn2, n2 = self._queries_in_set(lists)
         cells = self.ctx.pairwise_topk(self.sset, n2, k, n, n + nq, 0, n, exclude_self=True)
+        exact = self._exact(lists, cells) if self.hs is not None else None
         out = []
         for qi in range(nq):
             if verbose:
@@ -171,7 +213,8 @@ class SearchIndex:
             if qn2[qi] == 0:                                        # :184 query_norm == 0 -> nothing
                 out.append([])
                 continue
-            mine = cells[cells["row"] == n + qi]
+            sel = np.nonzero(cells["row"] == n + qi)[0]
+            mine = cells[sel]
             inter = mine["dot"].astype(np.float64) / d
             nn2 = norms[mine["col"]] * norms[mine["col"]]
             jac = inter / (nn2 + qn2[qi] - inter)                   # the kernel's score, bit for bit
@@ -179,11 +222,13 @@ class SearchIndex:
             res = []
             for rank, t in enumerate(order):
                 c = int(mine["col"][t])
+                more = () if exact is None else (float(exact[0][sel[t]]), float(exact[1][sel[t]]))
                 if verbose:
                     ip = inter[t] / (np.sqrt(qn2[qi]) * norms[c])
                     print("  Neighbor %d: %s (jaccard: %.4f), inner_product: %.4f %s %s"
-                          % (rank, names[c], jac[t], ip, norms[c], np.sqrt(qn2[qi])))
-                res.append((names[c], float(jac[t])))
+                          % (rank, names[c], jac[t], ip, norms[c], np.sqrt(qn2[qi]))
+                          + ("" if exact is None else " exact_jaccard: %.4f containment: %.4f" % more))
+                res.append((names[c], float(jac[t])) + more)
             out.append(res)
         return out
 
@@ -208,12 +253,14 @@ class SearchIndex:
                     raise
                 cap = int(e.needed)
         ctx.synchronize()
+        exact = self._exact(lists, self._hits[:cnt]) if self.hs is not None else None
         hits = self._hits[:cnt].cpu().numpy()
         out = []
         for qi in range(nq):
             if qn2[qi] == 0:                                        # :204-205 query_norm == 0 -> skipped
                 continue
-            mine = hits[hits[:, 0] == n + qi]
+            sel = np.nonzero(hits[:, 0] == n + qi)[0]
+            mine = hits[sel]
             inter = mine[:, 2].astype(np.float64) / d
             nn2 = norms[mine[:, 1]] ** 2
             jac = inter / (nn2 + qn2[qi] - inter)                   # :199
@@ -224,29 +271,33 @@ class SearchIndex:
                 if not jac[k] > j:
                     continue
                 nid = names[mine[k, 1]]
+                more = () if exact is None else (float(exact[0][sel[k]]), float(exact[1][sel[k]]))
                 if verbose:
                     ip = inter[k] / (np.sqrt(qn2[qi]) * norms[mine[k, 1]])
                     print("  Neighbor %d: %s (jaccard: %.4f), inner_product: %.4f %s %s"
-                          % (rank, nid, jac[k], ip, norms[mine[k, 1]], np.sqrt(qn2[qi])))
-                out.append((q_first + qi, nid, float(jac[k])))
+                          % (rank, nid, jac[k], ip, norms[mine[k, 1]], np.sqrt(qn2[qi]))
+                          + ("" if exact is None else " exact_jaccard: %.4f containment: %.4f" % more))
+                out.append((q_first + qi, nid, float(jac[k])) + more)
         return out
 
 
-def search_index(index_folder, query_file, j, ctx=None, verbose=True):
+def search_index(index_folder, query_file, j, ctx=None, verbose=True, hashes_db=None):
     """-> list of (query_index, neighbor_id, jaccard), per query sorted by jaccard descending
     (what src/jaccard.py:63-224 returns).  Loads the DB for this one call, as the reference loads its faiss.index;
-    keep a SearchIndex to query a resident DB repeatedly."""
+    keep a SearchIndex to query a resident DB repeatedly.  hashes_db (the hash file the DB was sketched from): every
+    tuple also carries the hit's exact Jaccard and the containment of the query in it."""
     nq = sum(1 for line in open(query_file) if line.strip())
-    with SearchIndex(index_folder, ctx=ctx, max_queries=max(1, min(nq, 4096))) as idx:
+    with SearchIndex(index_folder, ctx=ctx, max_queries=max(1, min(nq, 4096)), hashes_db=hashes_db) as idx:
         if ctx is not None:
             idx._own = False
         return idx.search(query_file, j, verbose=verbose)
 
 
-def search_index_topk(index_folder, query_file, k, ctx=None, verbose=True):
-    """search_index's top-k form: per query its k best database samples [(name, jaccard)], best first, no threshold."""
+def search_index_topk(index_folder, query_file, k, ctx=None, verbose=True, hashes_db=None):
+    """search_index's top-k form: per query its k best database samples [(name, jaccard)], best first, no threshold
+    (with hashes_db: (name, jaccard, exact jaccard, containment of the query))."""
     nq = sum(1 for line in open(query_file) if line.strip())
-    with SearchIndex(index_folder, ctx=ctx, max_queries=max(1, min(nq, 4096))) as idx:
+    with SearchIndex(index_folder, ctx=ctx, max_queries=max(1, min(nq, 4096)), hashes_db=hashes_db) as idx:
         if ctx is not None:
             idx._own = False
         return idx.search_topk(query_file, k, verbose=verbose)
@@ -288,6 +339,8 @@ def build_parser():
     parser_search.add_argument("-t", "--threads", type=int, default=1, help="Number of threads [1] (accepted, unused)")
     parser_search.add_argument("--top", type=int, default=None, metavar="K",
                                help="Report every query's K nearest datasets (1..256) instead of those above -j (extension)")
+    # (kept out of the usage text, which stays the reference's plus --top: see the module docstring)
+    parser_search.add_argument("--hashes_db", type=str, default=None, metavar="FILE", help=argparse.SUPPRESS)
     parser.add_argument("-v", "--version", action="store_true", help="Show version and date")
     return parser
 
@@ -310,9 +363,9 @@ def main(argv=None):
             return 2
         try:
             if args.top is not None:
-                search_index_topk(folder, args.query_file, args.top)
+                search_index_topk(folder, args.query_file, args.top, hashes_db=args.hashes_db)
             else:
-                search_index(folder, args.query_file, args.j)
+                search_index(folder, args.query_file, args.j, hashes_db=args.hashes_db)
         except ValueError as e:
             if str(e).startswith("ERROR 332"):                     # the reference prints the line and exits 332 (:82-84)
                 print(e)
