@@ -509,6 +509,68 @@ int mvs_cluster_destroy(mvs_cluster* cluster);
 int mvs_ctx_cluster_stats(const mvs_ctx* ctx, double* compare_ms, double* union_ms, int64_t* edges, int64_t* row_blocks,
                           int64_t* rounds);
 
+/* ---- the single-linkage tree: maximum spanning forest of the kept cells -------------------------------------------------------
+ * mvs_pairwise_cluster answers one level.  The maximum spanning forest of the thresholded Jaccard graph is the single-linkage
+ * dendrogram: at most n - 1 links, and cutting it at any level >= the level it was built at gives exactly the connected
+ * components of the graph cut at that level -- one comparison at the lowest level of interest instead of one per level.  The
+ * reference has nothing of the kind.
+ *
+ * Graph.  For n samples, norms n2, dimension d and a level 0 < t < 1, the edge set is mvs_pairwise_cluster's: i != j linked iff
+ *   (double)P / (double)d > (t / (1.0 + t)) * (n2[i] + n2[j]),  P the wrapped int32 dot.  A NaN or +inf norm links to nothing.
+ * Weight.  The weight of an edge is mvs_pairwise_topk's score: inter = (double)P / d; J = inter / (n2[i] + n2[j] - inter), fp64
+ *   in that order.  It is symmetric bit for bit.
+ * Order.  Edges are totally ordered "best first" by (key(J) descending, lo ascending, hi ascending): lo = min(i, j),
+ *   hi = max(i, j); key is the order-preserving map of mvs_pairwise_topk (-0.0 folded into +0.0, +-inf ordinary values); a
+ *   cell whose J is NaN is ignored, as top-k ignores it.
+ * Result.  The maximum spanning forest under that order -- unique, because the order is total -- as mvs_link records
+ *   { a = lo, b = hi, dot, q, jaccard } (24 bytes), SORTED BEST FIRST: n - C links for C components.  dot and q are exactly what
+ *   mvs_pairwise_rows / mvs_search_block report for that cell, jaccard is the fp64 J above, bit for bit.
+ * Exactness.  The forest is a function of the edge set and the norms only: the blocking, the options, the comparison path, the
+ *   order of cells and the number of times a cell is fed do not change it.  It equals a host Kruskal under the same order, bit
+ *   for bit.  Parallel copies of a pair, (r, c) and (c, r), are one edge.  Feeding a list twice changes nothing (`degree` of
+ *   mvs_cluster does not have this property).
+ * Cut property.  For any level u the links with jaccard > u form a prefix of the output, and their components equal the
+ *   components of {edges of the graph with J > u}.  That equals mvs_pairwise_cluster at u whenever the two forms of the test,
+ *   J > u and the product-form keep test, agree on every pair -- always, except for a pair within a rounding error of the level.
+ *
+ * mvs_linkage_create    an empty forest over n samples of dimension d on the context's device; norms_sq (n doubles) is copied
+ *                       to the device and decides every weight.  Resets the statistics mvs_ctx_linkage_stats reports.
+ * mvs_linkage_add_cells replaces the forest F by the maximum spanning forest of F and the cells of a DEVICE list.  Unlike
+ *                       mvs_cluster_add_cells it reads `dot`, so any producer that reports real dots may feed it
+ *                       (mvs_pairwise_rows, mvs_pairwise_block, mvs_search_block, mvs_pairwise_topk).  Cells with row == col
+ *                       and cells whose J is NaN are ignored.  MVS_E_RANGE: a cell named a sample outside [0, n) -- that cell is
+ *                       ignored and every other cell is consumed (the rule of mvs_cluster_add_cells).
+ * mvs_pairwise_linkage  the one-call producer: mvs_pairwise_cluster's loop with this consumer -- same launch, same staging
+ *                       buffer, same halving and grow rule, same options cluster_cells / cluster_block_rows, same argument
+ *                       checks and error codes.  norms_sq here feeds the keep test; pass the norms the linkage was created with.
+ * mvs_linkage_finish    sorts the links best first and writes them (`mem_out` says where).  capacity too small: MVS_E_CAPACITY,
+ *                       *n_links = the needed count.  May be called again after more cells.
+ * mvs_linkage_cells     the links with jaccard > level as a DEVICE cell list (row = a, col = b, dot, q), best first: ready for
+ *                       mvs_cluster_add_cells (labels, sizes and representatives at that level -- `degree` of a cluster fed
+ *                       this way is the FOREST's degree, not the graph's) and for mvs_intersect_cells (the exact Jaccard of the
+ *                       backbone).  MVS_E_CAPACITY reports the needed count in *n_cells; a NaN level is MVS_E_INVALID.
+ * mvs_ctx_linkage_stats since the context's last mvs_linkage_create: time of the comparison kernels and of the forest kernels
+ *                       (rounds + the sort of finish; both 0 unless mvs_ctx_set_timing is on), fed cells with row != col,
+ *                       row blocks of mvs_pairwise_linkage, the most rounds any list needed.  Any pointer may be NULL.
+ * All synchronous.  The kernels and the argument for their exactness are in mvs_linkage.hip. */
+typedef struct mvs_link {
+    int32_t a;         /* the smaller sample index */
+    int32_t b;         /* the larger one */
+    int32_t dot;
+    int32_t q;
+    double jaccard;
+} mvs_link;
+typedef struct mvs_linkage mvs_linkage;
+int mvs_linkage_create(mvs_ctx* ctx, int64_t n, int d, const double* norms_sq, int mem_norms, mvs_linkage** linkage);
+int mvs_linkage_add_cells(mvs_linkage* linkage, const mvs_cell* d_cells, int64_t n_cells);
+int mvs_pairwise_linkage(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double min_jaccard,
+                         mvs_linkage* linkage);
+int mvs_linkage_finish(mvs_linkage* linkage, mvs_link* links, int64_t capacity, int mem_out, int64_t* n_links);
+int mvs_linkage_cells(mvs_linkage* linkage, double level, mvs_cell* d_cells, int64_t capacity, int64_t* n_cells);
+int mvs_linkage_destroy(mvs_linkage* linkage);
+int mvs_ctx_linkage_stats(const mvs_ctx* ctx, double* compare_ms, double* forest_ms, int64_t* edges, int64_t* row_blocks,
+                          int64_t* rounds);
+
 /* ---- exact hash-set intersections for kept pairs --------------------------------------------------------------------------
  * Everything above reports the ESTIMATE of a pair: dot, q, the top-k lists and the clusters are exact with respect to the
  * reference's arithmetic, which estimates |A n B| from two +-1 random projections.  These calls compute the quantity itself

@@ -21,6 +21,7 @@ LIMBS_K3 = 0x103
 BLOCK_SYMMETRIC, BLOCK_MIRROR_ALL = 1, 2
 
 CELL_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("dot", "<i4"), ("q", "<i4")])
+LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("dot", "<i4"), ("q", "<i4"), ("jaccard", "<f8")])      # mvs_link
 
 # every symbol include/mvs_hip.h declares: (name, restype, argtypes)
 _c = ctypes
@@ -111,6 +112,14 @@ SYMBOLS = [
     ("mvs_cluster_finish", _c.c_int, [_P, _P, _c.c_int, _P, _P, _P, _P, _c.c_int, _c.POINTER(_c.c_int64)]),
     ("mvs_cluster_destroy", _c.c_int, [_P]),
     ("mvs_ctx_cluster_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
+                                          _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_linkage_create", _c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_int, _c.POINTER(_P)]),
+    ("mvs_linkage_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
+    ("mvs_pairwise_linkage", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
+    ("mvs_linkage_finish", _c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int64)]),
+    ("mvs_linkage_cells", _c.c_int, [_P, _c.c_double, _P, _c.c_int64, _c.POINTER(_c.c_int64)]),
+    ("mvs_linkage_destroy", _c.c_int, [_P]),
+    ("mvs_ctx_linkage_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                           _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     ("mvs_hash_set_create", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_hash_set_info", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int)]),
@@ -341,6 +350,144 @@ class Cluster:
             pass
 
 
+class LinkageResult:
+    """What Linkage.finish / Context.linkage return: the maximum spanning forest of the thresholded Jaccard graph -- the
+    single-linkage tree -- as numpy arrays `a`, `b` (the link's samples, a < b), `dot`, `q` (int32) and `jaccard` (float64),
+    sorted best first (jaccard descending, then a, then b), and `n`, the number of samples."""
+
+    def __init__(self, n, links):
+        self.n = int(n)
+        self.a, self.b = np.ascontiguousarray(links["a"]), np.ascontiguousarray(links["b"])
+        self.dot, self.q = np.ascontiguousarray(links["dot"]), np.ascontiguousarray(links["q"])
+        self.jaccard = np.ascontiguousarray(links["jaccard"])
+
+    def __len__(self):
+        return len(self.a)
+
+    def _merge(self, count):
+        """union-find over the first `count` links -> (root of every sample, size of the merged cluster after each link)"""
+        parent = list(range(self.n))
+        size = [1] * self.n
+        merged = np.empty(count, dtype=np.int64)
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+        for i, (a, b) in enumerate(zip(self.a[:count].tolist(), self.b[:count].tolist())):
+            ra, rb = find(a), find(b)
+            if ra != rb:                              # (always: a forest has no cycle)
+                lo, hi = min(ra, rb), max(ra, rb)
+                parent[hi] = lo
+                size[lo] += size[hi]
+                ra = lo
+            merged[i] = size[ra]
+        return np.array([find(i) for i in range(self.n)], dtype=np.int64), merged
+
+    def cut(self, level):
+        """-> (labels, sizes) of the clusters at Jaccard > level (level >= the level the forest was built at): the components
+        of the links with jaccard > level, a prefix of the list; clusters numbered by ascending smallest member, as
+        ClusterResult numbers them"""
+        with np.errstate(invalid="ignore"):
+            above = self.jaccard > level
+        count = int(above.sum())
+        assert not above[count:].any()
+        roots, _ = self._merge(count)
+        uniq = np.unique(roots)                       # a root is its cluster's smallest member
+        labels = np.searchsorted(uniq, roots).astype(np.int32)
+        return labels, np.bincount(labels, minlength=len(uniq)).astype(np.int32)
+
+    def merge_sizes(self):
+        """the size of the merged cluster after each link, in the list's order (int64)"""
+        return self._merge(len(self))[1]
+
+    def __repr__(self):
+        return "LinkageResult(%d samples, %d links)" % (self.n, len(self))
+
+
+class Linkage:
+    """The single-linkage tree of n samples, built on the device from lists of cells (mvs_linkage): the maximum spanning
+    forest of everything it was fed, under the order (jaccard descending, a, b).  norms_sq (n doubles) and d decide every
+    weight.  Feed it with add_cells (any device list with real dots: the output of Context.search_block / pairwise_block, a
+    torch int32 tensor [m, 4] or a raw device pointer) or Context.linkage_into; read it with finish or cells."""
+
+    def __init__(self, ctx, n, d, norms_sq):
+        self.ctx, self.n, self.d = ctx, int(n), int(d)
+        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        if len(norms_sq) != self.n:
+            raise ValueError("norms_sq must hold n values")
+        h = _P()
+        _check(ctx.lib.mvs_linkage_create(ctx._h, self.n, self.d, np_, nm, ctypes.byref(h)))
+        self._h = h
+        ctx._linkages.add(self)
+
+    def add_cells(self, cells, n_cells=None):
+        """cells: torch CUDA tensor (int32 [m, 4]; the first n_cells rows, default all) or a device address (int) with n_cells.
+        Feeding a list twice changes nothing."""
+        if _is_torch(cells):
+            cp, cm, ck = _buf(cells)
+            if cm != MEM_DEVICE:
+                raise ValueError("cells must be a device buffer")
+            if n_cells is None:
+                n_cells = cells.shape[0]
+            elif n_cells > cells.shape[0]:
+                raise ValueError("n_cells beyond the tensor")
+        else:
+            if n_cells is None:
+                raise ValueError("a raw device pointer needs n_cells")
+            cp = _P(int(cells)) if int(cells) else None
+        _check(self.ctx.lib.mvs_linkage_add_cells(self._h, cp, int(n_cells)))
+
+    def finish(self, capacity=None):
+        """-> LinkageResult.  capacity: room for that many links (default n - 1, which always suffices); too little raises
+        MvsError MVS_E_CAPACITY with `needed`."""
+        if capacity is None:
+            capacity = max(self.n - 1, 0)
+        links = np.empty(max(int(capacity), 1), dtype=LINK_DTYPE)
+        count = _c.c_int64()
+        rc = self.ctx.lib.mvs_linkage_finish(self._h, links.ctypes.data, int(capacity), MEM_HOST, ctypes.byref(count))
+        if rc == MVS_E_CAPACITY:
+            raise MvsError(rc, self.ctx.lib.mvs_last_error().decode("utf-8", "replace"), needed=count.value)
+        _check(rc)
+        return LinkageResult(self.n, links[:count.value])
+
+    def cells(self, level, out=None):
+        """the links with jaccard > level as a device cell list, best first -> (torch int32 tensor [capacity, 4], count):
+        ready for Cluster.add_cells and Context.intersect_cells.  out: a device tensor to write into (default: room for
+        n - 1 cells); too little room raises MvsError MVS_E_CAPACITY with `needed`."""
+        if out is None:
+            import torch
+            out = torch.empty((max(self.n - 1, 1), 4), dtype=torch.int32, device=torch.device("cuda", self.ctx.device))
+        op, om, ok = _buf(out)
+        if om != MEM_DEVICE:
+            raise ValueError("out must be a device buffer")
+        count = _c.c_int64()
+        rc = self.ctx.lib.mvs_linkage_cells(self._h, float(level), op, out.shape[0], ctypes.byref(count))
+        if rc == MVS_E_CAPACITY:
+            raise MvsError(rc, self.ctx.lib.mvs_last_error().decode("utf-8", "replace"), needed=count.value)
+        _check(rc)
+        return out, count.value
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.mvs_linkage_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HashSet:
     """Hash lists of n samples resident in HBM, per sample sorted and de-duplicated (mvs_hash_set): what
     Context.intersect_cells intersects.  `n` samples, `total` distinct hashes, `was_sorted`: the input was already strictly
@@ -468,6 +615,7 @@ class Context:
         self._sets = weakref.WeakSet()   # sketch sets hold a pointer to the context: close them first
         self._comms = weakref.WeakSet()  # communicators likewise
         self._clusters = weakref.WeakSet()
+        self._linkages = weakref.WeakSet()
         self._hash_sets = weakref.WeakSet()
         if stream is not None:
             self.set_stream(stream)
@@ -479,6 +627,8 @@ class Context:
             for m in list(self._comms):
                 m.close()
             for k in list(self._clusters):
+                k.close()
+            for k in list(self._linkages):
                 k.close()
             for k in list(self._hash_sets):
                 k.close()
@@ -1040,6 +1190,30 @@ class Context:
         _check(self.lib.mvs_ctx_cluster_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n),
                                               ctypes.byref(r)))
         return {"compare_ms": a.value, "union_ms": b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
+
+    # ---- the single-linkage tree (include/mvs_hip.h "the single-linkage tree") ----
+    def linkage_into(self, linkage, sset, norms_sq, min_jaccard):
+        """mvs_pairwise_linkage: compare `sset` with itself and feed every pair whose Jaccard estimate exceeds min_jaccard
+        (0 < min_jaccard < 1) into `linkage`, on the device"""
+        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        _check(self.lib.mvs_pairwise_linkage(self._h, sset._h, np_, nm, float(min_jaccard), linkage._h))
+
+    def linkage(self, sset, norms_sq, min_jaccard):
+        """The single-linkage tree of the samples of `sset` at Jaccard > min_jaccard -> LinkageResult: the maximum spanning
+        forest of the thresholded graph, links sorted best first.  result.cut(u) for any u >= min_jaccard gives the clusters
+        Context.cluster(u) would.  Exact: equal to a host Kruskal under the same order.  No cell leaves the device."""
+        with Linkage(self, sset.n, sset.d, norms_sq) as k:
+            self.linkage_into(k, sset, norms_sq, min_jaccard)
+            return k.finish()
+
+    def linkage_stats(self):
+        """-> dict since this context's last Linkage was created: compare_ms / forest_ms (kernel times, timing on), edges (fed
+        cells with row != col), row_blocks, rounds (most Boruvka rounds a list needed)"""
+        a, b = _c.c_double(), _c.c_double()
+        e, n, r = _c.c_int64(), _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_linkage_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n),
+                                              ctypes.byref(r)))
+        return {"compare_ms": a.value, "forest_ms": b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
 
     # ---- exact hash-set intersections (include/mvs_hip.h "exact hash-set intersections") ----
     def hash_set(self, hashes, offsets):

@@ -1,0 +1,305 @@
+// linkage_sketches -- the single-linkage tree of the samples of a sketch DB, computed on the MI355X: the maximum spanning
+// forest of the graph "Jaccard estimate > t".  One comparison at the lowest level of interest answers every higher level:
+// the links above a level u >= t connect exactly the clusters cluster_sketches would report at u.  The reference has no
+// such tool.  The comparison's kept cells never leave the device (mvs_pairwise_linkage); the answer is one line per link.
+//
+//   linkage_sketches --db <folder>/ --min_jaccard <t> --output <file> [--cut <level>]... [--device <i>] [--help]
+//
+// Reads the DB the way cluster_sketches does (dimension.txt, dtype.txt, vector_norms.txt, vectors.bin).  The output is
+// tab-separated, written under <file>.part and renamed when complete, one line per link, best first:
+//   #rank  sample_a  sample_b  jaccard  dot  size
+// rank from 0, the samples' NAMES (a before b in DB order), the link's Jaccard estimate (:661-662, %.17g), the dot, and the
+// size of the merged cluster after this link.  Each --cut <u> (t <= u < 1) adds <file>.cut<k>.tsv, k = 0, 1, ... in
+// command-line order:
+//   #sample  cluster  representative  size
+// one line per sample in DB order, by cluster_sketches' definitions at level u (no degree column: the tree does not know the
+// graph's degrees), built on the device from the links above u (mvs_linkage_cells -> mvs_cluster_*).  One line on stdout:
+//   Linked <n> samples at Jaccard > <t>: <L> links, <C> components, weakest link <J>        (<J> = "none" without a link)
+// Exit codes: 1 bad arguments or DB, 2 device errors.  One GPU (--device, else MVS_DEVICE, else 0).
+#include "mvs_host.hpp"
+
+namespace fs = std::filesystem;
+using namespace mvs_host;
+
+namespace {
+
+struct Options {
+    std::string db_folder, output, bad_flag;
+    double min_jaccard = 0.0;
+    std::vector<double> cuts;
+    int device = -1;
+    bool show_help = false, have_db = false, have_t = false, have_out = false, unknown = false;
+};
+
+void print_usage(const char* argv0) {
+    std::cout << "Usage:\n"
+              << "        " << argv0 << " --db <folder> --min_jaccard <float in (0,1)> --output <file> [--cut <float in [min_jaccard,1)>]... [--device <int>] [--help]"
+              << std::endl;
+}
+
+// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
+void parse(int argc, char* argv[], Options& o) {
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        const bool has_value = i + 1 < argc;
+        auto bad = [&](const char* flag) {
+            if (o.bad_flag.empty()) o.bad_flag = flag;
+        };
+        char* end = nullptr;
+        if (a == "--help") {
+            o.show_help = true;
+        } else if (a == "--db" || a == "--output") {
+            if (!has_value) {
+                o.unknown = true;
+                continue;
+            }
+            (a == "--db" ? o.db_folder : o.output) = argv[++i];
+            (a == "--db" ? o.have_db : o.have_out) = true;
+        } else if (a == "--min_jaccard") {
+            o.have_t = true;
+            const std::string v = has_value ? argv[++i] : "";
+            const double t = strtod(v.c_str(), &end);
+            if (v.empty() || end == v.c_str() || *end || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
+            else o.min_jaccard = t;
+        } else if (a == "--cut") {
+            const std::string v = has_value ? argv[++i] : "";
+            const double u = strtod(v.c_str(), &end);
+            if (v.empty() || end == v.c_str() || *end || !(u > 0.0) || !(u < 1.0)) bad("--cut");
+            else o.cuts.push_back(u);
+        } else if (a == "--device") {
+            const std::string v = has_value ? argv[++i] : "";
+            const long m = strtol(v.c_str(), &end, 10);
+            if (v.empty() || end == v.c_str() || *end || m < 0 || m > 1023) bad("--device");
+            else o.device = (int)m;
+        } else {
+            o.unknown = true;
+        }
+    }
+    if (!o.have_t && o.bad_flag.empty()) o.bad_flag = "--min_jaccard";
+    if (o.bad_flag.empty())
+        for (double u : o.cuts)
+            if (u < o.min_jaccard) o.bad_flag = "--cut";              // a level below the one the tree is built at
+}
+
+struct Gpu {
+    mvs_ctx* ctx = nullptr;
+    mvs_sketch_set* set = nullptr;
+    mvs_linkage* linkage = nullptr;
+    mvs_cluster* cluster = nullptr;
+    void* d_cells = nullptr;
+    ~Gpu() {
+        if (cluster) mvs_cluster_destroy(cluster);
+        if (linkage) mvs_linkage_destroy(linkage);
+        if (d_cells) mvs_device_free(ctx, d_cells);
+        if (set) mvs_sketch_set_destroy(set);
+        if (ctx) mvs_ctx_destroy(ctx);
+    }
+};
+
+int gpu_fail(const char* what) {
+    std::cerr << "linkage_sketches: " << what << ": " << mvs_last_error() << std::endl;
+    return 2;
+}
+
+// vectors.bin -> limb planes, in row chunks straight from the mapping; two limbs unless a chunk's largest |v| asks for more
+int load_db(Gpu& g, const std::string& matrix_file, int elem_bytes, int64_t n, int d) {
+    const int64_t row_bytes = (int64_t)d * elem_bytes;
+    const int64_t chunk_rows = std::max<int64_t>(1, (1LL << 30) / row_bytes);
+    const int fd = ::open(matrix_file.c_str(), O_RDONLY);
+    if (fd < 0) {
+        std::cerr << "Error opening file: " << matrix_file << std::endl;       // :35-38
+        return 1;
+    }
+    const size_t bytes = (size_t)(n * row_bytes);
+    const char* base = nullptr;
+    if (bytes) {
+        void* m = ::mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m == MAP_FAILED) {
+            ::close(fd);
+            std::cerr << "Error reading file: " << matrix_file << std::endl;
+            return 1;
+        }
+        ::madvise(m, bytes, MADV_SEQUENTIAL);
+        base = (const char*)m;
+    }
+    ::close(fd);
+    int rc = 0;
+    for (int limbs = 2, attempt = 0; attempt < 4 && !rc; ++attempt) {
+        if (g.set) {
+            mvs_sketch_set_destroy(g.set);
+            g.set = nullptr;
+        }
+        if (mvs_sketch_set_alloc(g.ctx, n, d, limbs, &g.set) != MVS_OK) {
+            rc = gpu_fail("allocating sketch set");
+            break;
+        }
+        int64_t max_abs = 0;
+        for (int64_t r0 = 0; r0 < n && !rc && mvs_limbs_for_max_abs(max_abs) <= limbs; r0 += chunk_rows) {
+            int64_t m = 0;
+            if (mvs_sketch_set_fill_stats(g.set, base + r0 * row_bytes, elem_bytes, MVS_MEM_HOST, r0, std::min(chunk_rows, n - r0), &m) != MVS_OK)
+                rc = gpu_fail("re-coding vectors.bin");
+            max_abs = std::max(max_abs, m);
+        }
+        if (mvs_limbs_for_max_abs(max_abs) <= limbs) break;
+        limbs = mvs_limbs_for_max_abs(max_abs);
+    }
+    if (bytes) ::munmap((void*)base, bytes);
+    return rc;
+}
+
+// `text` under <path>.part, then renamed
+int write_file(const std::string& path, const std::string& text) {
+    const std::string part = path + ".part";
+    {
+        std::ofstream out(part, std::ios::binary | std::ios::trunc);
+        out << text;
+        out.flush();
+        if (!out) {
+            std::cerr << "linkage_sketches: cannot write " << part << std::endl;
+            ::unlink(part.c_str());
+            return 1;
+        }
+    }
+    if (::rename(part.c_str(), path.c_str()) != 0) {
+        std::cerr << "linkage_sketches: cannot rename " << part << " to " << path << std::endl;
+        ::unlink(part.c_str());
+        return 1;
+    }
+    return 0;
+}
+
+std::string g17(double v) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%.17g", v);
+    return buf;
+}
+
+}  // namespace
+
+int main(int argc, char* argv[]) {
+    Options o;
+    parse(argc, argv, o);
+    if (o.show_help) {
+        print_usage(argv[0]);
+        return 0;
+    }
+    if (!o.bad_flag.empty()) {
+        if (o.bad_flag == "--min_jaccard") std::cerr << "linkage_sketches: --min_jaccard takes a number in the open range (0,1)" << std::endl;
+        else if (o.bad_flag == "--cut") std::cerr << "linkage_sketches: --cut takes a number in [min_jaccard,1)" << std::endl;
+        else std::cerr << "linkage_sketches: --device takes a device index" << std::endl;
+        return 1;
+    }
+    if (o.unknown || !o.have_db || !o.have_out) {
+        print_usage(argv[0]);
+        return 1;
+    }
+    const std::string db_folder = o.db_folder;
+    const std::string norms_file = db_folder + "vector_norms.txt";                // raw concatenation, as :853-891
+    if (!fs::exists(norms_file)) {                                                // :855-858
+        std::cerr << "Error: Required file 'vector_norms.txt' not found in output folder: " << db_folder << std::endl;
+        return 1;
+    }
+    std::string dtype = "int32";
+    {
+        std::ifstream dtype_in(db_folder + "dtype.txt");                          // :859-865
+        if (dtype_in) std::getline(dtype_in, dtype);
+    }
+    int dimension = 0;
+    {
+        std::ifstream dim_in(db_folder + "dimension.txt");                        // :866-873
+        if (dim_in) dim_in >> dimension;
+    }
+    if (dimension <= 0) {
+        std::cerr << "Error: could not read a positive dimension from " << db_folder << "dimension.txt" << std::endl;
+        return 1;
+    }
+    const int elem_bytes = dtype == "int16" ? 2 : 4;
+    const std::string matrix_file = db_folder + "vectors.bin";                    // :891
+    DbInfo db;
+    read_norms(norms_file, db);                                                   // :893-901
+    int64_t file_size = 0;
+    {
+        std::ifstream file(matrix_file, std::ios::ate | std::ios::binary);        // :911-914
+        file_size = file ? (int64_t)file.tellg() : 0;
+    }
+    const int64_t n = file_size / ((int64_t)dimension * elem_bytes);
+    if ((int64_t)db.norms_sq.size() < n) {
+        std::cerr << "Error: vector_norms.txt has " << db.norms_sq.size() << " entries for " << n << " vectors" << std::endl;
+        return 1;
+    }
+    db.norms_sq.resize((size_t)n);
+    db.names.resize((size_t)n);
+
+    std::vector<mvs_link> links((size_t)std::max<int64_t>(n, 1));
+    int64_t n_links = 0;
+    std::vector<std::string> cut_texts;
+    if (n > 0) {
+        Gpu g;
+        const int device = o.device >= 0 ? o.device : pick_device();
+        if (mvs_ctx_create(device, &g.ctx) != MVS_OK) return gpu_fail("creating context");
+        const int rc = load_db(g, matrix_file, elem_bytes, n, dimension);
+        if (rc) return rc;
+        if (mvs_linkage_create(g.ctx, n, dimension, db.norms_sq.data(), MVS_MEM_HOST, &g.linkage) != MVS_OK)
+            return gpu_fail("allocating the forest");
+        if (mvs_pairwise_linkage(g.ctx, g.set, db.norms_sq.data(), MVS_MEM_HOST, o.min_jaccard, g.linkage) != MVS_OK)
+            return gpu_fail("comparing");
+        if (mvs_linkage_finish(g.linkage, links.data(), (int64_t)links.size(), MVS_MEM_HOST, &n_links) != MVS_OK)
+            return gpu_fail("sorting the links");
+        if (!o.cuts.empty() && mvs_device_alloc(g.ctx, (size_t)n * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK)
+            return gpu_fail("allocating the cell buffer");
+        std::vector<int32_t> labels((size_t)n), reps((size_t)n), sizes((size_t)n);
+        for (double u : o.cuts) {
+            int64_t m = 0, n_clusters = 0;
+            if (mvs_linkage_cells(g.linkage, u, (mvs_cell*)g.d_cells, n, &m) != MVS_OK) return gpu_fail("listing the links above a cut");
+            if (mvs_cluster_create(g.ctx, n, &g.cluster) != MVS_OK) return gpu_fail("allocating a cut's clusters");
+            if (mvs_cluster_add_cells(g.cluster, (const mvs_cell*)g.d_cells, m) != MVS_OK) return gpu_fail("clustering a cut");
+            if (mvs_cluster_finish(g.cluster, db.norms_sq.data(), MVS_MEM_HOST, labels.data(), nullptr, reps.data(), sizes.data(),
+                                   MVS_MEM_HOST, &n_clusters) != MVS_OK)
+                return gpu_fail("numbering a cut's clusters");
+            mvs_cluster_destroy(g.cluster);
+            g.cluster = nullptr;
+            std::ostringstream text;
+            text << "#sample\tcluster\trepresentative\tsize\n";
+            for (int64_t i = 0; i < n; ++i) {
+                const int32_t c = labels[(size_t)i];
+                text << db.names[(size_t)i] << '\t' << c << '\t' << db.names[(size_t)reps[(size_t)c]] << '\t' << sizes[(size_t)c] << '\n';
+            }
+            cut_texts.push_back(text.str());
+        }
+    } else {
+        cut_texts.assign(o.cuts.size(), "#sample\tcluster\trepresentative\tsize\n");
+    }
+
+    // the size of the merged cluster after each link: a union-find over the links in order
+    std::vector<int64_t> parent((size_t)n), size((size_t)n, 1);
+    for (int64_t i = 0; i < n; ++i) parent[(size_t)i] = i;
+    auto find = [&](int64_t x) {
+        while (parent[(size_t)x] != x) {
+            parent[(size_t)x] = parent[(size_t)parent[(size_t)x]];
+            x = parent[(size_t)x];
+        }
+        return x;
+    };
+    std::ostringstream text;
+    text << "#rank\tsample_a\tsample_b\tjaccard\tdot\tsize\n";
+    for (int64_t i = 0; i < n_links; ++i) {
+        const mvs_link& l = links[(size_t)i];
+        int64_t ra = find(l.a);
+        const int64_t rb = find(l.b);
+        if (ra != rb) {
+            parent[(size_t)rb] = ra;
+            size[(size_t)ra] += size[(size_t)rb];
+        }
+        text << i << '\t' << db.names[(size_t)l.a] << '\t' << db.names[(size_t)l.b] << '\t' << g17(l.jaccard) << '\t' << l.dot << '\t'
+             << size[(size_t)ra] << '\n';
+    }
+    for (size_t k = 0; k < cut_texts.size(); ++k) {
+        const int rc = write_file(o.output + ".cut" + std::to_string(k) + ".tsv", cut_texts[k]);
+        if (rc) return rc;
+    }
+    const int rc = write_file(o.output, text.str());
+    if (rc) return rc;
+    std::cout << "Linked " << n << " samples at Jaccard > " << o.min_jaccard << ": " << n_links << " links, " << n - n_links
+              << " components, weakest link " << (n_links ? g17(links[(size_t)n_links - 1].jaccard) : std::string("none")) << std::endl;
+    return 0;
+}

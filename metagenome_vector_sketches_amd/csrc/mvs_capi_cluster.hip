@@ -21,14 +21,6 @@ namespace {
 
 constexpr int kMaxRounds = 64;   // hook -> flatten -> verify rounds per list before the call gives up (one is the normal case)
 
-struct EventPair {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~EventPair() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
 // the union-find rounds over one device list; the list is consumed when this returns
 int consume_cells(mvs_cluster* k, const mvs_cell* d_cells, int64_t n_cells) {
     mvs_ctx* c = k->ctx;
@@ -83,6 +75,69 @@ int give_out(mvs_ctx* c, T* dst, const void* d_src, int64_t count, int mem_out) 
 }
 
 }  // namespace
+
+namespace mvs_capi {
+
+// The threshold comparison of a sketch set with itself at level min_jaccard, row block by row block: each block's unsorted
+// cells (every ordered pair of linked samples exactly once) are handed to `consume` while they sit in the staging buffer.
+// Shared by mvs_pairwise_cluster and mvs_pairwise_linkage (mvs_capi_linkage.hip): one launch, one staging buffer, one halving
+// and grow rule.  d_n2: the norms on the device; *compare_ms (timing on) and *row_blocks are added to.
+int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, double min_jaccard, double* compare_ms, long long* row_blocks,
+                  const std::function<int(const mvs_cell*, int64_t)>& consume) {
+    const int64_t n = s->n;
+    // J > t  <=>  double(P)/d > t/(1+t) * (n2r + n2c): mvs_search_block's coefficient
+    const double coeff = min_jaccard / (1.0 + min_jaccard);
+    // rows per block: the bound mvs_pairwise_rows puts on its chunks (borders on multiples of 256 rows: the symmetric schedule)
+    int64_t R = (int64_t)(c->opt.pairwise_block_cells / (double)n);
+    R = std::max<int64_t>(256, R / 256 * 256);
+    if (c->opt.cluster_block_rows > 0) R = std::min<int64_t>(R, std::max<int64_t>(256, (int64_t)c->opt.cluster_block_rows / 256 * 256));
+    // the staging buffer: a fixed share of the free memory, never more than the first block can produce
+    int64_t capacity = c->opt.cluster_cells;
+    if (capacity <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const size_t have = free_b + c->pw_tmp_bytes;               // (the buffer below is the context's own, counted as free)
+        capacity = (int64_t)std::min<size_t>(std::max<size_t>(4096, have / 4 / sizeof(mvs_cell)), (size_t)1 << 30);   // (the option's range)
+        const double block = (double)std::min(R, n) * (double)n;
+        if (block < (double)capacity) capacity = (int64_t)block;
+    }
+    capacity = std::max<int64_t>(capacity, 1);
+    int rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)capacity * sizeof(mvs_cell));
+    if (rc) return rc;
+    for (int64_t rb = 0; rb < n;) {
+        const int64_t re = std::min(n, rb + R);
+        unsigned long long count = 0;
+        rc = pairwise_launch(c, s, d_n2, MVS_KEEP_INT16, rb, re, 0, n, true, false, (mvs_cell*)c->pw_tmp, capacity, 0, &count, coeff);
+        if (rc) return rc;
+        if (count == ~0ULL) {
+            rc = read_back(c, c->stream, {{&count, c->d_counter, 8}});
+            if (rc) return rc;
+        }
+        if (c->timing && c->ev_valid[1]) {
+            float ms = 0.f;
+            if (mvs_ctx_kernel_ms(c, 1, &ms) == MVS_OK) *compare_ms += ms;
+        }
+        if ((int64_t)count > capacity) {
+            // a dense block: the list was cut off at the buffer's end.  Half the rows and again; a block of 256 rows cannot
+            // shrink (the symmetric schedule's granule), so there the buffer takes what the block was seen to need.
+            if (re - rb > 256) {
+                R = std::max<int64_t>(256, ((re - rb) / 2 + 255) / 256 * 256);
+                continue;
+            }
+            capacity = (int64_t)count;
+            rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)capacity * sizeof(mvs_cell));
+            if (rc) return rc;
+            continue;
+        }
+        rc = consume((const mvs_cell*)c->pw_tmp, (int64_t)count);
+        if (rc) return rc;
+        ++*row_blocks;
+        rb = re;
+    }
+    return MVS_OK;
+}
+
+}  // namespace mvs_capi
 
 extern "C" {
 
@@ -142,56 +197,8 @@ int mvs_pairwise_cluster(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
         HIP_TRY(hipMemcpyAsync(dn.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
         d_n2 = (const double*)dn.p;
     }
-    // J > t  <=>  double(P)/d > t/(1+t) * (n2r + n2c): mvs_search_block's coefficient
-    const double coeff = min_jaccard / (1.0 + min_jaccard);
-    // rows per block: the bound mvs_pairwise_rows puts on its chunks (borders on multiples of 256 rows: the symmetric schedule)
-    int64_t R = (int64_t)(c->opt.pairwise_block_cells / (double)n);
-    R = std::max<int64_t>(256, R / 256 * 256);
-    if (c->opt.cluster_block_rows > 0) R = std::min<int64_t>(R, std::max<int64_t>(256, (int64_t)c->opt.cluster_block_rows / 256 * 256));
-    // the staging buffer: a fixed share of the free memory, never more than the first block can produce
-    int64_t capacity = c->opt.cluster_cells;
-    if (capacity <= 0) {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        const size_t have = free_b + c->pw_tmp_bytes;               // (the buffer below is the context's own, counted as free)
-        capacity = (int64_t)std::min<size_t>(std::max<size_t>(4096, have / 4 / sizeof(mvs_cell)), (size_t)1 << 30);   // (the option's range)
-        const double block = (double)std::min(R, n) * (double)n;
-        if (block < (double)capacity) capacity = (int64_t)block;
-    }
-    capacity = std::max<int64_t>(capacity, 1);
-    int rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)capacity * sizeof(mvs_cell));
-    if (rc) return rc;
-    for (int64_t rb = 0; rb < n;) {
-        const int64_t re = std::min(n, rb + R);
-        unsigned long long count = 0;
-        rc = pairwise_launch(c, s, d_n2, MVS_KEEP_INT16, rb, re, 0, n, true, false, (mvs_cell*)c->pw_tmp, capacity, 0, &count, coeff);
-        if (rc) return rc;
-        if (count == ~0ULL) {
-            rc = read_back(c, c->stream, {{&count, c->d_counter, 8}});
-            if (rc) return rc;
-        }
-        if (c->timing && c->ev_valid[1]) {
-            float ms = 0.f;
-            if (mvs_ctx_kernel_ms(c, 1, &ms) == MVS_OK) c->cl_compare_ms += ms;
-        }
-        if ((int64_t)count > capacity) {
-            // a dense block: the list was cut off at the buffer's end.  Half the rows and again; a block of 256 rows cannot
-            // shrink (the symmetric schedule's granule), so there the buffer takes what the block was seen to need.
-            if (re - rb > 256) {
-                R = std::max<int64_t>(256, ((re - rb) / 2 + 255) / 256 * 256);
-                continue;
-            }
-            capacity = (int64_t)count;
-            rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)capacity * sizeof(mvs_cell));
-            if (rc) return rc;
-            continue;
-        }
-        rc = consume_cells(k, (const mvs_cell*)c->pw_tmp, (int64_t)count);
-        if (rc) return rc;
-        ++c->cl_blocks;
-        rb = re;
-    }
-    return MVS_OK;
+    return pairwise_feed(c, s, d_n2, min_jaccard, &c->cl_compare_ms, &c->cl_blocks,
+                         [k](const mvs_cell* d_cells, int64_t n_cells) { return consume_cells(k, d_cells, n_cells); });
 }
 
 int mvs_cluster_finish(mvs_cluster* k, const double* norms_sq, int mem_norms, int32_t* labels, int32_t* degree,

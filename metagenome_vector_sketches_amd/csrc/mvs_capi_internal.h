@@ -156,6 +156,9 @@ struct mvs_ctx {
     // what the clustering calls did since the last mvs_cluster_create on this context (mvs_ctx_cluster_stats)
     double cl_compare_ms = 0.0, cl_union_ms = 0.0;
     long long cl_edges = 0, cl_blocks = 0, cl_rounds = 0;
+    // ... and the linkage calls since the last mvs_linkage_create (mvs_ctx_linkage_stats)
+    double lk_compare_ms = 0.0, lk_forest_ms = 0.0;
+    long long lk_edges = 0, lk_blocks = 0, lk_rounds = 0;
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
     // did (mvs_ctx_intersect_stats)
     void* ix_work = nullptr;    size_t ix_work_bytes = 0;
@@ -206,6 +209,15 @@ struct DevBuf {
         if (p) (void)hipFree(p);
     }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+};
+
+// a pair of events around a stretch of kernels whose time a statistic reports
+struct EventPair {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~EventPair() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
 };
 
 int ensure_buf(mvs_ctx* c, void** p, size_t* have, size_t bytes);
@@ -283,6 +295,11 @@ int pairwise_launch(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int
                     int64_t cb, int64_t ce, bool symmetric, bool mirror_all, mvs_cell* raw, int64_t capacity,
                     unsigned long long start, unsigned long long* count, double keep_coeff = 0.05,
                     const PackedOut* po = nullptr, const DenseOut* dn = nullptr, const mvs::Options* o = nullptr);
+
+// ---- mvs_capi_cluster.hip ----
+// the threshold comparison of a set with itself at a Jaccard level, each row block's unsorted cells handed to `consume`
+int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, double min_jaccard, double* compare_ms, long long* row_blocks,
+                  const std::function<int(const mvs_cell*, int64_t)>& consume);
 }  // namespace mvs_capi
 
 #endif

@@ -1,0 +1,284 @@
+// mvs_capi_linkage.hip -- C ABI of the single-linkage tree: mvs_linkage_create / _add_cells / _finish / _cells / _destroy (a
+// consumer of DEVICE cell lists that keeps the maximum spanning forest of everything it was fed), mvs_pairwise_linkage (the
+// one-call producer: mvs_pairwise_cluster's row-block loop with this consumer) and mvs_ctx_linkage_stats.  The kernels and the
+// argument for their exactness are in mvs_linkage.hip.  What comes back is at most n - 1 links of 24 bytes.
+#include "mvs_capi_internal.h"
+
+#include <hip/hip_runtime.h>
+
+using namespace mvs_capi;
+
+struct mvs_linkage {
+    mvs_ctx* ctx = nullptr;
+    int64_t n = 0;
+    int d = 0;
+    double* norms_sq = nullptr;              // the linkage's own copy: every weight comes from it
+    mvs_cell* forest[2] = {nullptr, nullptr};   // the forest and the one the rounds build; `cur` says which is which
+    int cur = 0;
+    int64_t n_forest = 0;
+    int32_t* comp = nullptr;
+    int32_t* next = nullptr;
+    unsigned long long* slots = nullptr;     // best_key | best_pair | best_idx, n words each
+    unsigned long long* counters = nullptr;  // mvs_internal.h: LinkState
+    mvs_link* links = nullptr;               // the forest sorted best first (n_forest entries) while links_valid
+    bool links_valid = false;
+};
+
+namespace {
+
+constexpr int kMaxRounds = 64;   // Boruvka rounds per list before the call gives up (at most ceil(log2 n) are needed)
+
+mvs::LinkState state_of(const mvs_linkage* k) {
+    mvs::LinkState s;
+    const size_t words = (size_t)std::max<int64_t>(k->n, 1);
+    s.n = k->n;
+    s.d = k->d;
+    s.norms_sq = k->norms_sq;
+    s.forest = k->forest[k->cur];
+    s.n_forest = k->n_forest;
+    s.forest_next = k->forest[k->cur ^ 1];
+    s.capacity = std::max<int64_t>(k->n - 1, 0);
+    s.comp = k->comp;
+    s.next = k->next;
+    s.best_key = k->slots;
+    s.best_pair = k->slots + words;
+    s.best_idx = k->slots + 2 * words;
+    s.counters = k->counters;
+    return s;
+}
+
+// forest := the maximum spanning forest of forest u list; the list is consumed when this returns
+int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
+    mvs_ctx* c = k->ctx;
+    if (n_cells == 0) return MVS_OK;
+    EventPair ev;
+    if (c->timing) {
+        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    }
+    const mvs::LinkState s = state_of(k);
+    HIP_TRY(hipMemsetAsync(k->counters, 0, 8 * sizeof(unsigned long long), c->stream));
+    int rc = mvs::launch_link_identity(c->stream, k->comp, k->n);
+    if (!rc) rc = check_kernel("k_link_identity");
+    if (rc) return rc;
+    unsigned long long back[5] = {0, 0, 0, 0, 0};
+    int round = 0;
+    for (;;) {
+        rc = mvs::launch_link_slots(c->stream, s);
+        if (!rc) rc = check_kernel("k_link_slots");
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(k->counters + 2, 0, sizeof(unsigned long long), c->stream));
+        rc = mvs::launch_link_select(c->stream, s, d_cells, n_cells, 0, round == 0);
+        if (!rc) rc = check_kernel("k_link_select<0>");
+        if (rc) return rc;
+        rc = read_back(c, c->stream, {{back, k->counters, sizeof(back)}});
+        if (rc) return rc;
+        if (back[4] != 0) return fail(MVS_E_HIP, "internal: the forest rounds left their bounds (flag %llu)", back[4]);
+        if (back[2] == 0) break;
+        if (round >= kMaxRounds)
+            return fail(MVS_E_HIP, "internal: %llu edges still join different components after %d rounds", back[2], round);
+        ++round;
+        for (int pass = 1; pass <= 2 && !rc; ++pass) {
+            rc = mvs::launch_link_select(c->stream, s, d_cells, n_cells, pass, false);
+            if (!rc) rc = check_kernel("k_link_select");
+        }
+        if (!rc) rc = mvs::launch_link_hook(c->stream, s, d_cells);
+        if (!rc) rc = check_kernel("k_link_hook");
+        if (!rc) rc = mvs::launch_link_jump(c->stream, s);
+        if (!rc) rc = check_kernel("k_link_flatten");
+        if (rc) return rc;
+    }
+    if ((int64_t)back[3] > s.capacity) return fail(MVS_E_HIP, "internal: a forest of %llu edges over %lld samples", back[3], (long long)k->n);
+    k->cur ^= 1;
+    k->n_forest = (int64_t)back[3];
+    k->links_valid = false;
+    if (c->timing) {
+        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+        HIP_TRY(hipEventSynchronize(ev.e[1]));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        c->lk_forest_ms += ms;
+    }
+    c->lk_edges += (long long)back[0];
+    c->lk_rounds = std::max<long long>(c->lk_rounds, round);
+    if (back[1] != 0)
+        return fail(MVS_E_RANGE, "%llu cells name a sample outside [0, %lld): they were ignored", back[1], (long long)k->n);
+    return MVS_OK;
+}
+
+// k->links := the forest sorted best first
+int sort_links(mvs_linkage* k) {
+    if (k->links_valid || k->n_forest == 0) {
+        k->links_valid = true;
+        return MVS_OK;
+    }
+    mvs_ctx* c = k->ctx;
+    const mvs::LinkState s = state_of(k);
+    DevBuf dtmp, dscratch;
+    size_t need = 0;
+    int rc = mvs::link_sorted(c->stream, s, nullptr, nullptr, nullptr, 0, &need);
+    if (rc) return fail(rc, "linkage finish: sort sizing failed");
+    HIP_TRY(dtmp.alloc((size_t)k->n_forest * sizeof(mvs_link)));
+    HIP_TRY(dscratch.alloc(need));
+    EventPair ev;
+    if (c->timing) {
+        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    }
+    rc = mvs::link_sorted(c->stream, s, (mvs_link*)dtmp.p, k->links, dscratch.p, need, nullptr);
+    if (rc) return fail(rc, "linkage finish: sort failed");
+    rc = check_kernel("k_link_links");
+    if (rc) return rc;
+    if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (also before the DevBufs free the scratch)
+    if (c->timing) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        c->lk_forest_ms += ms;
+    }
+    k->links_valid = true;
+    return MVS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvs_linkage_create(mvs_ctx* c, int64_t n, int d, const double* norms_sq, int mem_norms, mvs_linkage** out) {
+    if (!c || !out) return fail(MVS_E_INVALID, "NULL argument");
+    *out = nullptr;
+    if (n < 0) return fail(MVS_E_INVALID, "n = %lld is negative", (long long)n);
+    if (d <= 0) return fail(MVS_E_INVALID, "d = %d is not positive", d);
+    if (!mem_ok(mem_norms)) return fail(MVS_E_INVALID, "bad argument");
+    if (n > 0 && !norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
+    if (n >= (1LL << 31) - 256) return fail(MVS_E_RANGE, "n too large for int32 sample indices");
+    HIP_TRY(hipSetDevice(c->device));
+    mvs_linkage* k = new (std::nothrow) mvs_linkage();
+    if (!k) return fail(MVS_E_NOMEM, "out of host memory");
+    k->ctx = c;
+    k->n = n;
+    k->d = d;
+    const size_t words = (size_t)std::max<int64_t>(n, 1);
+    if (hipMalloc((void**)&k->norms_sq, words * 8) != hipSuccess || hipMalloc((void**)&k->forest[0], words * sizeof(mvs_cell)) != hipSuccess ||
+        hipMalloc((void**)&k->forest[1], words * sizeof(mvs_cell)) != hipSuccess || hipMalloc((void**)&k->comp, words * 4) != hipSuccess ||
+        hipMalloc((void**)&k->next, words * 4) != hipSuccess || hipMalloc((void**)&k->slots, 3 * words * 8) != hipSuccess ||
+        hipMalloc((void**)&k->links, words * sizeof(mvs_link)) != hipSuccess || hipMalloc((void**)&k->counters, 64) != hipSuccess) {
+        mvs_linkage_destroy(k);
+        return fail(MVS_E_NOMEM, "hipMalloc of the forest of %lld samples failed", (long long)n);
+    }
+    if (n > 0) {
+        const hipError_t e = hipMemcpyAsync(k->norms_sq, norms_sq, (size_t)n * 8,
+                                            mem_norms == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream);
+        const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+        if (e2 != hipSuccess) {
+            mvs_linkage_destroy(k);
+            return fail(MVS_E_HIP, "copying the norms: %s", hipGetErrorString(e2));
+        }
+    }
+    c->lk_compare_ms = c->lk_forest_ms = 0.0;
+    c->lk_edges = c->lk_blocks = c->lk_rounds = 0;
+    *out = k;
+    return MVS_OK;
+}
+
+int mvs_linkage_add_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
+    if (!k) return fail(MVS_E_INVALID, "NULL linkage");
+    if (n_cells < 0 || (n_cells > 0 && !d_cells)) return fail(MVS_E_INVALID, "bad cell list");
+    HIP_TRY(hipSetDevice(k->ctx->device));
+    const Range range(k->ctx, "mvs_linkage_add_cells");
+    return consume_cells(k, d_cells, n_cells);
+}
+
+int mvs_pairwise_linkage(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int mem_norms, double min_jaccard,
+                         mvs_linkage* k) {
+    if (!c || !s || !k) return fail(MVS_E_INVALID, "NULL argument");
+    if (!(min_jaccard > 0.0) || !(min_jaccard < 1.0)) return fail(MVS_E_INVALID, "min_jaccard = %g outside (0, 1)", min_jaccard);
+    if (!mem_ok(mem_norms)) return fail(MVS_E_INVALID, "bad argument");
+    if (k->ctx != c) return fail(MVS_E_INVALID, "the linkage belongs to another context");
+    if (k->n != s->n) return fail(MVS_E_INVALID, "the linkage holds %lld samples, the sketch set %lld", (long long)k->n, (long long)s->n);
+    if (k->d != s->d) return fail(MVS_E_INVALID, "the linkage was created for dimension %d, the sketch set has %d", k->d, s->d);
+    const int64_t n = s->n;
+    if (n == 0) return MVS_OK;
+    if (!norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
+    const Range range(c, "mvs_pairwise_linkage");
+    HIP_TRY(hipSetDevice(c->device));
+
+    DevBuf dn;
+    const double* d_n2 = norms_sq;
+    if (mem_norms == MVS_MEM_HOST) {
+        HIP_TRY(dn.alloc((size_t)n * 8));
+        HIP_TRY(hipMemcpyAsync(dn.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        d_n2 = (const double*)dn.p;
+    }
+    return pairwise_feed(c, s, d_n2, min_jaccard, &c->lk_compare_ms, &c->lk_blocks,
+                         [k](const mvs_cell* d_cells, int64_t n_cells) { return consume_cells(k, d_cells, n_cells); });
+}
+
+int mvs_linkage_finish(mvs_linkage* k, mvs_link* links, int64_t capacity, int mem_out, int64_t* n_links) {
+    if (!k) return fail(MVS_E_INVALID, "NULL linkage");
+    if (!mem_ok(mem_out) || capacity < 0) return fail(MVS_E_INVALID, "bad argument");
+    if (n_links) *n_links = k->n_forest;
+    if (k->n_forest > capacity)
+        return fail(MVS_E_CAPACITY, "the forest has %lld links, the buffer holds %lld", (long long)k->n_forest, (long long)capacity);
+    if (k->n_forest == 0) return MVS_OK;
+    if (!links) return fail(MVS_E_INVALID, "links is NULL");
+    mvs_ctx* c = k->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const Range range(c, "mvs_linkage_finish");
+    const int rc = sort_links(k);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(links, k->links, (size_t)k->n_forest * sizeof(mvs_link),
+                           mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MVS_OK;
+}
+
+int mvs_linkage_cells(mvs_linkage* k, double level, mvs_cell* d_cells, int64_t capacity, int64_t* n_cells) {
+    if (!k) return fail(MVS_E_INVALID, "NULL linkage");
+    if (n_cells) *n_cells = 0;
+    if (!(level == level)) return fail(MVS_E_INVALID, "level is NaN");
+    if (capacity < 0 || (capacity > 0 && !d_cells)) return fail(MVS_E_INVALID, "bad cell buffer");
+    if (k->n_forest == 0) return MVS_OK;
+    mvs_ctx* c = k->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const Range range(c, "mvs_linkage_cells");
+    int rc = sort_links(k);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(k->counters + 5, 0, sizeof(unsigned long long), c->stream));
+    rc = mvs::launch_link_cells(c->stream, k->links, k->n_forest, level, d_cells, capacity, k->counters);
+    if (!rc) rc = check_kernel("k_link_cells");
+    if (rc) return rc;
+    unsigned long long above = 0;
+    rc = read_back(c, c->stream, {{&above, k->counters + 5, 8}});
+    if (rc) return rc;
+    if (n_cells) *n_cells = (int64_t)above;
+    if ((int64_t)above > capacity)
+        return fail(MVS_E_CAPACITY, "%llu links lie above the level, the buffer holds %lld", above, (long long)capacity);
+    return MVS_OK;
+}
+
+int mvs_linkage_destroy(mvs_linkage* k) {
+    if (!k) return MVS_OK;
+    if (k->ctx) {
+        (void)hipSetDevice(k->ctx->device);
+        (void)hipStreamSynchronize(k->ctx->stream);
+    }
+    void* bufs[] = {k->norms_sq, k->forest[0], k->forest[1], k->comp, k->next, k->slots, k->counters, k->links};
+    for (void* p : bufs)
+        if (p) (void)hipFree(p);
+    delete k;
+    return MVS_OK;
+}
+
+int mvs_ctx_linkage_stats(const mvs_ctx* c, double* compare_ms, double* forest_ms, int64_t* edges, int64_t* row_blocks,
+                          int64_t* rounds) {
+    if (!c) return fail(MVS_E_INVALID, "NULL context");
+    if (compare_ms) *compare_ms = c->lk_compare_ms;
+    if (forest_ms) *forest_ms = c->lk_forest_ms;
+    if (edges) *edges = c->lk_edges;
+    if (row_blocks) *row_blocks = c->lk_blocks;
+    if (rounds) *rounds = c->lk_rounds;
+    return MVS_OK;
+}
+
+}  // extern "C"

@@ -287,6 +287,34 @@ int launch_cluster_verify(hipStream_t stream, const mvs_cell* d_cells, int64_t n
 int cluster_finish(hipStream_t stream, const int32_t* d_parent, const double* d_norms_sq, int64_t n, int32_t* d_is_root, int32_t* d_ids,
                    int32_t* d_labels, int32_t* d_sizes, int32_t* d_rep, unsigned long long* d_best, void* d_scratch,
                    size_t scratch_bytes, size_t* scratch_needed);
+// the single-linkage tree over device cell lists (mvs_linkage.hip): Boruvka rounds that turn the forest and a list into the
+// maximum spanning forest of both.  One round = slots, select passes 0 (key; counts the crossing edges) / 1 (pair) / 2 (pick),
+// hook, jump.  d_counters (8 words): [0] fed cells with row != col in range, [1] fed cells with an index outside [0, n),
+// [2] edges between different components, [3] cells in forest_next, [4] internal faults (must stay 0), [5] links above a level
+struct LinkState {
+    int64_t n = 0;
+    int d = 0;
+    const double* norms_sq = nullptr;       // n doubles on the device
+    const mvs_cell* forest = nullptr;       // n_forest cells, row < col
+    int64_t n_forest = 0;
+    mvs_cell* forest_next = nullptr;        // room for `capacity` cells
+    int64_t capacity = 0;
+    int32_t* comp = nullptr;                // n each
+    int32_t* next = nullptr;
+    unsigned long long* best_key = nullptr;
+    unsigned long long* best_pair = nullptr;
+    unsigned long long* best_idx = nullptr;
+    unsigned long long* counters = nullptr;
+};
+int launch_link_identity(hipStream_t stream, int32_t* d_comp, int64_t n);
+int launch_link_slots(hipStream_t stream, const LinkState& s);
+int launch_link_select(hipStream_t stream, const LinkState& s, const mvs_cell* d_cells, int64_t n_cells, int pass, bool first);
+int launch_link_hook(hipStream_t stream, const LinkState& s, const mvs_cell* d_cells);
+int launch_link_jump(hipStream_t stream, const LinkState& s);
+int link_sorted(hipStream_t stream, const LinkState& s, mvs_link* d_tmp, mvs_link* d_links, void* d_scratch, size_t scratch_bytes,
+                size_t* scratch_needed);
+int launch_link_cells(hipStream_t stream, const mvs_link* d_links, int64_t n_links, double level, mvs_cell* d_cells, int64_t capacity,
+                      unsigned long long* d_counters);
 // two-stage comparison for two base-256 limbs: coarse plane + row statistics from the limb planes,
 // per-call filter constants, the one-pass filter
 // that appends candidate pairs, and the exact re-check of the candidates that appends kept cells
