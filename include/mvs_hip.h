@@ -571,6 +571,69 @@ int mvs_linkage_destroy(mvs_linkage* linkage);
 int mvs_ctx_linkage_stats(const mvs_ctx* ctx, double* compare_ms, double* forest_ms, int64_t* edges, int64_t* row_blocks,
                           int64_t* rounds);
 
+/* ---- greedy dereplication: representatives with a radius guarantee -------------------------------------------------------------
+ * Single linkage chains: a cluster's representative may have nothing in common with most of its members.  Dereplication wants
+ * what greedy incremental clustering gives (the rule of dRep, galah, CD-HIT, linclust): the lexicographically first maximal
+ * independent set of the threshold graph under a priority order.  The reference has nothing of the kind.
+ *
+ * Graph.  Exactly mvs_pairwise_cluster's: samples i != j are linked iff
+ *   (double)P / (double)d > (t / (1.0 + t)) * (n2[i] + n2[j]),  P the wrapped int32 dot, 0 < t < 1.  A NaN or +inf norm links to
+ *   nothing.
+ * Order.  A permutation order[0..n) of the samples; order[0] goes first.  The default is norms_sq descending under the key of
+ *   mvs_cluster_finish's representatives (NaN ranks below every number, -0.0 ties with +0.0), equal keys by the smaller index.
+ * Result.  Walk the samples in that order.  A sample becomes a REPRESENTATIVE iff none of the samples linked to it that come
+ *   earlier in the order is a representative; otherwise it is a MEMBER of the earliest-in-order representative linked to it.
+ *   In the caller's index space:
+ *   rep_of[i]               the sample's representative; i itself for a representative
+ *   link_dot[i], link_q[i]  dot and q of the cell (i, rep_of[i]), exactly as mvs_pairwise_rows reports them; 0 and -1 for a
+ *                           representative
+ *   sizes[i]                samples assigned to i including itself; 0 for a member
+ *   *n_reps                 the number of representatives
+ * Properties.  No two representatives are linked.  Every member is linked to its representative.  The result is a function of
+ *   (edge set, order) only: independent of the blocking, the options, the comparison path, the order of cells in a list and of
+ *   duplicate or mirrored cells.  rep_of[i] lies in i's single-linkage cluster at the same level, hence n_reps >= n_clusters, with
+ *   equality iff every cluster is a star around its best member.
+ *
+ * mvs_sketch_set_gather an owned set of n_rows rows, same d and limb code: row i is row rows[i] of src (rows may repeat; `rows`
+ *                       lives where mem_rows says).  A row outside [0, src n): MVS_E_RANGE, no set is returned.
+ * mvs_derep_create      n undecided samples on the context's device, greedy in ROW order (row 0 first: the caller has permuted
+ *                       its samples into the order it wants, see mvs_dereplicate); resets the statistics
+ *                       mvs_ctx_derep_stats reports.
+ * mvs_derep_add_rows    decides rows [row_begin, row_end) from a DEVICE list that holds every cell (r, c), c < r, of those rows;
+ *                       cells with c >= r are ignored (row c's own list brings (c, r)), copies of a cell change nothing.
+ *                       row_begin must equal the number of rows decided so far, else MVS_E_INVALID: everything before a block is
+ *                       final when the block arrives, which is why nothing is kept between blocks.  A cell naming a row outside
+ *                       [row_begin, row_end) or a column outside [0, n): MVS_E_RANGE -- that cell is ignored and every other
+ *                       cell is consumed (the rule of mvs_cluster_add_cells).  The list is consumed when the call returns.
+ * mvs_pairwise_derep    the one-call producer: mvs_pairwise_cluster's loop with this consumer -- same launch, same staging
+ *                       buffer, same halving and grow rule, same options cluster_cells / cluster_block_rows, same argument
+ *                       checks and error codes.  The dereplication must not have decided any row yet.
+ * mvs_derep_finish      writes the arrays (`mem_out` says where all four live; any pointer may be NULL).  order (n int32 where
+ *                       mem_order says; NULL = identity) maps rows back to the caller's samples: row r is sample order[r].
+ *                       Not a permutation of [0, n), or rows still undecided: MVS_E_INVALID.
+ * mvs_ctx_derep_stats   since the context's last mvs_derep_create: time of the comparison kernels and of the greedy kernels
+ *                       (both 0 unless mvs_ctx_set_timing is on), cells with row != col consumed, row blocks of
+ *                       mvs_pairwise_derep, the most rounds any block needed.  Any pointer may be NULL.
+ * mvs_dereplicate       the one call: builds the order (order: n HOST int32, or NULL = by norm as above; not a permutation of
+ *                       [0, n): MVS_E_INVALID), gathers the set and the norms into that order unless it is the identity, then
+ *                       mvs_derep_create, mvs_pairwise_derep and mvs_derep_finish with the order.
+ * All synchronous.  The kernels and the argument for their exactness are in mvs_derep.hip. */
+int mvs_sketch_set_gather(mvs_ctx* ctx, const mvs_sketch_set* src, const int32_t* rows, int mem_rows, int64_t n_rows,
+                          mvs_sketch_set** out);
+typedef struct mvs_derep mvs_derep;
+int mvs_derep_create(mvs_ctx* ctx, int64_t n, mvs_derep** derep);
+int mvs_derep_add_rows(mvs_derep* derep, const mvs_cell* d_cells, int64_t n_cells, int64_t row_begin, int64_t row_end);
+int mvs_pairwise_derep(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double min_jaccard,
+                       mvs_derep* derep);
+int mvs_derep_finish(mvs_derep* derep, const int32_t* order, int mem_order, int32_t* rep_of, int32_t* link_dot, int32_t* link_q,
+                     int32_t* sizes, int mem_out, int64_t* n_reps);
+int mvs_derep_destroy(mvs_derep* derep);
+int mvs_ctx_derep_stats(const mvs_ctx* ctx, double* compare_ms, double* greedy_ms, int64_t* edges, int64_t* row_blocks,
+                        int64_t* rounds);
+int mvs_dereplicate(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double min_jaccard,
+                    const int32_t* order, int32_t* rep_of, int32_t* link_dot, int32_t* link_q, int32_t* sizes, int mem_out,
+                    int64_t* n_reps);
+
 /* ---- exact hash-set intersections for kept pairs --------------------------------------------------------------------------
  * Everything above reports the ESTIMATE of a pair: dot, q, the top-k lists and the clusters are exact with respect to the
  * reference's arithmetic, which estimates |A n B| from two +-1 random projections.  These calls compute the quantity itself

@@ -121,6 +121,15 @@ SYMBOLS = [
     ("mvs_linkage_destroy", _c.c_int, [_P]),
     ("mvs_ctx_linkage_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                           _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_sketch_set_gather", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_int64, _c.POINTER(_P)]),
+    ("mvs_derep_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
+    ("mvs_derep_add_rows", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64]),
+    ("mvs_pairwise_derep", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
+    ("mvs_derep_finish", _c.c_int, [_P, _P, _c.c_int, _P, _P, _P, _P, _c.c_int, _c.POINTER(_c.c_int64)]),
+    ("mvs_derep_destroy", _c.c_int, [_P]),
+    ("mvs_ctx_derep_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
+                                        _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_dereplicate", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P, _P, _P, _P, _P, _c.c_int, _c.POINTER(_c.c_int64)]),
     ("mvs_hash_set_create", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_hash_set_info", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int)]),
     ("mvs_hash_set_sizes", _c.c_int, [_P, _P, _c.c_int]),
@@ -261,6 +270,16 @@ class SketchSet:
         _check(self.ctx.lib.mvs_sketch_set_fill_stats(self._h, p, eb, m, int(row_offset), n, ctypes.byref(mx)))
         return mx.value
 
+    def gather(self, rows):
+        """-> a new SketchSet whose row i is row rows[i] of this one (mvs_sketch_set_gather): same d and limb code, rows may
+        repeat; rows: int32 indices, numpy or a torch tensor (host or device).  A row outside [0, n) raises MVS_E_RANGE."""
+        rp, rm, rk = _buf(rows) if _is_torch(rows) else _buf(rows, np.int32)
+        if _is_torch(rows) and str(rows.dtype) != "torch.int32":
+            raise ValueError("rows must be int32")
+        h = _P()
+        _check(self.ctx.lib.mvs_sketch_set_gather(self.ctx._h, self._h, rp, rm, len(rows), ctypes.byref(h)))
+        return SketchSet(self.ctx, h)
+
     def touch(self):
         """the caller has rewritten the planes: data the library derived from them is rebuilt on the next comparison"""
         _check(self.ctx.lib.mvs_sketch_set_touch(self._h))
@@ -334,6 +353,99 @@ class Cluster:
     def close(self):
         if self._h:
             self.ctx.lib.mvs_cluster_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DerepResult:
+    """What Derep.finish / Context.dereplicate return: numpy int32 arrays over the samples -- `rep_of` (the sample's
+    representative, itself for a representative), `link_dot` / `link_q` (dot and q of the cell (i, rep_of[i]); 0 and -1 for a
+    representative), `sizes` (samples assigned to i, itself included; 0 for a member) -- and `is_rep`, `representatives` (the
+    ascending indices), `n_representatives`."""
+
+    def __init__(self, rep_of, link_dot, link_q, sizes):
+        self.rep_of, self.link_dot, self.link_q, self.sizes = rep_of, link_dot, link_q, sizes
+        self.is_rep = rep_of == np.arange(len(rep_of), dtype=np.int32)
+        self.representatives = np.flatnonzero(self.is_rep).astype(np.int32)
+        self.n_representatives = len(self.representatives)
+
+    def jaccard(self, norms_sq, d):
+        """the fp64 Jaccard estimate of every sample to its representative, in mvs_pairwise_topk's order of operations
+        (inter = dot / d; J = inter / (n2[i] + n2[rep] - inter)); 1.0 for a representative"""
+        n2 = np.asarray(norms_sq, dtype=np.float64)
+        inter = self.link_dot.astype(np.float64) / float(d)
+        with np.errstate(all="ignore"):
+            j = inter / (n2 + n2[self.rep_of] - inter)
+        j[self.is_rep] = 1.0
+        return j
+
+    def __repr__(self):
+        return "DerepResult(%d samples, %d representatives, largest %d)" % (
+            len(self.rep_of), self.n_representatives, int(self.sizes.max()) if len(self.sizes) else 0)
+
+
+class Derep:
+    """Greedy dereplication of n samples in ROW order (mvs_derep): row 0 goes first, a row becomes a representative iff no
+    representative before it is linked to it.  Feed it row block by row block with add_rows (each list holds every cell
+    (r, c), c < r, of the block's rows) or in one go with Context.derep_into, read it with finish."""
+
+    def __init__(self, ctx, n):
+        self.ctx, self.n = ctx, int(n)
+        h = _P()
+        _check(ctx.lib.mvs_derep_create(ctx._h, self.n, ctypes.byref(h)))
+        self._h = h
+        ctx._dereps.add(self)
+
+    def add_rows(self, cells, row_begin, row_end, n_cells=None):
+        """cells: torch CUDA tensor (int32 [m, 4]; the first n_cells rows, default all) or a device address (int) with n_cells:
+        the cells of rows [row_begin, row_end); row_begin must continue the rows decided so far"""
+        if _is_torch(cells):
+            cp, cm, ck = _buf(cells)
+            if cm != MEM_DEVICE:
+                raise ValueError("cells must be a device buffer")
+            if n_cells is None:
+                n_cells = cells.shape[0]
+            elif n_cells > cells.shape[0]:
+                raise ValueError("n_cells beyond the tensor")
+        else:
+            if n_cells is None:
+                raise ValueError("a raw device pointer needs n_cells")
+            cp = _P(int(cells)) if int(cells) else None
+        _check(self.ctx.lib.mvs_derep_add_rows(self._h, cp, int(n_cells), int(row_begin), int(row_end)))
+
+    def finish(self, order=None):
+        """-> DerepResult in the caller's index space: order (int32 permutation, numpy or torch; None = identity) says which
+        sample each row is"""
+        op, om = None, MEM_HOST
+        if order is not None:
+            op, om, ok = _buf(order) if _is_torch(order) else _buf(order, np.int32)
+            if len(order) != self.n:
+                raise ValueError("order must have n entries")
+        n = self.n
+        rep_of, link_dot = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        link_q, sizes = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        count = _c.c_int64()
+        _check(self.ctx.lib.mvs_derep_finish(self._h, op, om, rep_of.ctypes.data, link_dot.ctypes.data, link_q.ctypes.data,
+                                             sizes.ctypes.data, MEM_HOST, ctypes.byref(count)))
+        res = DerepResult(rep_of, link_dot, link_q, sizes)
+        assert res.n_representatives == count.value
+        return res
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.mvs_derep_destroy(self._h)
             self._h = None
 
     def __enter__(self):
@@ -616,6 +728,7 @@ class Context:
         self._comms = weakref.WeakSet()  # communicators likewise
         self._clusters = weakref.WeakSet()
         self._linkages = weakref.WeakSet()
+        self._dereps = weakref.WeakSet()
         self._hash_sets = weakref.WeakSet()
         if stream is not None:
             self.set_stream(stream)
@@ -629,6 +742,8 @@ class Context:
             for k in list(self._clusters):
                 k.close()
             for k in list(self._linkages):
+                k.close()
+            for k in list(self._dereps):
                 k.close()
             for k in list(self._hash_sets):
                 k.close()
@@ -1214,6 +1329,44 @@ class Context:
         _check(self.lib.mvs_ctx_linkage_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n),
                                               ctypes.byref(r)))
         return {"compare_ms": a.value, "forest_ms": b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
+
+    # ---- greedy dereplication (include/mvs_hip.h "greedy dereplication") ----
+    def derep_into(self, derep, sset, norms_sq, min_jaccard):
+        """mvs_pairwise_derep: compare `sset` with itself at Jaccard > min_jaccard (0 < min_jaccard < 1) and decide every row
+        of `derep` in ROW order, row block by row block, on the device"""
+        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        _check(self.lib.mvs_pairwise_derep(self._h, sset._h, np_, nm, float(min_jaccard), derep._h))
+
+    def dereplicate(self, sset, norms_sq, min_jaccard, order=None):
+        """Greedy dereplication of the samples of `sset` at Jaccard > min_jaccard -> DerepResult (rep_of, link_dot, link_q,
+        sizes, is_rep, representatives, n_representatives): every member is linked to its representative, no two
+        representatives are linked.  order: an int32 permutation, order[0] goes first; None = the largest norms_sq first, equal
+        norms by the smaller index, NaN last.  Exact: equal to the sequential walk.  No cell leaves the device."""
+        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        op = None
+        if order is not None:
+            order = np.ascontiguousarray(order.cpu().numpy() if _is_torch(order) else order, dtype=np.int32)
+            if order.shape != (sset.n,):
+                raise MvsError(MVS_E_INVALID, "order must have n entries")
+            op = order.ctypes.data
+        n = sset.n
+        rep_of, link_dot = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        link_q, sizes = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        count = _c.c_int64()
+        _check(self.lib.mvs_dereplicate(self._h, sset._h, np_, nm, float(min_jaccard), op, rep_of.ctypes.data,
+                                        link_dot.ctypes.data, link_q.ctypes.data, sizes.ctypes.data, MEM_HOST, ctypes.byref(count)))
+        res = DerepResult(rep_of, link_dot, link_q, sizes)
+        assert res.n_representatives == count.value
+        return res
+
+    def derep_stats(self):
+        """-> dict since this context's last Derep was created: compare_ms / greedy_ms (kernel times, timing on), edges (cells
+        with row != col consumed), row_blocks, rounds (most scan -> decide rounds a row block needed)"""
+        a, b = _c.c_double(), _c.c_double()
+        e, n, r = _c.c_int64(), _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_derep_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n),
+                                            ctypes.byref(r)))
+        return {"compare_ms": a.value, "greedy_ms": b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
 
     # ---- exact hash-set intersections (include/mvs_hip.h "exact hash-set intersections") ----
     def hash_set(self, hashes, offsets):

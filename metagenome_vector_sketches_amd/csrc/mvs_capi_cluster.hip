@@ -80,10 +80,11 @@ namespace mvs_capi {
 
 // The threshold comparison of a sketch set with itself at level min_jaccard, row block by row block: each block's unsorted
 // cells (every ordered pair of linked samples exactly once) are handed to `consume` while they sit in the staging buffer.
-// Shared by mvs_pairwise_cluster and mvs_pairwise_linkage (mvs_capi_linkage.hip): one launch, one staging buffer, one halving
-// and grow rule.  d_n2: the norms on the device; *compare_ms (timing on) and *row_blocks are added to.
+// Shared by mvs_pairwise_cluster, mvs_pairwise_linkage (mvs_capi_linkage.hip) and mvs_pairwise_derep (mvs_capi_derep.hip): one
+// launch, one staging buffer, one halving and grow rule.  `consume` is also told the block's rows [rb, re): the blocks come in
+// ascending order.  d_n2: the norms on the device; *compare_ms (timing on) and *row_blocks are added to.
 int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, double min_jaccard, double* compare_ms, long long* row_blocks,
-                  const std::function<int(const mvs_cell*, int64_t)>& consume) {
+                  const std::function<int(const mvs_cell*, int64_t, int64_t, int64_t)>& consume) {
     const int64_t n = s->n;
     // J > t  <=>  double(P)/d > t/(1+t) * (n2r + n2c): mvs_search_block's coefficient
     const double coeff = min_jaccard / (1.0 + min_jaccard);
@@ -129,7 +130,7 @@ int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, doubl
             if (rc) return rc;
             continue;
         }
-        rc = consume((const mvs_cell*)c->pw_tmp, (int64_t)count);
+        rc = consume((const mvs_cell*)c->pw_tmp, (int64_t)count, rb, re);
         if (rc) return rc;
         ++*row_blocks;
         rb = re;
@@ -198,7 +199,7 @@ int mvs_pairwise_cluster(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
         d_n2 = (const double*)dn.p;
     }
     return pairwise_feed(c, s, d_n2, min_jaccard, &c->cl_compare_ms, &c->cl_blocks,
-                         [k](const mvs_cell* d_cells, int64_t n_cells) { return consume_cells(k, d_cells, n_cells); });
+                         [k](const mvs_cell* d_cells, int64_t n_cells, int64_t, int64_t) { return consume_cells(k, d_cells, n_cells); });
 }
 
 int mvs_cluster_finish(mvs_cluster* k, const double* norms_sq, int mem_norms, int32_t* labels, int32_t* degree,

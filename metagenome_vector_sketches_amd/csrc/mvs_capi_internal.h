@@ -159,6 +159,9 @@ struct mvs_ctx {
     // ... and the linkage calls since the last mvs_linkage_create (mvs_ctx_linkage_stats)
     double lk_compare_ms = 0.0, lk_forest_ms = 0.0;
     long long lk_edges = 0, lk_blocks = 0, lk_rounds = 0;
+    // ... and the dereplication calls since the last mvs_derep_create (mvs_ctx_derep_stats)
+    double dr_compare_ms = 0.0, dr_greedy_ms = 0.0;
+    long long dr_edges = 0, dr_blocks = 0, dr_rounds = 0;
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
     // did (mvs_ctx_intersect_stats)
     void* ix_work = nullptr;    size_t ix_work_bytes = 0;
@@ -297,9 +300,10 @@ int pairwise_launch(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int
                     const PackedOut* po = nullptr, const DenseOut* dn = nullptr, const mvs::Options* o = nullptr);
 
 // ---- mvs_capi_cluster.hip ----
-// the threshold comparison of a set with itself at a Jaccard level, each row block's unsorted cells handed to `consume`
+// the threshold comparison of a set with itself at a Jaccard level, each row block's unsorted cells handed to
+// consume(cells, n_cells, row_begin, row_end); the blocks arrive in ascending row order and tile [0, n)
 int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, double min_jaccard, double* compare_ms, long long* row_blocks,
-                  const std::function<int(const mvs_cell*, int64_t)>& consume);
+                  const std::function<int(const mvs_cell*, int64_t, int64_t, int64_t)>& consume);
 }  // namespace mvs_capi
 
 #endif

@@ -211,7 +211,7 @@ int mvs_pairwise_linkage(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
         d_n2 = (const double*)dn.p;
     }
     return pairwise_feed(c, s, d_n2, min_jaccard, &c->lk_compare_ms, &c->lk_blocks,
-                         [k](const mvs_cell* d_cells, int64_t n_cells) { return consume_cells(k, d_cells, n_cells); });
+                         [k](const mvs_cell* d_cells, int64_t n_cells, int64_t, int64_t) { return consume_cells(k, d_cells, n_cells); });
 }
 
 int mvs_linkage_finish(mvs_linkage* k, mvs_link* links, int64_t capacity, int mem_out, int64_t* n_links) {

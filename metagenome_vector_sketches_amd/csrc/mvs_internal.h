@@ -315,6 +315,37 @@ int link_sorted(hipStream_t stream, const LinkState& s, mvs_link* d_tmp, mvs_lin
                 size_t* scratch_needed);
 int launch_link_cells(hipStream_t stream, const mvs_link* d_links, int64_t n_links, double level, mvs_cell* d_cells, int64_t capacity,
                       unsigned long long* d_counters);
+// greedy dereplication over device cell lists in rank space (mvs_derep.hip): rows arrive block by block in ascending order.
+// Per block: pre (cells against the rows before the block; counts the fed cells), then rounds of scan + decide until no row
+// of the block is undecided, a last scan (members decided early may still find an earlier representative), link.
+// d_counters (8 words): [0] fed cells with row != col in range, [1] fed cells naming a row outside the block or a column
+// outside [0, n), [2] rows of the block still undecided after a decide, [3] representatives (finish), [4] entries of an order
+// that is no permutation (finish)
+constexpr int32_t kDerepUndecided = 0, kDerepRep = 1, kDerepMember = 2;
+constexpr int32_t kDerepNone = 0x7fffffff;      // assign[r]: no representative linked to r has been seen
+struct DerepState {
+    int64_t n = 0;
+    int32_t* state = nullptr;                 // n each
+    int32_t* assign = nullptr;                // the earliest representative linked to the row so far
+    int32_t* blocked = nullptr;               // the last round in which the row had an undecided earlier neighbour
+    int2* link = nullptr;                     // (dot, q) of the cell (row, assign[row]); (0, -1) for a representative
+    unsigned long long* counters = nullptr;
+};
+int launch_derep_init(hipStream_t stream, const DerepState& s);
+int launch_derep_pre(hipStream_t stream, const DerepState& s, const mvs_cell* d_cells, int64_t n_cells, int64_t rb, int64_t re);
+int launch_derep_scan(hipStream_t stream, const DerepState& s, const mvs_cell* d_cells, int64_t n_cells, int64_t rb, int64_t re,
+                      int round);
+int launch_derep_decide(hipStream_t stream, const DerepState& s, int64_t rb, int64_t re, int round);
+int launch_derep_link(hipStream_t stream, const DerepState& s, const mvs_cell* d_cells, int64_t n_cells, int64_t rb, int64_t re);
+// order == NULL: identity.  check: marks (n int32, zeroed) count how often each sample is named -> counters[4];
+// scatter: rows -> the caller's samples (d_sizes zeroed by the caller), representatives -> counters[3]
+int launch_derep_order_check(hipStream_t stream, const int32_t* d_order, int64_t n, int32_t* d_marks, unsigned long long* d_counters);
+int launch_derep_scatter(hipStream_t stream, const DerepState& s, const int32_t* d_order, int32_t* d_rep_of, int32_t* d_link_dot,
+                         int32_t* d_link_q, int32_t* d_sizes);
+// row i of dst (n_rows rows of row_bytes bytes, a multiple of 16) = row d_rows[i] of src; rows outside [0, n_src) are counted in
+// *d_bad and left alone
+int launch_gather_rows(hipStream_t stream, const int8_t* d_src, int64_t n_src, const int32_t* d_rows, int64_t n_rows, int64_t row_bytes,
+                       int8_t* d_dst, unsigned long long* d_bad);
 // two-stage comparison for two base-256 limbs: coarse plane + row statistics from the limb planes,
 // per-call filter constants, the one-pass filter
 // that appends candidate pairs, and the exact re-check of the candidates that appends kept cells
