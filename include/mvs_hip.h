@@ -818,6 +818,8 @@ int mvs_cells_sort_rows_ahead(mvs_ctx* ctx, const mvs_cell* cells_in, int64_t in
  * records, through the same callbacks under the same rules (pinned buffers of the library, a worker thread, a non-zero return
  * aborts).  A process that owns several shards (src/pairwise_comp_optimized.cpp:937-940: one row range each) compares the union
  * of their rows ONCE and calls this per shard folder with that shard's row range; cells outside the range are skipped.
+ * The contract the kernels rely on (they index by these values, nothing checks them): the cells are ordered by (row, col) with
+ * the columns strictly ascending inside a row, 0 <= col < 2^31 and 0 <= q <= 65535 (q is kept in 16 bits and truncated).
  * *n_delivered (optional): the cells handed over.  Synchronous.  Writer loop replaced: src/pairwise_comp_optimized.cpp:700-790. */
 int mvs_cells_stream(mvs_ctx* ctx, const mvs_cell* cells, int64_t n_cells, int64_t row_begin, int64_t row_end,
                      mvs_row_block_cb cb, void* user, int64_t* n_delivered);

@@ -243,6 +243,98 @@ def _buf(x, dtype=None, writable=False):
     return a.ctypes.data, MEM_HOST, a
 
 
+class _Pieces:
+    """What the streaming calls share: a ctypes callback that copies every piece out of the library's pinned buffer (an
+    exception inside it must not unwind through the C frames: it is kept and raised after the call)."""
+
+    def __init__(self, cb_type):
+        self.parts, self.errors = [], []
+        self.cb = cb_type(self._trampoline)
+
+    def _trampoline(self, _user, bp):
+        try:
+            return self.take(bp.contents)
+        except BaseException as e:      # noqa: BLE001
+            self.errors.append(e)
+            return -1
+
+    def check(self, rc):
+        if self.errors:
+            raise self.errors[0]
+        _check(rc)
+
+
+class _RowBlockPieces(_Pieces):
+    """CSR pieces (mvs_row_block) of mvs_pairwise_stream / mvs_cells_stream"""
+
+    def __init__(self, on_block):
+        super().__init__(ROW_BLOCK_CB)
+        self.on_block = on_block
+
+    def take(self, b):
+        rows, n = b.row_end - b.row_begin, b.n_cells
+        rp = np.ctypeslib.as_array(b.row_ptr, shape=(rows + 1,)).copy()
+        col = np.ctypeslib.as_array(b.col, shape=(n,)).copy() if n else np.empty(0, np.int32)
+        if n == 0:
+            q = np.empty(0, np.uint8)
+        elif b.q:
+            q = np.ctypeslib.as_array(b.q, shape=(n,)).copy()
+        else:
+            q = np.ctypeslib.as_array(b.q16, shape=(n,)).copy()
+        if self.on_block is not None:
+            return 1 if self.on_block(b.row_begin, b.row_end, rp, col, q) else 0
+        self.parts.append((b.row_begin, b.row_end, rp, col, q))
+        return 0
+
+    def join(self, row_begin, row_end, count):
+        parts = self.parts
+        rows = row_end - row_begin
+        row_ptr = np.zeros(rows + 1, dtype=np.int64)
+        at, expect = 0, row_begin
+        for (b0, b1, rp, col, q) in parts:
+            assert b0 == expect and rp[0] == 0, "pieces must arrive in ascending row order, each row once"
+            row_ptr[b0 - row_begin:b1 - row_begin + 1] = rp + at
+            at += int(rp[-1])
+            expect = b1
+        assert expect == row_end and at == count
+        wide = any(p[4].dtype == np.uint16 for p in parts)
+        col = np.concatenate([p[3] for p in parts]) if parts else np.empty(0, np.int32)
+        q = np.concatenate([p[4].astype(np.uint16 if wide else np.uint8) for p in parts]) if parts else np.empty(0, np.uint8)
+        return {"row_ptr": row_ptr, "col": col, "q": None if wide else q, "q16": q if wide else None, "n_cells": count,
+                "pieces": len(parts)}
+
+
+class _EncodedPieces(_Pieces):
+    """pieces of finished shard records (mvs_encoded_rows) of mvs_pairwise_stream_encoded / mvs_cells_stream_encoded"""
+
+    def __init__(self):
+        super().__init__(ENCODED_ROWS_CB)
+
+    def take(self, b):
+        r, nb = b.n_rows, b.n_bytes
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.empty(0, dt)
+        self.parts.append((b.row_begin, b.row_end, arr(b.rows, r, np.uint32), arr(b.first_col, r, np.uint32),
+                           arr(b.offset, r, np.uint64), arr(b.jac_bytes, r, np.uint32), arr(b.bytes, nb, np.uint8), b.n_cells))
+        return 0
+
+    def join(self, row_begin, row_end, count):
+        parts = self.parts
+        expect, at = row_begin, 0
+        offs = []
+        for p in parts:
+            assert p[0] == expect, "pieces must arrive in ascending row order"
+            expect = p[1]
+            offs.append(p[4] + np.uint64(at))
+            at += len(p[6])
+        assert expect == row_end and sum(p[7] for p in parts) == count
+        cat = lambda i, dt: np.concatenate([p[i] for p in parts]) if parts else np.empty(0, dt)   # noqa: E731
+        return {"rows": cat(2, np.uint32), "first_col": cat(3, np.uint32),
+                "offset": np.concatenate(offs) if offs else np.empty(0, np.uint64), "jac_bytes": cat(5, np.uint32),
+                "bytes": cat(6, np.uint8), "n_cells": count, "pieces": len(parts)}
+
+
 class SketchSet:
     """Limb planes of N samples resident in HBM (mvs_sketch_set)."""
 
@@ -1008,50 +1100,15 @@ class Context:
         if row_end is None:
             row_end = sset.n
         np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
-        parts, errors = [], []
-
-        def trampoline(_user, bp):
-            try:
-                b = bp.contents
-                rows, n = b.row_end - b.row_begin, b.n_cells
-                rp = np.ctypeslib.as_array(b.row_ptr, shape=(rows + 1,)).copy()
-                col = np.ctypeslib.as_array(b.col, shape=(n,)).copy() if n else np.empty(0, np.int32)
-                if n == 0:
-                    q = np.empty(0, np.uint8)
-                elif b.q:
-                    q = np.ctypeslib.as_array(b.q, shape=(n,)).copy()
-                else:
-                    q = np.ctypeslib.as_array(b.q16, shape=(n,)).copy()
-                if on_block is not None:
-                    return 1 if on_block(b.row_begin, b.row_end, rp, col, q) else 0
-                parts.append((b.row_begin, b.row_end, rp, col, q))
-                return 0
-            except BaseException as e:      # noqa: BLE001 -- an exception must not unwind through the C frames
-                errors.append(e)
-                return -1
-
-        cb = ROW_BLOCK_CB(trampoline)
+        pieces = _RowBlockPieces(on_block)
         count = _c.c_int64()
         rc = self.lib.mvs_pairwise_stream(self._h, sset._h, np_, nm, keep_mode, int(row_begin), int(row_end),
-                                          int(device_budget_bytes), cb, None, ctypes.byref(count))
-        if errors:
-            raise errors[0]
-        _check(rc)
+                                          int(device_budget_bytes), pieces.cb, None, ctypes.byref(count))
+        pieces.check(rc)
         if on_block is not None:
             return count.value
-        rows = row_end - row_begin
-        row_ptr = np.zeros(rows + 1, dtype=np.int64)
-        at, expect = 0, row_begin
-        for (b0, b1, rp, col, q) in parts:
-            assert b0 == expect and rp[0] == 0, "pieces must arrive in ascending row order, each row once"
-            row_ptr[b0 - row_begin:b1 - row_begin + 1] = rp + at
-            at += int(rp[-1])
-            expect = b1
-        assert expect == row_end and at == count.value
-        wide = any(p[4].dtype == np.uint16 for p in parts)
-        col = np.concatenate([p[3] for p in parts]) if parts else np.empty(0, np.int32)
-        q = np.concatenate([p[4].astype(np.uint16 if wide else np.uint8) for p in parts]) if parts else np.empty(0, np.uint8)
-        return row_ptr, col, q, count.value
+        got = pieces.join(row_begin, row_end, count.value)
+        return got["row_ptr"], got["col"], got["q"] if got["q"] is not None else got["q16"], count.value
 
     def pairwise_stream_encoded(self, sset, norms_sq, row_begin=0, row_end=None, keep_mode=KEEP_INT32, device_budget_bytes=0):
         """mvs_pairwise_stream_encoded, pieces collected: returns dict(rows uint32 [R], first_col uint32 [R], offset uint64
@@ -1059,41 +1116,50 @@ class Context:
         if row_end is None:
             row_end = sset.n
         np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
-        parts, errors = [], []
-
-        def trampoline(_user, bp):
-            try:
-                b = bp.contents
-                r, nb = b.n_rows, b.n_bytes
-
-                def arr(ptr, n, dt):
-                    return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.empty(0, dt)
-                parts.append((b.row_begin, b.row_end, arr(b.rows, r, np.uint32), arr(b.first_col, r, np.uint32),
-                              arr(b.offset, r, np.uint64), arr(b.jac_bytes, r, np.uint32), arr(b.bytes, nb, np.uint8), b.n_cells))
-                return 0
-            except BaseException as e:      # noqa: BLE001
-                errors.append(e)
-                return -1
-
-        cb = ENCODED_ROWS_CB(trampoline)
+        pieces = _EncodedPieces()
         count = _c.c_int64()
         rc = self.lib.mvs_pairwise_stream_encoded(self._h, sset._h, np_, nm, keep_mode, int(row_begin), int(row_end),
-                                                  int(device_budget_bytes), cb, None, ctypes.byref(count))
-        if errors:
-            raise errors[0]
-        _check(rc)
-        expect, at = row_begin, 0
-        offs = []
-        for p in parts:
-            assert p[0] == expect, "pieces must arrive in ascending row order"
-            expect = p[1]
-            offs.append(p[4] + np.uint64(at))
-            at += len(p[6])
-        assert expect == row_end and sum(p[7] for p in parts) == count.value
-        cat = lambda i, dt: np.concatenate([p[i] for p in parts]) if parts else np.empty(0, dt)   # noqa: E731
-        return {"rows": cat(2, np.uint32), "first_col": cat(3, np.uint32),
-                "offset": np.concatenate(offs) if offs else np.empty(0, np.uint64), "jac_bytes": cat(5, np.uint32),
-                "bytes": cat(6, np.uint8), "n_cells": count.value, "pieces": len(parts)}
+                                                  int(device_budget_bytes), pieces.cb, None, ctypes.byref(count))
+        pieces.check(rc)
+        return pieces.join(row_begin, row_end, count.value)
+
+    def _device_cells(self, cells):
+        """-> (device pointer or None, number of cells, keepalive) of a sorted cell list: a torch int32 device tensor [m, 4]
+        (row, col, dot, q) as cells_sort takes it, or a numpy CELL_DTYPE array, which is uploaded"""
+        if not _is_torch(cells):
+            import torch
+            a = np.ascontiguousarray(cells)
+            if a.dtype != CELL_DTYPE:
+                raise ValueError("cells must be CELL_DTYPE records or a torch int32 device tensor [m, 4]")
+            cells = torch.from_numpy(a.view("<i4").reshape(-1, 4)).to(torch.device("cuda", self.device))
+        if str(cells.dtype) != "torch.int32" or cells.dim() != 2 or cells.shape[1] != 4:
+            raise ValueError("cells must be int32 [m, 4]")
+        cp, cm, ck = _buf(cells)
+        if cm != MEM_DEVICE:
+            raise ValueError("cells must be a device buffer")
+        return (_P(cp) if cells.shape[0] else None), int(cells.shape[0]), ck
+
+    def cells_stream(self, cells, row_begin, row_end):
+        """mvs_cells_stream, pieces collected: rows [row_begin, row_end) of a cell list ordered by (row, col) as CSR arrays.
+        cells: torch int32 device tensor [m, 4] (row, col, dot, q) or a numpy CELL_DTYPE array (uploaded).  Returns
+        dict(row_ptr int64 [rows + 1], col int32 [n], q uint8 [n] or None, q16 uint16 [n] or None -- the one the pieces came
+        with --, n_cells, pieces)."""
+        cp, m, _keepalive = self._device_cells(cells)      # holds the uploaded tensor until the call has returned
+        pieces = _RowBlockPieces(None)
+        count = _c.c_int64()
+        rc = self.lib.mvs_cells_stream(self._h, cp, m, int(row_begin), int(row_end), pieces.cb, None, ctypes.byref(count))
+        pieces.check(rc)
+        return pieces.join(row_begin, row_end, count.value)
+
+    def cells_stream_encoded(self, cells, row_begin, row_end):
+        """mvs_cells_stream_encoded, pieces collected: the shard records of rows [row_begin, row_end) of a cell list ordered
+        by (row, col); cells as for cells_stream.  Returns the dict pairwise_stream_encoded returns."""
+        cp, m, _keepalive = self._device_cells(cells)      # holds the uploaded tensor until the call has returned
+        pieces = _EncodedPieces()
+        count = _c.c_int64()
+        rc = self.lib.mvs_cells_stream_encoded(self._h, cp, m, int(row_begin), int(row_end), pieces.cb, None, ctypes.byref(count))
+        pieces.check(rc)
+        return pieces.join(row_begin, row_end, count.value)
 
     def stream_stats(self):
         """what the last pairwise_stream did: dict(kernel_ms, bytes, row_blocks, pieces, two_stage: 0 exact kernel, 1 two-stage as one list, 2 two-stage through the dense byte matrix)"""
