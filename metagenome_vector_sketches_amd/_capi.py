@@ -243,6 +243,52 @@ def _buf(x, dtype=None, writable=False):
     return a.ctypes.data, MEM_HOST, a
 
 
+def _norms(norms_sq):
+    """_buf of n squared norms: a torch tensor as it is (host or device), anything else as a float64 array"""
+    return _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+
+
+def _cell_list(cells, n_cells):
+    """-> (device pointer, n_cells, keepalive) of a device cell list: a torch CUDA tensor (int32 [m, 4]; the first n_cells
+    rows, default all) or a device address (int) with n_cells"""
+    if _is_torch(cells):
+        cp, cm, ck = _buf(cells)
+        if cm != MEM_DEVICE:
+            raise ValueError("cells must be a device buffer")
+        if n_cells is None:
+            n_cells = cells.shape[0]
+        elif n_cells > cells.shape[0]:
+            raise ValueError("n_cells beyond the tensor")
+        return cp, int(n_cells), ck
+    if n_cells is None:
+        raise ValueError("a raw device pointer needs n_cells")
+    return (_P(int(cells)) if int(cells) else None), int(n_cells), None
+
+
+class _Handle:
+    """An object of the library held through its handle `_h` on the context `ctx`: close() destroys it once, through the
+    library function `_destroy` names; a context manager; closed when collected."""
+    _destroy = None
+
+    def close(self):
+        if self._h:
+            getattr(self.ctx.lib, self._destroy)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _Pieces:
     """What the streaming calls share: a ctypes callback that copies every piece out of the library's pinned buffer (an
     exception inside it must not unwind through the C frames: it is kept and raised after the call)."""
@@ -335,8 +381,9 @@ class _EncodedPieces(_Pieces):
                 "bytes": cat(6, np.uint8), "n_cells": count, "pieces": len(parts)}
 
 
-class SketchSet:
+class SketchSet(_Handle):
     """Limb planes of N samples resident in HBM (mvs_sketch_set)."""
+    _destroy = "mvs_sketch_set_destroy"
 
     def __init__(self, ctx, handle, keep=None):
         self.ctx, self._h, self._keep = ctx, handle, keep
@@ -376,17 +423,6 @@ class SketchSet:
         """the caller has rewritten the planes: data the library derived from them is rebuilt on the next comparison"""
         _check(self.ctx.lib.mvs_sketch_set_touch(self._h))
 
-    def close(self):
-        if self._h:
-            self.ctx.lib.mvs_sketch_set_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class ClusterResult:
     """What Cluster.finish / Context.cluster return: numpy int32 arrays `labels` (cluster of every sample; clusters numbered
@@ -402,38 +438,28 @@ class ClusterResult:
             len(self.labels), self.n_clusters, int(self.sizes.max()) if self.n_clusters else 0)
 
 
-class Cluster:
+class Cluster(_Handle):
     """Single-linkage clusters of n samples, built on the device from lists of cells (mvs_cluster): every cell (row, col)
     says "these two belong together".  Feed it with add_cells (any device list: the output of Context.search_block /
     pairwise_block, a torch int32 tensor [m, 4] or a raw device pointer) or Context.cluster_into, read it with finish."""
+    _destroy = "mvs_cluster_destroy"
 
     def __init__(self, ctx, n):
         self.ctx, self.n = ctx, int(n)
         h = _P()
         _check(ctx.lib.mvs_cluster_create(ctx._h, self.n, ctypes.byref(h)))
         self._h = h
-        ctx._clusters.add(self)
+        ctx._children.add(self)
 
     def add_cells(self, cells, n_cells=None):
         """cells: torch CUDA tensor (int32 [m, 4]; the first n_cells rows, default all) or a device address (int) with n_cells.
         degree[row] grows by one per cell with row != col: feeding a list twice changes `degree`, nothing else."""
-        if _is_torch(cells):
-            cp, cm, ck = _buf(cells)
-            if cm != MEM_DEVICE:
-                raise ValueError("cells must be a device buffer")
-            if n_cells is None:
-                n_cells = cells.shape[0]
-            elif n_cells > cells.shape[0]:
-                raise ValueError("n_cells beyond the tensor")
-        else:
-            if n_cells is None:
-                raise ValueError("a raw device pointer needs n_cells")
-            cp = _P(int(cells)) if int(cells) else None
-        _check(self.ctx.lib.mvs_cluster_add_cells(self._h, cp, int(n_cells)))
+        cp, n_cells, ck = _cell_list(cells, n_cells)
+        _check(self.ctx.lib.mvs_cluster_add_cells(self._h, cp, n_cells))
 
     def finish(self, norms_sq):
         """-> ClusterResult; norms_sq (n doubles, numpy or torch) decides the representatives"""
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         n = self.n
         labels, degree = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
         reps, sizes = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
@@ -441,24 +467,6 @@ class Cluster:
         _check(self.ctx.lib.mvs_cluster_finish(self._h, np_, nm, labels.ctypes.data, degree.ctypes.data, reps.ctypes.data,
                                                sizes.ctypes.data, MEM_HOST, ctypes.byref(count)))
         return ClusterResult(labels, degree, reps[:count.value].copy(), sizes[:count.value].copy())
-
-    def close(self):
-        if self._h:
-            self.ctx.lib.mvs_cluster_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DerepResult:
@@ -488,34 +496,24 @@ class DerepResult:
             len(self.rep_of), self.n_representatives, int(self.sizes.max()) if len(self.sizes) else 0)
 
 
-class Derep:
+class Derep(_Handle):
     """Greedy dereplication of n samples in ROW order (mvs_derep): row 0 goes first, a row becomes a representative iff no
     representative before it is linked to it.  Feed it row block by row block with add_rows (each list holds every cell
     (r, c), c < r, of the block's rows) or in one go with Context.derep_into, read it with finish."""
+    _destroy = "mvs_derep_destroy"
 
     def __init__(self, ctx, n):
         self.ctx, self.n = ctx, int(n)
         h = _P()
         _check(ctx.lib.mvs_derep_create(ctx._h, self.n, ctypes.byref(h)))
         self._h = h
-        ctx._dereps.add(self)
+        ctx._children.add(self)
 
     def add_rows(self, cells, row_begin, row_end, n_cells=None):
         """cells: torch CUDA tensor (int32 [m, 4]; the first n_cells rows, default all) or a device address (int) with n_cells:
         the cells of rows [row_begin, row_end); row_begin must continue the rows decided so far"""
-        if _is_torch(cells):
-            cp, cm, ck = _buf(cells)
-            if cm != MEM_DEVICE:
-                raise ValueError("cells must be a device buffer")
-            if n_cells is None:
-                n_cells = cells.shape[0]
-            elif n_cells > cells.shape[0]:
-                raise ValueError("n_cells beyond the tensor")
-        else:
-            if n_cells is None:
-                raise ValueError("a raw device pointer needs n_cells")
-            cp = _P(int(cells)) if int(cells) else None
-        _check(self.ctx.lib.mvs_derep_add_rows(self._h, cp, int(n_cells), int(row_begin), int(row_end)))
+        cp, n_cells, ck = _cell_list(cells, n_cells)
+        _check(self.ctx.lib.mvs_derep_add_rows(self._h, cp, n_cells, int(row_begin), int(row_end)))
 
     def finish(self, order=None):
         """-> DerepResult in the caller's index space: order (int32 permutation, numpy or torch; None = identity) says which
@@ -534,24 +532,6 @@ class Derep:
         res = DerepResult(rep_of, link_dot, link_q, sizes)
         assert res.n_representatives == count.value
         return res
-
-    def close(self):
-        if self._h:
-            self.ctx.lib.mvs_derep_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class LinkageResult:
@@ -610,38 +590,28 @@ class LinkageResult:
         return "LinkageResult(%d samples, %d links)" % (self.n, len(self))
 
 
-class Linkage:
+class Linkage(_Handle):
     """The single-linkage tree of n samples, built on the device from lists of cells (mvs_linkage): the maximum spanning
     forest of everything it was fed, under the order (jaccard descending, a, b).  norms_sq (n doubles) and d decide every
     weight.  Feed it with add_cells (any device list with real dots: the output of Context.search_block / pairwise_block, a
     torch int32 tensor [m, 4] or a raw device pointer) or Context.linkage_into; read it with finish or cells."""
+    _destroy = "mvs_linkage_destroy"
 
     def __init__(self, ctx, n, d, norms_sq):
         self.ctx, self.n, self.d = ctx, int(n), int(d)
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         if len(norms_sq) != self.n:
             raise ValueError("norms_sq must hold n values")
         h = _P()
         _check(ctx.lib.mvs_linkage_create(ctx._h, self.n, self.d, np_, nm, ctypes.byref(h)))
         self._h = h
-        ctx._linkages.add(self)
+        ctx._children.add(self)
 
     def add_cells(self, cells, n_cells=None):
         """cells: torch CUDA tensor (int32 [m, 4]; the first n_cells rows, default all) or a device address (int) with n_cells.
         Feeding a list twice changes nothing."""
-        if _is_torch(cells):
-            cp, cm, ck = _buf(cells)
-            if cm != MEM_DEVICE:
-                raise ValueError("cells must be a device buffer")
-            if n_cells is None:
-                n_cells = cells.shape[0]
-            elif n_cells > cells.shape[0]:
-                raise ValueError("n_cells beyond the tensor")
-        else:
-            if n_cells is None:
-                raise ValueError("a raw device pointer needs n_cells")
-            cp = _P(int(cells)) if int(cells) else None
-        _check(self.ctx.lib.mvs_linkage_add_cells(self._h, cp, int(n_cells)))
+        cp, n_cells, ck = _cell_list(cells, n_cells)
+        _check(self.ctx.lib.mvs_linkage_add_cells(self._h, cp, n_cells))
 
     def finish(self, capacity=None):
         """-> LinkageResult.  capacity: room for that many links (default n - 1, which always suffices); too little raises
@@ -673,33 +643,16 @@ class Linkage:
         _check(rc)
         return out, count.value
 
-    def close(self):
-        if self._h:
-            self.ctx.lib.mvs_linkage_destroy(self._h)
-            self._h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HashSet:
+class HashSet(_Handle):
     """Hash lists of n samples resident in HBM, per sample sorted and de-duplicated (mvs_hash_set): what
     Context.intersect_cells intersects.  `n` samples, `total` distinct hashes, `was_sorted`: the input was already strictly
     increasing inside every sample (it is then used as uploaded)."""
+    _destroy = "mvs_hash_set_destroy"
 
     def __init__(self, ctx, handle):
         self.ctx, self._h = ctx, handle
-        ctx._hash_sets.add(self)
+        ctx._children.add(self)
         n, total, ws = _c.c_int64(), _c.c_int64(), _c.c_int()
         _check(ctx.lib.mvs_hash_set_info(handle, ctypes.byref(n), ctypes.byref(total), ctypes.byref(ws)))
         self.n, self.total, self.was_sorted = n.value, total.value, bool(ws.value)
@@ -712,24 +665,6 @@ class HashSet:
         _check(self.ctx.lib.mvs_hash_set_sizes(self._h, op, om))
         return out
 
-    def close(self):
-        if self._h:
-            self.ctx.lib.mvs_hash_set_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 COMM_ID_BYTES = 128
 PLAN_MIRROR_OUTSIDE = 1
@@ -738,9 +673,10 @@ WIRE_MAX_ABS = 32004          # mvs_sketch_set_planes_from_wire: largest |v| for
 PLAN_STALE = 1 << 62          # mvs_plan_finish under option plan_speculate: the cell count of a plan that must run again
 
 
-class Comm:
+class Comm(_Handle):
     """Communicator of the multi-GPU exchange step (mvs_comm): RCCL (one process per GPU), the file transport
     (ranks sharing a device), or caller-supplied collectives."""
+    _destroy = "mvs_comm_destroy"
 
     def __init__(self, ctx, handle, keep=None):
         self.ctx, self._h, self._keep = ctx, handle, keep
@@ -779,17 +715,6 @@ class Comm:
         _check(self.ctx.lib.mvs_allreduce_max_i64(self.ctx._h, self._h, ctypes.byref(v)))
         return v.value
 
-    def close(self):
-        if self._h:
-            self.ctx.lib.mvs_comm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def comm_library():
     """(path, version) of the RCCL the library's communicators use -- bound at run time; raises MvsError without one"""
@@ -818,10 +743,7 @@ class Context:
         self.device = device
         self._sets = weakref.WeakSet()   # sketch sets hold a pointer to the context: close them first
         self._comms = weakref.WeakSet()  # communicators likewise
-        self._clusters = weakref.WeakSet()
-        self._linkages = weakref.WeakSet()
-        self._dereps = weakref.WeakSet()
-        self._hash_sets = weakref.WeakSet()
+        self._children = weakref.WeakSet()   # clusters, linkages, dereplications, hash sets: after those two, before the context
         if stream is not None:
             self.set_stream(stream)
 
@@ -831,13 +753,7 @@ class Context:
                 s.close()
             for m in list(self._comms):
                 m.close()
-            for k in list(self._clusters):
-                k.close()
-            for k in list(self._linkages):
-                k.close()
-            for k in list(self._dereps):
-                k.close()
-            for k in list(self._hash_sets):
+            for k in list(self._children):
                 k.close()
             self.lib.mvs_ctx_destroy(self._h)
             self._h = None
@@ -1071,7 +987,7 @@ class Context:
         and retries on MVS_E_CAPACITY."""
         if row_end is None:
             row_end = sset.n
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         count = _c.c_int64()
         if cells_out is not None:
             cp, cm, ck = _buf(cells_out)
@@ -1099,7 +1015,7 @@ class Context:
         pieces are collected: returns (row_ptr int64 [rows + 1], col int32 [n], q [n], n)."""
         if row_end is None:
             row_end = sset.n
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         pieces = _RowBlockPieces(on_block)
         count = _c.c_int64()
         rc = self.lib.mvs_pairwise_stream(self._h, sset._h, np_, nm, keep_mode, int(row_begin), int(row_end),
@@ -1115,7 +1031,7 @@ class Context:
         [R] into `bytes`, jac_bytes uint32 [R], bytes uint8 [B] = what the shard writer appends to matrix.bin, n_cells)"""
         if row_end is None:
             row_end = sset.n
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         pieces = _EncodedPieces()
         count = _c.c_int64()
         rc = self.lib.mvs_pairwise_stream_encoded(self._h, sset._h, np_, nm, keep_mode, int(row_begin), int(row_end),
@@ -1328,7 +1244,7 @@ class Context:
             row_end = sset.n
         if col_end is None:
             col_end = sset.n
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         flags = TOPK_EXCLUDE_SELF if exclude_self else 0
         count = _c.c_int64()
         if cells_out is not None:
@@ -1349,11 +1265,19 @@ class Context:
         _check(self.lib.mvs_ctx_topk_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)))
         return {"dots_ms": a.value, "select_ms": b.value, "row_blocks": n.value, "block_rows": r.value}
 
+    def _consumer_stats(self, fn, work_key):
+        """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time
+        of the consumer's own kernels"""
+        a, b = _c.c_double(), _c.c_double()
+        e, n, r = _c.c_int64(), _c.c_int64(), _c.c_int64()
+        _check(fn(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n), ctypes.byref(r)))
+        return {"compare_ms": a.value, work_key: b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
+
     # ---- single-linkage clustering (include/mvs_hip.h "Single-linkage clustering") ----
     def cluster_into(self, cluster, sset, norms_sq, min_jaccard):
         """mvs_pairwise_cluster: compare `sset` with itself and feed every pair whose Jaccard estimate exceeds min_jaccard
         (0 < min_jaccard < 1) into `cluster`, on the device"""
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         _check(self.lib.mvs_pairwise_cluster(self._h, sset._h, np_, nm, float(min_jaccard), cluster._h))
 
     def cluster(self, sset, norms_sq, min_jaccard):
@@ -1366,17 +1290,13 @@ class Context:
     def cluster_stats(self):
         """-> dict since this context's last Cluster was created: compare_ms / union_ms (kernel times, timing on), edges
         (cells with row != col consumed), row_blocks, rounds (most hook -> flatten -> verify rounds a list needed)"""
-        a, b = _c.c_double(), _c.c_double()
-        e, n, r = _c.c_int64(), _c.c_int64(), _c.c_int64()
-        _check(self.lib.mvs_ctx_cluster_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n),
-                                              ctypes.byref(r)))
-        return {"compare_ms": a.value, "union_ms": b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
+        return self._consumer_stats(self.lib.mvs_ctx_cluster_stats, "union_ms")
 
     # ---- the single-linkage tree (include/mvs_hip.h "the single-linkage tree") ----
     def linkage_into(self, linkage, sset, norms_sq, min_jaccard):
         """mvs_pairwise_linkage: compare `sset` with itself and feed every pair whose Jaccard estimate exceeds min_jaccard
         (0 < min_jaccard < 1) into `linkage`, on the device"""
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         _check(self.lib.mvs_pairwise_linkage(self._h, sset._h, np_, nm, float(min_jaccard), linkage._h))
 
     def linkage(self, sset, norms_sq, min_jaccard):
@@ -1390,17 +1310,13 @@ class Context:
     def linkage_stats(self):
         """-> dict since this context's last Linkage was created: compare_ms / forest_ms (kernel times, timing on), edges (fed
         cells with row != col), row_blocks, rounds (most Boruvka rounds a list needed)"""
-        a, b = _c.c_double(), _c.c_double()
-        e, n, r = _c.c_int64(), _c.c_int64(), _c.c_int64()
-        _check(self.lib.mvs_ctx_linkage_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n),
-                                              ctypes.byref(r)))
-        return {"compare_ms": a.value, "forest_ms": b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
+        return self._consumer_stats(self.lib.mvs_ctx_linkage_stats, "forest_ms")
 
     # ---- greedy dereplication (include/mvs_hip.h "greedy dereplication") ----
     def derep_into(self, derep, sset, norms_sq, min_jaccard):
         """mvs_pairwise_derep: compare `sset` with itself at Jaccard > min_jaccard (0 < min_jaccard < 1) and decide every row
         of `derep` in ROW order, row block by row block, on the device"""
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         _check(self.lib.mvs_pairwise_derep(self._h, sset._h, np_, nm, float(min_jaccard), derep._h))
 
     def dereplicate(self, sset, norms_sq, min_jaccard, order=None):
@@ -1408,7 +1324,7 @@ class Context:
         sizes, is_rep, representatives, n_representatives): every member is linked to its representative, no two
         representatives are linked.  order: an int32 permutation, order[0] goes first; None = the largest norms_sq first, equal
         norms by the smaller index, NaN last.  Exact: equal to the sequential walk.  No cell leaves the device."""
-        np_, nm, nk = _buf(norms_sq) if _is_torch(norms_sq) else _buf(norms_sq, np.float64)
+        np_, nm, nk = _norms(norms_sq)
         op = None
         if order is not None:
             order = np.ascontiguousarray(order.cpu().numpy() if _is_torch(order) else order, dtype=np.int32)
@@ -1428,11 +1344,7 @@ class Context:
     def derep_stats(self):
         """-> dict since this context's last Derep was created: compare_ms / greedy_ms (kernel times, timing on), edges (cells
         with row != col consumed), row_blocks, rounds (most scan -> decide rounds a row block needed)"""
-        a, b = _c.c_double(), _c.c_double()
-        e, n, r = _c.c_int64(), _c.c_int64(), _c.c_int64()
-        _check(self.lib.mvs_ctx_derep_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n),
-                                            ctypes.byref(r)))
-        return {"compare_ms": a.value, "greedy_ms": b.value, "edges": e.value, "row_blocks": n.value, "rounds": r.value}
+        return self._consumer_stats(self.lib.mvs_ctx_derep_stats, "greedy_ms")
 
     # ---- exact hash-set intersections (include/mvs_hip.h "exact hash-set intersections") ----
     def hash_set(self, hashes, offsets):

@@ -18,11 +18,13 @@
 //   Dereplicated <n> samples at Jaccard > <t>: <R> representatives, <S> singletons, largest <L>
 // Exit codes: 1 bad arguments or DB, 2 device errors.  One GPU (--device, else MVS_DEVICE, else 0).
 #include "mvs_host.hpp"
+#include "mvs_tool.hpp"
 
-namespace fs = std::filesystem;
 using namespace mvs_host;
 
 namespace {
+
+constexpr const char* kProg = "dereplicate_sketches";
 
 struct Options {
     std::string db_folder, output, bad_flag;
@@ -46,7 +48,6 @@ void parse(int argc, char* argv[], Options& o) {
         auto bad = [&](const char* flag) {
             if (o.bad_flag.empty()) o.bad_flag = flag;
         };
-        char* end = nullptr;
         if (a == "--help") {
             o.show_help = true;
         } else if (a == "--db" || a == "--output") {
@@ -58,19 +59,15 @@ void parse(int argc, char* argv[], Options& o) {
             (a == "--db" ? o.have_db : o.have_out) = true;
         } else if (a == "--min_jaccard") {
             o.have_t = true;
-            const std::string v = has_value ? argv[++i] : "";
-            const double t = strtod(v.c_str(), &end);
-            if (v.empty() || end == v.c_str() || *end || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
+            double t = 0.0;
+            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
             else o.min_jaccard = t;
         } else if (a == "--order") {
             const std::string v = has_value ? argv[++i] : "";
             if (v != "norm" && v != "index") bad("--order");
             else o.by_index = v == "index";
         } else if (a == "--device") {
-            const std::string v = has_value ? argv[++i] : "";
-            const long m = strtol(v.c_str(), &end, 10);
-            if (v.empty() || end == v.c_str() || *end || m < 0 || m > 1023) bad("--device");
-            else o.device = (int)m;
+            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
         } else {
             o.unknown = true;
         }
@@ -85,57 +82,6 @@ struct Gpu {
         if (ctx) mvs_ctx_destroy(ctx);
     }
 };
-
-int gpu_fail(const char* what) {
-    std::cerr << "dereplicate_sketches: " << what << ": " << mvs_last_error() << std::endl;
-    return 2;
-}
-
-// vectors.bin -> limb planes, in row chunks straight from the mapping; two limbs unless a chunk's largest |v| asks for more
-int load_db(Gpu& g, const std::string& matrix_file, int elem_bytes, int64_t n, int d) {
-    const int64_t row_bytes = (int64_t)d * elem_bytes;
-    const int64_t chunk_rows = std::max<int64_t>(1, (1LL << 30) / row_bytes);
-    const int fd = ::open(matrix_file.c_str(), O_RDONLY);
-    if (fd < 0) {
-        std::cerr << "Error opening file: " << matrix_file << std::endl;       // :35-38
-        return 1;
-    }
-    const size_t bytes = (size_t)(n * row_bytes);
-    const char* base = nullptr;
-    if (bytes) {
-        void* m = ::mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) {
-            ::close(fd);
-            std::cerr << "Error reading file: " << matrix_file << std::endl;
-            return 1;
-        }
-        ::madvise(m, bytes, MADV_SEQUENTIAL);
-        base = (const char*)m;
-    }
-    ::close(fd);
-    int rc = 0;
-    for (int limbs = 2, attempt = 0; attempt < 4 && !rc; ++attempt) {
-        if (g.set) {
-            mvs_sketch_set_destroy(g.set);
-            g.set = nullptr;
-        }
-        if (mvs_sketch_set_alloc(g.ctx, n, d, limbs, &g.set) != MVS_OK) {
-            rc = gpu_fail("allocating sketch set");
-            break;
-        }
-        int64_t max_abs = 0;
-        for (int64_t r0 = 0; r0 < n && !rc && mvs_limbs_for_max_abs(max_abs) <= limbs; r0 += chunk_rows) {
-            int64_t m = 0;
-            if (mvs_sketch_set_fill_stats(g.set, base + r0 * row_bytes, elem_bytes, MVS_MEM_HOST, r0, std::min(chunk_rows, n - r0), &m) != MVS_OK)
-                rc = gpu_fail("re-coding vectors.bin");
-            max_abs = std::max(max_abs, m);
-        }
-        if (mvs_limbs_for_max_abs(max_abs) <= limbs) break;
-        limbs = mvs_limbs_for_max_abs(max_abs);
-    }
-    if (bytes) ::munmap((void*)base, bytes);
-    return rc;
-}
 
 }  // namespace
 
@@ -157,51 +103,18 @@ int main(int argc, char* argv[]) {
         print_usage(argv[0]);
         return 1;
     }
-    const std::string db_folder = o.db_folder;
-    const std::string norms_file = db_folder + "vector_norms.txt";                // raw concatenation, as :853-891
-    if (!fs::exists(norms_file)) {                                                // :855-858
-        std::cerr << "Error: Required file 'vector_norms.txt' not found in output folder: " << db_folder << std::endl;
-        return 1;
-    }
-    std::string dtype = "int32";
-    {
-        std::ifstream dtype_in(db_folder + "dtype.txt");                          // :859-865
-        if (dtype_in) std::getline(dtype_in, dtype);
-    }
-    int dimension = 0;
-    {
-        std::ifstream dim_in(db_folder + "dimension.txt");                        // :866-873
-        if (dim_in) dim_in >> dimension;
-    }
-    if (dimension <= 0) {
-        std::cerr << "Error: could not read a positive dimension from " << db_folder << "dimension.txt" << std::endl;
-        return 1;
-    }
-    const int elem_bytes = dtype == "int16" ? 2 : 4;
-    const std::string matrix_file = db_folder + "vectors.bin";                    // :891
-    DbInfo db;
-    read_norms(norms_file, db);                                                   // :893-901
-    int64_t file_size = 0;
-    {
-        std::ifstream file(matrix_file, std::ios::ate | std::ios::binary);        // :911-914
-        file_size = file ? (int64_t)file.tellg() : 0;
-    }
-    const int64_t n = file_size / ((int64_t)dimension * elem_bytes);
-    if ((int64_t)db.norms_sq.size() < n) {
-        std::cerr << "Error: vector_norms.txt has " << db.norms_sq.size() << " entries for " << n << " vectors" << std::endl;
-        return 1;
-    }
-    db.norms_sq.resize((size_t)n);
-    db.names.resize((size_t)n);
+    SketchDb sdb;
+    if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
+    const DbInfo& db = sdb.info;
+    const int64_t n = sdb.n;
+    const int dimension = sdb.dimension;
 
     std::vector<int32_t> rep_of((size_t)n), link_dot((size_t)n), link_q((size_t)n), sizes((size_t)n);
     int64_t n_reps = 0;
     if (n > 0) {
         Gpu g;
-        const int device = o.device >= 0 ? o.device : pick_device();
-        if (mvs_ctx_create(device, &g.ctx) != MVS_OK) return gpu_fail("creating context");
-        const int rc = load_db(g, matrix_file, elem_bytes, n, dimension);
-        if (rc) return rc;
+        if (mvs_ctx_create(choose_device(o.device), &g.ctx) != MVS_OK) return gpu_fail(kProg, "creating context");
+        if (const int rc = load_sketch_db(kProg, g.ctx, sdb, &g.set)) return rc;
         std::vector<int32_t> index_order;
         if (o.by_index) {
             index_order.resize((size_t)n);
@@ -209,40 +122,27 @@ int main(int argc, char* argv[]) {
         }
         if (mvs_dereplicate(g.ctx, g.set, db.norms_sq.data(), MVS_MEM_HOST, o.min_jaccard, o.by_index ? index_order.data() : nullptr,
                             rep_of.data(), link_dot.data(), link_q.data(), sizes.data(), MVS_MEM_HOST, &n_reps) != MVS_OK)
-            return gpu_fail("dereplicating");
+            return gpu_fail(kProg, "dereplicating");
     }
     int64_t singletons = 0, largest = 0;
     for (int64_t i = 0; i < n; ++i) {
         singletons += sizes[(size_t)i] == 1;
         largest = std::max<int64_t>(largest, sizes[(size_t)i]);
     }
-    const std::string part = o.output + ".part";
-    {
-        std::ofstream out(part, std::ios::binary | std::ios::trunc);
-        out << "#sample\trepresentative\tjaccard\tsize\n";
-        char buf[64];
-        for (int64_t i = 0; i < n; ++i) {
-            const int32_t r = rep_of[(size_t)i];
-            double j = 1.0;
-            if (r != (int32_t)i) {                                                // the estimate before its clamp, as --top_k scores it
-                const double inter = (double)link_dot[(size_t)i] / (double)dimension;
-                j = inter / (db.norms_sq[(size_t)i] + db.norms_sq[(size_t)r] - inter);
-            }
-            snprintf(buf, sizeof(buf), "%.9g", j);
-            out << db.names[(size_t)i] << '\t' << db.names[(size_t)r] << '\t' << buf << '\t' << sizes[(size_t)r] << '\n';
+    std::ostringstream text;
+    text << "#sample\trepresentative\tjaccard\tsize\n";
+    char buf[64];
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t r = rep_of[(size_t)i];
+        double j = 1.0;
+        if (r != (int32_t)i) {                                                    // the estimate before its clamp, as --top_k scores it
+            const double inter = (double)link_dot[(size_t)i] / (double)dimension;
+            j = inter / (db.norms_sq[(size_t)i] + db.norms_sq[(size_t)r] - inter);
         }
-        out.flush();
-        if (!out) {
-            std::cerr << "dereplicate_sketches: cannot write " << part << std::endl;
-            ::unlink(part.c_str());
-            return 1;
-        }
+        snprintf(buf, sizeof(buf), "%.9g", j);
+        text << db.names[(size_t)i] << '\t' << db.names[(size_t)r] << '\t' << buf << '\t' << sizes[(size_t)r] << '\n';
     }
-    if (::rename(part.c_str(), o.output.c_str()) != 0) {
-        std::cerr << "dereplicate_sketches: cannot rename " << part << " to " << o.output << std::endl;
-        ::unlink(part.c_str());
-        return 1;
-    }
+    if (const int rc = write_then_rename(kProg, o.output, text.str())) return rc;
     std::cout << "Dereplicated " << n << " samples at Jaccard > " << o.min_jaccard << ": " << n_reps << " representatives, " << singletons
               << " singletons, largest " << largest << std::endl;
     return 0;

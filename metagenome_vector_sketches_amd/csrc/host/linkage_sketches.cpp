@@ -17,11 +17,13 @@
 //   Linked <n> samples at Jaccard > <t>: <L> links, <C> components, weakest link <J>        (<J> = "none" without a link)
 // Exit codes: 1 bad arguments or DB, 2 device errors.  One GPU (--device, else MVS_DEVICE, else 0).
 #include "mvs_host.hpp"
+#include "mvs_tool.hpp"
 
-namespace fs = std::filesystem;
 using namespace mvs_host;
 
 namespace {
+
+constexpr const char* kProg = "linkage_sketches";
 
 struct Options {
     std::string db_folder, output, bad_flag;
@@ -45,7 +47,6 @@ void parse(int argc, char* argv[], Options& o) {
         auto bad = [&](const char* flag) {
             if (o.bad_flag.empty()) o.bad_flag = flag;
         };
-        char* end = nullptr;
         if (a == "--help") {
             o.show_help = true;
         } else if (a == "--db" || a == "--output") {
@@ -57,20 +58,15 @@ void parse(int argc, char* argv[], Options& o) {
             (a == "--db" ? o.have_db : o.have_out) = true;
         } else if (a == "--min_jaccard") {
             o.have_t = true;
-            const std::string v = has_value ? argv[++i] : "";
-            const double t = strtod(v.c_str(), &end);
-            if (v.empty() || end == v.c_str() || *end || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
+            double t = 0.0;
+            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
             else o.min_jaccard = t;
         } else if (a == "--cut") {
-            const std::string v = has_value ? argv[++i] : "";
-            const double u = strtod(v.c_str(), &end);
-            if (v.empty() || end == v.c_str() || *end || !(u > 0.0) || !(u < 1.0)) bad("--cut");
+            double u = 0.0;
+            if (!parse_number(has_value ? argv[++i] : "", &u) || !(u > 0.0) || !(u < 1.0)) bad("--cut");
             else o.cuts.push_back(u);
         } else if (a == "--device") {
-            const std::string v = has_value ? argv[++i] : "";
-            const long m = strtol(v.c_str(), &end, 10);
-            if (v.empty() || end == v.c_str() || *end || m < 0 || m > 1023) bad("--device");
-            else o.device = (int)m;
+            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
         } else {
             o.unknown = true;
         }
@@ -95,78 +91,6 @@ struct Gpu {
         if (ctx) mvs_ctx_destroy(ctx);
     }
 };
-
-int gpu_fail(const char* what) {
-    std::cerr << "linkage_sketches: " << what << ": " << mvs_last_error() << std::endl;
-    return 2;
-}
-
-// vectors.bin -> limb planes, in row chunks straight from the mapping; two limbs unless a chunk's largest |v| asks for more
-int load_db(Gpu& g, const std::string& matrix_file, int elem_bytes, int64_t n, int d) {
-    const int64_t row_bytes = (int64_t)d * elem_bytes;
-    const int64_t chunk_rows = std::max<int64_t>(1, (1LL << 30) / row_bytes);
-    const int fd = ::open(matrix_file.c_str(), O_RDONLY);
-    if (fd < 0) {
-        std::cerr << "Error opening file: " << matrix_file << std::endl;       // :35-38
-        return 1;
-    }
-    const size_t bytes = (size_t)(n * row_bytes);
-    const char* base = nullptr;
-    if (bytes) {
-        void* m = ::mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) {
-            ::close(fd);
-            std::cerr << "Error reading file: " << matrix_file << std::endl;
-            return 1;
-        }
-        ::madvise(m, bytes, MADV_SEQUENTIAL);
-        base = (const char*)m;
-    }
-    ::close(fd);
-    int rc = 0;
-    for (int limbs = 2, attempt = 0; attempt < 4 && !rc; ++attempt) {
-        if (g.set) {
-            mvs_sketch_set_destroy(g.set);
-            g.set = nullptr;
-        }
-        if (mvs_sketch_set_alloc(g.ctx, n, d, limbs, &g.set) != MVS_OK) {
-            rc = gpu_fail("allocating sketch set");
-            break;
-        }
-        int64_t max_abs = 0;
-        for (int64_t r0 = 0; r0 < n && !rc && mvs_limbs_for_max_abs(max_abs) <= limbs; r0 += chunk_rows) {
-            int64_t m = 0;
-            if (mvs_sketch_set_fill_stats(g.set, base + r0 * row_bytes, elem_bytes, MVS_MEM_HOST, r0, std::min(chunk_rows, n - r0), &m) != MVS_OK)
-                rc = gpu_fail("re-coding vectors.bin");
-            max_abs = std::max(max_abs, m);
-        }
-        if (mvs_limbs_for_max_abs(max_abs) <= limbs) break;
-        limbs = mvs_limbs_for_max_abs(max_abs);
-    }
-    if (bytes) ::munmap((void*)base, bytes);
-    return rc;
-}
-
-// `text` under <path>.part, then renamed
-int write_file(const std::string& path, const std::string& text) {
-    const std::string part = path + ".part";
-    {
-        std::ofstream out(part, std::ios::binary | std::ios::trunc);
-        out << text;
-        out.flush();
-        if (!out) {
-            std::cerr << "linkage_sketches: cannot write " << part << std::endl;
-            ::unlink(part.c_str());
-            return 1;
-        }
-    }
-    if (::rename(part.c_str(), path.c_str()) != 0) {
-        std::cerr << "linkage_sketches: cannot rename " << part << " to " << path << std::endl;
-        ::unlink(part.c_str());
-        return 1;
-    }
-    return 0;
-}
 
 std::string g17(double v) {
     char buf[64];
@@ -193,69 +117,35 @@ int main(int argc, char* argv[]) {
         print_usage(argv[0]);
         return 1;
     }
-    const std::string db_folder = o.db_folder;
-    const std::string norms_file = db_folder + "vector_norms.txt";                // raw concatenation, as :853-891
-    if (!fs::exists(norms_file)) {                                                // :855-858
-        std::cerr << "Error: Required file 'vector_norms.txt' not found in output folder: " << db_folder << std::endl;
-        return 1;
-    }
-    std::string dtype = "int32";
-    {
-        std::ifstream dtype_in(db_folder + "dtype.txt");                          // :859-865
-        if (dtype_in) std::getline(dtype_in, dtype);
-    }
-    int dimension = 0;
-    {
-        std::ifstream dim_in(db_folder + "dimension.txt");                        // :866-873
-        if (dim_in) dim_in >> dimension;
-    }
-    if (dimension <= 0) {
-        std::cerr << "Error: could not read a positive dimension from " << db_folder << "dimension.txt" << std::endl;
-        return 1;
-    }
-    const int elem_bytes = dtype == "int16" ? 2 : 4;
-    const std::string matrix_file = db_folder + "vectors.bin";                    // :891
-    DbInfo db;
-    read_norms(norms_file, db);                                                   // :893-901
-    int64_t file_size = 0;
-    {
-        std::ifstream file(matrix_file, std::ios::ate | std::ios::binary);        // :911-914
-        file_size = file ? (int64_t)file.tellg() : 0;
-    }
-    const int64_t n = file_size / ((int64_t)dimension * elem_bytes);
-    if ((int64_t)db.norms_sq.size() < n) {
-        std::cerr << "Error: vector_norms.txt has " << db.norms_sq.size() << " entries for " << n << " vectors" << std::endl;
-        return 1;
-    }
-    db.norms_sq.resize((size_t)n);
-    db.names.resize((size_t)n);
+    SketchDb sdb;
+    if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
+    const DbInfo& db = sdb.info;
+    const int64_t n = sdb.n;
 
     std::vector<mvs_link> links((size_t)std::max<int64_t>(n, 1));
     int64_t n_links = 0;
     std::vector<std::string> cut_texts;
     if (n > 0) {
         Gpu g;
-        const int device = o.device >= 0 ? o.device : pick_device();
-        if (mvs_ctx_create(device, &g.ctx) != MVS_OK) return gpu_fail("creating context");
-        const int rc = load_db(g, matrix_file, elem_bytes, n, dimension);
-        if (rc) return rc;
-        if (mvs_linkage_create(g.ctx, n, dimension, db.norms_sq.data(), MVS_MEM_HOST, &g.linkage) != MVS_OK)
-            return gpu_fail("allocating the forest");
+        if (mvs_ctx_create(choose_device(o.device), &g.ctx) != MVS_OK) return gpu_fail(kProg, "creating context");
+        if (const int rc = load_sketch_db(kProg, g.ctx, sdb, &g.set)) return rc;
+        if (mvs_linkage_create(g.ctx, n, sdb.dimension, db.norms_sq.data(), MVS_MEM_HOST, &g.linkage) != MVS_OK)
+            return gpu_fail(kProg, "allocating the forest");
         if (mvs_pairwise_linkage(g.ctx, g.set, db.norms_sq.data(), MVS_MEM_HOST, o.min_jaccard, g.linkage) != MVS_OK)
-            return gpu_fail("comparing");
+            return gpu_fail(kProg, "comparing");
         if (mvs_linkage_finish(g.linkage, links.data(), (int64_t)links.size(), MVS_MEM_HOST, &n_links) != MVS_OK)
-            return gpu_fail("sorting the links");
+            return gpu_fail(kProg, "sorting the links");
         if (!o.cuts.empty() && mvs_device_alloc(g.ctx, (size_t)n * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK)
-            return gpu_fail("allocating the cell buffer");
+            return gpu_fail(kProg, "allocating the cell buffer");
         std::vector<int32_t> labels((size_t)n), reps((size_t)n), sizes((size_t)n);
         for (double u : o.cuts) {
             int64_t m = 0, n_clusters = 0;
-            if (mvs_linkage_cells(g.linkage, u, (mvs_cell*)g.d_cells, n, &m) != MVS_OK) return gpu_fail("listing the links above a cut");
-            if (mvs_cluster_create(g.ctx, n, &g.cluster) != MVS_OK) return gpu_fail("allocating a cut's clusters");
-            if (mvs_cluster_add_cells(g.cluster, (const mvs_cell*)g.d_cells, m) != MVS_OK) return gpu_fail("clustering a cut");
+            if (mvs_linkage_cells(g.linkage, u, (mvs_cell*)g.d_cells, n, &m) != MVS_OK) return gpu_fail(kProg, "listing the links above a cut");
+            if (mvs_cluster_create(g.ctx, n, &g.cluster) != MVS_OK) return gpu_fail(kProg, "allocating a cut's clusters");
+            if (mvs_cluster_add_cells(g.cluster, (const mvs_cell*)g.d_cells, m) != MVS_OK) return gpu_fail(kProg, "clustering a cut");
             if (mvs_cluster_finish(g.cluster, db.norms_sq.data(), MVS_MEM_HOST, labels.data(), nullptr, reps.data(), sizes.data(),
                                    MVS_MEM_HOST, &n_clusters) != MVS_OK)
-                return gpu_fail("numbering a cut's clusters");
+                return gpu_fail(kProg, "numbering a cut's clusters");
             mvs_cluster_destroy(g.cluster);
             g.cluster = nullptr;
             std::ostringstream text;
@@ -294,11 +184,9 @@ int main(int argc, char* argv[]) {
              << size[(size_t)ra] << '\n';
     }
     for (size_t k = 0; k < cut_texts.size(); ++k) {
-        const int rc = write_file(o.output + ".cut" + std::to_string(k) + ".tsv", cut_texts[k]);
-        if (rc) return rc;
+        if (const int rc = write_then_rename(kProg, o.output + ".cut" + std::to_string(k) + ".tsv", cut_texts[k])) return rc;
     }
-    const int rc = write_file(o.output, text.str());
-    if (rc) return rc;
+    if (const int rc = write_then_rename(kProg, o.output, text.str())) return rc;
     std::cout << "Linked " << n << " samples at Jaccard > " << o.min_jaccard << ": " << n_links << " links, " << n - n_links
               << " components, weakest link " << (n_links ? g17(links[(size_t)n_links - 1].jaccard) : std::string("none")) << std::endl;
     return 0;

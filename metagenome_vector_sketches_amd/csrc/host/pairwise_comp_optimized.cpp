@@ -33,6 +33,7 @@
 
 #include "mvs_host.hpp"
 #include "mvs_step.hpp"
+#include "mvs_tool.hpp"
 
 namespace fs = std::filesystem;
 using namespace mvs_host;
@@ -121,66 +122,16 @@ static bool legacy16_output() {
     return e && e[0] == '1';
 }
 
-static int gpu_fail(const char* what) {
-    std::cerr << "pairwise_comp_optimized: " << what << ": " << mvs_last_error() << std::endl;
-    return 2;
-}
+static int gpu_fail(const char* what) { return gpu_fail("pairwise_comp_optimized", what); }
 
-// vectors.bin goes through the device in row chunks straight from the page cache (the file is mapped, the
-// library copies from the mapping) and is re-coded into the limb planes
+// the whole vectors.bin -> g.set (mvs_tool.hpp: the loader every tool over a sketch DB uses)
 static int load_db(Gpu& g, const std::string& matrix_file, int elem_bytes, int64_t n, int d) {
-    const int64_t row_bytes = (int64_t)d * elem_bytes;
-    const int64_t chunk_rows = std::max<int64_t>(1, (1LL << 30) / row_bytes);
-    const int fd = ::open(matrix_file.c_str(), O_RDONLY);
-    if (fd < 0) {
-        std::cerr << "Error opening file: " << matrix_file << std::endl;       // :35-38
-        return 1;
-    }
-    const size_t bytes = (size_t)(n * row_bytes);
-    const char* base = nullptr;
-    if (bytes) {
-        void* m = ::mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) {
-            ::close(fd);
-            std::cerr << "Error reading file: " << matrix_file << std::endl;
-            return 1;
-        }
-        ::madvise(m, bytes, MADV_SEQUENTIAL);
-        base = (const char*)m;
-    }
-    ::close(fd);
-    // One pass in the common case: the planes are allocated for two limbs (|v| <= 32639, i.e. samples of up to tens
-    // of millions of hashes) and every chunk reports its largest |v| with the same upload; only if a chunk needs
-    // more limbs than the set has does the load start over with the limb count the data seen so far asks for.
-    int rc = 0;
-    int limbs = 2;
-    for (int attempt = 0; attempt < 4 && !rc; ++attempt) {
-        if (g.set) {
-            mvs_sketch_set_destroy(g.set);
-            g.set = nullptr;
-        }
-        if (mvs_sketch_set_alloc(g.ctx, n, d, limbs, &g.set) != MVS_OK) {
-            rc = gpu_fail("allocating sketch set");
-            break;
-        }
-        int64_t max_abs = 0;
-        bool restart = false;
-        for (int64_t r0 = 0; r0 < n && !rc; r0 += chunk_rows) {
-            const int64_t rows = std::min(chunk_rows, n - r0);
-            int64_t m = 0;
-            if (mvs_sketch_set_fill_stats(g.set, base + r0 * row_bytes, elem_bytes, MVS_MEM_HOST, r0, rows, &m) != MVS_OK)
-                rc = gpu_fail("re-coding vectors.bin");
-            max_abs = std::max(max_abs, m);
-            if (mvs_limbs_for_max_abs(max_abs) > limbs) {
-                restart = true;
-                break;
-            }
-        }
-        if (!restart) break;
-        limbs = mvs_limbs_for_max_abs(max_abs);
-    }
-    if (bytes) ::munmap((void*)base, bytes);
-    return rc;
+    SketchDb db;
+    db.matrix_file = matrix_file;
+    db.elem_bytes = elem_bytes;
+    db.n = n;
+    db.dimension = d;
+    return load_sketch_db("pairwise_comp_optimized", g.ctx, db, &g.set);
 }
 
 // Rendezvous of the shard processes of one job: they meet under <output_folder>/.mvs_comm_<token> through the

@@ -19,11 +19,13 @@
 // the RMSE and the largest absolute error of the estimate over the kept pairs, and kernel and wall times.
 // Exit codes: 1 bad arguments, DB or hash file, 2 device errors.  One GPU (--device, else MVS_DEVICE, else 0).
 #include "mvs_host.hpp"
+#include "mvs_tool.hpp"
 
-namespace fs = std::filesystem;
 using namespace mvs_host;
 
 namespace {
+
+constexpr const char* kProg = "verify_pairs";
 
 struct Options {
     std::string db_folder, hash_file, output, report, bad_flag;
@@ -48,7 +50,6 @@ void parse(int argc, char* argv[], Options& o) {
         auto bad = [&](const char* flag) {
             if (o.bad_flag.empty()) o.bad_flag = flag;
         };
-        char* end = nullptr;
         if (a == "--help") {
             o.show_help = true;
         } else if (a == "--db" || a == "--output" || a == "--report") {
@@ -66,20 +67,15 @@ void parse(int argc, char* argv[], Options& o) {
             else o.hash_file = v;
         } else if (a == "--min_jaccard") {
             o.have_t = true;
-            const std::string v = has_value ? argv[++i] : "";
-            const double t = strtod(v.c_str(), &end);
-            if (v.empty() || end == v.c_str() || *end || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
+            double t = 0.0;
+            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
             else o.min_jaccard = t;
         } else if (a == "--exact_min") {
-            const std::string v = has_value ? argv[++i] : "";
-            const double u = strtod(v.c_str(), &end);
-            if (v.empty() || end == v.c_str() || *end || !(u >= 0.0) || !(u < 1.0)) bad("--exact_min");
+            double u = 0.0;
+            if (!parse_number(has_value ? argv[++i] : "", &u) || !(u >= 0.0) || !(u < 1.0)) bad("--exact_min");
             else o.exact_min = u;
         } else if (a == "--device") {
-            const std::string v = has_value ? argv[++i] : "";
-            const long m = strtol(v.c_str(), &end, 10);
-            if (v.empty() || end == v.c_str() || *end || m < 0 || m > 1023) bad("--device");
-            else o.device = (int)m;
+            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
         } else {
             o.unknown = true;
         }
@@ -105,58 +101,6 @@ struct Gpu {
     }
 };
 
-int gpu_fail(const char* what) {
-    std::cerr << "verify_pairs: " << what << ": " << mvs_last_error() << std::endl;
-    return 2;
-}
-
-// vectors.bin -> limb planes, in row chunks straight from the mapping; two limbs unless a chunk's largest |v| asks for more
-// (as cluster_sketches loads it)
-int load_db(Gpu& g, const std::string& matrix_file, int elem_bytes, int64_t n, int d) {
-    const int64_t row_bytes = (int64_t)d * elem_bytes;
-    const int64_t chunk_rows = std::max<int64_t>(1, (1LL << 30) / row_bytes);
-    const int fd = ::open(matrix_file.c_str(), O_RDONLY);
-    if (fd < 0) {
-        std::cerr << "Error opening file: " << matrix_file << std::endl;       // :35-38
-        return 1;
-    }
-    const size_t bytes = (size_t)(n * row_bytes);
-    const char* base = nullptr;
-    if (bytes) {
-        void* m = ::mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) {
-            ::close(fd);
-            std::cerr << "Error reading file: " << matrix_file << std::endl;
-            return 1;
-        }
-        ::madvise(m, bytes, MADV_SEQUENTIAL);
-        base = (const char*)m;
-    }
-    ::close(fd);
-    int rc = 0;
-    for (int limbs = 2, attempt = 0; attempt < 4 && !rc; ++attempt) {
-        if (g.set) {
-            mvs_sketch_set_destroy(g.set);
-            g.set = nullptr;
-        }
-        if (mvs_sketch_set_alloc(g.ctx, n, d, limbs, &g.set) != MVS_OK) {
-            rc = gpu_fail("allocating sketch set");
-            break;
-        }
-        int64_t max_abs = 0;
-        for (int64_t r0 = 0; r0 < n && !rc && mvs_limbs_for_max_abs(max_abs) <= limbs; r0 += chunk_rows) {
-            int64_t m = 0;
-            if (mvs_sketch_set_fill_stats(g.set, base + r0 * row_bytes, elem_bytes, MVS_MEM_HOST, r0, std::min(chunk_rows, n - r0), &m) != MVS_OK)
-                rc = gpu_fail("re-coding vectors.bin");
-            max_abs = std::max(max_abs, m);
-        }
-        if (mvs_limbs_for_max_abs(max_abs) <= limbs) break;
-        limbs = mvs_limbs_for_max_abs(max_abs);
-    }
-    if (bytes) ::munmap((void*)base, bytes);
-    return rc;
-}
-
 struct Pair {
     int32_t row, col, dot, inter;
 };
@@ -169,26 +113,6 @@ std::string fmt(double v) {
 }
 
 double ratio(double num, double den) { return den == 0.0 ? std::nan("") : num / den; }
-
-bool write_atomically(const std::string& path, const std::string& text) {
-    const std::string part = path + ".part";
-    {
-        std::ofstream out(part, std::ios::binary | std::ios::trunc);
-        out << text;
-        out.flush();
-        if (!out) {
-            std::cerr << "verify_pairs: cannot write " << part << std::endl;
-            ::unlink(part.c_str());
-            return false;
-        }
-    }
-    if (::rename(part.c_str(), path.c_str()) != 0) {
-        std::cerr << "verify_pairs: cannot rename " << part << " to " << path << std::endl;
-        ::unlink(part.c_str());
-        return false;
-    }
-    return true;
-}
 
 }  // namespace
 
@@ -213,42 +137,11 @@ int main(int argc, char* argv[]) {
         print_usage(argv[0]);
         return 1;
     }
-    const std::string db_folder = o.db_folder;
-    const std::string norms_file = db_folder + "vector_norms.txt";                // raw concatenation, as :853-891
-    if (!fs::exists(norms_file)) {                                                // :855-858
-        std::cerr << "Error: Required file 'vector_norms.txt' not found in output folder: " << db_folder << std::endl;
-        return 1;
-    }
-    std::string dtype = "int32";
-    {
-        std::ifstream dtype_in(db_folder + "dtype.txt");                          // :859-865
-        if (dtype_in) std::getline(dtype_in, dtype);
-    }
-    int dimension = 0;
-    {
-        std::ifstream dim_in(db_folder + "dimension.txt");                        // :866-873
-        if (dim_in) dim_in >> dimension;
-    }
-    if (dimension <= 0) {
-        std::cerr << "Error: could not read a positive dimension from " << db_folder << "dimension.txt" << std::endl;
-        return 1;
-    }
-    const int elem_bytes = dtype == "int16" ? 2 : 4;
-    const std::string matrix_file = db_folder + "vectors.bin";                    // :891
-    DbInfo db;
-    read_norms(norms_file, db);                                                   // :893-901
-    int64_t file_size = 0;
-    {
-        std::ifstream file(matrix_file, std::ios::ate | std::ios::binary);        // :911-914
-        file_size = file ? (int64_t)file.tellg() : 0;
-    }
-    const int64_t n = file_size / ((int64_t)dimension * elem_bytes);
-    if ((int64_t)db.norms_sq.size() < n) {
-        std::cerr << "Error: vector_norms.txt has " << db.norms_sq.size() << " entries for " << n << " vectors" << std::endl;
-        return 1;
-    }
-    db.norms_sq.resize((size_t)n);
-    db.names.resize((size_t)n);
+    SketchDb sdb;
+    if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
+    const DbInfo& db = sdb.info;
+    const int64_t n = sdb.n;
+    const int dimension = sdb.dimension;
 
     // the hash lists: the parsed form `project_everything sketch` left next to the text when it is valid, else the text
     HashSets sets;
@@ -268,8 +161,8 @@ int main(int argc, char* argv[]) {
     if ((int64_t)sets.names.size() != n || !std::equal(sets.names.begin(), sets.names.end(), db.names.begin())) {
         size_t at = 0;
         while (at < sets.names.size() && at < (size_t)n && sets.names[at] == db.names[at]) ++at;
-        std::cerr << "verify_pairs: the samples of " << o.hash_file << " (" << sets.names.size() << ") are not those of " << norms_file << " ("
-                  << n << ") in the same order: first difference at sample " << at << std::endl;
+        std::cerr << "verify_pairs: the samples of " << o.hash_file << " (" << sets.names.size() << ") are not those of " << sdb.folder
+                  << "vector_norms.txt (" << n << ") in the same order: first difference at sample " << at << std::endl;
         return 1;
     }
 
@@ -278,17 +171,15 @@ int main(int argc, char* argv[]) {
     double compare_ms = 0.0, intersect_ms = 0.0;
     if (n > 0) {
         Gpu g;
-        const int device = o.device >= 0 ? o.device : pick_device();
-        if (mvs_ctx_create(device, &g.ctx) != MVS_OK) return gpu_fail("creating context");
+        if (mvs_ctx_create(choose_device(o.device), &g.ctx) != MVS_OK) return gpu_fail(kProg, "creating context");
         mvs_ctx_set_timing(g.ctx, 1);
-        const int rc = load_db(g, matrix_file, elem_bytes, n, dimension);
-        if (rc) return rc;
+        if (const int rc = load_sketch_db(kProg, g.ctx, sdb, &g.set)) return rc;
         if (mvs_hash_set_create(g.ctx, sets.hashes.data(), MVS_MEM_HOST, sets.offsets.data(), n, &g.hs) != MVS_OK)
-            return gpu_fail("uploading the hash lists");
-        if (mvs_hash_set_sizes(g.hs, sizes.data(), MVS_MEM_HOST) != MVS_OK) return gpu_fail("reading the set sizes");
+            return gpu_fail(kProg, "uploading the hash lists");
+        if (mvs_hash_set_sizes(g.hs, sizes.data(), MVS_MEM_HOST) != MVS_OK) return gpu_fail(kProg, "reading the set sizes");
         if (mvs_device_alloc(g.ctx, (size_t)n * 8, 0, &g.d_norms) != MVS_OK ||
             mvs_device_copy(g.ctx, g.d_norms, MVS_MEM_DEVICE, db.norms_sq.data(), MVS_MEM_HOST, (size_t)n * 8) != MVS_OK)
-            return gpu_fail("uploading the norms");
+            return gpu_fail(kProg, "uploading the norms");
         // row blocks of the search comparison; a block that keeps more than the buffer holds reports what it needs
         const int64_t block_rows = std::max<int64_t>(256, std::min<int64_t>(n, (1LL << 28) / std::max<int64_t>(n, 1) / 256 * 256));
         int64_t capacity = 0;
@@ -300,7 +191,7 @@ int main(int argc, char* argv[]) {
                 capacity = 1 << 20;
                 if (mvs_device_alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK ||
                     mvs_device_alloc(g.ctx, (size_t)capacity * 4, 0, &g.d_inter) != MVS_OK)
-                    return gpu_fail("allocating the cell buffers");
+                    return gpu_fail(kProg, "allocating the cell buffers");
             }
             int64_t count = 0;
             const int src = mvs_search_block(g.ctx, g.set, (const double*)g.d_norms, o.min_jaccard, rb, re, 0, n, (mvs_cell*)g.d_cells,
@@ -314,14 +205,14 @@ int main(int argc, char* argv[]) {
                 capacity = count + count / 8 + 1024;
                 if (mvs_device_alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK ||
                     mvs_device_alloc(g.ctx, (size_t)capacity * 4, 0, &g.d_inter) != MVS_OK)
-                    return gpu_fail("allocating the cell buffers");
+                    return gpu_fail(kProg, "allocating the cell buffers");
                 continue;
             }
-            if (src != MVS_OK) return gpu_fail("comparing");
+            if (src != MVS_OK) return gpu_fail(kProg, "comparing");
             if (count > 0) {
                 if (mvs_intersect_cells(g.ctx, g.hs, nullptr, (const mvs_cell*)g.d_cells, MVS_MEM_DEVICE, count, (int32_t*)g.d_inter,
                                         MVS_MEM_DEVICE) != MVS_OK)
-                    return gpu_fail("intersecting");
+                    return gpu_fail(kProg, "intersecting");
                 double kms = 0.0;
                 mvs_ctx_intersect_stats(g.ctx, &kms, nullptr, nullptr, nullptr);
                 intersect_ms += kms;
@@ -329,7 +220,7 @@ int main(int argc, char* argv[]) {
                 inter.resize((size_t)count);
                 if (mvs_device_copy(g.ctx, cells.data(), MVS_MEM_HOST, g.d_cells, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_cell)) != MVS_OK ||
                     mvs_device_copy(g.ctx, inter.data(), MVS_MEM_HOST, g.d_inter, MVS_MEM_DEVICE, (size_t)count * 4) != MVS_OK)
-                    return gpu_fail("downloading");
+                    return gpu_fail(kProg, "downloading");
                 for (int64_t i = 0; i < count; ++i)                    // sorted by (row, col) inside a block, blocks ascend
                     if (cells[(size_t)i].row < cells[(size_t)i].col)
                         pairs.push_back({cells[(size_t)i].row, cells[(size_t)i].col, cells[(size_t)i].dot, inter[(size_t)i]});
@@ -362,7 +253,7 @@ int main(int argc, char* argv[]) {
                 fmt(ratio(in, sb)) + '\n';
         ++written;
     }
-    if (!write_atomically(o.output, text)) return 1;
+    if (const int rc = write_then_rename(kProg, o.output, text)) return rc;
     const double wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall_begin).count();
     if (!o.report.empty()) {
         std::string rep;
@@ -377,7 +268,7 @@ int main(int argc, char* argv[]) {
         rep += "compare_kernel_ms\t" + fmt(compare_ms) + "\n";
         rep += "intersect_kernel_ms\t" + fmt(intersect_ms) + "\n";
         rep += "wall_s\t" + fmt(wall_s) + "\n";
-        if (!write_atomically(o.report, rep)) return 1;
+        if (const int rc = write_then_rename(kProg, o.report, rep)) return rc;
     }
     std::cout << "Verified " << pairs.size() << " pairs of " << n << " samples kept at Jaccard > " << o.min_jaccard << ": " << above
               << " above exactly, " << below << " at or below; " << written << " written" << std::endl;

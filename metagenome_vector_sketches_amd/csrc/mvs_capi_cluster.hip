@@ -25,17 +25,15 @@ constexpr int kMaxRounds = 64;   // hook -> flatten -> verify rounds per list be
 int consume_cells(mvs_cluster* k, const mvs_cell* d_cells, int64_t n_cells) {
     mvs_ctx* c = k->ctx;
     if (n_cells == 0) return MVS_OK;
-    EventPair ev;
-    if (c->timing) {
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-    }
+    StageTimer timer;
+    int rc = timer.begin(c);
+    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(k->counters, 0, 3 * sizeof(unsigned long long), c->stream));
     unsigned long long back[3] = {0, 0, 0};
     int round = 0;
     for (;;) {
         ++round;
-        int rc = mvs::launch_cluster_hook(c->stream, d_cells, n_cells, k->parent, k->degree, k->n, round == 1, k->counters);
+        rc = mvs::launch_cluster_hook(c->stream, d_cells, n_cells, k->parent, k->degree, k->n, round == 1, k->counters);
         if (!rc) rc = check_kernel("k_cluster_hook");
         if (rc) return rc;
         rc = mvs::launch_cluster_flatten(c->stream, k->parent, k->n);
@@ -52,25 +50,13 @@ int consume_cells(mvs_cluster* k, const mvs_cell* d_cells, int64_t n_cells) {
         if (round >= kMaxRounds)
             return fail(MVS_E_HIP, "internal: %llu cells still join different trees after %d union-find rounds", back[2], round);
     }
-    if (c->timing) {
-        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
-        HIP_TRY(hipEventSynchronize(ev.e[1]));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        c->cl_union_ms += ms;
-    }
-    c->cl_edges += (long long)back[0];
-    c->cl_rounds = std::max<long long>(c->cl_rounds, round);
+    rc = timer.mark_end();
+    if (!rc) rc = timer.add_to(&c->cl.work_ms);
+    if (rc) return rc;
+    c->cl.edges += (long long)back[0];
+    c->cl.rounds = std::max<long long>(c->cl.rounds, round);
     if (back[1] != 0)
         return fail(MVS_E_RANGE, "%llu cells name a sample outside [0, %lld): they were ignored", back[1], (long long)k->n);
-    return MVS_OK;
-}
-
-template <typename T>
-int give_out(mvs_ctx* c, T* dst, const void* d_src, int64_t count, int mem_out) {
-    if (!dst || count <= 0) return MVS_OK;
-    HIP_TRY(hipMemcpyAsync(dst, d_src, (size_t)count * sizeof(T), mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                           c->stream));
     return MVS_OK;
 }
 
@@ -80,11 +66,12 @@ namespace mvs_capi {
 
 // The threshold comparison of a sketch set with itself at level min_jaccard, row block by row block: each block's unsorted
 // cells (every ordered pair of linked samples exactly once) are handed to `consume` while they sit in the staging buffer.
-// Shared by mvs_pairwise_cluster, mvs_pairwise_linkage (mvs_capi_linkage.hip) and mvs_pairwise_derep (mvs_capi_derep.hip): one
-// launch, one staging buffer, one halving and grow rule.  `consume` is also told the block's rows [rb, re): the blocks come in
-// ascending order.  d_n2: the norms on the device; *compare_ms (timing on) and *row_blocks are added to.
+// Shared by mvs_pairwise_cluster, mvs_pairwise_linkage (mvs_capi_linkage.hip) and mvs_pairwise_derep (mvs_capi_derep.hip)
+// through feed_consumer: one launch, one staging buffer, one halving and grow rule.  `consume` is also told the block's rows
+// [rb, re): the blocks come in ascending order.  d_n2: the norms on the device; *compare_ms (timing on) and *row_blocks are
+// added to.
 int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, double min_jaccard, double* compare_ms, long long* row_blocks,
-                  const std::function<int(const mvs_cell*, int64_t, int64_t, int64_t)>& consume) {
+                  const ConsumeCells& consume) {
     const int64_t n = s->n;
     // J > t  <=>  double(P)/d > t/(1+t) * (n2r + n2c): mvs_search_block's coefficient
     const double coeff = min_jaccard / (1.0 + min_jaccard);
@@ -138,6 +125,42 @@ int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, doubl
     return MVS_OK;
 }
 
+int norms_on_device(mvs_ctx* c, const double* norms_sq, int mem_norms, int64_t n, DevBuf& staging, const double** d_n2) {
+    *d_n2 = norms_sq;
+    if (mem_norms == MVS_MEM_HOST) {
+        HIP_TRY(staging.alloc((size_t)n * 8));
+        HIP_TRY(hipMemcpyAsync(staging.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        *d_n2 = (const double*)staging.p;
+    }
+    return MVS_OK;
+}
+
+int feed_consumer(const char* entry, mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int mem_norms, double min_jaccard,
+                  ConsumerStats& st, const ConsumeCells& consume) {
+    const int64_t n = s->n;
+    if (n == 0) return MVS_OK;
+    if (!norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
+    const Range range(c, entry);
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf dn;
+    const double* d_n2 = nullptr;
+    const int rc = norms_on_device(c, norms_sq, mem_norms, n, dn, &d_n2);
+    if (rc) return rc;
+    return pairwise_feed(c, s, d_n2, min_jaccard, &st.compare_ms, &st.blocks, consume);
+}
+
+int consumer_stats_out(const mvs_ctx* c, ConsumerStats mvs_ctx::*which, double* compare_ms, double* work_ms, int64_t* edges,
+                       int64_t* row_blocks, int64_t* rounds) {
+    if (!c) return fail(MVS_E_INVALID, "NULL context");
+    const ConsumerStats& st = c->*which;
+    if (compare_ms) *compare_ms = st.compare_ms;
+    if (work_ms) *work_ms = st.work_ms;
+    if (edges) *edges = st.edges;
+    if (row_blocks) *row_blocks = st.blocks;
+    if (rounds) *rounds = st.rounds;
+    return MVS_OK;
+}
+
 }  // namespace mvs_capi
 
 extern "C" {
@@ -164,8 +187,7 @@ int mvs_cluster_create(mvs_ctx* c, int64_t n, mvs_cluster** out) {
         mvs_cluster_destroy(k);
         return rc;
     }
-    c->cl_compare_ms = c->cl_union_ms = 0.0;
-    c->cl_edges = c->cl_blocks = c->cl_rounds = 0;
+    c->cl.reset();
     *out = k;
     return MVS_OK;
 }
@@ -180,25 +202,9 @@ int mvs_cluster_add_cells(mvs_cluster* k, const mvs_cell* d_cells, int64_t n_cel
 
 int mvs_pairwise_cluster(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int mem_norms, double min_jaccard,
                          mvs_cluster* k) {
-    if (!c || !s || !k) return fail(MVS_E_INVALID, "NULL argument");
-    if (!(min_jaccard > 0.0) || !(min_jaccard < 1.0)) return fail(MVS_E_INVALID, "min_jaccard = %g outside (0, 1)", min_jaccard);
-    if (!mem_ok(mem_norms)) return fail(MVS_E_INVALID, "bad argument");
-    if (k->ctx != c) return fail(MVS_E_INVALID, "the cluster belongs to another context");
-    if (k->n != s->n) return fail(MVS_E_INVALID, "the cluster holds %lld samples, the sketch set %lld", (long long)k->n, (long long)s->n);
-    const int64_t n = s->n;
-    if (n == 0) return MVS_OK;
-    if (!norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
-    const Range range(c, "mvs_pairwise_cluster");
-    HIP_TRY(hipSetDevice(c->device));
-
-    DevBuf dn;
-    const double* d_n2 = norms_sq;
-    if (mem_norms == MVS_MEM_HOST) {
-        HIP_TRY(dn.alloc((size_t)n * 8));
-        HIP_TRY(hipMemcpyAsync(dn.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        d_n2 = (const double*)dn.p;
-    }
-    return pairwise_feed(c, s, d_n2, min_jaccard, &c->cl_compare_ms, &c->cl_blocks,
+    const int rc = consumer_checks("cluster", c, s, k, mem_norms, min_jaccard);
+    if (rc) return rc;
+    return feed_consumer("mvs_pairwise_cluster", c, s, norms_sq, mem_norms, min_jaccard, c->cl,
                          [k](const mvs_cell* d_cells, int64_t n_cells, int64_t, int64_t) { return consume_cells(k, d_cells, n_cells); });
 }
 
@@ -214,12 +220,9 @@ int mvs_cluster_finish(mvs_cluster* k, const double* norms_sq, int mem_norms, in
     HIP_TRY(hipSetDevice(c->device));
     const Range range(c, "mvs_cluster_finish");
     DevBuf dn, dwork, dbest, dscan;
-    const double* d_n2 = norms_sq;
-    if (mem_norms == MVS_MEM_HOST) {
-        HIP_TRY(dn.alloc((size_t)n * 8));
-        HIP_TRY(hipMemcpyAsync(dn.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        d_n2 = (const double*)dn.p;
-    }
+    const double* d_n2 = nullptr;
+    int rc = norms_on_device(c, norms_sq, mem_norms, n, dn, &d_n2);
+    if (rc) return rc;
     // is_root, ids (n + 1 each), labels, sizes, representatives (n each)
     const size_t np1 = ((size_t)n + 1 + 63) / 64 * 64;
     HIP_TRY(dwork.alloc(5 * np1 * 4));
@@ -230,15 +233,13 @@ int mvs_cluster_finish(mvs_cluster* k, const double* norms_sq, int mem_norms, in
     int32_t* d_sizes = d_labels + np1;
     int32_t* d_rep = d_sizes + np1;
     size_t need = 0;
-    int rc = mvs::cluster_finish(c->stream, k->parent, d_n2, n, d_is_root, d_ids, d_labels, d_sizes, d_rep, (unsigned long long*)dbest.p,
-                                 nullptr, 0, &need);
+    rc = mvs::cluster_finish(c->stream, k->parent, d_n2, n, d_is_root, d_ids, d_labels, d_sizes, d_rep, (unsigned long long*)dbest.p,
+                             nullptr, 0, &need);
     if (rc) return fail(rc, "cluster finish: scan sizing failed");
     HIP_TRY(dscan.alloc(need));
-    EventPair ev;
-    if (c->timing) {
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-    }
+    StageTimer timer;
+    rc = timer.begin(c);
+    if (rc) return rc;
     rc = mvs::launch_cluster_flatten(c->stream, k->parent, n);
     if (!rc) rc = check_kernel("k_cluster_flatten");
     if (rc) return rc;
@@ -247,15 +248,12 @@ int mvs_cluster_finish(mvs_cluster* k, const double* norms_sq, int mem_norms, in
     if (rc) return fail(rc, "cluster finish failed");
     rc = check_kernel("k_cluster_label");
     if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    rc = timer.mark_end();
+    if (rc) return rc;
     int32_t total = 0;
     rc = read_back(c, c->stream, {{&total, d_ids + n, 4}});
+    if (!rc) rc = timer.add_to(&c->cl.work_ms);
     if (rc) return rc;
-    if (c->timing) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        c->cl_union_ms += ms;
-    }
     if (n_clusters) *n_clusters = total;
     rc = give_out(c, labels, d_labels, n, mem_out);
     if (!rc) rc = give_out(c, degree, k->degree, n, mem_out);
@@ -281,13 +279,7 @@ int mvs_cluster_destroy(mvs_cluster* k) {
 
 int mvs_ctx_cluster_stats(const mvs_ctx* c, double* compare_ms, double* union_ms, int64_t* edges, int64_t* row_blocks,
                           int64_t* rounds) {
-    if (!c) return fail(MVS_E_INVALID, "NULL context");
-    if (compare_ms) *compare_ms = c->cl_compare_ms;
-    if (union_ms) *union_ms = c->cl_union_ms;
-    if (edges) *edges = c->cl_edges;
-    if (row_blocks) *row_blocks = c->cl_blocks;
-    if (rounds) *rounds = c->cl_rounds;
-    return MVS_OK;
+    return consumer_stats_out(c, &mvs_ctx::cl, compare_ms, union_ms, edges, row_blocks, rounds);
 }
 
 }  // extern "C"

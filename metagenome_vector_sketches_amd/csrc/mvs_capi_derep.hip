@@ -42,14 +42,12 @@ int consume_rows(mvs_derep* k, const mvs_cell* d_cells, int64_t n_cells, int64_t
                     (long long)k->decided);
     if (re < rb || re > k->n) return fail(MVS_E_INVALID, "rows [%lld, %lld) outside [0, %lld)", (long long)rb, (long long)re, (long long)k->n);
     if (re == rb) return MVS_OK;
-    EventPair ev;
-    if (c->timing) {
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-    }
+    StageTimer timer;
+    int rc = timer.begin(c);
+    if (rc) return rc;
     const mvs::DerepState s = state_of(k);
     HIP_TRY(hipMemsetAsync(k->counters, 0, 3 * sizeof(unsigned long long), c->stream));
-    int rc = mvs::launch_derep_pre(c->stream, s, d_cells, n_cells, rb, re);
+    rc = mvs::launch_derep_pre(c->stream, s, d_cells, n_cells, rb, re);
     if (!rc) rc = check_kernel("k_derep_pre");
     if (rc) return rc;
     unsigned long long back[3] = {0, 0, 0};
@@ -81,29 +79,17 @@ int consume_rows(mvs_derep* k, const mvs_cell* d_cells, int64_t n_cells, int64_t
     rc = mvs::launch_derep_link(c->stream, s, d_cells, n_cells, rb, re);
     if (!rc) rc = check_kernel("k_derep_link");
     if (rc) return rc;
-    if (c->timing) {
-        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
-        HIP_TRY(hipEventSynchronize(ev.e[1]));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        c->dr_greedy_ms += ms;
-    } else {
-        HIP_TRY(hipStreamSynchronize(c->stream));   // the list is the caller's again
-    }
+    // the list is the caller's again when this returns: the timer waits for its end mark, without it the stream is waited for
+    rc = timer.mark_end();
+    if (!rc) rc = timer.add_to(&c->dr.work_ms);
+    if (rc) return rc;
+    if (!timer.on) HIP_TRY(hipStreamSynchronize(c->stream));
     k->decided = re;
-    c->dr_edges += (long long)back[0];
-    c->dr_rounds = std::max<long long>(c->dr_rounds, round);
+    c->dr.edges += (long long)back[0];
+    c->dr.rounds = std::max<long long>(c->dr.rounds, round);
     if (back[1] != 0)
         return fail(MVS_E_RANGE, "%llu cells name a row outside [%lld, %lld) or a column outside [0, %lld): they were ignored", back[1],
                     (long long)rb, (long long)re, (long long)k->n);
-    return MVS_OK;
-}
-
-template <typename T>
-int give_out(mvs_ctx* c, T* dst, const void* d_src, int64_t count, int mem_out) {
-    if (!dst || count <= 0) return MVS_OK;
-    HIP_TRY(hipMemcpyAsync(dst, d_src, (size_t)count * sizeof(T), mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                           c->stream));
     return MVS_OK;
 }
 
@@ -186,8 +172,7 @@ int mvs_derep_create(mvs_ctx* c, int64_t n, mvs_derep** out) {
         mvs_derep_destroy(k);
         return rc;
     }
-    c->dr_compare_ms = c->dr_greedy_ms = 0.0;
-    c->dr_edges = c->dr_blocks = c->dr_rounds = 0;
+    c->dr.reset();
     *out = k;
     return MVS_OK;
 }
@@ -202,26 +187,10 @@ int mvs_derep_add_rows(mvs_derep* k, const mvs_cell* d_cells, int64_t n_cells, i
 }
 
 int mvs_pairwise_derep(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int mem_norms, double min_jaccard, mvs_derep* k) {
-    if (!c || !s || !k) return fail(MVS_E_INVALID, "NULL argument");
-    if (!(min_jaccard > 0.0) || !(min_jaccard < 1.0)) return fail(MVS_E_INVALID, "min_jaccard = %g outside (0, 1)", min_jaccard);
-    if (!mem_ok(mem_norms)) return fail(MVS_E_INVALID, "bad argument");
-    if (k->ctx != c) return fail(MVS_E_INVALID, "the dereplication belongs to another context");
-    if (k->n != s->n) return fail(MVS_E_INVALID, "the dereplication holds %lld samples, the sketch set %lld", (long long)k->n, (long long)s->n);
+    const int rc = consumer_checks("dereplication", c, s, k, mem_norms, min_jaccard);
+    if (rc) return rc;
     if (k->decided != 0) return fail(MVS_E_INVALID, "%lld rows of the dereplication are decided already", (long long)k->decided);
-    const int64_t n = s->n;
-    if (n == 0) return MVS_OK;
-    if (!norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
-    const Range range(c, "mvs_pairwise_derep");
-    HIP_TRY(hipSetDevice(c->device));
-
-    DevBuf dn;
-    const double* d_n2 = norms_sq;
-    if (mem_norms == MVS_MEM_HOST) {
-        HIP_TRY(dn.alloc((size_t)n * 8));
-        HIP_TRY(hipMemcpyAsync(dn.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        d_n2 = (const double*)dn.p;
-    }
-    return pairwise_feed(c, s, d_n2, min_jaccard, &c->dr_compare_ms, &c->dr_blocks,
+    return feed_consumer("mvs_pairwise_derep", c, s, norms_sq, mem_norms, min_jaccard, c->dr,
                          [k](const mvs_cell* d_cells, int64_t n_cells, int64_t rb, int64_t re) { return consume_rows(k, d_cells, n_cells, rb, re); });
 }
 
@@ -251,14 +220,11 @@ int mvs_derep_finish(mvs_derep* k, const int32_t* order, int mem_order, int32_t*
     int32_t* d_link_q = d_link_dot + np;
     int32_t* d_sizes = d_link_q + np;
     const mvs::DerepState s = state_of(k);
-    EventPair ev;
-    if (c->timing) {
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-    }
+    StageTimer timer;
+    int rc = timer.begin(c);
+    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(k->counters + 3, 0, 2 * sizeof(unsigned long long), c->stream));
     unsigned long long back[2] = {0, 0};
-    int rc = MVS_OK;
     if (d_order) {
         HIP_TRY(hipMemsetAsync(d_sizes, 0, (size_t)n * 4, c->stream));
         rc = mvs::launch_derep_order_check(c->stream, d_order, n, d_sizes, k->counters);
@@ -271,14 +237,11 @@ int mvs_derep_finish(mvs_derep* k, const int32_t* order, int mem_order, int32_t*
     rc = mvs::launch_derep_scatter(c->stream, s, d_order, d_rep_of, d_link_dot, d_link_q, d_sizes);
     if (!rc) rc = check_kernel("k_derep_scatter");
     if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
-    rc = read_back(c, c->stream, {{back, k->counters + 3, sizeof(back)}});
+    rc = timer.mark_end();
     if (rc) return rc;
-    if (c->timing) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        c->dr_greedy_ms += ms;
-    }
+    rc = read_back(c, c->stream, {{back, k->counters + 3, sizeof(back)}});
+    if (!rc) rc = timer.add_to(&c->dr.work_ms);
+    if (rc) return rc;
     if (n_reps) *n_reps = (int64_t)back[0];
     rc = give_out(c, rep_of, d_rep_of, n, mem_out);
     if (!rc) rc = give_out(c, link_dot, d_link_dot, n, mem_out);
@@ -303,13 +266,7 @@ int mvs_derep_destroy(mvs_derep* k) {
 }
 
 int mvs_ctx_derep_stats(const mvs_ctx* c, double* compare_ms, double* greedy_ms, int64_t* edges, int64_t* row_blocks, int64_t* rounds) {
-    if (!c) return fail(MVS_E_INVALID, "NULL context");
-    if (compare_ms) *compare_ms = c->dr_compare_ms;
-    if (greedy_ms) *greedy_ms = c->dr_greedy_ms;
-    if (edges) *edges = c->dr_edges;
-    if (row_blocks) *row_blocks = c->dr_blocks;
-    if (rounds) *rounds = c->dr_rounds;
-    return MVS_OK;
+    return consumer_stats_out(c, &mvs_ctx::dr, compare_ms, greedy_ms, edges, row_blocks, rounds);
 }
 
 int mvs_dereplicate(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int mem_norms, double min_jaccard, const int32_t* order,

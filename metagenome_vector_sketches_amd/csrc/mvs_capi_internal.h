@@ -35,6 +35,17 @@ struct mvs_tile_order {
     unsigned per = 0;
 };
 
+namespace mvs_capi {
+// what the calls of one consumer of kept cells (clustering, linkage, dereplication) did on a context since that consumer's
+// last *_create there: kernel times of the comparison and of the consumer's own work (timing enabled), cells with row != col
+// consumed, row blocks, the most rounds a list needed
+struct ConsumerStats {
+    double compare_ms = 0.0, work_ms = 0.0;
+    long long edges = 0, blocks = 0, rounds = 0;
+    void reset() { *this = ConsumerStats(); }
+};
+}  // namespace mvs_capi
+
 struct mvs_ctx {
     int device = 0;
     std::vector<mvs_tile_order> tile_orders;
@@ -153,15 +164,9 @@ struct mvs_ctx {
     // what the last mvs_pairwise_topk did (mvs_ctx_topk_stats): kernel times summed over its row blocks (timing enabled)
     double tk_dots_ms = 0.0, tk_select_ms = 0.0;
     long long tk_blocks = 0, tk_block_rows = 0;
-    // what the clustering calls did since the last mvs_cluster_create on this context (mvs_ctx_cluster_stats)
-    double cl_compare_ms = 0.0, cl_union_ms = 0.0;
-    long long cl_edges = 0, cl_blocks = 0, cl_rounds = 0;
-    // ... and the linkage calls since the last mvs_linkage_create (mvs_ctx_linkage_stats)
-    double lk_compare_ms = 0.0, lk_forest_ms = 0.0;
-    long long lk_edges = 0, lk_blocks = 0, lk_rounds = 0;
-    // ... and the dereplication calls since the last mvs_derep_create (mvs_ctx_derep_stats)
-    double dr_compare_ms = 0.0, dr_greedy_ms = 0.0;
-    long long dr_edges = 0, dr_blocks = 0, dr_rounds = 0;
+    // what the clustering, linkage and dereplication calls did since the last mvs_cluster_create / mvs_linkage_create /
+    // mvs_derep_create on this context (mvs_ctx_cluster_stats, mvs_ctx_linkage_stats, mvs_ctx_derep_stats)
+    mvs_capi::ConsumerStats cl, lk, dr;
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
     // did (mvs_ctx_intersect_stats)
     void* ix_work = nullptr;    size_t ix_work_bytes = 0;
@@ -220,6 +225,37 @@ struct EventPair {
     ~EventPair() {
         for (hipEvent_t x : e)
             if (x) (void)hipEventDestroy(x);
+    }
+};
+
+// The time of a stretch of kernels on the context's stream, for a statistic.  With timing off every method does nothing: a
+// call site synchronises exactly where it did without the timer.
+struct StageTimer {
+    EventPair ev;
+    hipStream_t stream = nullptr;
+    bool on = false;
+    // the stretch begins here
+    int begin(mvs_ctx* c) {
+        on = c->timing;
+        if (!on) return MVS_OK;
+        stream = c->stream;
+        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(hipEventRecord(ev.e[0], stream));
+        return MVS_OK;
+    }
+    // ... and ends here (nothing waits)
+    int mark_end() {
+        if (on) HIP_TRY(hipEventRecord(ev.e[1], stream));
+        return MVS_OK;
+    }
+    // waits for the end mark (at once where the caller has synchronised the stream since) and adds the stretch's time
+    int add_to(double* ms) {
+        if (!on) return MVS_OK;
+        HIP_TRY(hipEventSynchronize(ev.e[1]));
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, ev.e[0], ev.e[1]));
+        *ms += t;
+        return MVS_OK;
     }
 };
 
@@ -299,11 +335,40 @@ int pairwise_launch(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int
                     unsigned long long start, unsigned long long* count, double keep_coeff = 0.05,
                     const PackedOut* po = nullptr, const DenseOut* dn = nullptr, const mvs::Options* o = nullptr);
 
-// ---- mvs_capi_cluster.hip ----
+// ---- mvs_capi_cluster.hip: what the consumers of kept cells share (clustering, linkage, dereplication) ----
 // the threshold comparison of a set with itself at a Jaccard level, each row block's unsorted cells handed to
 // consume(cells, n_cells, row_begin, row_end); the blocks arrive in ascending row order and tile [0, n)
+using ConsumeCells = std::function<int(const mvs_cell*, int64_t, int64_t, int64_t)>;
 int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, double min_jaccard, double* compare_ms, long long* row_blocks,
-                  const std::function<int(const mvs_cell*, int64_t, int64_t, int64_t)>& consume);
+                  const ConsumeCells& consume);
+// *d_n2 := n norms on the device: norms_sq itself, or a copy of the host's in `staging` (queued on the context's stream)
+int norms_on_device(mvs_ctx* c, const double* norms_sq, int mem_norms, int64_t n, DevBuf& staging, const double** d_n2);
+// The argument checks of mvs_pairwise_cluster / _linkage / _derep, `noun` naming the consumer `k` (any of the three objects);
+// an entry point's own checks follow them.
+template <typename K>
+int consumer_checks(const char* noun, const mvs_ctx* c, const mvs_sketch_set* s, const K* k, int mem_norms, double min_jaccard) {
+    if (!c || !s || !k) return fail(MVS_E_INVALID, "NULL argument");
+    if (!(min_jaccard > 0.0) || !(min_jaccard < 1.0)) return fail(MVS_E_INVALID, "min_jaccard = %g outside (0, 1)", min_jaccard);
+    if (!mem_ok(mem_norms)) return fail(MVS_E_INVALID, "bad argument");
+    if (k->ctx != c) return fail(MVS_E_INVALID, "the %s belongs to another context", noun);
+    if (k->n != s->n) return fail(MVS_E_INVALID, "the %s holds %lld samples, the sketch set %lld", noun, (long long)k->n, (long long)s->n);
+    return MVS_OK;
+}
+// ... and what follows the checks: nothing for an empty set, else the norms to the device and pairwise_feed under the marker
+// range `entry`, with the comparison's time and row blocks added to `st`
+int feed_consumer(const char* entry, mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int mem_norms, double min_jaccard,
+                  ConsumerStats& st, const ConsumeCells& consume);
+// the body of mvs_ctx_cluster_stats / _linkage_stats / _derep_stats
+int consumer_stats_out(const mvs_ctx* c, ConsumerStats mvs_ctx::*which, double* compare_ms, double* work_ms, int64_t* edges,
+                       int64_t* row_blocks, int64_t* rounds);
+// `count` results of a *_finish to the caller's buffer (NULL: not wanted), queued on the context's stream
+template <typename T>
+int give_out(mvs_ctx* c, T* dst, const void* d_src, int64_t count, int mem_out) {
+    if (!dst || count <= 0) return MVS_OK;
+    HIP_TRY(hipMemcpyAsync(dst, d_src, (size_t)count * sizeof(T), mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                           c->stream));
+    return MVS_OK;
+}
 }  // namespace mvs_capi
 
 #endif

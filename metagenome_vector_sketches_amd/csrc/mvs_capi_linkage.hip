@@ -51,14 +51,12 @@ mvs::LinkState state_of(const mvs_linkage* k) {
 int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
     mvs_ctx* c = k->ctx;
     if (n_cells == 0) return MVS_OK;
-    EventPair ev;
-    if (c->timing) {
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-    }
+    StageTimer timer;
+    int rc = timer.begin(c);
+    if (rc) return rc;
     const mvs::LinkState s = state_of(k);
     HIP_TRY(hipMemsetAsync(k->counters, 0, 8 * sizeof(unsigned long long), c->stream));
-    int rc = mvs::launch_link_identity(c->stream, k->comp, k->n);
+    rc = mvs::launch_link_identity(c->stream, k->comp, k->n);
     if (!rc) rc = check_kernel("k_link_identity");
     if (rc) return rc;
     unsigned long long back[5] = {0, 0, 0, 0, 0};
@@ -92,15 +90,11 @@ int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
     k->cur ^= 1;
     k->n_forest = (int64_t)back[3];
     k->links_valid = false;
-    if (c->timing) {
-        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
-        HIP_TRY(hipEventSynchronize(ev.e[1]));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        c->lk_forest_ms += ms;
-    }
-    c->lk_edges += (long long)back[0];
-    c->lk_rounds = std::max<long long>(c->lk_rounds, round);
+    rc = timer.mark_end();
+    if (!rc) rc = timer.add_to(&c->lk.work_ms);
+    if (rc) return rc;
+    c->lk.edges += (long long)back[0];
+    c->lk.rounds = std::max<long long>(c->lk.rounds, round);
     if (back[1] != 0)
         return fail(MVS_E_RANGE, "%llu cells name a sample outside [0, %lld): they were ignored", back[1], (long long)k->n);
     return MVS_OK;
@@ -120,22 +114,18 @@ int sort_links(mvs_linkage* k) {
     if (rc) return fail(rc, "linkage finish: sort sizing failed");
     HIP_TRY(dtmp.alloc((size_t)k->n_forest * sizeof(mvs_link)));
     HIP_TRY(dscratch.alloc(need));
-    EventPair ev;
-    if (c->timing) {
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-    }
+    StageTimer timer;
+    rc = timer.begin(c);
+    if (rc) return rc;
     rc = mvs::link_sorted(c->stream, s, (mvs_link*)dtmp.p, k->links, dscratch.p, need, nullptr);
     if (rc) return fail(rc, "linkage finish: sort failed");
     rc = check_kernel("k_link_links");
     if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    rc = timer.mark_end();
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));   // (also before the DevBufs free the scratch)
-    if (c->timing) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        c->lk_forest_ms += ms;
-    }
+    rc = timer.add_to(&c->lk.work_ms);
+    if (rc) return rc;
     k->links_valid = true;
     return MVS_OK;
 }
@@ -175,8 +165,7 @@ int mvs_linkage_create(mvs_ctx* c, int64_t n, int d, const double* norms_sq, int
             return fail(MVS_E_HIP, "copying the norms: %s", hipGetErrorString(e2));
         }
     }
-    c->lk_compare_ms = c->lk_forest_ms = 0.0;
-    c->lk_edges = c->lk_blocks = c->lk_rounds = 0;
+    c->lk.reset();
     *out = k;
     return MVS_OK;
 }
@@ -191,26 +180,10 @@ int mvs_linkage_add_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cel
 
 int mvs_pairwise_linkage(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int mem_norms, double min_jaccard,
                          mvs_linkage* k) {
-    if (!c || !s || !k) return fail(MVS_E_INVALID, "NULL argument");
-    if (!(min_jaccard > 0.0) || !(min_jaccard < 1.0)) return fail(MVS_E_INVALID, "min_jaccard = %g outside (0, 1)", min_jaccard);
-    if (!mem_ok(mem_norms)) return fail(MVS_E_INVALID, "bad argument");
-    if (k->ctx != c) return fail(MVS_E_INVALID, "the linkage belongs to another context");
-    if (k->n != s->n) return fail(MVS_E_INVALID, "the linkage holds %lld samples, the sketch set %lld", (long long)k->n, (long long)s->n);
+    const int rc = consumer_checks("linkage", c, s, k, mem_norms, min_jaccard);
+    if (rc) return rc;
     if (k->d != s->d) return fail(MVS_E_INVALID, "the linkage was created for dimension %d, the sketch set has %d", k->d, s->d);
-    const int64_t n = s->n;
-    if (n == 0) return MVS_OK;
-    if (!norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
-    const Range range(c, "mvs_pairwise_linkage");
-    HIP_TRY(hipSetDevice(c->device));
-
-    DevBuf dn;
-    const double* d_n2 = norms_sq;
-    if (mem_norms == MVS_MEM_HOST) {
-        HIP_TRY(dn.alloc((size_t)n * 8));
-        HIP_TRY(hipMemcpyAsync(dn.p, norms_sq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        d_n2 = (const double*)dn.p;
-    }
-    return pairwise_feed(c, s, d_n2, min_jaccard, &c->lk_compare_ms, &c->lk_blocks,
+    return feed_consumer("mvs_pairwise_linkage", c, s, norms_sq, mem_norms, min_jaccard, c->lk,
                          [k](const mvs_cell* d_cells, int64_t n_cells, int64_t, int64_t) { return consume_cells(k, d_cells, n_cells); });
 }
 
@@ -272,13 +245,7 @@ int mvs_linkage_destroy(mvs_linkage* k) {
 
 int mvs_ctx_linkage_stats(const mvs_ctx* c, double* compare_ms, double* forest_ms, int64_t* edges, int64_t* row_blocks,
                           int64_t* rounds) {
-    if (!c) return fail(MVS_E_INVALID, "NULL context");
-    if (compare_ms) *compare_ms = c->lk_compare_ms;
-    if (forest_ms) *forest_ms = c->lk_forest_ms;
-    if (edges) *edges = c->lk_edges;
-    if (row_blocks) *row_blocks = c->lk_blocks;
-    if (rounds) *rounds = c->lk_rounds;
-    return MVS_OK;
+    return consumer_stats_out(c, &mvs_ctx::lk, compare_ms, forest_ms, edges, row_blocks, rounds);
 }
 
 }  // extern "C"

@@ -92,3 +92,41 @@ def test_generated_code_of_the_hand_counted_loads():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_isa.py"), "--self-test"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "direct-B kernels pass" in r.stdout and "all 3 mutations" in r.stdout
+
+
+@pytest.mark.gpu
+def test_handles_close_once_and_in_order():
+    """Cluster, Linkage, Derep and HashSet share one base (_capi._Handle): the context closes its children before itself, a
+    second close is a no-op, and each is a context manager"""
+    import numpy as np
+    ctx = _capi.Context(0)
+    try:
+        n2 = np.ones(8)
+        kids = [_capi.Cluster(ctx, 8), _capi.Linkage(ctx, 8, 64, n2), _capi.Derep(ctx, 8),
+                ctx.hash_set(np.arange(16, dtype=np.uint64), np.arange(0, 17, 2, dtype=np.int64))]
+        sset = ctx.sketch_set(np.ones((8, 64), dtype=np.int32))
+        assert [type(k).__name__ for k in kids] == ["Cluster", "Linkage", "Derep", "HashSet"]
+        assert all(isinstance(k, _capi._Handle) and k._h for k in kids) and sset._h
+        calls = []
+        for k in kids + [sset]:
+            k.close = (lambda k=k, close=k.close: (calls.append(type(k).__name__), close()))
+        ctx.close()
+        assert ctx._h is None and all(k._h is None for k in kids) and sset._h is None
+        assert calls[0] == "SketchSet" and sorted(calls[1:]) == ["Cluster", "Derep", "HashSet", "Linkage"]
+        for k in kids + [sset]:
+            del k.close
+            k.close()                                                         # closed already: nothing happens
+            assert k._h is None
+        ctx.close()
+    finally:
+        ctx.close()
+    ctx = _capi.Context(0)
+    try:
+        with _capi.Cluster(ctx, 4) as k:
+            assert k._h
+        assert k._h is None
+        with _capi.Derep(ctx, 4) as k2, _capi.Linkage(ctx, 4, 64, np.ones(4)) as k3:
+            assert k2._h and k3._h
+        assert k2._h is None and k3._h is None
+    finally:
+        ctx.close()

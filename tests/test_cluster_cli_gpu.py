@@ -103,3 +103,48 @@ def test_20k_db_file_equals_brute_force(ctx, tmp_path):
     assert len(want["sizes"]) == n // 5 and (want["degree"] == 4).all()     # not degenerate
     assert got == _lines(names, want) + [""]
     assert stats == (n, t, n // 5, 0, 5)
+
+
+def _limb_db():
+    """96 x 64 int32, small values except one of 40000 in row 85: two limbs hold |v| <= 32639, so the tool's loader allocates
+    for two, meets the value and starts over with three.  Rows 0-4 and 40-42 are near copies; column 5 is zero except in
+    rows 84 and 85, and row 85's norm in the file (200) is far below its true one (5000), which links the two at t = 0.3
+    (estimate 0.45)."""
+    rng = np.random.default_rng(23)
+    sk = rng.integers(-9, 10, size=(96, 64)).astype(np.int32)
+    for rows in ((0, 1, 2, 3, 4), (40, 41, 42)):
+        sk[list(rows)] = sk[rows[0]] + rng.integers(-1, 2, size=(len(rows), 64))
+    sk[:, 5] = 0
+    sk[84, 5] = 20
+    sk[85, 5] = 40000
+    texts = [repr(float(np.sqrt(s / 64.0))) for s in (sk.astype(np.int64) ** 2).sum(axis=1)]
+    texts[85] = "200.0"
+    return sk, texts, np.array([float(x) * float(x) for x in texts])
+
+
+def test_db_that_needs_more_limbs_equals_the_library(ctx, tmp_path):
+    """the shared loader's restart (mvs_tool.hpp: load_sketch_db) through an analysis tool: the file equals what
+    Context.cluster gives on a set the library sized itself, and both equal the brute force"""
+    sk, texts, n2 = _limb_db()
+    n, d, t = 96, 64, 0.3
+    names = ["L%02d" % i for i in range(n)]
+    db = str(tmp_path / "db") + "/"
+    _write_db(db, sk, "".join("%s %s\n" % (a, b) for a, b in zip(names, texts)), "int32")
+    sset = ctx.sketch_set(sk)
+    try:
+        assert sset.limbs == 3
+        res = ctx.cluster(sset, n2, t)
+    finally:
+        sset.close()
+    lib = dict(labels=res.labels, degree=res.degree, representatives=res.representatives, sizes=res.sizes)
+    dots = (sk.astype(np.int64) @ sk.astype(np.int64).T)
+    assert np.abs(dots).max() < 2**31
+    r, c = brute_edges(dots.astype(np.int32), n2, d, t)
+    want = brute_cluster(n, r, c, n2)
+    assert (want["sizes"] > 1).sum() >= 2 and (84, 85) in set(zip(r.tolist(), c.tolist()))         # not degenerate
+    assert want["labels"][84] == want["labels"][85] and want["degree"][85] == 1
+    out = str(tmp_path / "clusters.tsv")
+    got, stats = _cluster(db, out, t)
+    assert got == _lines(names, lib) + [""]
+    assert got == _lines(names, want) + [""]
+    assert stats == (n, t, len(want["sizes"]), int((want["sizes"] == 1).sum()), int(want["sizes"].max()))

@@ -406,3 +406,47 @@ def test_edge_cases(ctx):
         assert (got.link_dot.tolist(), got.link_q.tolist()) == ([64 * 25, 0, 0], [255, -1, -1])
     finally:
         sset.close()
+
+
+def test_timing_on_and_off_give_the_same_results_and_consistent_statistics(ctx, gold):
+    """the three consumers of kept cells share one timer and one statistics record (mvs_capi_internal.h: StageTimer,
+    ConsumerStats): timing changes the two times and nothing else, and creating one consumer resets only its own record"""
+    sk, n2 = _toy(gold)
+    t = 0.2
+    runs = (("cluster", lambda: ctx.cluster(sset, n2, t), ctx.cluster_stats, "union_ms",
+             ("labels", "degree", "representatives", "sizes")),
+            ("linkage", lambda: ctx.linkage(sset, n2, t), ctx.linkage_stats, "forest_ms", ("a", "b", "dot", "q", "jaccard")),
+            ("derep", lambda: ctx.dereplicate(sset, n2, t), ctx.derep_stats, "greedy_ms",
+             ("rep_of", "link_dot", "link_q", "sizes")))
+    sset = ctx.sketch_set(sk)
+    try:
+        seen = {}
+        for timing in (True, False):
+            ctx.set_timing(timing)
+            for name, run, stats, work_key, fields in runs:
+                res, st = run(), stats()
+                print(name, "timing", timing, st)
+                assert sorted(st) == sorted(["compare_ms", work_key, "edges", "row_blocks", "rounds"])
+                if timing:
+                    assert st["compare_ms"] > 0 and st[work_key] > 0, (name, st)
+                else:
+                    assert st["compare_ms"] == 0.0 and st[work_key] == 0.0, (name, st)
+                seen[name, timing] = (res, st)
+        for name, _, _, _, fields in runs:
+            (on, st_on), (off, st_off) = seen[name, True], seen[name, False]
+            for f in fields:
+                assert np.array_equal(getattr(on, f), getattr(off, f)), (name, f)
+            for key in ("edges", "row_blocks", "rounds"):
+                assert st_on[key] == st_off[key], (name, key)
+            assert st_on["edges"] == 406 and st_on["row_blocks"] == 1 and st_on["rounds"] >= 1, (name, st_on)
+        # a new consumer resets its own record only
+        before = ctx.cluster_stats()
+        ctx.linkage(sset, n2, 0.5)
+        ctx.dereplicate(sset, n2, 0.5)
+        assert ctx.cluster_stats() == before and before["edges"] == 406
+        assert ctx.linkage_stats()["edges"] == 16 and ctx.derep_stats()["edges"] == 16
+        ctx.cluster(sset, n2, 0.5)
+        assert ctx.cluster_stats()["edges"] == 16 and ctx.linkage_stats()["edges"] == 16
+    finally:
+        ctx.set_timing(False)
+        sset.close()
