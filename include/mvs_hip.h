@@ -136,6 +136,9 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   topk_dots, topk_block_rows
  *                         mvs_pairwise_topk: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds
  *                         the rows of a block (0: by the device budget)
+ *   contain_dots, contain_block_rows
+ *                         mvs_pairwise_contain: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds
+ *                         the rows of a block (0: by the device budget)
  *   cluster_cells, cluster_block_rows
  *                         mvs_pairwise_cluster: cells the staging buffer of a row block holds (0, default: a quarter of the free
  *                         device memory) and an upper bound on the rows of a block (0: by pairwise_block_cells); a block that
@@ -459,6 +462,47 @@ int mvs_pairwise_topk(mvs_ctx* ctx, const mvs_sketch_set* set, const double* nor
                       int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int flags,
                       mvs_cell* cells, int mem_cells, int64_t* n_cells);
 int mvs_ctx_topk_stats(const mvs_ctx* ctx, double* dots_ms, double* select_ms, int64_t* row_blocks, int64_t* block_rows);
+
+/* Containment from sketches: the cells whose ESTIMATED CONTAINMENT of the row's sample in the column's sample exceeds a level.
+ * Every call above scores a pair by its Jaccard estimate, which the size ratio of the two samples bounds (a sample wholly
+ * contained in one 30 x its size has J <= 0.033, under every keep level here); dot / d estimates |A n B| and n2 estimates |A|,
+ * so the containment |A n B| / |A| is in the same data.  The reference has nothing of the kind.
+ *
+ * The rule.  Row i, column j, i != j; P the int32 dot as mvs_pairwise_dots returns it (wrapped); c = min_containment,
+ * 0 < c < 1; z = slack, any finite double.  Everything is fp64 and each line is ONE rounding:
+ *     inter = (double)P / (double)d
+ *     t     = c * n2[i]
+ *     e     = inter - t                       (never fused with the product above)
+ *     ok    = n2[i] > 0 && n2[i] < inf && n2[j] >= 0 && n2[j] < inf      (NaN fails)
+ *     z == 0 : dir(i,j) = ok && e > 0
+ *     z  > 0 : dir(i,j) = ok && e > 0 && (e*e)*(double)d > (z*z) * (n2[i]*n2[j])
+ *     z  < 0 : dir(i,j) = ok && (e > 0 || (e*e)*(double)d < (z*z) * (n2[i]*n2[j]))
+ * -- "the estimated containment of i in j exceeds c by more than z standard errors": the variance of inter is about
+ * n2[i] n2[j] / d, and the test is written in squares so that no square root is taken.  z > 0 buys precision, z < 0 recall:
+ * candidate lists for an exact step (mvs_intersect_cells).
+ *   flags : MVS_CONTAIN_ROW  a cell is kept iff dir(i,j);
+ *           MVS_CONTAIN_MAX  a cell is kept iff dir(i,j) || dir(j,i): max-containment, symmetric bit for bit, so its cells may
+ *                            feed mvs_cluster_add_cells / mvs_linkage_add_cells.
+ *   Cells with row == col are never reported.
+ *   q     : Cq = inter / n2[i]; !(Cq > 0) -> 0; Cq > 1 -> 1; q = (int32)round(Cq * 255), halves away from zero.  In MAX mode
+ *           the larger of the two directions' values, a direction whose row norm is not in (0, inf) counting 0.  0 <= q <= 255;
+ *           0 occurs at z < 0.  dot = P.
+ *   cells : `capacity` entries (`mem_cells`); on success *n_cells kept cells sorted by (row, col).  More than `capacity` kept:
+ *           MVS_E_CAPACITY and *n_cells is the number needed (capacity 0 with cells NULL asks for the count alone).
+ *   norms_sq : n doubles (`mem_norms`).
+ *   min_containment outside (0, 1), a non-finite slack, unknown flags, ranges outside the set: MVS_E_INVALID.  An empty row or
+ *   column range: MVS_OK with 0 cells.
+ * Exact and deterministic: bit-identical to a brute-force evaluation of the rule above, whatever the device, the blocking or
+ * the options.  Rows go in blocks sized as mvs_pairwise_topk sizes them (option contain_block_rows bounds them, option
+ * contain_dots = 1 computes the dots on the vector ALUs); one dense-dots launch per block, no N x N buffer.  Synchronous.
+ * mvs_ctx_contain_stats: what the last call did -- dots and selection kernel times summed over its row blocks (0 unless
+ * mvs_ctx_set_timing is on), the number of row blocks and the rows per block.  Any pointer may be NULL. */
+#define MVS_CONTAIN_ROW 0
+#define MVS_CONTAIN_MAX 1
+int mvs_pairwise_contain(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double min_containment,
+                         double slack, int flags, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                         mvs_cell* cells, int mem_cells, int64_t capacity, int64_t* n_cells);
+int mvs_ctx_contain_stats(const mvs_ctx* ctx, double* dots_ms, double* select_ms, int64_t* row_blocks, int64_t* block_rows);
 
 /* Single-linkage clustering of the samples at a Jaccard level, on the device: samples i != j are LINKED iff
  *   (double)dot / (double)d > (t / (1.0 + t)) * (n2[i] + n2[j])        (fp64, in that order; t = min_jaccard, 0 < t < 1)

@@ -17,6 +17,7 @@ MVS_OK, MVS_E_INVALID, MVS_E_HIP, MVS_E_CAPACITY, MVS_E_NOMEM, MVS_E_RANGE, MVS_
 MEM_HOST, MEM_DEVICE = 0, 1
 KEEP_INT32, KEEP_INT16 = 0, 1
 TOPK_EXCLUDE_SELF = 1
+CONTAIN_ROW, CONTAIN_MAX = 0, 1
 LIMBS_K3 = 0x103
 BLOCK_SYMMETRIC, BLOCK_MIRROR_ALL = 1, 2
 
@@ -106,6 +107,10 @@ SYMBOLS = [
                                       _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_int64)]),
     ("mvs_ctx_topk_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                        _c.POINTER(_c.c_int64)]),
+    ("mvs_pairwise_contain", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _c.c_double, _c.c_int, _c.c_int64, _c.c_int64,
+                                         _c.c_int64, _c.c_int64, _P, _c.c_int, _c.c_int64, _c.POINTER(_c.c_int64)]),
+    ("mvs_ctx_contain_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
+                                          _c.POINTER(_c.c_int64)]),
     ("mvs_cluster_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_cluster_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
     ("mvs_pairwise_cluster", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
@@ -1263,6 +1268,55 @@ class Context:
         a, b = _c.c_double(), _c.c_double()
         n, r = _c.c_int64(), _c.c_int64()
         _check(self.lib.mvs_ctx_topk_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)))
+        return {"dots_ms": a.value, "select_ms": b.value, "row_blocks": n.value, "block_rows": r.value}
+
+    def pairwise_contain(self, sset, norms_sq, min_containment, slack=0.0, mode="row", row_begin=0, row_end=None, col_begin=0,
+                         col_end=None, cells_out=None):
+        """mvs_pairwise_contain: the cells (row, col), row != col, whose estimated containment of the row's sample in the
+        column's exceeds min_containment (0 < c < 1) by more than `slack` standard errors (include/mvs_hip.h states the rule);
+        mode "row" keeps the directed cells, "max" a cell that passes in either direction.  Returns a structured CELL_DTYPE
+        array sorted by (row, col) -- q is the quantised containment estimate -- or, with a device buffer `cells_out` (torch
+        int32 tensor [capacity, 4]), (cells_out, n_cells); a buffer that is too small raises MvsError with `needed` set."""
+        if mode not in ("row", "max"):
+            raise ValueError("mode must be 'row' or 'max'")
+        if row_end is None:
+            row_end = sset.n
+        if col_end is None:
+            col_end = sset.n
+        np_, nm, nk = _norms(norms_sq)
+        flags = CONTAIN_MAX if mode == "max" else CONTAIN_ROW
+        count = _c.c_int64()
+
+        def call(ptr, mem, capacity):
+            rc = self.lib.mvs_pairwise_contain(self._h, sset._h, np_, nm, float(min_containment), float(slack), flags,
+                                               int(row_begin), int(row_end), int(col_begin), int(col_end), ptr, mem,
+                                               int(capacity), ctypes.byref(count))
+            if rc == MVS_E_CAPACITY:
+                raise MvsError(rc, self.lib.mvs_last_error().decode("utf-8", "replace"), needed=count.value)
+            _check(rc)
+
+        if cells_out is not None:
+            cp, cm, ck = _buf(cells_out)
+            call(cp, cm, cells_out.shape[0])
+            return cells_out, count.value
+        capacity = max(1024, 16 * max(0, int(row_end) - int(row_begin)))
+        for attempt in range(2):
+            cells = np.empty(capacity, dtype=CELL_DTYPE)
+            try:
+                call(cells.ctypes.data, MEM_HOST, capacity)
+                break
+            except MvsError as e:
+                if e.code != MVS_E_CAPACITY or attempt:
+                    raise
+                capacity = int(e.needed)
+        return cells[:count.value]
+
+    def contain_stats(self):
+        """-> dict of the last pairwise_contain: dots_ms / select_ms (kernel times over its row blocks, timing on), row_blocks,
+        block_rows"""
+        a, b = _c.c_double(), _c.c_double()
+        n, r = _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_contain_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)))
         return {"dots_ms": a.value, "select_ms": b.value, "row_blocks": n.value, "block_rows": r.value}
 
     def _consumer_stats(self, fn, work_key):

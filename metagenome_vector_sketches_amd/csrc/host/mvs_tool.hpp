@@ -1,6 +1,6 @@
 // mvs_tool.hpp -- what the tools over a sketch DB share (cluster_sketches, linkage_sketches, dereplicate_sketches, verify_pairs,
 // and pairwise_comp_optimized for the loader): opening the DB folder, loading vectors.bin into a sketch set, reporting a
-// device error, writing an output file under <file>.part, and the parsing of flag values.  Header-only; include it after
+// device error, writing an output file under <file>.part, the hash file a DB was sketched from, and the parsing of flag values.  Header-only; include it after
 // mvs_host.hpp.  Each tool keeps its own parse() chain, usage text, Gpu holder and output format.
 #ifndef MVS_TOOL_HPP
 #define MVS_TOOL_HPP
@@ -156,6 +156,35 @@ inline int load_sketch_db(const char* prog, mvs_ctx* ctx, const SketchDb& db, mv
     }
     if (bytes) ::munmap((void*)base, bytes);
     return rc;
+}
+
+// ---- the hash file a DB was sketched from ----
+// The hash lists of the DB's samples: the parsed form `project_everything sketch` left next to the text (<file>.csr) when it
+// is valid, else the text.  The file's sample names must be the DB's names in the DB's order.  0, or 1 after a message on
+// stderr; no device is needed.
+inline int load_db_hashes(const char* prog, const std::string& hash_file, const SketchDb& db, HashSets& sets) {
+    bool parsed = load_csr_cache(hash_file, sets);
+    if (!parsed) {
+        try {
+            parsed = read_hash_file(hash_file, true, sets);
+        } catch (const std::exception& e) {
+            std::cerr << prog << ": reading " << hash_file << ": " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if (!parsed) {
+        std::cerr << "Error opening " << hash_file << " for reading." << std::endl;
+        return 1;
+    }
+    const std::vector<std::string>& names = db.info.names;
+    if ((int64_t)sets.names.size() != db.n || !std::equal(sets.names.begin(), sets.names.end(), names.begin())) {
+        size_t at = 0;
+        while (at < sets.names.size() && at < (size_t)db.n && sets.names[at] == names[at]) ++at;
+        std::cerr << prog << ": the samples of " << hash_file << " (" << sets.names.size() << ") are not those of " << db.folder
+                  << "vector_norms.txt (" << db.n << ") in the same order: first difference at sample " << at << std::endl;
+        return 1;
+    }
+    return 0;
 }
 
 }  // namespace mvs_host

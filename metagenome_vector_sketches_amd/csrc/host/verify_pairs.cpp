@@ -143,28 +143,8 @@ int main(int argc, char* argv[]) {
     const int64_t n = sdb.n;
     const int dimension = sdb.dimension;
 
-    // the hash lists: the parsed form `project_everything sketch` left next to the text when it is valid, else the text
     HashSets sets;
-    bool parsed = load_csr_cache(o.hash_file, sets);
-    if (!parsed) {
-        try {
-            parsed = read_hash_file(o.hash_file, true, sets);
-        } catch (const std::exception& e) {
-            std::cerr << "verify_pairs: reading " << o.hash_file << ": " << e.what() << std::endl;
-            return 1;
-        }
-    }
-    if (!parsed) {
-        std::cerr << "Error opening " << o.hash_file << " for reading." << std::endl;
-        return 1;
-    }
-    if ((int64_t)sets.names.size() != n || !std::equal(sets.names.begin(), sets.names.end(), db.names.begin())) {
-        size_t at = 0;
-        while (at < sets.names.size() && at < (size_t)n && sets.names[at] == db.names[at]) ++at;
-        std::cerr << "verify_pairs: the samples of " << o.hash_file << " (" << sets.names.size() << ") are not those of " << sdb.folder
-                  << "vector_norms.txt (" << n << ") in the same order: first difference at sample " << at << std::endl;
-        return 1;
-    }
+    if (const int rc = load_db_hashes(kProg, o.hash_file, sdb, sets)) return rc;
 
     std::vector<Pair> pairs;
     std::vector<int32_t> sizes((size_t)n);

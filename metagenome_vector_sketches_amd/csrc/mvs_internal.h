@@ -109,6 +109,9 @@ struct Options {
     int topk_dots = 0;              // mvs_pairwise_topk: dots of a row block from 0 = the matrix-core kernels (launch_pairwise algo 0),
                                     // 1 = the vector-ALU kernel (A/B, tests); same selection, same result
     int topk_block_rows = 0;        // mvs_pairwise_topk: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
+    int contain_dots = 0;           // mvs_pairwise_contain: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU
+                                    // kernel (A/B, tests); same selection, same result
+    int contain_block_rows = 0;     // mvs_pairwise_contain: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
     int cluster_cells = 0;          // mvs_pairwise_cluster: cells the staging buffer of a row block holds; 0 = a quarter of the free
                                     // device memory (never more than the block can produce); tests lower it
     int cluster_block_rows = 0;     // mvs_pairwise_cluster: > 0 = upper bound on the rows of a block (tests); 0 = by pairwise_block_cells
@@ -275,6 +278,22 @@ int launch_topk_select(hipStream_t stream, const int32_t* d_dots, int64_t rows, 
                        int64_t out_row0);
 int launch_topk_compact(hipStream_t stream, const mvs_cell* d_pad, const int* d_counts, const int64_t* d_offs, int64_t rows,
                         int k, mvs_cell* d_out);
+// containment selection over a block of dense dots (mvs_contain.hip; the rule is stated there and in include/mvs_hip.h):
+// zz = slack * slack (one rounding, on the host), zsign = the sign of slack, dd = (double)d, pretest = 1 for slack >= 0.
+// thr: the integer pre-test value of every sample; count: kept cells per row of the block; scan: offs[r] = *d_total + cells of
+// the block's earlier rows, *d_total advances; fill: the rows' cells in (row, col) order at their offsets -- a row that does
+// not fit `capacity` is left out
+struct ContainRule {
+    double c, zz, dd;
+    int zsign, mode, pretest;
+};
+int launch_contain_thr(hipStream_t stream, const double* d_norms_sq, int64_t n, const ContainRule& ru, int* d_thr);
+int launch_contain_count(hipStream_t stream, const int32_t* d_dots, int64_t rows, int64_t ld, int64_t row0, int64_t c0,
+                         const double* d_norms_sq, const int* d_thr, const ContainRule& ru, int* d_counts);
+int launch_contain_scan(hipStream_t stream, const int* d_counts, int64_t rows, long long* d_offs, unsigned long long* d_total);
+int launch_contain_fill(hipStream_t stream, const int32_t* d_dots, int64_t rows, int64_t ld, int64_t row0, int64_t c0,
+                        const double* d_norms_sq, const int* d_thr, const ContainRule& ru, const int* d_counts,
+                        const long long* d_offs, mvs_cell* d_cells, int64_t capacity);
 // single-linkage clustering over device cell lists (mvs_cluster.hip): union-find rounds over parent[n] -- d_counters: [0] cells
 // with row != col, [1] cells with an index outside [0, n), [2] cells whose endpoints still have different roots -- and the
 // finish passes (cluster ids by ascending root, sizes, representatives)

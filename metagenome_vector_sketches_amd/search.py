@@ -17,6 +17,10 @@ Extension: `search ... --hashes_db FILE` (FILE = the hash file the DB was sketch
 verifies every reported hit on the hash sets themselves: each hit also carries its EXACT Jaccard and the containment of the
 query in the hit, |Q n H| / |Q| (Context.intersect_cells on the hits while they are still on the device).  Without the flag
 nothing changes.
+
+Extension: `search ... --containment C [--slack Z]` reports, instead of the samples above -j, the database samples that CONTAIN
+each query: containment estimate (dot/d) / query_norm^2 above C by more than Z standard errors (SearchIndex.search_containment;
+the rule of mvs_pairwise_contain).  Both flags stay out of the usage text, like --hashes_db.
 """
 import os
 
@@ -154,6 +158,59 @@ class SearchIndex:
         out = []
         for q0 in range(0, len(lists), self.max_queries):
             out += self._topk_lists(lists[q0:q0 + self.max_queries], q0, k, verbose)
+        return out
+
+    def search_containment(self, query_file, c, slack=0.0, verbose=False):
+        """-> list of (query_index, name, containment_estimate): per query the database samples that CONTAIN it -- those whose
+        containment estimate (dot/d) / query_norm^2 exceeds c (0 < c < 1) by more than `slack` standard errors (the rule of
+        mvs_pairwise_contain, include/mvs_hip.h) --, best first (ties: the earlier sample).  A sample many times the query's
+        size is found here where its Jaccard stays under every -j.  With hashes_db every tuple also carries the exact Jaccard
+        and the exact containment of the query in the hit.  A query with norm 0 gets nothing."""
+        qnames, lists = read_queries(query_file)
+        out = []
+        for q0 in range(0, len(lists), self.max_queries):
+            out += self._contain_lists(lists[q0:q0 + self.max_queries], q0, float(c), float(slack), verbose)
+        return out
+
+    def _contain_lists(self, lists, q_first, c, slack, verbose):
+        """_search_lists with the containment rule: rows are the queries, columns the database, one grow-only hits buffer"""
+        import torch
+        ctx, n, d, names, dev = self.ctx, self.n, self.d, self.names, self.dev
+        nq = len(lists)
+        if nq == 0:
+            return []
+        qn2, n2 = self._queries_in_set(lists)
+        cap = max(1 << 16, 256 * nq) if self._hits is None else self._hits.shape[0]
+        for attempt in range(2):
+            if self._hits is None or self._hits.shape[0] < cap:
+                self._hits = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+            try:
+                _, cnt = ctx.pairwise_contain(self.sset, n2, c, slack, "row", n, n + nq, 0, n, cells_out=self._hits)
+                break
+            except _capi.MvsError as e:
+                if e.code != _capi.MVS_E_CAPACITY or attempt or not e.needed:
+                    raise
+                cap = int(e.needed)
+        ctx.synchronize()
+        exact = self._exact(lists, self._hits[:cnt]) if self.hs is not None and cnt else None
+        hits = self._hits[:cnt].cpu().numpy()
+        out = []
+        for qi in range(nq):
+            if qn2[qi] == 0:
+                continue
+            sel = np.nonzero(hits[:, 0] == n + qi)[0]
+            mine = hits[sel]
+            est = mine[:, 2].astype(np.float64) / d / qn2[qi]
+            order = np.argsort(-est, kind="stable")
+            if verbose:
+                print("Query %d:" % (q_first + qi))
+            for rank, k in enumerate(order):
+                nid = names[mine[k, 1]]
+                more = () if exact is None else (float(exact[0][sel[k]]), float(exact[1][sel[k]]))
+                if verbose:
+                    print("  Container %d: %s (containment: %.4f)" % (rank, nid, est[k])
+                          + ("" if exact is None else " exact_jaccard: %.4f exact_containment: %.4f" % more))
+                out.append((q_first + qi, nid, float(est[k])) + more)
         return out
 
     def _queries_in_set(self, lists):
@@ -303,6 +360,16 @@ def search_index_topk(index_folder, query_file, k, ctx=None, verbose=True, hashe
         return idx.search_topk(query_file, k, verbose=verbose)
 
 
+def search_index_containment(index_folder, query_file, c, slack=0.0, ctx=None, verbose=True, hashes_db=None):
+    """search_index's containment form: [(query_index, name, containment estimate)] of the database samples that contain each
+    query (with hashes_db: also the exact Jaccard and the exact containment of the query in the hit)."""
+    nq = sum(1 for line in open(query_file) if line.strip())
+    with SearchIndex(index_folder, ctx=ctx, max_queries=max(1, min(nq, 4096)), hashes_db=hashes_db) as idx:
+        if ctx is not None:
+            idx._own = False
+        return idx.search_containment(query_file, c, slack, verbose=verbose)
+
+
 def index_vectors(output_dir, verbose=True):
     """The reference's `index` step (src/jaccard.py:18-61) reads vectors.bin, L2-normalises a float copy and writes
     faiss.index.  Nothing of that is needed here -- the search runs on the integer sketches -- so this only checks that
@@ -341,6 +408,8 @@ def build_parser():
                                help="Report every query's K nearest datasets (1..256) instead of those above -j (extension)")
     # (kept out of the usage text, which stays the reference's plus --top: see the module docstring)
     parser_search.add_argument("--hashes_db", type=str, default=None, metavar="FILE", help=argparse.SUPPRESS)
+    parser_search.add_argument("--containment", type=float, default=None, metavar="C", help=argparse.SUPPRESS)
+    parser_search.add_argument("--slack", type=float, default=0.0, metavar="Z", help=argparse.SUPPRESS)
     parser.add_argument("-v", "--version", action="store_true", help="Show version and date")
     return parser
 
@@ -361,8 +430,13 @@ def main(argv=None):
         if args.top is not None and not 1 <= args.top <= 256:
             print("--top takes an integer in the range 1..256")
             return 2
+        if args.containment is not None and not (0.0 < args.containment < 1.0 and np.isfinite(args.slack)):
+            print("--containment takes a number in the open range (0,1), --slack a finite number")
+            return 2
         try:
-            if args.top is not None:
+            if args.containment is not None:
+                search_index_containment(folder, args.query_file, args.containment, args.slack, hashes_db=args.hashes_db)
+            elif args.top is not None:
                 search_index_topk(folder, args.query_file, args.top, hashes_db=args.hashes_db)
             else:
                 search_index(folder, args.query_file, args.j, hashes_db=args.hashes_db)
