@@ -139,6 +139,9 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   contain_dots, contain_block_rows
  *                         mvs_pairwise_contain: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds
  *                         the rows of a block (0: by the device budget)
+ *   levels_dots, levels_block_rows
+ *                         mvs_pairwise_levels: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds
+ *                         the rows of a block (0: by the device budget)
  *   cluster_cells, cluster_block_rows
  *                         mvs_pairwise_cluster: cells the staging buffer of a row block holds (0, default: a quarter of the free
  *                         device memory) and an upper bound on the rows of a block (0: by pairwise_block_cells); a block that
@@ -503,6 +506,41 @@ int mvs_pairwise_contain(mvs_ctx* ctx, const mvs_sketch_set* set, const double* 
                          double slack, int flags, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
                          mvs_cell* cells, int mem_cells, int64_t capacity, int64_t* n_cells);
 int mvs_ctx_contain_stats(const mvs_ctx* ctx, double* dots_ms, double* select_ms, int64_t* row_blocks, int64_t* block_rows);
+
+/* Neighbour counts at many Jaccard levels in one pass: how many samples every sample would be linked to at each of up to 64
+ * levels -- what a level keeps, what it leaves isolated and where the neighbour counts collapse, before mvs_pairwise_cluster,
+ * _linkage, _derep or mvs_search_block is run at one of them.  (The reference asks the same of its output:
+ * src/interpret_pairwise_comp.py ends with a histogram of neighbours per sample.)
+ *
+ * The rule.  Levels t_0 < t_1 < ... < t_{m-1}, 1 <= m <= MVS_MAX_LEVELS, each 0 < t_l < 1; coef_l = t_l / (1.0 + t_l), computed
+ * on the host in fp64.  Row i, column j, i != j by sample index; P the int32 dot as mvs_pairwise_dots returns it (wrapped).
+ * Everything is fp64 and each line is ONE rounding; a NaN compares false:
+ *     inter = (double)P / (double)d
+ *     s     = n2[i] + n2[j]
+ *     pass_l(i,j) = inter > coef_l * s
+ *     deg[i][l]   = #{ j in [col_begin, col_end), j != i : pass_l(i,j) }
+ *     total[l]    = sum over i in [row_begin, row_end) of deg[i][l]            (int64)
+ * -- the link rule of mvs_pairwise_cluster / mvs_search_block, evaluated independently per level: over the full square,
+ * deg[i][l] is the `degree` mvs_cluster_finish reports at min_jaccard = t_l, and total[l] is twice the number of linked pairs.
+ * The contract is per level and holds for any norms (NaN, +-inf, 0, negative).
+ *   levels   : n_levels doubles on the HOST.
+ *   degrees  : (row_end - row_begin) x n_levels int32, row-major (`mem_degrees`); NULL when only the totals are wanted.
+ *   totals   : n_levels int64 on the HOST; may be NULL.
+ *   norms_sq : n doubles (`mem_norms`).
+ *   n_levels outside 1 .. MVS_MAX_LEVELS, a level outside (0, 1) or NaN, levels that are not strictly ascending, computed
+ *   coefficients that are not non-decreasing (two levels an ulp apart can round that way), ranges outside the set, levels or
+ *   norms_sq NULL where needed: MVS_E_INVALID.  An empty row or column range: MVS_OK, nothing written to degrees, totals 0.
+ * Exact and deterministic: equal to a brute-force evaluation of the rule above, whatever the device, the blocking or the
+ * options.  Rows go in blocks sized as mvs_pairwise_contain sizes them (option levels_block_rows bounds them, option
+ * levels_dots = 1 computes the dots on the vector ALUs); one dense-dots launch and one counting launch per block; device
+ * memory besides the set is the dots block plus O(block rows x n_levels), never N x N.  Synchronous.
+ * mvs_ctx_levels_stats: what the last call did -- dots and counting kernel times summed over its row blocks (0 unless
+ * mvs_ctx_set_timing is on), the number of row blocks and the rows per block.  Any pointer may be NULL. */
+#define MVS_MAX_LEVELS 64
+int mvs_pairwise_levels(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, const double* levels,
+                        int n_levels, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int32_t* degrees,
+                        int mem_degrees, int64_t* totals);
+int mvs_ctx_levels_stats(const mvs_ctx* ctx, double* dots_ms, double* count_ms, int64_t* row_blocks, int64_t* block_rows);
 
 /* Single-linkage clustering of the samples at a Jaccard level, on the device: samples i != j are LINKED iff
  *   (double)dot / (double)d > (t / (1.0 + t)) * (n2[i] + n2[j])        (fp64, in that order; t = min_jaccard, 0 < t < 1)

@@ -111,6 +111,10 @@ SYMBOLS = [
                                          _c.c_int64, _c.c_int64, _P, _c.c_int, _c.c_int64, _c.POINTER(_c.c_int64)]),
     ("mvs_ctx_contain_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                           _c.POINTER(_c.c_int64)]),
+    ("mvs_pairwise_levels", _c.c_int, [_P, _P, _P, _c.c_int, _P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P,
+                                        _c.c_int, _P]),
+    ("mvs_ctx_levels_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
+                                         _c.POINTER(_c.c_int64)]),
     ("mvs_cluster_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_cluster_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
     ("mvs_pairwise_cluster", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
@@ -1318,6 +1322,47 @@ class Context:
         n, r = _c.c_int64(), _c.c_int64()
         _check(self.lib.mvs_ctx_contain_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)))
         return {"dots_ms": a.value, "select_ms": b.value, "row_blocks": n.value, "block_rows": r.value}
+
+    def pairwise_levels(self, sset, norms_sq, levels, row_begin=0, row_end=None, col_begin=0, col_end=None, degrees_out=None):
+        """mvs_pairwise_levels: for every row of [row_begin, row_end) the number of columns of [col_begin, col_end), self
+        excluded, it is linked to at each of the strictly ascending Jaccard `levels` (1 .. 64 values in (0, 1);
+        include/mvs_hip.h states the rule: the link rule of the clustering, per level).  Returns (degrees int32 [rows, m],
+        totals int64 [m]), totals[l] = the rows' sum at level l.  `degrees_out`: a torch device tensor (int32 [rows, m]) or a
+        numpy int32 array to fill and return instead of a new array; False: totals only, (None, totals)."""
+        if row_end is None:
+            row_end = sset.n
+        if col_end is None:
+            col_end = sset.n
+        np_, nm, nk = _norms(norms_sq)
+        lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+        m = len(lv)
+        rows = max(0, int(row_end) - int(row_begin))
+        totals = np.zeros(max(m, 1), dtype=np.int64)
+        if degrees_out is False:
+            degrees, dp, dm = None, None, MEM_HOST
+        elif degrees_out is None:
+            degrees = np.zeros((rows, m), dtype=np.int32)
+            dp, dm = degrees.ctypes.data, MEM_HOST
+        else:
+            if tuple(degrees_out.shape) != (rows, m):
+                raise ValueError("degrees_out must have shape (%d, %d)" % (rows, m))
+            if _is_torch(degrees_out):
+                import torch
+                if degrees_out.dtype != torch.int32:
+                    raise ValueError("degrees_out must be an int32 tensor")
+            degrees = degrees_out
+            dp, dm, dk = _buf(degrees_out, np.int32, writable=True)
+        _check(self.lib.mvs_pairwise_levels(self._h, sset._h, np_, nm, lv.ctypes.data, m, int(row_begin), int(row_end), int(col_begin),
+                                            int(col_end), dp, dm, totals.ctypes.data))
+        return degrees, totals[:m]
+
+    def levels_stats(self):
+        """-> dict of the last pairwise_levels: dots_ms / count_ms (kernel times over its row blocks, timing on), row_blocks,
+        block_rows"""
+        a, b = _c.c_double(), _c.c_double()
+        n, r = _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_levels_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)))
+        return {"dots_ms": a.value, "count_ms": b.value, "row_blocks": n.value, "block_rows": r.value}
 
     def _consumer_stats(self, fn, work_key):
         """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time

@@ -200,6 +200,8 @@ const OptionSpec kOptions[] = {
     {"topk_block_rows", &mvs::Options::topk_block_rows, nullptr, 0, 1 << 30},
     {"contain_dots", &mvs::Options::contain_dots, nullptr, 0, 1},
     {"contain_block_rows", &mvs::Options::contain_block_rows, nullptr, 0, 1 << 30},
+    {"levels_dots", &mvs::Options::levels_dots, nullptr, 0, 1},
+    {"levels_block_rows", &mvs::Options::levels_block_rows, nullptr, 0, 1 << 30},
     {"cluster_cells", &mvs::Options::cluster_cells, nullptr, 0, 1 << 30},
     {"cluster_block_rows", &mvs::Options::cluster_block_rows, nullptr, 0, 1 << 30},
     {"intersect_unit", &mvs::Options::intersect_unit, nullptr, 64, 1 << 30},

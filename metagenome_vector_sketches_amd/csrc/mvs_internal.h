@@ -112,6 +112,9 @@ struct Options {
     int contain_dots = 0;           // mvs_pairwise_contain: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU
                                     // kernel (A/B, tests); same selection, same result
     int contain_block_rows = 0;     // mvs_pairwise_contain: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
+    int levels_dots = 0;            // mvs_pairwise_levels: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU
+                                    // kernel (A/B, tests); same counts
+    int levels_block_rows = 0;      // mvs_pairwise_levels: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
     int cluster_cells = 0;          // mvs_pairwise_cluster: cells the staging buffer of a row block holds; 0 = a quarter of the free
                                     // device memory (never more than the block can produce); tests lower it
     int cluster_block_rows = 0;     // mvs_pairwise_cluster: > 0 = upper bound on the rows of a block (tests); 0 = by pairwise_block_cells
@@ -120,6 +123,7 @@ struct Options {
 };
 
 constexpr int kMaxTopk = 256;   // largest k of mvs_pairwise_topk
+constexpr int kMaxLevels = 64;  // most levels of mvs_pairwise_levels (MVS_MAX_LEVELS)
 
 constexpr int kCandRegion = 8;   // candidate entries a filter wave can leave in its own region (one 64-byte line)
 
@@ -294,6 +298,15 @@ int launch_contain_scan(hipStream_t stream, const int* d_counts, int64_t rows, l
 int launch_contain_fill(hipStream_t stream, const int32_t* d_dots, int64_t rows, int64_t ld, int64_t row0, int64_t c0,
                         const double* d_norms_sq, const int* d_thr, const ContainRule& ru, const int* d_counts,
                         const long long* d_offs, mvs_cell* d_cells, int64_t capacity);
+// neighbour counts at m Jaccard levels over a block of dense dots (mvs_levels.hip; the rule is stated there and in
+// include/mvs_hip.h).  prep: d_thr[i] = every sample's part of the integer pre-test at the lowest level's coefficient, *d_flag = 1
+// if a column of the range has a negative norm (the caller zeroes it first).  count: row r of the block -> d_deg[r * m + l]
+// (NULL: not wanted), the rows' values added to d_total[l]; d_coef: m coefficients t / (1 + t)
+int launch_levels_prep(hipStream_t stream, const double* d_norms_sq, int64_t n, int64_t col_begin, int64_t col_end, double coef0, int d,
+                       int* d_thr, int* d_flag);
+int launch_levels_count(hipStream_t stream, const int32_t* d_dots, int64_t rows, int64_t ld, int64_t row0, int64_t c0,
+                        const double* d_norms_sq, const double* d_coef, int m, int d, const int* d_thr, const int* d_neg_flag,
+                        int32_t* d_deg, unsigned long long* d_total);
 // single-linkage clustering over device cell lists (mvs_cluster.hip): union-find rounds over parent[n] -- d_counters: [0] cells
 // with row != col, [1] cells with an index outside [0, n), [2] cells whose endpoints still have different roots -- and the
 // finish passes (cluster ids by ascending root, sizes, representatives)
