@@ -6,11 +6,14 @@
 //
 // MI355X design (see DESIGN.md "K1"):
 //   * the +-1 matrix is implicit (hash generated), so there is nothing to stage from HBM; the kernel
-//     is integer-VALU bound (19 VALU per splitmix64, 6 of them 32-bit multiplies);
+//     is integer-VALU bound (19 VALU per splitmix64 on its own, 6 of them 32-bit multiplies; the last xorshift's
+//     two xors are not among the kernel's: they happen inside the counters' first adder, see absorb);
 //   * each LANE hashes its own stream of hashes (coalesced 8-byte loads, 512 B per wave load) and
 //     counts set bits per position with BIT-SLICED counters: a Harley-Seal carry-save tree built from
 //     v_bitop3_b32 full adders (xor3 / majority), ~4.6 VALU per (hash, 64-dim block) instead of 128
-//     extract+add;
+//     extract+add; the level-1 adder takes the hash as (w, w >> 31) and needs 3 bitop3 per two leaf words where
+//     2 xors + 2 bitop3 were 4.  Hot loop of the default variant (24): 19.38 VALU per (hash, block)
+//     (tools/check_project_isa.py);
 //   * one wave owns BPW 64-dim blocks of one (sample, hash-chunk) unit; at the end the 64 lanes'
 //     bit-sliced counters are summed by a butterfly of bit-sliced ripple adders (ds_bpermute) and
 //     lane k extracts count_k;
@@ -26,18 +29,53 @@ namespace {
 constexpr int kLV = 11;            // bit-sliced counter depth per lane: counts up to 2047
 constexpr uint64_t kGolden = 0x9e3779b97f4a7c15ULL;
 
+// truth table of a three-input boolean function as v_bitop3_b32 wants it: bit (src0 << 2 | src1 << 1 | src2) of the
+// constant is f(src0, src1, src2)
+template <class F>
+constexpr uint32_t bitop3_table(F f) {
+    uint32_t t = 0;
+    for (uint32_t i = 0; i < 8; ++i)
+        if (f((i >> 2) & 1u, (i >> 1) & 1u, i & 1u) & 1u) t |= 1u << i;
+    return t;
+}
+constexpr uint32_t bit_xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
+constexpr uint32_t bit_maj3(uint32_t a, uint32_t b, uint32_t c) { return (a & b) | (a & c) | (b & c); }
+// the carry of s + a + b from s, u = s ^ a and m = s ^ a ^ b (the two running sums a level-1 adder forms anyway):
+// a = s ^ u and b = u ^ m.  Not symmetric in its operands.
+constexpr uint32_t bit_carry_sum(uint32_t s, uint32_t u, uint32_t m) { return bit_maj3(s, s ^ u, u ^ m); }
+constexpr uint32_t kXor3 = bitop3_table(bit_xor3), kMaj3 = bitop3_table(bit_maj3), kCarrySum = bitop3_table(bit_carry_sum);
+static_assert(kXor3 == 0x96 && kMaj3 == 0xE8, "operand order of the bitop3 truth table");
+
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+    return __builtin_amdgcn_bitop3_b32(a, b, c, kXor3);
 }
 __device__ __forceinline__ uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
+    return __builtin_amdgcn_bitop3_b32(a, b, c, kMaj3);
+}
+__device__ __forceinline__ uint32_t carry_sum(uint32_t s, uint32_t u, uint32_t m) {
+    return __builtin_amdgcn_bitop3_b32(s, u, m, kCarrySum);
 }
 
-// src/random_projection.cpp:14-17 applied to z = hash + i + 0x9e37... (the adds of :13-14 are folded
-// into one 64-bit add by the caller)
-__device__ __forceinline__ uint64_t splitmix_tail(uint64_t z) {
+// v >> N as ONE v_lshrrev_b64.  Where only the halves of the result are used, the compiler splits a plain 64-bit shift
+// into v_alignbit_b32 + v_lshrrev_b32, two instructions of the same issue class as the one.  Not volatile: it schedules
+// like any other instruction.
+template <int N>
+__device__ __forceinline__ uint64_t shr64(uint64_t v) {
+    static_assert(N > 0 && N < 64, "shift count");
+    uint64_t r;
+    asm("v_lshrrev_b64 %0, %1, %2" : "=v"(r) : "n"(N), "v"(v));
+    return r;
+}
+
+// src/random_projection.cpp:14-16 applied to z = hash + i + 0x9e37... (the adds of :13-14 are folded
+// into one 64-bit add by the caller): splitmix64 up to its second multiply
+__device__ __forceinline__ uint64_t splitmix_mul2(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+    return (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+}
+// ... and :17, the last xorshift
+__device__ __forceinline__ uint64_t splitmix_tail(uint64_t z) {
+    z = splitmix_mul2(z);
     return z ^ (z >> 31);
 }
 
@@ -49,10 +87,33 @@ struct Acc {
 
 // Harley-Seal: absorb 2^LEVEL inputs into the persistent bit-sliced digits s[0..LEVEL-1]; returns
 // (in clo/chi) the carry word of weight 2^LEVEL.  2^LEVEL - 1 full adders per 2^LEVEL inputs.
+//
+// The level-1 adder takes its two leaves unfinished: a leaf is w ^ t with t = w >> 31 (the last xorshift of splitmix64),
+// and nothing else ever reads it, so the xor happens inside the adder.  With u = s ^ a and m = s ^ a ^ b
+//     u = xor3(s, wa, ta),   m = xor3(u, wb, tb) (the new digit),   carry = maj(s, a, b) = carry_sum(s, u, m)
+// are three bitop3 per word where xor, xor, xor3, maj3 were four.  Leaf A is produced and folded into u for every block
+// before leaf B is produced: with both leaves' (w, t) alive at once the BPW = 4 kernels do not fit two waves per SIMD.
 template <int LEVEL, int BPW, class Gen>
 __device__ __forceinline__ void absorb(Acc<BPW>& s, Gen& g, uint32_t (&clo)[BPW], uint32_t (&chi)[BPW]) {
     if constexpr (LEVEL == 0) {
         g.next(clo, chi);
+    } else if constexpr (LEVEL == 1) {
+        uint32_t wl[BPW], wh[BPW], tl[BPW], th[BPW], ul[BPW], uh[BPW];
+        g.next_unmixed(wl, wh, tl, th);
+#pragma unroll
+        for (int b = 0; b < BPW; ++b) {
+            ul[b] = xor3(s.lo[b][0], wl[b], tl[b]);
+            uh[b] = xor3(s.hi[b][0], wh[b], th[b]);
+        }
+        g.next_unmixed(wl, wh, tl, th);
+#pragma unroll
+        for (int b = 0; b < BPW; ++b) {
+            const uint32_t ml = xor3(ul[b], wl[b], tl[b]), mh = xor3(uh[b], wh[b], th[b]);
+            clo[b] = carry_sum(s.lo[b][0], ul[b], ml);
+            chi[b] = carry_sum(s.hi[b][0], uh[b], mh);
+            s.lo[b][0] = ml;
+            s.hi[b][0] = mh;
+        }
     } else {
         uint32_t alo[BPW], ahi[BPW], blo[BPW], bhi[BPW];
         absorb<LEVEL - 1, BPW>(s, g, alo, ahi);
@@ -107,6 +168,25 @@ struct BatchGen {
             hi[b] = (uint32_t)(x >> 32);
         }
     }
+    // the same hash without its last xorshift, for the level-1 adder: w after the second multiply and t = w >> 31
+    // (leaf = w ^ t); an invalid slot yields four zero words
+    __device__ __forceinline__ void next_unmixed(uint32_t (&wl)[BPW], uint32_t (&wh)[BPW], uint32_t (&tl)[BPW],
+                                                 uint32_t (&th)[BPW]) {
+        const uint64_t hv = h[j];
+        bool valid = true;
+        if constexpr (MASKED) valid = (int64_t)j * 64 < remaining;
+        ++j;
+#pragma unroll
+        for (int b = 0; b < BPW; ++b) {
+            uint64_t w = splitmix_mul2(hv + cb[b]);
+            if constexpr (MASKED) w = valid ? w : 0ULL;
+            const uint64_t t = shr64<31>(w);
+            wl[b] = (uint32_t)w;
+            wh[b] = (uint32_t)(w >> 32);
+            tl[b] = (uint32_t)t;
+            th[b] = (uint32_t)(t >> 32);
+        }
+    }
 };
 
 // The same values for a wave that owns BPW CONSECUTIVE blocks, with the part of the first splitmix64 round that the
@@ -125,22 +205,27 @@ struct BatchGenShared {
     const uint64_t (&x)[8];      // hash + 64 * first block + golden (the sums hazard() has looked at)
     int j = 0;
     __device__ __forceinline__ explicit BatchGenShared(const uint64_t (&x_)[8]) : x(x_) {}
-    __device__ __forceinline__ void next(uint32_t (&lo)[BPW], uint32_t (&hi)[BPW]) {
+    // without the last xorshift, for the level-1 adder: (w, t = w >> 31) with w the value after the second multiply,
+    // leaf = w ^ t.  The only producer: this generator feeds whole batches (absorb<3>), never a lone leaf.
+    __device__ __forceinline__ void next_unmixed(uint32_t (&wl)[BPW], uint32_t (&wh)[BPW], uint32_t (&tl)[BPW],
+                                                 uint32_t (&th)[BPW]) {
         const uint64_t x0 = x[j++];
-        const uint64_t t = x0 >> 30;
-        const uint32_t x0l = (uint32_t)x0, tl = (uint32_t)t;
-        const uint32_t zh = (uint32_t)(x0 >> 32) ^ (uint32_t)(t >> 32);
+        const uint64_t t0 = shr64<30>(x0);
+        const uint32_t x0l = (uint32_t)x0, t0l = (uint32_t)t0;
+        const uint32_t zh = (uint32_t)(x0 >> 32) ^ (uint32_t)(t0 >> 32);
         const uint32_t p = zh * kC1Lo;
 #pragma unroll
         for (int b = 0; b < BPW; ++b) {
-            const uint32_t zl = (x0l + 64u * (uint32_t)b) ^ tl;
+            const uint32_t zl = (x0l + 64u * (uint32_t)b) ^ t0l;
             const uint64_t m = (uint64_t)zl * (uint64_t)kC1Lo;
             const uint32_t whi = (uint32_t)(m >> 32) + zl * kC1Hi + p;
-            uint64_t w = ((uint64_t)whi << 32) | (uint64_t)(uint32_t)m;
-            w = (w ^ (w >> 27)) * 0x94d049bb133111ebULL;
-            w ^= w >> 31;
-            lo[b] = (uint32_t)w;
-            hi[b] = (uint32_t)(w >> 32);
+            const uint64_t v = ((uint64_t)whi << 32) | (uint64_t)(uint32_t)m;
+            const uint64_t w = (v ^ (v >> 27)) * 0x94d049bb133111ebULL;
+            const uint64_t t = shr64<31>(w);
+            wl[b] = (uint32_t)w;
+            wh[b] = (uint32_t)(w >> 32);
+            tl[b] = (uint32_t)t;
+            th[b] = (uint32_t)(t >> 32);
         }
     }
 };
@@ -318,8 +403,14 @@ __device__ __forceinline__ void wave_sum_max_valu(unsigned long long& ss, uint32
 // batches per iteration and gets one weight-32 carry out of them; carries of weight 32 and 64 wait in p32 / p64 until a
 // second one of the same weight exists, and the two are full-added into digit 5 / 6 at once.  A ripple (half adders through
 // digits 7..10) follows once per 128 hashes instead of through 5..10 once per 32, so counting costs ~2.05 bitop3 per
-// input word instead of ~2.45.  The branches on the iteration number are wave-uniform.  The epilogue is
-// reduce_counts_valu.
+// input word instead of ~2.45; the level-1 adder that also does the hash's last xor (absorb) adds 0.5 to either figure and
+// takes the v_xor_b32 per input word of that xorshift away.  The branches on the iteration number are wave-uniform.  The
+// epilogue is reduce_counts_valu.
+//
+// Main loop, VALU instructions per (hash, 64-dim block) as compiled (tools/check_project_isa.py): variant 24 19.38,
+// 14 20.04, 12 21.27, 2 21.94, 1 22.12 (20.63 / 21.29 / 22.77 / 22.94 / 23.12 with the xorshift outside the adder and the
+// shared round's 64-bit shift split in two).  252 / 254 VGPRs for BPW 4 (two waves per SIMD), 138 for BPW 2 (three),
+// 124 for BPW 1 (four); no AGPRs, no scratch.
 template <int BPW, bool STATS, bool SHARED = false, bool DEEP = false>
 __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ hashes,
                                                  const ProjUnit* __restrict__ units, long long n_units, int ny,
