@@ -8,6 +8,10 @@
 //   * the +-1 matrix is implicit (hash generated), so there is nothing to stage from HBM; the kernel
 //     is integer-VALU bound (19 VALU per splitmix64 on its own, 6 of them 32-bit multiplies; the last xorshift's
 //     two xors are not among the kernel's: they happen inside the counters' first adder, see absorb);
+//   * the instructions are not equally expensive: xor, two-operand add and bitop3 issue in 2.7-2.8 cycles, every multiply,
+//     shift and three-operand add in 4.2-4.65.  Each 64-bit multiply of the hash is v_mad_u64_u32(lo, C.lo, {0, cross
+//     terms}) (mad64): the addend of the mad, which is free, carries what a v_add3_u32 added behind it, and a v_add_u32
+//     is what is left.  Same count, cheaper mix (tools/check_project_isa.py prices it);
 //   * each LANE hashes its own stream of hashes (coalesced 8-byte loads, 512 B per wave load) and
 //     counts set bits per position with BIT-SLICED counters: a Harley-Seal carry-save tree built from
 //     v_bitop3_b32 full adders (xor3 / majority), ~4.6 VALU per (hash, 64-dim block) instead of 128
@@ -67,15 +71,51 @@ __device__ __forceinline__ uint64_t shr64(uint64_t v) {
     return r;
 }
 
+constexpr uint32_t kC1Lo = 0x1ce4e5b9u, kC1Hi = 0xbf58476du;
+constexpr uint32_t kC2Lo = 0x133111ebu, kC2Hi = 0x94d049bbu;
+
+// a * b + c as ONE v_mad_u64_u32 whose 64-bit addend does work: a 64-bit multiply by a constant C is
+//     lo * C.lo + ((lo * C.hi + hi * C.lo) << 32)   (mod 2^64),
+// and with the cross terms in the addend's high half the sum behind the multiply is a two-operand v_add_u32 (or nothing)
+// where a zero addend leaves a v_add3_u32, an instruction of the multiplies' issue class.  Inline asm because the compiler
+// will not form it: it splits c off again (v_mul_lo_u32 + adds) or wraps the mad in moves to align its register pairs.
+// b is a constant in an SGPR; the carry out goes to an SGPR pair nobody reads.
+__device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) {
+    uint64_t r, carry;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry) : "v"(a), "s"(b), "v"(c));
+    return r;
+}
+// a * b with the multiply hidden from the compiler, which would fold it and the add behind it into a v_mad_u64_u32 of its
+// own, with a 32-bit addend widened by two moves
+__device__ __forceinline__ uint32_t mul_lo(uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_mul_lo_u32 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
+    return r;
+}
+
+// z * C for a constant C = {clo, chi}, cross terms in the mad's addend; zero is a register that holds 0 (see k_project)
+__device__ __forceinline__ uint64_t mul64_mad(uint64_t z, uint32_t clo, uint32_t chi, uint32_t zero) {
+    const uint32_t zl = (uint32_t)z, zh = (uint32_t)(z >> 32);
+    const uint32_t cross = mul_lo(zl, chi) + mul_lo(zh, clo);
+    return mad64(zl, clo, ((uint64_t)cross << 32) | (uint64_t)zero);
+}
+
 // src/random_projection.cpp:14-16 applied to z = hash + i + 0x9e37... (the adds of :13-14 are folded
-// into one 64-bit add by the caller): splitmix64 up to its second multiply
-__device__ __forceinline__ uint64_t splitmix_mul2(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    return (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+// into one 64-bit add by the caller): splitmix64 up to its second multiply.  MAD: both multiplies as mul64_mad.
+template <bool MAD>
+__device__ __forceinline__ uint64_t splitmix_mul2(uint64_t z, uint32_t zero) {
+    if constexpr (MAD) {
+        z = mul64_mad(z ^ (z >> 30), kC1Lo, kC1Hi, zero);
+        return mul64_mad(z ^ (z >> 27), kC2Lo, kC2Hi, zero);
+    } else {
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+        return (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+    }
 }
 // ... and :17, the last xorshift
-__device__ __forceinline__ uint64_t splitmix_tail(uint64_t z) {
-    z = splitmix_mul2(z);
+template <bool MAD>
+__device__ __forceinline__ uint64_t splitmix_tail(uint64_t z, uint32_t zero) {
+    z = splitmix_mul2<MAD>(z, zero);
     return z ^ (z >> 31);
 }
 
@@ -147,14 +187,15 @@ __device__ __forceinline__ void ripple(Acc<BPW>& s, uint32_t (&clo)[BPW], uint32
 
 // yields SM(h + 64*block) for the next hash of a register-resident batch, for each of the wave's BPW
 // blocks.  The batch (8 hashes per lane = 512 per wave) was loaded one batch ahead of its use.
-template <int BPW, bool MASKED>
+template <int BPW, bool MASKED, bool MAD>
 struct BatchGen {
     const uint64_t (&h)[8];
     const uint64_t (&cb)[BPW];   // 64*block + golden
+    const uint32_t (&zero)[BPW]; // MAD: registers that hold 0
     int64_t remaining;           // MASKED: hashes left from this lane's first hash of the batch
     int j = 0;
-    __device__ __forceinline__ BatchGen(const uint64_t (&h_)[8], const uint64_t (&cb_)[BPW], int64_t rem)
-        : h(h_), cb(cb_), remaining(rem) {}
+    __device__ __forceinline__ BatchGen(const uint64_t (&h_)[8], const uint64_t (&cb_)[BPW], const uint32_t (&zero_)[BPW], int64_t rem)
+        : h(h_), cb(cb_), zero(zero_), remaining(rem) {}
     __device__ __forceinline__ void next(uint32_t (&lo)[BPW], uint32_t (&hi)[BPW]) {
         const uint64_t hv = h[j];
         bool valid = true;
@@ -162,7 +203,7 @@ struct BatchGen {
         ++j;
 #pragma unroll
         for (int b = 0; b < BPW; ++b) {
-            uint64_t x = splitmix_tail(hv + cb[b]);
+            uint64_t x = splitmix_tail<MAD>(hv + cb[b], zero[b]);
             if constexpr (MASKED) x = valid ? x : 0ULL;
             lo[b] = (uint32_t)x;
             hi[b] = (uint32_t)(x >> 32);
@@ -178,7 +219,7 @@ struct BatchGen {
         ++j;
 #pragma unroll
         for (int b = 0; b < BPW; ++b) {
-            uint64_t w = splitmix_mul2(hv + cb[b]);
+            uint64_t w = splitmix_mul2<MAD>(hv + cb[b], zero[b]);
             if constexpr (MASKED) w = valid ? w : 0ULL;
             const uint64_t t = shr64<31>(w);
             wl[b] = (uint32_t)w;
@@ -198,13 +239,15 @@ struct BatchGen {
 // (9 quarter-rate instructions per hash at BPW = 4).  The carry case -- bits 8..29 of x_0 all ones, one hash in 4 million
 // -- is detected per batch by hazard() and such a batch goes through BatchGen (the wave-uniform branch costs nothing
 // when it is not taken), so every value is exact.
-constexpr uint32_t kC1Lo = 0x1ce4e5b9u, kC1Hi = 0xbf58476du;
-
-template <int BPW>
+// ROUND2: the second multiply the same way.  Its addend is {0, cross}, and the zero low half has to cost nothing: zero[b] is a
+// register the kernel writes once (opaque to the compiler, which would otherwise write a fresh zero per multiply), one per
+// block so that consecutive blocks' addends can be alive together.
+template <int BPW, bool ROUND2>
 struct BatchGenShared {
     const uint64_t (&x)[8];      // hash + 64 * first block + golden (the sums hazard() has looked at)
+    const uint32_t (&zero)[BPW];
     int j = 0;
-    __device__ __forceinline__ explicit BatchGenShared(const uint64_t (&x_)[8]) : x(x_) {}
+    __device__ __forceinline__ BatchGenShared(const uint64_t (&x_)[8], const uint32_t (&zero_)[BPW]) : x(x_), zero(zero_) {}
     // without the last xorshift, for the level-1 adder: (w, t = w >> 31) with w the value after the second multiply,
     // leaf = w ^ t.  The only producer: this generator feeds whole batches (absorb<3>), never a lone leaf.
     __device__ __forceinline__ void next_unmixed(uint32_t (&wl)[BPW], uint32_t (&wh)[BPW], uint32_t (&tl)[BPW],
@@ -213,14 +256,22 @@ struct BatchGenShared {
         const uint64_t t0 = shr64<30>(x0);
         const uint32_t x0l = (uint32_t)x0, t0l = (uint32_t)t0;
         const uint32_t zh = (uint32_t)(x0 >> 32) ^ (uint32_t)(t0 >> 32);
-        const uint32_t p = zh * kC1Lo;
+        const uint64_t p64 = (uint64_t)(zh * kC1Lo) << 32;       // the shared cross term, where the mad adds it
 #pragma unroll
         for (int b = 0; b < BPW; ++b) {
             const uint32_t zl = (x0l + 64u * (uint32_t)b) ^ t0l;
-            const uint64_t m = (uint64_t)zl * (uint64_t)kC1Lo;
-            const uint32_t whi = (uint32_t)(m >> 32) + zl * kC1Hi + p;
+            const uint64_t m = mad64(zl, kC1Lo, p64);
+            const uint32_t whi = (uint32_t)(m >> 32) + mul_lo(zl, kC1Hi);
             const uint64_t v = ((uint64_t)whi << 32) | (uint64_t)(uint32_t)m;
-            const uint64_t w = (v ^ (v >> 27)) * 0x94d049bb133111ebULL;
+            const uint64_t u = v ^ (v >> 27);
+            uint64_t w;
+            if constexpr (ROUND2) {
+                const uint32_t ul = (uint32_t)u, uh = (uint32_t)(u >> 32);
+                const uint32_t cross = mul_lo(ul, kC2Hi) + mul_lo(uh, kC2Lo);
+                w = mad64(ul, kC2Lo, ((uint64_t)cross << 32) | (uint64_t)zero[b]);
+            } else {
+                w = u * 0x94d049bb133111ebULL;
+            }
             const uint64_t t = shr64<31>(w);
             wl[b] = (uint32_t)w;
             wh[b] = (uint32_t)(w >> 32);
@@ -409,8 +460,10 @@ __device__ __forceinline__ void wave_sum_max_valu(unsigned long long& ss, uint32
 //
 // Main loop, VALU instructions per (hash, 64-dim block) as compiled (tools/check_project_isa.py): variant 24 19.38,
 // 14 20.04, 12 21.27, 2 21.94, 1 22.12 (20.63 / 21.29 / 22.77 / 22.94 / 23.12 with the xorshift outside the adder and the
-// shared round's 64-bit shift split in two).  252 / 254 VGPRs for BPW 4 (two waves per SIMD), 138 for BPW 2 (three),
-// 124 for BPW 1 (four); no AGPRs, no scratch.
+// shared round's 64-bit shift split in two).  The multiplies through mad64 leave these counts as they are and turn two
+// v_add3_u32 per pair into v_add_u32 in variants 24, 2 and 1 (both rounds) and one in 14 and 12 (first round).  246 / 256
+// VGPRs for BPW 4 (variant 24 / 14: two waves per SIMD), 138 / 137 for BPW 2 (three), 103 for BPW 1 (four); no AGPRs, no
+// scratch.
 template <int BPW, bool STATS, bool SHARED = false, bool DEEP = false>
 __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ hashes,
                                                  const ProjUnit* __restrict__ units, long long n_units, int ny,
@@ -440,6 +493,24 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
 #pragma unroll
     for (int b = 0; b < BPW; ++b) cb[b] = (uint64_t)(b0 + b) * 64ULL + kGolden;
 
+    // Which instantiations take which multiply through mad64 (decided by an A/B on the flagship, LABNOTES round 10).  The second
+    // multiply of the shared generator needs a register per block that holds zero: the DEEP kernel has room for them, the
+    // other BPW-4 kernels (variant 14) would drop to one wave per SIMD and keep the first round alone.  The general generator
+    // uses the same registers, so it follows wherever they exist or cost no wave (variants 24, 2 and 1).
+    constexpr bool kRound2 = SHARED && DEEP;
+    constexpr bool kMadGeneral = !SHARED || kRound2;
+    // The zero low halves of the addends {0, cross} (mul64_mad, BatchGenShared): opaque to the compiler, which would write a
+    // fresh zero in front of every multiply if it knew the value.  The statements are identical and have no inputs, so the
+    // compiler is free to merge or rematerialise them; that it keeps one register per block, written once, and pays no move
+    // for them is a property of the machine code, held by tests/test_project_mad_isa_cpu.py (v_mov_b32 per pair), not of
+    // this source.  Any outcome computes the same values.  Where no multiply uses them they are plain zeros, never read.
+    uint32_t zero[BPW];
+#pragma unroll
+    for (int b = 0; b < BPW; ++b) {
+        if constexpr (kRound2 || kMadGeneral) asm("v_mov_b32 %0, 0" : "=v"(zero[b]));
+        else zero[b] = 0u;
+    }
+
     // Batches of 8 hashes per lane (512 per wave); batch i+1 is loaded while batch i is hashed.
     if (count > 0) {
         const int64_t last = count - 1;
@@ -461,10 +532,10 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
                 load_batch<false>(hn, base, (b + sb + 1) << 9, lane, last);
                 uint64_t xv[8];
                 if (SHARED && !hazard(hv, cb[0], xv)) {
-                    BatchGenShared<BPW> g(xv);
+                    BatchGenShared<BPW, kRound2> g(xv, zero);
                     absorb<3, BPW>(s, g, c8lo[sb], c8hi[sb]);
                 } else {
-                    BatchGen<BPW, false> g(hv, cb, 0);
+                    BatchGen<BPW, false, kMadGeneral> g(hv, cb, zero, 0);
                     absorb<3, BPW>(s, g, c8lo[sb], c8hi[sb]);
                 }
 #pragma unroll
@@ -531,7 +602,7 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
         // leftover full batches
         for (; b < nfull; ++b) {
             load_batch<true>(hn, base, (b + 1) << 9, lane, last);
-            BatchGen<BPW, false> g(hv, cb, 0);
+            BatchGen<BPW, false, kMadGeneral> g(hv, cb, zero, 0);
             uint32_t clo[BPW], chi[BPW];
             absorb<3, BPW>(s, g, clo, chi);
             ripple<3, BPW>(s, clo, chi);
@@ -542,7 +613,7 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
         // 100 hashes needs 2 of them, not 8)
         if ((count & 511) != 0) {
             const int rem = (int)(count & 511);
-            BatchGen<BPW, true> g(hv, cb, count - (nfull << 9) - lane);
+            BatchGen<BPW, true, kMadGeneral> g(hv, cb, zero, count - (nfull << 9) - lane);
             uint32_t clo[BPW], chi[BPW];
             if (rem <= 64) {
                 absorb<0, BPW>(s, g, clo, chi);

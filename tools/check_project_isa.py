@@ -11,10 +11,17 @@ about:
     is exactly the binary counter of the pending weight-32 / weight-64 carries.  The expected instruction count of one
     iteration over the pairs it covers (its global_load_dwordx2 count, i.e. hashes per lane, times the blocks per wave)
     gives instructions and VALU instructions per (hash, block);
+  * the same paths by mnemonic: VALU instructions per pair of each kind, their sum priced with the measured issue costs
+    (SIMD cycles per wave instruction, profiles/r01_valu_rates_microbench.txt) and the s_nop per pair.  The instructions
+    are not equally expensive -- an xor, a two-operand add or a bitop3 issues in 2.7-2.8 cycles, every multiply, shift and
+    three-operand add in 4.2-4.65 -- so the count alone does not say how fast the loop is; the price does.  A mnemonic
+    the table does not hold is listed as unpriced and counted at 4.4.  A second sum uses the prices the same bodies have at
+    two waves per SIMD, k_project's occupancy (profiles/r10_valu_rates_microbench.txt: v_bitop3_b32 is 3.07 there, not
+    2.71), and adds the s_nop at their measured 0.76 cycles;
   * LDS instructions anywhere in the kernel (the VALU epilogue has none);
   * VGPRs and scratch, from the code object's metadata.
 
-Usage: check_project_isa.py [--lib libmvs_hip.so] [--variant 24|14|...] [--max-valu-per-pair X] [--json]
+Usage: check_project_isa.py [--lib libmvs_hip.so] [--variant 24|14|...] [--max-valu-per-pair X] [--json] [--mix]
 Exit code 1 if a budget given on the command line is exceeded.
 """
 import argparse
@@ -31,6 +38,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "metagenome_vector_sketches_amd", "libmvs_hip.so")
 # project_variant -> (blocks per wave, SHARED, DEEP) of k_project<BPW, STATS, SHARED, DEEP>
 VARIANTS = {1: (1, False, False), 2: (2, False, False), 12: (2, True, False), 14: (4, True, False), 24: (4, True, True)}
+# issue cost in SIMD cycles per wave64 instruction: profiles/r01_valu_rates_microbench.txt (256 CUs, eight waves per SIMD), and
+# the same bodies at two waves per SIMD, k_project's occupancy (profiles/r10_valu_rates_microbench.txt, second half).  Only what
+# those files hold: anything else is unpriced.
+ISSUE_CYCLES = {
+    "v_xor_b32": 2.80, "v_add_u32": 2.82, "v_lshlrev_b32": 4.41, "v_bitop3_b32": 2.71, "v_add3_u32": 4.65,
+    "v_lshl_add_u32": 4.46, "v_alignbit_b32": 4.42, "v_mul_lo_u32": 4.53, "v_mul_hi_u32": 4.25, "v_mul_u32_u24": 4.27,
+    "v_mul_hi_u32_u24": 4.14, "v_mad_u32_u24": 4.40, "v_mad_u32_u16": 4.45, "v_lshrrev_b64": 4.19, "v_lshl_add_u64": 4.40,
+    "v_mad_u64_u32": 4.34,
+}
+ISSUE_CYCLES_2_WAVES = {
+    "v_xor_b32": 2.81, "v_add_u32": 2.80, "v_lshlrev_b32": 4.39, "v_bitop3_b32": 3.07, "v_add3_u32": 4.62,
+    "v_lshl_add_u32": 4.52, "v_alignbit_b32": 4.41, "v_mul_lo_u32": 4.50, "v_mul_hi_u32": 4.25, "v_mul_u32_u24": 4.30,
+    "v_mul_hi_u32_u24": 4.17, "v_mad_u32_u24": 4.38, "v_mad_u32_u16": 4.36, "v_lshrrev_b64": 4.22, "v_lshl_add_u64": 4.37,
+    "v_mad_u64_u32": 4.42,
+}
+S_NOP_CYCLES_2_WAVES = 0.76   # same file: (3.00 - 2.81) x 4, v_xor_b32 with an s_nop 0 behind every fourth against v_xor_b32 alone
+UNPRICED_CYCLES = 4.4
+
+
+def base_mnemonic(mnem):
+    """the disassembler's name without its encoding suffix: v_xor_b32_e32 -> v_xor_b32"""
+    return re.sub(r"_(e32|e64|dpp|sdwa)$", "", mnem)
 
 
 def kernel_symbol(variant, stats):
@@ -171,17 +200,29 @@ def analyse(lib, variant, stats=True, text=None):
     head, tail = main_loop(insns)
     paths = loop_paths(insns, head, tail)
     bpw = VARIANTS[variant][0]
-    total = valu = 0.0
+    total = valu = nops = 0.0
+    mix = {}
     hashes = set()
     for w, p in paths:
         total += w * len(p)
         valu += w * sum(1 for i in p if insns[i].mnem.startswith("v_"))
+        nops += w * sum(1 for i in p if insns[i].mnem == "s_nop")
+        for i in p:
+            if insns[i].mnem.startswith("v_"):
+                m = base_mnemonic(insns[i].mnem)
+                mix[m] = mix.get(m, 0.0) + w
         hashes.add(sum(1 for i in p if insns[i].mnem == "global_load_dwordx2"))
     if len(hashes) != 1:
         raise SystemExit("check_project_isa: paths load different numbers of hashes: %s" % sorted(hashes))
     pairs = hashes.pop() * bpw
     vgpr, agpr, scratch = kernel_resources(lib, tag)
+    mix = {m: round(c / pairs, 4) for m, c in sorted(mix.items(), key=lambda kv: (-kv[1], kv[0]))}
     return {
+        "valu_mix_per_pair": mix, "unpriced": sorted(m for m in mix if m not in ISSUE_CYCLES),
+        "valu_cycles_per_pair": round(sum(c * ISSUE_CYCLES.get(m, UNPRICED_CYCLES) for m, c in mix.items()), 3),
+        "valu_cycles_per_pair_2_waves": round(sum(c * ISSUE_CYCLES_2_WAVES.get(m, UNPRICED_CYCLES) for m, c in mix.items())
+                                              + nops / pairs * S_NOP_CYCLES_2_WAVES, 3),
+        "s_nop_per_pair": round(nops / pairs, 4),
         "kernel": tag, "variant": variant, "loop_instructions": len(insns[head:tail + 1]), "loop_paths": len(paths),
         "pairs_per_iteration": pairs, "insts_per_pair": round(total / pairs, 3), "valu_per_pair": round(valu / pairs, 3),
         "lds_insts": sum(1 for ins in insns if ins.mnem.startswith("ds_")),
@@ -197,6 +238,7 @@ def main():
     ap.add_argument("--variant", type=int, action="append", help="project_variant(s) to report (default 24 and 14)")
     ap.add_argument("--max-valu-per-pair", type=float, help="budget for the main loop's VALU instructions per (hash, block)")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--mix", action="store_true", help="also print the VALU instructions per pair by mnemonic, with their prices")
     a = ap.parse_args()
     text = disassembly(a.lib)
     ok = True
@@ -210,6 +252,12 @@ def main():
                       "VGPRs %d, scratch %d B" % (r["kernel"], r["loop_instructions"], r["loop_paths"], r["pairs_per_iteration"],
                                                   r["insts_per_pair"], r["valu_per_pair"], r["lds_insts"], r["vgprs"],
                                                   r["scratch_bytes"]))
+                print("%-32s priced %.2f SIMD cycles (%.2f with the prices at two waves per SIMD and the s_nop), %.3f s_nop per (hash, block)%s"
+                      % ("", r["valu_cycles_per_pair"], r["valu_cycles_per_pair_2_waves"], r["s_nop_per_pair"],
+                         "; unpriced (at %.1f): %s" % (UNPRICED_CYCLES, " ".join(r["unpriced"])) if r["unpriced"] else ""))
+                if a.mix:
+                    for m, c in r["valu_mix_per_pair"].items():
+                        print("%-32s   %-18s %7.3f x %s" % ("", m, c, "%.2f" % ISSUE_CYCLES[m] if m in ISSUE_CYCLES else "unpriced"))
             if a.max_valu_per_pair is not None and r["valu_per_pair"] > a.max_valu_per_pair:
                 ok = False
     return 0 if ok else 1
