@@ -142,6 +142,10 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   levels_dots, levels_block_rows
  *                         mvs_pairwise_levels: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds
  *                         the rows of a block (0: by the device budget)
+ *   gram_slab_rows        mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536 (default
+ *                         65536; rounded down to a multiple of 64)
+ *   gram_variant          tile kernel of the moments: 0 (default) by shape -- 128 x 128 tiles for one or two limbs and d >= 128, else
+ *                         64 x 64 --, 1 always 64 x 64 (A/B, tests)
  *   cluster_cells, cluster_block_rows
  *                         mvs_pairwise_cluster: cells the staging buffer of a row block holds (0, default: a quarter of the free
  *                         device memory) and an upper bound on the rows of a block (0: by pairwise_block_cells); a block that
@@ -916,6 +920,59 @@ int mvs_cells_sort(mvs_ctx* ctx, const mvs_cell* cells_in, int64_t n, mvs_cell* 
  * and small problems.  `algo` 0 = matrix-core path, 1 = plain vector-ALU path (independent check). */
 int mvs_pairwise_dots(mvs_ctx* ctx, const mvs_sketch_set* set, int64_t r0, int64_t r1, int64_t c0,
                       int64_t c1, int32_t* out, int mem_out, int algo);
+
+/* ---- ordination: exact moments over the sample axis, PCA -------------------------------------------------------
+ * What the reference's src/clusters.py does with scikit-learn on a dense float copy of vectors.bin: a PCA of the samples whose
+ * norm is at least 10, and the projection of a second, larger set (big_vectors.bin) onto its axes.  Here the part of a PCA that
+ * matters is exact: the Gram matrix over the SAMPLE axis, bit for bit, from the resident limb planes.
+ *
+ * x[i][a] is the integer a set's limbs encode: sum_l limb_l * 256^l (MVS_LIMBS_K3: l0 + 128 * l1); 0 <= a < d.
+ *
+ * mvs_sketch_moments  n = row_end - row_begin >= 1:
+ *                         col_sums[a]     = sum_i x[i][a]                 int64 [d]
+ *                         gram[a * d + b] = sum_i x[i][a] * x[i][b]       int64 [d * d], the full symmetric matrix, row-major
+ *                     over the rows of [row_begin, row_end) only; exact for every limb code, any d and any range: padding rows,
+ *                     padding columns and rows outside the range contribute nothing.  Both outputs live where mem_out says.
+ *                     With B the largest magnitude the limb code holds (127, 32 639, 2^23, 2^31; MVS_LIMBS_K3: 8 127), a call
+ *                     with n * B^2 > 2^62 returns MVS_E_RANGE before any launch.  n < 1, a range outside the set, a NULL
+ *                     output: MVS_E_INVALID.  Option gram_slab_rows bounds the scratch copy (slab rows x limbs x d bytes).
+ * mvs_pca_fit         n >= 2, 1 <= components <= min(64, d), 0 <= tol < 1, max_iters >= 1 (else MVS_E_INVALID; the range rule
+ *                     of the moments applies).  From the moments, on the host, each numerator formed exactly in 128-bit
+ *                     integers, converted with one rounding and divided once:
+ *                         mean[a] = (double)col_sums[a] / (double)n
+ *                         C[a][b] = (double)(n * gram[a][b] - col_sums[a] * col_sums[b]) / ((double)n * (double)(n - 1))
+ *                         total_variance = sum_a C[a][a]
+ *                     The leading eigenpairs of C by block subspace iteration with a Rayleigh-Ritz step (block of
+ *                     min(d, components + 8) columns; the d x d x block products and the residuals on the device, in fp64; the
+ *                     block's orthonormalisation and the small symmetric eigenproblem, by cyclic Jacobi, on the host; no
+ *                     library beyond what libmvs_hip.so links anyway).  It stops when max_i ||C v_i - lambda_i v_i||_2 <=
+ *                     tol * lambda_1 over the components, or after max_iters iterations.  Not converging is not an error: the
+ *                     call returns MVS_OK with converged = 0, the iterations used and every component's residual.  lambda comes
+ *                     back descending; every axis has unit length and is signed so that its entry of largest magnitude (the
+ *                     smaller index on ties) is positive.  Deterministic bit for bit from run to run: the start block is a
+ *                     fixed function of (row, column) through splitmix64, nothing uses floating-point atomics, every reduction
+ *                     order is fixed.  1e-10 and 300 are the defaults of the Python binding and of pca_sketches.
+ * mvs_pca_info        any pointer may be NULL.
+ * mvs_pca_get         HOST arrays, any may be NULL: mean[d], axes[components * d] (axis j at j * d), variances[components]
+ *                     (lambda), residuals[components] (||C v - lambda v||_2 of the returned pair).
+ * mvs_pca_transform   scores[(i - row_begin) * components + j] = sum_a (x[i][a] - mean[a]) * axes[j][a] in fp64, for the rows
+ *                     of ANY set of the same d on the same context (the fitted one, or another DB); evaluated as
+ *                     sum_a x V - sum_a mean V.  scores lives where mem_out says.  Another d: MVS_E_INVALID.
+ * mvs_ctx_pca_stats   of the context's last mvs_sketch_moments / mvs_pca_fit (gram_ms, slabs), mvs_pca_fit (eigen_ms: the
+ *                     solver from its first product to its last residual, iterations) and mvs_pca_transform (scores_ms); the
+ *                     times are 0 unless mvs_ctx_set_timing is on.  Any pointer may be NULL.
+ * All synchronous.  The kernels are in csrc/mvs_gram.hip. */
+typedef struct mvs_pca mvs_pca;
+int mvs_sketch_moments(mvs_ctx* ctx, const mvs_sketch_set* set, int64_t row_begin, int64_t row_end, int64_t* gram,
+                       int64_t* col_sums, int mem_out);
+int mvs_pca_fit(mvs_ctx* ctx, const mvs_sketch_set* set, int64_t row_begin, int64_t row_end, int components, double tol,
+                int max_iters, mvs_pca** pca);
+int mvs_pca_info(const mvs_pca* pca, int* d, int* components, int64_t* n, int* iterations, int* converged, double* total_variance);
+int mvs_pca_get(const mvs_pca* pca, double* mean, double* axes, double* variances, double* residuals);
+int mvs_pca_transform(mvs_ctx* ctx, const mvs_pca* pca, const mvs_sketch_set* set, int64_t row_begin, int64_t row_end,
+                      double* scores, int mem_out);
+int mvs_pca_destroy(mvs_pca* pca);
+int mvs_ctx_pca_stats(const mvs_ctx* ctx, double* gram_ms, double* eigen_ms, double* scores_ms, int64_t* slabs, int64_t* iterations);
 
 /* ---- multi-GPU exchange ---------------------------------------------------------------------------
  * One process per GPU; shard k of src/pairwise_comp_optimized.cpp:938-940 is rank k.  Where the reference's shard

@@ -115,6 +115,15 @@ SYMBOLS = [
                                         _c.c_int, _P]),
     ("mvs_ctx_levels_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                          _c.POINTER(_c.c_int64)]),
+    ("mvs_sketch_moments", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int]),
+    ("mvs_pca_fit", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_double, _c.c_int, _c.POINTER(_P)]),
+    ("mvs_pca_info", _c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int),
+                                 _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
+    ("mvs_pca_get", _c.c_int, [_P, _P, _P, _P, _P]),
+    ("mvs_pca_transform", _c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int]),
+    ("mvs_pca_destroy", _c.c_int, [_P]),
+    ("mvs_ctx_pca_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
+                                      _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     ("mvs_cluster_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_cluster_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
     ("mvs_pairwise_cluster", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
@@ -653,6 +662,43 @@ class Linkage(_Handle):
         return out, count.value
 
 
+class Pca(_Handle):
+    """A fitted PCA of the rows of a sketch set (mvs_pca; Context.pca makes one): numpy float64 arrays `mean` [d], `axes` [c, d]
+    (unit length, one axis per row), `explained_variance` [c] (the eigenvalues of the covariance, descending),
+    `explained_variance_ratio` [c] (explained_variance / total_variance), `residuals` [c] (||C v - lambda v||_2 of every
+    returned pair); `iterations`, `converged`, `n` (fitted samples), `total_variance`.  Closes with its context."""
+    _destroy = "mvs_pca_destroy"
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+        ctx._children.add(self)
+        d, c, n, it, cv, tv = _c.c_int(), _c.c_int(), _c.c_int64(), _c.c_int(), _c.c_int(), _c.c_double()
+        _check(ctx.lib.mvs_pca_info(handle, ctypes.byref(d), ctypes.byref(c), ctypes.byref(n), ctypes.byref(it), ctypes.byref(cv),
+                                    ctypes.byref(tv)))
+        self.d, self.components, self.n = d.value, c.value, n.value
+        self.iterations, self.converged, self.total_variance = it.value, bool(cv.value), tv.value
+        self.mean = np.empty(self.d, dtype=np.float64)
+        self.axes = np.empty((self.components, self.d), dtype=np.float64)
+        self.explained_variance = np.empty(self.components, dtype=np.float64)
+        self.residuals = np.empty(self.components, dtype=np.float64)
+        _check(ctx.lib.mvs_pca_get(handle, self.mean.ctypes.data, self.axes.ctypes.data, self.explained_variance.ctypes.data,
+                                   self.residuals.ctypes.data))
+        with np.errstate(all="ignore"):
+            self.explained_variance_ratio = self.explained_variance / self.total_variance
+
+    def transform(self, sset, row_begin=0, row_end=None):
+        """scores of rows [row_begin, row_end) of `sset` -- the fitted set or any other of the same dimension -- on the axes:
+        float64 [rows, c], sum_a (x[i][a] - mean[a]) * axes[j][a]"""
+        if self._h is None:
+            raise ValueError("the pca is closed")
+        if row_end is None:
+            row_end = sset.n
+        rows = max(0, int(row_end) - int(row_begin))
+        out = np.empty((rows, self.components), dtype=np.float64)
+        _check(self.ctx.lib.mvs_pca_transform(self.ctx._h, self._h, sset._h, int(row_begin), int(row_end), out.ctypes.data, MEM_HOST))
+        return out
+
+
 class HashSet(_Handle):
     """Hash lists of n samples resident in HBM, per sample sorted and de-duplicated (mvs_hash_set): what
     Context.intersect_cells intersects.  `n` samples, `total` distinct hashes, `was_sorted`: the input was already strictly
@@ -752,7 +798,7 @@ class Context:
         self.device = device
         self._sets = weakref.WeakSet()   # sketch sets hold a pointer to the context: close them first
         self._comms = weakref.WeakSet()  # communicators likewise
-        self._children = weakref.WeakSet()   # clusters, linkages, dereplications, hash sets: after those two, before the context
+        self._children = weakref.WeakSet()   # clusters, linkages, dereplications, hash sets, PCAs: after those two, before the context
         if stream is not None:
             self.set_stream(stream)
 
@@ -1363,6 +1409,34 @@ class Context:
         n, r = _c.c_int64(), _c.c_int64()
         _check(self.lib.mvs_ctx_levels_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(r)))
         return {"dots_ms": a.value, "count_ms": b.value, "row_blocks": n.value, "block_rows": r.value}
+
+    # ---- ordination (include/mvs_hip.h "ordination") ----
+    def sketch_moments(self, sset, row_begin=0, row_end=None):
+        """mvs_sketch_moments: the exact moments of rows [row_begin, row_end) over the sample axis -> (gram int64 [d, d],
+        col_sums int64 [d]); gram[a, b] = sum_i x[i, a] x[i, b]"""
+        if row_end is None:
+            row_end = sset.n
+        gram = np.empty((sset.d, sset.d), dtype=np.int64)
+        sums = np.empty(sset.d, dtype=np.int64)
+        _check(self.lib.mvs_sketch_moments(self._h, sset._h, int(row_begin), int(row_end), gram.ctypes.data, sums.ctypes.data, MEM_HOST))
+        return gram, sums
+
+    def pca(self, sset, components, row_begin=0, row_end=None, tol=1e-10, max_iters=300):
+        """mvs_pca_fit: the `components` leading principal axes of rows [row_begin, row_end) of `sset` -> Pca.  A fit that did
+        not reach `tol` within `max_iters` iterations still returns (Pca.converged is False)."""
+        if row_end is None:
+            row_end = sset.n
+        h = _P()
+        _check(self.lib.mvs_pca_fit(self._h, sset._h, int(row_begin), int(row_end), int(components), float(tol), int(max_iters),
+                                    ctypes.byref(h)))
+        return Pca(self, h)
+
+    def pca_stats(self):
+        """-> dict of the last sketch_moments / pca / Pca.transform: gram_ms, eigen_ms, scores_ms (timing on), slabs, iterations"""
+        a, b, s = _c.c_double(), _c.c_double(), _c.c_double()
+        n, r = _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_pca_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(s), ctypes.byref(n), ctypes.byref(r)))
+        return {"gram_ms": a.value, "eigen_ms": b.value, "scores_ms": s.value, "slabs": n.value, "iterations": r.value}
 
     def _consumer_stats(self, fn, work_key):
         """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time

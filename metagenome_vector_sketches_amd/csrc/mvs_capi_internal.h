@@ -170,6 +170,9 @@ struct mvs_ctx {
     // what the last mvs_pairwise_levels did (mvs_ctx_levels_stats): kernel times summed over its row blocks (timing enabled)
     double lv_dots_ms = 0.0, lv_count_ms = 0.0;
     long long lv_blocks = 0, lv_block_rows = 0;
+    // what the last mvs_sketch_moments / mvs_pca_fit / mvs_pca_transform did (mvs_ctx_pca_stats): times with timing enabled
+    double pc_gram_ms = 0.0, pc_eigen_ms = 0.0, pc_scores_ms = 0.0;
+    long long pc_slabs = 0, pc_iters = 0;
     // what the clustering, linkage and dereplication calls did since the last mvs_cluster_create / mvs_linkage_create /
     // mvs_derep_create on this context (mvs_ctx_cluster_stats, mvs_ctx_linkage_stats, mvs_ctx_derep_stats)
     mvs_capi::ConsumerStats cl, lk, dr;

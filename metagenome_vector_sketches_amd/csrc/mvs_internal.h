@@ -115,6 +115,10 @@ struct Options {
     int levels_dots = 0;            // mvs_pairwise_levels: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU
                                     // kernel (A/B, tests); same counts
     int levels_block_rows = 0;      // mvs_pairwise_levels: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
+    int gram_slab_rows = 65536;     // mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536
+                                    // (rounded down to a multiple of 64; tests lower it to force several slabs)
+    int gram_variant = 0;           // k_gram_tiles: 0 = by shape (128 x 128 tiles for one or two limbs and d >= 128, else 64 x 64),
+                                    // 1 = always 64 x 64 (A/B, tests); same result
     int cluster_cells = 0;          // mvs_pairwise_cluster: cells the staging buffer of a row block holds; 0 = a quarter of the free
                                     // device memory (never more than the block can produce); tests lower it
     int cluster_block_rows = 0;     // mvs_pairwise_cluster: > 0 = upper bound on the rows of a block (tests); 0 = by pairwise_block_cells
@@ -307,6 +311,22 @@ int launch_levels_prep(hipStream_t stream, const double* d_norms_sq, int64_t n, 
 int launch_levels_count(hipStream_t stream, const int32_t* d_dots, int64_t rows, int64_t ld, int64_t row0, int64_t c0,
                         const double* d_norms_sq, const double* d_coef, int m, int d, const int* d_thr, const int* d_neg_flag,
                         int32_t* d_deg, unsigned long long* d_total);
+// exact second moments over the sample axis and the device side of the PCA (mvs_gram.hip).  gram_limbs: limbs read and their
+// radix for a limb code.  gram_slab: rows [row0, row_end) (at most 65536) are transposed into d_T (gram_scratch_bytes) and
+// their products added to d_gram (d x d, zeroed by the caller before the first slab); variant: option gram_variant.  colsums: added to d_sums (d, zeroed).
+// pca_matmul: Y = C Q (C d x d, Q and Y d x b row-major).  pca_ritz: V = Q S, W = Y S, R = W - V diag(theta), res[i] = ||R[:, i]||.
+// pca_scores: rows [rb, re) of the planes against V (d x c row-major) minus off[c] -> d_scores ((re - rb) x c).
+void gram_limbs(int code, int* L, int* W);
+size_t gram_scratch_bytes(int d, int code, int64_t slab_rows);
+int launch_gram_slab(hipStream_t stream, const int8_t* d_planes, int code, int d, int d_pad, int64_t row0, int64_t row_end, int8_t* d_T,
+                     unsigned long long* d_gram, int variant);
+int launch_gram_colsums(hipStream_t stream, const int8_t* d_planes, int code, int d, int d_pad, int64_t rb, int64_t re,
+                        unsigned long long* d_sums);
+int launch_pca_matmul(hipStream_t stream, const double* d_C, const double* d_Q, int d, int b, double* d_Y);
+int launch_pca_ritz(hipStream_t stream, const double* d_Q, const double* d_Y, const double* d_S, const double* d_theta, int d, int b,
+                    double* d_V, double* d_W, double* d_R, double* d_res);
+int launch_pca_scores(hipStream_t stream, const int8_t* d_planes, int code, int d, int d_pad, int64_t rb, int64_t re, const double* d_V,
+                      const double* d_off, int c, double* d_scores);
 // single-linkage clustering over device cell lists (mvs_cluster.hip): union-find rounds over parent[n] -- d_counters: [0] cells
 // with row != col, [1] cells with an index outside [0, n), [2] cells whose endpoints still have different roots -- and the
 // finish passes (cluster ids by ascending root, sizes, representatives)
