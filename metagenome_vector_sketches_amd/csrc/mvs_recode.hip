@@ -138,7 +138,9 @@ static_assert(MVS_WIRE_RADIX_MAX == 252 && MVS_WIRE_MAX_ABS == 127 * 252, "the b
 // with step <= 8, and |r| is at most mc / 2 where the coarse value is not clamped and |v| - 127 mc <= 127 (m - mc) <= 15240
 // where it is: every factor fits the 24-bit multipliers (full rate; the 32-bit multiply and the 64-bit
 // multiply-add are quarter rate, and sixteen trials over every entry are what the kernels around this spend their time on),
-// and sixteen squares fit 32 bits (16 * 15240^2 = 3.72e9).
+// and sixteen squares fit 32 bits (16 * 15240^2 = 3.72e9).  (That is the bound of the sixteen trials alone.  The search stops at the
+// first radix that radix_keeps_high_limb refuses, so a clamped entry lies at most 254 - ceil(mc / 2) <= 253 beyond 127 mc and at most
+// three radices are ever tried: 15240 is never approached -- tests/test_recode_model_cpu.py goes through every radix.)
 constexpr int kTrialResidualMax = 15240;
 static_assert(16ull * kTrialResidualMax * kTrialResidualMax < (1ull << 32), "sixteen squared residuals per 32-bit partial sum");
 // (Written as instructions: left to itself the compiler turns the sum of squares into a chain of v_mad_u64_u32.)
@@ -219,7 +221,7 @@ __global__ __launch_bounds__(256) void k_coarse_build(const int8_t* __restrict__
             }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) r2c += __shfl_xor(r2c, o, 64);
-            if (r2c < best) {
+            if (r2c < best) {                                  // strictly: among equal sums the first, i.e. the larger, radix stays
                 best = r2c;
                 best_m = mc;
             }
