@@ -142,6 +142,9 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   levels_dots, levels_block_rows
  *                         mvs_pairwise_levels: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds
  *                         the rows of a block (0: by the device budget)
+ *   pcoa_dots, pcoa_block_rows
+ *                         mvs_jaccard_apply / mvs_pcoa_*: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0
+ *                         bounds the rows of a block (0: by the device budget)
  *   gram_slab_rows        mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536 (default
  *                         65536; rounded down to a multiple of 64)
  *   gram_variant          tile kernel of the moments: 0 (default) by shape -- 128 x 128 tiles for one or two limbs and d >= 128, else
@@ -973,6 +976,77 @@ int mvs_pca_transform(mvs_ctx* ctx, const mvs_pca* pca, const mvs_sketch_set* se
                       double* scores, int mem_out);
 int mvs_pca_destroy(mvs_pca* pca);
 int mvs_ctx_pca_stats(const mvs_ctx* ctx, double* gram_ms, double* eigen_ms, double* scores_ms, int64_t* slabs, int64_t* iterations);
+
+/* ---- principal coordinates of the Jaccard estimates, matrix-free --------------------------------------
+ * Every other analysis here judges two samples by their Jaccard estimate; this is the ordination in that geometry: classical
+ * PCoA of the distance sqrt(1 - k).  The n x n matrix it is defined on is never stored: the dense-dots kernels produce a block
+ * of rows, one kernel turns the block into Jaccard values and multiplies them into a thin block of vectors in the same pass.
+ *
+ * The rule.  n2 = norms_sq, d the set's dimension, 0 <= floor < 1; row i, column j by sample index; P the int32 dot as
+ * mvs_pairwise_dots returns it (wrapped).  Everything is fp64 and every line is ONE rounding; a NaN compares false:
+ *     i == j : k(i,j) = 1.0
+ *     i != j : inter = (double)P / (double)d
+ *              s     = n2[i] + n2[j]
+ *              den   = s - inter
+ *              J     = inter / den
+ *              k(i,j) = !(J > floor) ? 0.0 : (J > 1.0 ? 1.0 : J)
+ * -- the score of mvs_pairwise_topk with the writer's clamp.  k is symmetric bit for bit (n2[i] + n2[j] commutes) and defined
+ * for any norms: NaN, +-inf, 0, negative.
+ *
+ * mvs_jaccard_apply   Y[(i - row_begin) * b + c] = sum over j in [col_begin, col_end) of k(i,j) * X[(j - col_begin) * b + c]
+ *                     X: (col_end - col_begin) x b doubles, row-major (`mem_x`); Y: (row_end - row_begin) x b (`mem_y`);
+ *                     1 <= b <= 128.  fp64 on the matrix cores, no floating-point atomics; the order of every sum is a fixed
+ *                     function of the column range and of b only, so Y is bit-identical from run to run AND for every row
+ *                     blocking (option pcoa_block_rows, or the caller's own splitting of the row range).  Against the exact
+ *                     sum every entry is within (C + 4) 2^-53 sum_j |k| |X|, C the number of columns.  Rows go in blocks sized as
+ *                     mvs_pairwise_levels sizes them; per block one dense-dots launch (option pcoa_dots = 1: on the vector
+ *                     ALUs) and one apply launch; device memory besides the set is the dots block plus O((rows + cols) x b),
+ *                     never N x N.  An empty row range returns MVS_OK and writes nothing; an empty column range gives Y = 0.
+ *                     MVS_E_INVALID: floor outside [0, 1) or NaN, b outside 1 .. 128, ranges outside the set, a NULL buffer
+ *                     that is needed.
+ * mvs_pcoa_fit        F = [row_begin, row_end), m = its size >= 2, 1 <= components <= min(64, m - 1), 0 <= tol < 1,
+ *                     max_iters >= 1 (else MVS_E_INVALID).  K = k on F x F, H = I - 11^T / m, B = 1/2 H K H: classical PCoA,
+ *                     -1/2 H (D o D) H with D o D = 1 - K, the constant removed by the centring.  One apply against a column of
+ *                     ones gives
+ *                         rowmean[i] = (sum_j k(i,j)) / m,  grand = (sum_i rowmean[i]) / m,  trace = 1/2 m (1 - grand)
+ *                     (the host sums in index order).  The leading eigenpairs of B come from the solver of mvs_pca_fit: block
+ *                     min(m, components + 8), the same splitmix64 start block, orthonormalisation, Jacobi and Ritz step; B Q is
+ *                     formed as: centre Q's columns (host), mvs_jaccard_apply's passes (device), centre the result and halve it
+ *                     (host).  It stops at max_i ||B v_i - lambda_i v_i||_2 <= tol * lambda_1 or after max_iters; not
+ *                     converging is not an error (converged = 0, the iterations used and the residuals come back).  lambda
+ *                     descends by value; vectors have unit length and are signed as the PCA axes are;
+ *                     coordinates[i][c] = sqrt(max(lambda_c, 0)) * v[i][c].  Deterministic bit for bit.
+ *                     An estimated kernel need not be positive semi-definite, and the iteration finds the eigenvalues of
+ *                     largest MAGNITUDE: a returned pair is always a verified eigenpair -- its residual is returned -- but it
+ *                     is the top pair by value only where the top of the spectrum dominates the negative end.  negative_ritz
+ *                     counts the negative Ritz values of the final block.
+ * mvs_pcoa_info       any pointer may be NULL.
+ * mvs_pcoa_get        HOST arrays, any may be NULL: eigenvalues[components], vectors[m * components] and
+ *                     coordinates[m * components] (row-major, sample i at i * components), row_means[m], residuals[components].
+ * mvs_pcoa_transform  Gower's out-of-sample formula for rows [row_begin, row_end) of the SAME set handle (the fitted rows
+ *                     where they were, new samples appended behind them; `norms_sq` covers the whole set):
+ *                         score[x][c] = lambda_c > 0 ? (1/2 sum_{j in F} (k(x,j) - rowmean[j]) v[j][c]) / sqrt(lambda_c) : 0
+ *                     one apply over rows x F, evaluated as sum k v - sum rowmean v.  A fitted row reproduces its coordinate up
+ *                     to the pair's residual / sqrt(lambda).  Another set handle: MVS_E_INVALID.
+ * mvs_ctx_pcoa_stats  of the context's last call of this section: dense-dots and apply kernel times summed over passes and row
+ *                     blocks, the solver from its first product to its last residual (host work included), passes over K, row
+ *                     blocks, rows per block; the times are 0 unless mvs_ctx_set_timing is on.  Any pointer may be NULL.
+ * All synchronous.  The kernel is in csrc/mvs_kapply.hip. */
+typedef struct mvs_pcoa mvs_pcoa;
+int mvs_jaccard_apply(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double floor,
+                      int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, const double* X, int b, int mem_x,
+                      double* Y, int mem_y);
+int mvs_pcoa_fit(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, int64_t row_begin,
+                 int64_t row_end, int components, double floor, double tol, int max_iters, mvs_pcoa** pcoa);
+int mvs_pcoa_info(const mvs_pcoa* pcoa, int64_t* row_begin, int64_t* row_end, int* components, int* block, int* iterations,
+                  int* converged, int* negative_ritz, double* floor, double* grand_mean, double* trace);
+int mvs_pcoa_get(const mvs_pcoa* pcoa, double* eigenvalues, double* vectors, double* coordinates, double* row_means,
+                 double* residuals);
+int mvs_pcoa_transform(mvs_ctx* ctx, const mvs_pcoa* pcoa, const mvs_sketch_set* set, const double* norms_sq, int mem_norms,
+                       int64_t row_begin, int64_t row_end, double* scores, int mem_out);
+int mvs_pcoa_destroy(mvs_pcoa* pcoa);
+int mvs_ctx_pcoa_stats(const mvs_ctx* ctx, double* dots_ms, double* apply_ms, double* eigen_ms, int64_t* passes,
+                       int64_t* row_blocks, int64_t* block_rows);
 
 /* ---- multi-GPU exchange ---------------------------------------------------------------------------
  * One process per GPU; shard k of src/pairwise_comp_optimized.cpp:938-940 is rank k.  Where the reference's shard

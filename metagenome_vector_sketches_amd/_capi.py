@@ -124,6 +124,18 @@ SYMBOLS = [
     ("mvs_pca_destroy", _c.c_int, [_P]),
     ("mvs_ctx_pca_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                                       _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_jaccard_apply", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int,
+                                      _c.c_int, _P, _c.c_int]),
+    ("mvs_pcoa_fit", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_int,
+                                 _c.POINTER(_P)]),
+    ("mvs_pcoa_info", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
+                                  _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_double),
+                                  _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    ("mvs_pcoa_get", _c.c_int, [_P, _P, _P, _P, _P, _P]),
+    ("mvs_pcoa_transform", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _c.c_int64, _P, _c.c_int]),
+    ("mvs_pcoa_destroy", _c.c_int, [_P]),
+    ("mvs_ctx_pcoa_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
+                                       _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     ("mvs_cluster_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_cluster_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
     ("mvs_pairwise_cluster", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
@@ -696,6 +708,50 @@ class Pca(_Handle):
         rows = max(0, int(row_end) - int(row_begin))
         out = np.empty((rows, self.components), dtype=np.float64)
         _check(self.ctx.lib.mvs_pca_transform(self.ctx._h, self._h, sset._h, int(row_begin), int(row_end), out.ctypes.data, MEM_HOST))
+        return out
+
+
+class Pcoa(_Handle):
+    """Principal coordinates of the Jaccard estimates of the rows [row_begin, row_end) of a sketch set (mvs_pcoa; Context.pcoa
+    makes one): numpy float64 arrays `eigenvalues` [c] (of B = 1/2 H K H, descending), `vectors` [m, c] (unit columns),
+    `coordinates` [m, c] (sqrt(max(eigenvalue, 0)) * vector), `row_means` [m], `explained_ratio` [c] (eigenvalues / trace),
+    `residuals` [c] (||B v - lambda v||_2 of every returned pair); `grand_mean`, `trace`, `iterations`, `converged`,
+    `negative_ritz` (negative Ritz values in the solver's final block), `floor`.  The iteration finds the eigenvalues of
+    largest magnitude: see include/mvs_hip.h.  Closes with its context."""
+    _destroy = "mvs_pcoa_destroy"
+
+    def __init__(self, ctx, handle, sset, norms_sq):
+        self.ctx, self._h, self.sset, self.norms_sq = ctx, handle, sset, norms_sq
+        ctx._children.add(self)
+        rb, re = _c.c_int64(), _c.c_int64()
+        c, blk, it, cv, neg = _c.c_int(), _c.c_int(), _c.c_int(), _c.c_int(), _c.c_int()
+        fl, gm, tr = _c.c_double(), _c.c_double(), _c.c_double()
+        _check(ctx.lib.mvs_pcoa_info(handle, ctypes.byref(rb), ctypes.byref(re), ctypes.byref(c), ctypes.byref(blk), ctypes.byref(it),
+                                     ctypes.byref(cv), ctypes.byref(neg), ctypes.byref(fl), ctypes.byref(gm), ctypes.byref(tr)))
+        self.row_begin, self.row_end, self.components, self.block = rb.value, re.value, c.value, blk.value
+        self.n = self.row_end - self.row_begin
+        self.iterations, self.converged, self.negative_ritz = it.value, bool(cv.value), neg.value
+        self.floor, self.grand_mean, self.trace = fl.value, gm.value, tr.value
+        self.eigenvalues = np.empty(self.components, dtype=np.float64)
+        self.vectors = np.empty((self.n, self.components), dtype=np.float64)
+        self.coordinates = np.empty((self.n, self.components), dtype=np.float64)
+        self.row_means = np.empty(self.n, dtype=np.float64)
+        self.residuals = np.empty(self.components, dtype=np.float64)
+        _check(ctx.lib.mvs_pcoa_get(handle, self.eigenvalues.ctypes.data, self.vectors.ctypes.data, self.coordinates.ctypes.data,
+                                    self.row_means.ctypes.data, self.residuals.ctypes.data))
+        with np.errstate(all="ignore"):
+            self.explained_ratio = self.eigenvalues / self.trace
+
+    def transform(self, rows=None, norms_sq=None):
+        """Gower's out-of-sample scores of `rows` = (begin, end) of the fitted set handle (default: every row of it, the
+        samples appended behind the fitted ones included): float64 [rows, c].  norms_sq: the set's squared norms (default:
+        those the fit was given)."""
+        if self._h is None:
+            raise ValueError("the pcoa is closed")
+        rb, re = (0, self.sset.n) if rows is None else rows
+        np_, nm, nk = _norms(self.norms_sq if norms_sq is None else norms_sq)
+        out = np.empty((max(0, int(re) - int(rb)), self.components), dtype=np.float64)
+        _check(self.ctx.lib.mvs_pcoa_transform(self.ctx._h, self._h, self.sset._h, np_, nm, int(rb), int(re), out.ctypes.data, MEM_HOST))
         return out
 
 
@@ -1437,6 +1493,45 @@ class Context:
         n, r = _c.c_int64(), _c.c_int64()
         _check(self.lib.mvs_ctx_pca_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(s), ctypes.byref(n), ctypes.byref(r)))
         return {"gram_ms": a.value, "eigen_ms": b.value, "scores_ms": s.value, "slabs": n.value, "iterations": r.value}
+
+    # ---- principal coordinates of the Jaccard estimates (include/mvs_hip.h "principal coordinates") ----
+    def jaccard_apply(self, sset, norms_sq, X, rows=None, cols=None, floor=0.0):
+        """mvs_jaccard_apply: Y = K X over `rows` x `cols` (each a (begin, end) pair, default every sample), K the clamped
+        Jaccard estimates above `floor` with a unit diagonal (include/mvs_hip.h states the rule), never stored.  X: float64
+        [cols, b] (or [cols]), 1 <= b <= 128 -> float64 [rows, b] (or [rows])."""
+        rb, re = (0, sset.n) if rows is None else rows
+        cb, ce = (0, sset.n) if cols is None else cols
+        np_, nm, nk = _norms(norms_sq)
+        x = np.ascontiguousarray(X, dtype=np.float64)
+        flat = x.ndim == 1
+        if flat:
+            x = x.reshape(-1, 1)
+        if x.ndim != 2 or x.shape[0] != max(0, int(ce) - int(cb)):
+            raise ValueError("X must have one row per column of the range")
+        b = x.shape[1]
+        out = np.empty((max(0, int(re) - int(rb)), b), dtype=np.float64)
+        _check(self.lib.mvs_jaccard_apply(self._h, sset._h, np_, nm, float(floor), int(rb), int(re), int(cb), int(ce), x.ctypes.data, b,
+                                          MEM_HOST, out.ctypes.data, MEM_HOST))
+        return out[:, 0] if flat else out
+
+    def pcoa(self, sset, norms_sq, components, rows=None, floor=0.0, tol=1e-10, max_iters=300):
+        """mvs_pcoa_fit: principal coordinates of the Jaccard estimates of `rows` = (begin, end) of `sset` (default all) ->
+        Pcoa.  A fit that did not reach `tol` within `max_iters` iterations still returns (Pcoa.converged is False)."""
+        rb, re = (0, sset.n) if rows is None else rows
+        np_, nm, nk = _norms(norms_sq)
+        h = _P()
+        _check(self.lib.mvs_pcoa_fit(self._h, sset._h, np_, nm, int(rb), int(re), int(components), float(floor), float(tol), int(max_iters),
+                                     ctypes.byref(h)))
+        return Pcoa(self, h, sset, nk if nk is not None else norms_sq)
+
+    def pcoa_stats(self):
+        """-> dict of the last jaccard_apply / pcoa / Pcoa.transform: dots_ms, apply_ms (kernel times over passes and row blocks),
+        eigen_ms (the whole solver, host work included; timing on), passes, row_blocks, block_rows"""
+        a, b, e = _c.c_double(), _c.c_double(), _c.c_double()
+        n, r, k = _c.c_int64(), _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_pcoa_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n), ctypes.byref(r),
+                                           ctypes.byref(k)))
+        return {"dots_ms": a.value, "apply_ms": b.value, "eigen_ms": e.value, "passes": n.value, "row_blocks": r.value, "block_rows": k.value}
 
     def _consumer_stats(self, fn, work_key):
         """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time

@@ -1,5 +1,5 @@
 // mvs_tool.hpp -- what the tools over a sketch DB share (cluster_sketches, linkage_sketches, dereplicate_sketches, verify_pairs,
-// and pairwise_comp_optimized for the loader): opening the DB folder, loading vectors.bin into a sketch set, reporting a
+// pca_sketches, pcoa_sketches, and pairwise_comp_optimized for the loader): opening the DB folder, loading vectors.bin into a sketch set, reporting a
 // device error, writing an output file under <file>.part, the hash file a DB was sketched from, and the parsing of flag values.  Header-only; include it after
 // mvs_host.hpp.  Each tool keeps its own parse() chain, usage text, Gpu holder and output format.
 #ifndef MVS_TOOL_HPP
@@ -107,30 +107,45 @@ inline int open_sketch_db(const std::string& folder, SketchDb& db) {
     return 0;
 }
 
-// vectors.bin goes through the device in row chunks straight from the page cache (the file is mapped, the library copies
-// from the mapping) and is re-coded into the limb planes of *set (an earlier set there is destroyed).  Reads matrix_file,
-// elem_bytes, n and dimension of `db`.  0, 1 (the file) or 2 (the device), after a message on stderr.
-inline int load_sketch_db(const char* prog, mvs_ctx* ctx, const SketchDb& db, mvs_sketch_set** set) {
-    const int64_t n = db.n, row_bytes = (int64_t)db.dimension * db.elem_bytes;
-    const int64_t chunk_rows = std::max<int64_t>(1, (1LL << 30) / row_bytes);
-    const int fd = ::open(db.matrix_file.c_str(), O_RDONLY);
-    if (fd < 0) {
-        std::cerr << "Error opening file: " << db.matrix_file << std::endl;    // :35-38
-        return 1;
-    }
-    const size_t bytes = (size_t)(n * row_bytes);
-    const char* base = nullptr;
-    if (bytes) {
-        void* m = ::mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) {
-            ::close(fd);
-            std::cerr << "Error reading file: " << db.matrix_file << std::endl;
+// vectors.bin of every DB of `dbs` (same dimension), one behind the other, goes through the device in row chunks straight from
+// the page cache (the files are mapped, the library copies from the mappings) and is re-coded into the limb planes of *set (an
+// earlier set there is destroyed), with a limb code that suits them all.  Reads matrix_file, elem_bytes, n and dimension of
+// each.  0, 1 (a file) or 2 (the device), after a message on stderr.
+inline int load_sketch_dbs(const char* prog, mvs_ctx* ctx, const std::vector<const SketchDb*>& dbs, mvs_sketch_set** set) {
+    struct Mapping {
+        const char* base = nullptr;
+        size_t bytes = 0;
+    };
+    std::vector<Mapping> maps(dbs.size());
+    auto unmap_all = [&] {
+        for (const Mapping& m : maps)
+            if (m.bytes) ::munmap((void*)m.base, m.bytes);
+    };
+    int64_t n = 0;
+    for (size_t k = 0; k < dbs.size(); ++k) {
+        const SketchDb& db = *dbs[k];
+        const int fd = ::open(db.matrix_file.c_str(), O_RDONLY);
+        if (fd < 0) {
+            std::cerr << "Error opening file: " << db.matrix_file << std::endl;    // :35-38
+            unmap_all();
             return 1;
         }
-        ::madvise(m, bytes, MADV_SEQUENTIAL);
-        base = (const char*)m;
+        const size_t bytes = (size_t)(db.n * (int64_t)db.dimension * db.elem_bytes);
+        if (bytes) {
+            void* m = ::mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) {
+                ::close(fd);
+                std::cerr << "Error reading file: " << db.matrix_file << std::endl;
+                unmap_all();
+                return 1;
+            }
+            ::madvise(m, bytes, MADV_SEQUENTIAL);
+            maps[k].base = (const char*)m;
+            maps[k].bytes = bytes;
+        }
+        ::close(fd);
+        n += db.n;
     }
-    ::close(fd);
     // One pass in the common case: the planes are allocated for two limbs (|v| <= 32639, i.e. samples of up to tens
     // of millions of hashes) and every chunk reports its largest |v| with the same upload; only if a chunk needs
     // more limbs than the set has does the load start over with the limb count the data seen so far asks for.
@@ -140,22 +155,64 @@ inline int load_sketch_db(const char* prog, mvs_ctx* ctx, const SketchDb& db, mv
             mvs_sketch_set_destroy(*set);
             *set = nullptr;
         }
-        if (mvs_sketch_set_alloc(ctx, n, db.dimension, limbs, set) != MVS_OK) {
+        if (mvs_sketch_set_alloc(ctx, n, dbs[0]->dimension, limbs, set) != MVS_OK) {
             rc = gpu_fail(prog, "allocating sketch set");
             break;
         }
-        int64_t max_abs = 0;
-        for (int64_t r0 = 0; r0 < n && !rc && mvs_limbs_for_max_abs(max_abs) <= limbs; r0 += chunk_rows) {
-            int64_t m = 0;
-            if (mvs_sketch_set_fill_stats(*set, base + r0 * row_bytes, db.elem_bytes, MVS_MEM_HOST, r0, std::min(chunk_rows, n - r0), &m) != MVS_OK)
-                rc = gpu_fail(prog, "re-coding vectors.bin");
-            max_abs = std::max(max_abs, m);
+        int64_t max_abs = 0, first = 0;
+        for (size_t k = 0; k < dbs.size(); ++k) {
+            const SketchDb& db = *dbs[k];
+            const int64_t row_bytes = (int64_t)db.dimension * db.elem_bytes;
+            const int64_t chunk_rows = std::max<int64_t>(1, (1LL << 30) / row_bytes);
+            for (int64_t r0 = 0; r0 < db.n && !rc && mvs_limbs_for_max_abs(max_abs) <= limbs; r0 += chunk_rows) {
+                int64_t m = 0;
+                if (mvs_sketch_set_fill_stats(*set, maps[k].base + r0 * row_bytes, db.elem_bytes, MVS_MEM_HOST, first + r0,
+                                              std::min(chunk_rows, db.n - r0), &m) != MVS_OK)
+                    rc = gpu_fail(prog, "re-coding vectors.bin");
+                max_abs = std::max(max_abs, m);
+            }
+            first += db.n;
         }
         if (mvs_limbs_for_max_abs(max_abs) <= limbs) break;
         limbs = mvs_limbs_for_max_abs(max_abs);
     }
-    if (bytes) ::munmap((void*)base, bytes);
+    unmap_all();
     return rc;
+}
+inline int load_sketch_db(const char* prog, mvs_ctx* ctx, const SketchDb& db, mvs_sketch_set** set) {
+    return load_sketch_dbs(prog, ctx, {&db}, set);
+}
+
+// ---- what the ordination tools share (pca_sketches, pcoa_sketches) ----
+inline std::string fmt9(double v) {
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.9g", v);
+    return buf;
+}
+
+// the norms of vector_norms.txt as read_norms takes them (the text after the first space), not squared
+inline std::vector<double> read_plain_norms(const std::string& file, int64_t n) {
+    std::vector<double> norms;
+    std::ifstream in(file);
+    std::string line;
+    while ((int64_t)norms.size() < n && std::getline(in, line)) {
+        const size_t pos = line.find(' ');
+        if (pos == std::string::npos) continue;
+        norms.push_back(std::stod(line.substr(pos + 1)));
+    }
+    return norms;
+}
+
+// name  fitted(1/0)  c values as %.9g, one line per sample; fitted == nullptr: 0 throughout
+inline std::string scores_text(const std::vector<std::string>& names, const std::vector<char>* fitted, const std::vector<double>& scores, int c) {
+    std::string text;
+    for (size_t i = 0; i < names.size(); ++i) {
+        text += names[i];
+        text += fitted && (*fitted)[i] ? "\t1" : "\t0";
+        for (int j = 0; j < c; ++j) text += '\t' + fmt9(scores[i * (size_t)c + j]);
+        text += '\n';
+    }
+    return text;
 }
 
 // ---- the hash file a DB was sketched from ----

@@ -102,36 +102,6 @@ struct Gpu {
     }
 };
 
-std::string fmt(double v) {
-    char buf[64];
-    snprintf(buf, sizeof buf, "%.9g", v);
-    return buf;
-}
-
-// the norms of vector_norms.txt as read_norms takes them (the text after the first space), not squared
-std::vector<double> read_plain_norms(const std::string& file, int64_t n) {
-    std::vector<double> norms;
-    std::ifstream in(file);
-    std::string line;
-    while ((int64_t)norms.size() < n && std::getline(in, line)) {
-        const size_t pos = line.find(' ');
-        if (pos == std::string::npos) continue;
-        norms.push_back(std::stod(line.substr(pos + 1)));
-    }
-    return norms;
-}
-
-std::string scores_text(const std::vector<std::string>& names, const std::vector<char>* fitted, const std::vector<double>& scores, int c) {
-    std::string text;
-    for (size_t i = 0; i < names.size(); ++i) {
-        text += names[i];
-        text += fitted && (*fitted)[i] ? "\t1" : "\t0";
-        for (int j = 0; j < c; ++j) text += '\t' + fmt(scores[i * (size_t)c + j]);
-        text += '\n';
-    }
-    return text;
-}
-
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -203,7 +173,7 @@ int main(int argc, char* argv[]) {
     std::vector<double> mean((size_t)d), axes((size_t)c * d), variances((size_t)c), residuals((size_t)c);
     mvs_pca_get(g.pca, mean.data(), axes.data(), variances.data(), residuals.data());
     if (!converged)
-        std::cerr << kProg << ": warning: the fit did not converge to --tol " << fmt(o.tol) << " in " << iterations << " iterations" << std::endl;
+        std::cerr << kProg << ": warning: the fit did not converge to --tol " << fmt9(o.tol) << " in " << iterations << " iterations" << std::endl;
 
     std::vector<double> scores((size_t)n * c);
     if (mvs_pca_transform(g.ctx, g.pca, g.set, 0, n, scores.data(), MVS_MEM_HOST) != MVS_OK) return gpu_fail(kProg, "computing the scores");
@@ -221,8 +191,8 @@ int main(int argc, char* argv[]) {
     if (!o.axes.empty()) {
         std::string text;
         for (int k = 0; k < d; ++k) {
-            text += std::to_string(k) + '\t' + fmt(mean[(size_t)k]);
-            for (int j = 0; j < c; ++j) text += '\t' + fmt(axes[(size_t)j * d + k]);
+            text += std::to_string(k) + '\t' + fmt9(mean[(size_t)k]);
+            for (int j = 0; j < c; ++j) text += '\t' + fmt9(axes[(size_t)j * d + k]);
             text += '\n';
         }
         if (const int rc = write_then_rename(kProg, o.axes, text)) return rc;
@@ -232,15 +202,15 @@ int main(int argc, char* argv[]) {
     if (!o.report.empty()) {
         std::string text = "samples\t" + std::to_string(n) + "\nfitted\t" + std::to_string(n_fit) + "\ndimension\t" + std::to_string(d) +
                            "\ncomponents\t" + std::to_string(c) + "\niterations\t" + std::to_string(iterations) + "\nconverged\t" +
-                           std::to_string(converged) + "\ntotal_variance\t" + fmt(total_variance) + "\ncomponent\tvariance\tratio\tresidual\n";
+                           std::to_string(converged) + "\ntotal_variance\t" + fmt9(total_variance) + "\ncomponent\tvariance\tratio\tresidual\n";
         for (int j = 0; j < c; ++j)
-            text += std::to_string(j + 1) + '\t' + fmt(variances[(size_t)j]) + '\t' + fmt(variances[(size_t)j] / total_variance) + '\t' +
-                    fmt(residuals[(size_t)j]) + '\n';
-        text += "gram_ms\t" + fmt(gram_ms) + "\neigen_ms\t" + fmt(eigen_ms) + "\nscores_ms\t" + fmt(scores_ms) + "\nslabs\t" + std::to_string(slabs) +
-                "\nwall_ms\t" + fmt(wall_ms) + '\n';
+            text += std::to_string(j + 1) + '\t' + fmt9(variances[(size_t)j]) + '\t' + fmt9(variances[(size_t)j] / total_variance) + '\t' +
+                    fmt9(residuals[(size_t)j]) + '\n';
+        text += "gram_ms\t" + fmt9(gram_ms) + "\neigen_ms\t" + fmt9(eigen_ms) + "\nscores_ms\t" + fmt9(scores_ms) + "\nslabs\t" + std::to_string(slabs) +
+                "\nwall_ms\t" + fmt9(wall_ms) + '\n';
         if (const int rc = write_then_rename(kProg, o.report, text)) return rc;
     }
-    std::cout << "Fitted " << c << " components on " << n_fit << " of " << n << " samples in " << iterations << " iterations (gram " << fmt(gram_ms)
-              << " ms, eigen " << fmt(eigen_ms) << " ms, scores " << fmt(scores_ms) << " ms)" << std::endl;
+    std::cout << "Fitted " << c << " components on " << n_fit << " of " << n << " samples in " << iterations << " iterations (gram " << fmt9(gram_ms)
+              << " ms, eigen " << fmt9(eigen_ms) << " ms, scores " << fmt9(scores_ms) << " ms)" << std::endl;
     return 0;
 }

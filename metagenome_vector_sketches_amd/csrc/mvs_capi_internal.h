@@ -173,6 +173,10 @@ struct mvs_ctx {
     // what the last mvs_sketch_moments / mvs_pca_fit / mvs_pca_transform did (mvs_ctx_pca_stats): times with timing enabled
     double pc_gram_ms = 0.0, pc_eigen_ms = 0.0, pc_scores_ms = 0.0;
     long long pc_slabs = 0, pc_iters = 0;
+    // what the last mvs_jaccard_apply / mvs_pcoa_fit / mvs_pcoa_transform did (mvs_ctx_pcoa_stats): kernel times summed over its
+    // passes and row blocks, the solver's whole time (timing enabled)
+    double po_dots_ms = 0.0, po_apply_ms = 0.0, po_eigen_ms = 0.0;
+    long long po_passes = 0, po_blocks = 0, po_block_rows = 0;
     // what the clustering, linkage and dereplication calls did since the last mvs_cluster_create / mvs_linkage_create /
     // mvs_derep_create on this context (mvs_ctx_cluster_stats, mvs_ctx_linkage_stats, mvs_ctx_derep_stats)
     mvs_capi::ConsumerStats cl, lk, dr;
@@ -370,6 +374,20 @@ int feed_consumer(const char* entry, mvs_ctx* c, const mvs_sketch_set* s, const 
 // the body of mvs_ctx_cluster_stats / _linkage_stats / _derep_stats
 int consumer_stats_out(const mvs_ctx* c, ConsumerStats mvs_ctx::*which, double* compare_ms, double* work_ms, int64_t* edges,
                        int64_t* row_blocks, int64_t* rounds);
+// ---- mvs_capi_pca.hip: the eigensolver the ordinations share (mvs_pca_fit, mvs_pcoa_fit) ----
+// Block subspace iteration with a Rayleigh-Ritz step for the leading eigenpairs of a symmetric operator of size d (the loop is
+// described at the top of mvs_capi_pca.hip).  op(q, d_Q, d_Y): q is the orthonormal block on the host and d_Q the same on the
+// device, both d x b row-major; the callable leaves the operator applied to it in d_Y, queued on the context's stream.
+// -> theta (b Ritz values, descending), V (d x b row-major Ritz vectors), res (b residual norms) of the last iteration.
+struct SubspaceResult {
+    std::vector<double> theta, V, res;
+    int iterations = 0, converged = 0;
+    double ms = 0.0;   // the loop's time on the stream (timing enabled)
+};
+using SubspaceOp = std::function<int(const double* q, const double* d_Q, double* d_Y)>;
+int subspace_iterate(mvs_ctx* c, int d, int b, int components, double tol, int max_iters, const SubspaceOp& op, SubspaceResult& out);
+// column j of v (d x ld row-major) -> out[0 .. d): unit length, the entry of largest magnitude (the smaller index on ties) positive
+void signed_unit_column(const double* v, int64_t d, int ld, int j, double* out);
 // `count` results of a *_finish to the caller's buffer (NULL: not wanted), queued on the context's stream
 template <typename T>
 int give_out(mvs_ctx* c, T* dst, const void* d_src, int64_t count, int mem_out) {

@@ -12,6 +12,8 @@
 // W = C V is the power step applied to the Ritz vectors, so one d x d x b product per iteration serves both the Rayleigh
 // quotient and the next block.  Everything is a fixed function of the integers: the start block comes from splitmix64 of
 // (row, column), every sum runs in a fixed order on one host thread or one device thread, nothing uses floating-point atomics.
+// The loop is subspace_iterate (declared in mvs_capi_internal.h): it takes the product as a callable, and mvs_pcoa_fit
+// (mvs_capi_pcoa.hip) runs it on B = 1/2 H K H of the Jaccard kernel instead of C.
 #include "mvs_capi_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -169,6 +171,92 @@ void jacobi_eigen(std::vector<double>& t, int b, std::vector<double>& theta, std
 
 }  // namespace
 
+namespace mvs_capi {
+
+int subspace_iterate(mvs_ctx* c, int d, int b, int components, double tol, int max_iters, const SubspaceOp& op, SubspaceResult& out) {
+    DevBuf dQ, dY, dS, dTheta, dV, dW, dR, dRes;
+    const size_t db = (size_t)d * b * 8;
+    HIP_TRY(dQ.alloc(db));
+    HIP_TRY(dY.alloc(db));
+    HIP_TRY(dV.alloc(db));
+    HIP_TRY(dW.alloc(db));
+    HIP_TRY(dR.alloc(db));
+    HIP_TRY(dS.alloc((size_t)b * b * 8));
+    HIP_TRY(dTheta.alloc((size_t)b * 8));
+    HIP_TRY(dRes.alloc((size_t)b * 8));
+    StageTimer timer;
+    if (const int rc = timer.begin(c)) return rc;
+    std::vector<double> q((size_t)b * d), rowmajor((size_t)d * b), Y((size_t)d * b), W((size_t)d * b), T, S;
+    std::vector<double>&V = out.V, &theta = out.theta, &res = out.res;
+    V.assign((size_t)d * b, 0.0);
+    res.assign((size_t)b, 0.0);
+    for (int j = 0; j < b; ++j)
+        for (int a = 0; a < d; ++a)
+            q[(size_t)j * d + a] = (double)(splitmix64(((uint64_t)a << 20) + (uint64_t)j) >> 11) * 0x1p-53 - 0.5;
+    orthonormalise(q, d, b);
+    int iters = 0, converged = 0;
+    while (true) {
+        for (int a = 0; a < d; ++a)
+            for (int j = 0; j < b; ++j) rowmajor[(size_t)a * b + j] = q[(size_t)j * d + a];
+        HIP_TRY(hipMemcpyAsync(dQ.p, rowmajor.data(), db, hipMemcpyHostToDevice, c->stream));
+        if (const int rc = op(rowmajor.data(), (const double*)dQ.p, (double*)dY.p)) return rc;
+        HIP_TRY(hipMemcpyAsync(Y.data(), dY.p, db, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        T.assign((size_t)b * b, 0.0);
+        for (int a = 0; a < d; ++a)
+            for (int i = 0; i < b; ++i) {
+                const double qi = rowmajor[(size_t)a * b + i];
+                for (int j = 0; j < b; ++j) T[(size_t)i * b + j] += qi * Y[(size_t)a * b + j];
+            }
+        for (int i = 0; i < b; ++i)
+            for (int j = i + 1; j < b; ++j) T[(size_t)i * b + j] = T[(size_t)j * b + i] = 0.5 * (T[(size_t)i * b + j] + T[(size_t)j * b + i]);
+        jacobi_eigen(T, b, theta, S);
+        HIP_TRY(hipMemcpyAsync(dS.p, S.data(), (size_t)b * b * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(dTheta.p, theta.data(), (size_t)b * 8, hipMemcpyHostToDevice, c->stream));
+        if (const int rc = mvs::launch_pca_ritz(c->stream, (const double*)dQ.p, (const double*)dY.p, (const double*)dS.p, (const double*)dTheta.p, d, b,
+                                                (double*)dV.p, (double*)dW.p, (double*)dR.p, (double*)dRes.p))
+            return fail(rc, "eigensolver: Ritz launch rejected");
+        if (const int ck = check_kernel("k_pca_ritz")) return ck;
+        HIP_TRY(hipMemcpyAsync(V.data(), dV.p, db, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(W.data(), dW.p, db, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(res.data(), dRes.p, (size_t)b * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        ++iters;
+        double worst = 0.0;
+        bool finite = true;
+        for (int i = 0; i < components; ++i) {
+            worst = std::max(worst, res[(size_t)i]);
+            finite = finite && std::isfinite(res[(size_t)i]);
+        }
+        converged = finite && worst <= tol * theta[0];
+        if (converged || iters >= max_iters) break;
+        for (int j = 0; j < b; ++j)
+            for (int a = 0; a < d; ++a) q[(size_t)j * d + a] = W[(size_t)a * b + j];
+        orthonormalise(q, d, b);
+    }
+    if (const int rc = timer.mark_end()) return rc;
+    out.ms = 0.0;
+    if (const int rc = timer.add_to(&out.ms)) return rc;
+    out.iterations = iters;
+    out.converged = converged;
+    return MVS_OK;
+}
+
+void signed_unit_column(const double* v, int64_t d, int ld, int j, double* out) {
+    double norm2 = 0.0;
+    for (int64_t a = 0; a < d; ++a) {
+        out[a] = v[(size_t)a * ld + j];
+        norm2 += out[a] * out[a];
+    }
+    int64_t big = 0;
+    for (int64_t a = 1; a < d; ++a)
+        if (std::fabs(out[a]) > std::fabs(out[big])) big = a;
+    const double scale = (norm2 > 0.0 ? 1.0 / std::sqrt(norm2) : 1.0) * (out[big] < 0.0 ? -1.0 : 1.0);
+    for (int64_t a = 0; a < d; ++a) out[a] *= scale;
+}
+
+}  // namespace mvs_capi
+
 extern "C" {
 
 int mvs_sketch_moments(mvs_ctx* c, const mvs_sketch_set* s, int64_t rb, int64_t re, int64_t* gram, int64_t* col_sums, int mem_out) {
@@ -249,71 +337,18 @@ int mvs_pca_fit(mvs_ctx* c, const mvs_sketch_set* s, int64_t rb, int64_t re, int
     std::vector<int64_t>().swap(gram);
 
     // ---- leading eigenpairs ----
-    DevBuf dQ, dY, dS, dTheta, dV, dW, dR, dRes;
-    const size_t db = (size_t)d * b * 8;
-    HIP_TRY(dQ.alloc(db));
-    HIP_TRY(dY.alloc(db));
-    HIP_TRY(dV.alloc(db));
-    HIP_TRY(dW.alloc(db));
-    HIP_TRY(dR.alloc(db));
-    HIP_TRY(dS.alloc((size_t)b * b * 8));
-    HIP_TRY(dTheta.alloc((size_t)b * 8));
-    HIP_TRY(dRes.alloc((size_t)b * 8));
     HIP_TRY(hipMemcpyAsync(dC.p, C.data(), dd * 8, hipMemcpyHostToDevice, c->stream));
-    StageTimer timer;
-    if (const int rc = timer.begin(c)) return rc;
-    std::vector<double> q((size_t)b * d), rowmajor((size_t)d * b), Y((size_t)d * b), V((size_t)d * b), W((size_t)d * b), T, theta, S, res((size_t)b);
-    for (int j = 0; j < b; ++j)
-        for (int a = 0; a < d; ++a)
-            q[(size_t)j * d + a] = (double)(splitmix64(((uint64_t)a << 20) + (uint64_t)j) >> 11) * 0x1p-53 - 0.5;
-    orthonormalise(q, d, b);
-    int iters = 0, converged = 0;
-    while (true) {
-        for (int a = 0; a < d; ++a)
-            for (int j = 0; j < b; ++j) rowmajor[(size_t)a * b + j] = q[(size_t)j * d + a];
-        HIP_TRY(hipMemcpyAsync(dQ.p, rowmajor.data(), db, hipMemcpyHostToDevice, c->stream));
-        if (const int rc = mvs::launch_pca_matmul(c->stream, (const double*)dC.p, (const double*)dQ.p, d, b, (double*)dY.p))
-            return fail(rc, "pca: product launch rejected");
-        if (const int ck = check_kernel("k_pca_matmul")) return ck;
-        HIP_TRY(hipMemcpyAsync(Y.data(), dY.p, db, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        T.assign((size_t)b * b, 0.0);
-        for (int a = 0; a < d; ++a)
-            for (int i = 0; i < b; ++i) {
-                const double qi = rowmajor[(size_t)a * b + i];
-                for (int j = 0; j < b; ++j) T[(size_t)i * b + j] += qi * Y[(size_t)a * b + j];
-            }
-        for (int i = 0; i < b; ++i)
-            for (int j = i + 1; j < b; ++j) T[(size_t)i * b + j] = T[(size_t)j * b + i] = 0.5 * (T[(size_t)i * b + j] + T[(size_t)j * b + i]);
-        jacobi_eigen(T, b, theta, S);
-        HIP_TRY(hipMemcpyAsync(dS.p, S.data(), (size_t)b * b * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(dTheta.p, theta.data(), (size_t)b * 8, hipMemcpyHostToDevice, c->stream));
-        if (const int rc = mvs::launch_pca_ritz(c->stream, (const double*)dQ.p, (const double*)dY.p, (const double*)dS.p, (const double*)dTheta.p, d, b,
-                                                (double*)dV.p, (double*)dW.p, (double*)dR.p, (double*)dRes.p))
-            return fail(rc, "pca: Ritz launch rejected");
-        if (const int ck = check_kernel("k_pca_ritz")) return ck;
-        HIP_TRY(hipMemcpyAsync(V.data(), dV.p, db, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(W.data(), dW.p, db, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(res.data(), dRes.p, (size_t)b * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        ++iters;
-        double worst = 0.0;
-        bool finite = true;
-        for (int i = 0; i < components; ++i) {
-            worst = std::max(worst, res[(size_t)i]);
-            finite = finite && std::isfinite(res[(size_t)i]);
-        }
-        converged = finite && worst <= tol * theta[0];
-        if (converged || iters >= max_iters) break;
-        for (int j = 0; j < b; ++j)
-            for (int a = 0; a < d; ++a) q[(size_t)j * d + a] = W[(size_t)a * b + j];
-        orthonormalise(q, d, b);
-    }
-    if (const int rc = timer.mark_end()) return rc;
-    if (const int rc = timer.add_to(&c->pc_eigen_ms)) return rc;
-    c->pc_iters = iters;
-    p->iterations = iters;
-    p->converged = converged;
+    SubspaceResult sr;
+    const SubspaceOp product = [&](const double*, const double* d_Q, double* d_Y) -> int {
+        if (const int rc = mvs::launch_pca_matmul(c->stream, (const double*)dC.p, d_Q, d, b, d_Y)) return fail(rc, "pca: product launch rejected");
+        return check_kernel("k_pca_matmul");
+    };
+    if (const int rc = subspace_iterate(c, d, b, components, tol, max_iters, product, sr)) return rc;
+    c->pc_eigen_ms = sr.ms;
+    c->pc_iters = sr.iterations;
+    p->iterations = sr.iterations;
+    p->converged = sr.converged;
+    const std::vector<double>&theta = sr.theta, &res = sr.res;
 
     // ---- the axes: unit length, the entry of largest magnitude (the smaller index on ties) positive ----
     const int cc = components;
@@ -323,17 +358,8 @@ int mvs_pca_fit(mvs_ctx* c, const mvs_sketch_set* s, int64_t rb, int64_t re, int
     std::vector<double> vc((size_t)d * cc), off((size_t)cc, 0.0);
     for (int j = 0; j < cc; ++j) {
         double* ax = p->axes.data() + (size_t)j * d;
-        double norm2 = 0.0;
+        signed_unit_column(sr.V.data(), d, b, j, ax);
         for (int a = 0; a < d; ++a) {
-            ax[a] = V[(size_t)a * b + j];
-            norm2 += ax[a] * ax[a];
-        }
-        int big = 0;
-        for (int a = 1; a < d; ++a)
-            if (std::fabs(ax[a]) > std::fabs(ax[big])) big = a;
-        const double scale = (norm2 > 0.0 ? 1.0 / std::sqrt(norm2) : 1.0) * (ax[big] < 0.0 ? -1.0 : 1.0);
-        for (int a = 0; a < d; ++a) {
-            ax[a] *= scale;
             vc[(size_t)a * cc + j] = ax[a];
             off[(size_t)j] += p->mean[(size_t)a] * ax[a];
         }

@@ -115,6 +115,9 @@ struct Options {
     int levels_dots = 0;            // mvs_pairwise_levels: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU
                                     // kernel (A/B, tests); same counts
     int levels_block_rows = 0;      // mvs_pairwise_levels: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
+    int pcoa_dots = 0;              // mvs_jaccard_apply / mvs_pcoa_*: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU
+                                    // kernel (A/B, tests); same result
+    int pcoa_block_rows = 0;        // mvs_jaccard_apply / mvs_pcoa_*: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
     int gram_slab_rows = 65536;     // mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536
                                     // (rounded down to a multiple of 64; tests lower it to force several slabs)
     int gram_variant = 0;           // k_gram_tiles: 0 = by shape (128 x 128 tiles for one or two limbs and d >= 128, else 64 x 64),
@@ -327,6 +330,13 @@ int launch_pca_ritz(hipStream_t stream, const double* d_Q, const double* d_Y, co
                     double* d_V, double* d_W, double* d_R, double* d_res);
 int launch_pca_scores(hipStream_t stream, const int8_t* d_planes, int code, int d, int d_pad, int64_t rb, int64_t re, const double* d_V,
                       const double* d_off, int c, double* d_scores);
+// the Jaccard kernel matrix of a block of dense dots times a thin block of vectors (mvs_kapply.hip; the rule is stated there and in
+// include/mvs_hip.h): Y (rows x b) = k(rows x ld) Xp, Xp the ld x b operand zero-padded to apply_padded_cols(ld) rows of
+// apply_padded_b(b) doubles
+int64_t apply_padded_cols(int64_t cols);
+int apply_padded_b(int b);
+int launch_jaccard_apply(hipStream_t stream, const int32_t* d_dots, int64_t rows, int64_t ld, int64_t row0, int64_t c0,
+                         const double* d_norms_sq, int d, double floor_, const double* d_Xp, int b, double* d_Y);
 // single-linkage clustering over device cell lists (mvs_cluster.hip): union-find rounds over parent[n] -- d_counters: [0] cells
 // with row != col, [1] cells with an index outside [0, n), [2] cells whose endpoints still have different roots -- and the
 // finish passes (cluster ids by ascending root, sizes, representatives)
