@@ -155,6 +155,7 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *                         overflows the buffer is halved and redone, so neither changes a result
  *   intersect_unit        mvs_intersect_cells: elements of a pair's SHORTER hash list that one unit of work (one wave) covers,
  *                         64 .. 2^30 (default 2048); a pair with a longer one is cut into several units
+ *   gather_batch          mvs_gather: rounds of the walk queued between two read-backs of its state, 1 .. 1024 (default 16)
  *   stream_block_rows, encode_stage_words, pairwise_map, coarse_radix, cand_regions, recheck_mode, recheck_blocks
  *                         test / experiment switches (DESIGN.md, appendix "switches"; encode_stage_words below 64 also keeps
  *                         every row on the device encoder's general loop)
@@ -770,6 +771,58 @@ int mvs_hash_set_destroy(mvs_hash_set* set);
 int mvs_intersect_cells(mvs_ctx* ctx, const mvs_hash_set* hs_rows, const mvs_hash_set* hs_cols, const mvs_cell* cells,
                         int mem_cells, int64_t n_cells, int32_t* inter, int mem_out);
 int mvs_ctx_intersect_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* units, int64_t* cut_pairs, int64_t* bytes);
+
+/* ---- gather: the greedy decomposition of a query into samples of a hash set -------------------------------------------------
+ * Everything above asks about a PAIR of samples.  This call answers the set question "which DB samples make up my sample, and
+ * how much of it does each explain that the ones before it did not": the greedy minimum-set-cover walk (the rule of sourmash
+ * `gather`).  The reference has no counterpart -- its search (src/jaccard.py) is pairwise --, so nothing of it is replaced.
+ *
+ * Q = H_query(query) (set semantics), H(c) the samples of hs_db, C the candidates (sample indices of hs_db; NULL: every sample;
+ * duplicates are allowed and harmless), min_hashes >= 1, max_matches >= 0:
+ *     R = Q;  orig[c] = |Q n H(c)|
+ *     repeat:
+ *         f[c] = |R n H(c)|  for c in C
+ *         best = the c with the largest f[c]; ties go to the SMALLER sample index
+ *         stop if C is empty, f[best] < min_hashes, or max_matches records are written
+ *         R = R \ H(best)
+ *         write (sample = best, intersect = orig[best], unique = f[best], remaining = |R|)
+ * Exact and deterministic: equal to that walk on the sorted, de-duplicated lists whatever the options, the blocking, the order
+ * or multiplicity of C, or whether the lists arrived sorted.  Hash values are arbitrary 64-bit words (0 and 2^64 - 1 are
+ * ordinary values; no sentinel).  It follows that `unique` never rises from record to record, that the sum of `unique` plus the
+ * last `remaining` is |Q|, that the first record has unique == intersect and that no sample is reported twice.  Derived
+ * fractions (intersect / |Q|, intersect / |H|, unique / |Q|) are the caller's, in fp64.
+ *
+ * mvs_gather            the walk above.  candidates: n_candidates int32 where mem_candidates says (NULL: all of hs_db);
+ *                       out: room for max_matches records where mem_out says; *n_matches: records written; *query_size: |Q|
+ *                       (may be NULL; set whenever the query index is valid, max_matches == 0 included).  An empty query or an
+ *                       empty candidate sample is ordinary: it matches nothing.  A query index or a candidate outside its set:
+ *                       MVS_E_RANGE, nothing is written, *n_matches = 0.  min_hashes < 1, max_matches < 0, a NULL buffer that
+ *                       is needed, a set of another context: MVS_E_INVALID.  Synchronous.
+ *                       How: orig[] for all candidates comes from mvs_intersect_cells on the cells (query, c) -- which also
+ *                       makes this the context's last mvs_intersect_cells --, and the candidates below min_hashes are retired
+ *                       before anything is allocated for them (f only falls: they could never be written).  Every SURVIVOR gets
+ *                       a bit row over the positions of Q's sorted list; a round is then one streaming pass over the live rows
+ *                       (popcount(row & alive) per survivor, one 64-bit atomic max for the pick) and clears the winner's bits
+ *                       from `alive`.  Rounds are queued option gather_batch at a time (default 16) with one small read-back
+ *                       per batch and no host synchronisation in between; the option never changes a result.
+ *                       Memory besides the sets: survivors x ceil(|Q| / 64) x 8 bytes of bit rows (10^6 hashes against 10^4
+ *                       survivors: 1.25 GB) plus 16 bytes per candidate; where that does not fit the call returns MVS_E_NOMEM
+ *                       and mvs_last_error names the byte count.
+ * mvs_ctx_gather_stats  the context's last mvs_gather: survivors of the first phase, rounds run (the round that found nothing
+ *                       included), batches (= read-backs), bytes of the bit rows, and the times of the three phases --
+ *                       original overlaps, marking, rounds -- which are 0 unless mvs_ctx_set_timing is on.  Any pointer may
+ *                       be NULL.
+ * mvs_ctx_gather_round_bytes  what the rounds of that call streamed: live rows x ceil(|Q| / 64) x 8 bytes, summed over the
+ *                       rounds (a measurement divides it by rounds_ms).  The kernels are in csrc/mvs_gather.hip. */
+typedef struct {
+    int32_t sample, intersect, unique, remaining;
+} mvs_gather_match;
+int mvs_gather(mvs_ctx* ctx, const mvs_hash_set* hs_query, int64_t query, const mvs_hash_set* hs_db, const int32_t* candidates,
+               int mem_candidates, int64_t n_candidates, int32_t min_hashes, int64_t max_matches, mvs_gather_match* out, int mem_out,
+               int64_t* n_matches, int32_t* query_size);
+int mvs_ctx_gather_stats(const mvs_ctx* ctx, int64_t* survivors, int64_t* rounds, int64_t* batches, int64_t* row_bytes,
+                         double* overlap_ms, double* mark_ms, double* rounds_ms);
+int mvs_ctx_gather_round_bytes(const mvs_ctx* ctx, int64_t* bytes);
 
 /* ---- block plans: one rank's share of the symmetric multi-rank schedule, compared in few launches ----------------
  * The reference shards by rows and lets every shard process compute its rows against ALL columns

@@ -23,6 +23,7 @@ BLOCK_SYMMETRIC, BLOCK_MIRROR_ALL = 1, 2
 
 CELL_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("dot", "<i4"), ("q", "<i4")])
 LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("dot", "<i4"), ("q", "<i4"), ("jaccard", "<f8")])      # mvs_link
+GATHER_DTYPE = np.dtype([("sample", "<i4"), ("intersect", "<i4"), ("unique", "<i4"), ("remaining", "<i4")])  # mvs_gather_match
 
 # every symbol include/mvs_hip.h declares: (name, restype, argtypes)
 _c = ctypes
@@ -167,6 +168,12 @@ SYMBOLS = [
     ("mvs_intersect_cells", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _P, _c.c_int]),
     ("mvs_ctx_intersect_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
                                             _c.POINTER(_c.c_int64)]),
+    ("mvs_gather", _c.c_int, [_P, _P, _c.c_int64, _P, _P, _c.c_int, _c.c_int64, _c.c_int32, _c.c_int64, _P, _c.c_int,
+                               _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32)]),
+    ("mvs_ctx_gather_stats", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
+                                         _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
+                                         _c.POINTER(_c.c_double)]),
+    ("mvs_ctx_gather_round_bytes", _c.c_int, [_P, _c.POINTER(_c.c_int64)]),
     ("mvs_pairwise_dots", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int,
                                       _c.c_int]),
     ("mvs_sketch_set_planes", _c.c_int, [_P, _c.POINTER(_P)]),
@@ -775,6 +782,32 @@ class HashSet(_Handle):
         op, om, ok = _buf(out, np.int32, writable=True) if not _is_torch(out) else _buf(out)
         _check(self.ctx.lib.mvs_hash_set_sizes(self._h, op, om))
         return out
+
+
+class GatherResult:
+    """What Context.gather returns: `matches` (GATHER_DTYPE records in the order the walk found them: sample, intersect =
+    |Q n H|, unique = the hashes this match added, remaining = the query's hashes still unexplained after it), `query_size` =
+    |Q|, `db_sizes` = |H| of every matched sample (int32, one per record).  SearchIndex.gather also sets `query_name` and
+    `names` (the matched samples' names)."""
+
+    def __init__(self, matches, query_size, db_sizes):
+        self.matches, self.query_size, self.db_sizes = matches, int(query_size), db_sizes
+        self.query_name, self.names = None, None
+
+    def __len__(self):
+        return len(self.matches)
+
+    def fractions(self):
+        """-> (f_orig_query, f_match, f_unique_to_query): intersect / |Q|, intersect / |H|, unique / |Q|, float64"""
+        inter = self.matches["intersect"].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (inter / float(self.query_size), inter / self.db_sizes.astype(np.float64),
+                    self.matches["unique"].astype(np.float64) / float(self.query_size))
+
+    @property
+    def explained(self):
+        """hashes of the query that the matches explain: the sum of `unique` = |Q| - the last `remaining`"""
+        return int(self.matches["unique"].sum())
 
 
 COMM_ID_BYTES = 128
@@ -1684,6 +1717,50 @@ class Context:
         ms, u, k, b = _c.c_double(), _c.c_int64(), _c.c_int64(), _c.c_int64()
         _check(self.lib.mvs_ctx_intersect_stats(self._h, ctypes.byref(ms), ctypes.byref(u), ctypes.byref(k), ctypes.byref(b)))
         return {"kernel_ms": ms.value, "units": u.value, "cut_pairs": k.value, "bytes": b.value}
+
+    # ---- gather (include/mvs_hip.h "gather") ----
+    def gather(self, hs_query, query, hs_db, candidates=None, min_hashes=1, max_matches=None):
+        """mvs_gather: the greedy decomposition of sample `query` of hs_query into samples of hs_db -- repeatedly the
+        candidate with the largest overlap with what is left of the query (ties: the smaller sample index), until the best
+        adds fewer than min_hashes hashes or max_matches records exist (None: the number of distinct candidates).
+        candidates: sample indices of hs_db (int32 numpy array / sequence, or a torch device tensor; None: every sample;
+        order and duplicates do not matter).  -> GatherResult."""
+        cp, cm, ck, n_cand = None, MEM_HOST, None, 0
+        if candidates is not None:
+            if not _is_torch(candidates):
+                candidates = np.asarray(candidates, dtype=np.int32).reshape(-1)
+            elif str(candidates.dtype) != "torch.int32" or candidates.dim() != 1:
+                raise ValueError("candidates must be a one-dimensional int32 tensor")
+            n_cand = int(candidates.shape[0])
+            if n_cand == 0:                                            # an empty list is not "every sample": a non-NULL pointer
+                candidates = np.zeros(1, dtype=np.int32)
+            cp, cm, ck = _buf(candidates) if _is_torch(candidates) else _buf(candidates, np.int32)
+        if max_matches is None:
+            if candidates is None:
+                max_matches = hs_db.n
+            else:
+                max_matches = len(np.unique(ck.cpu().numpy() if _is_torch(ck) else ck)) if n_cand else 0
+        out = np.empty(max(int(max_matches), 1), dtype=GATHER_DTYPE)
+        count, q_size = _c.c_int64(), _c.c_int32()
+        _check(self.lib.mvs_gather(self._h, hs_query._h, int(query), hs_db._h, cp, cm, n_cand, int(min_hashes), int(max_matches),
+                                   out.ctypes.data, MEM_HOST, ctypes.byref(count), ctypes.byref(q_size)))
+        matches = out[:count.value].copy()
+        sizes = hs_db.sizes()[matches["sample"]] if count.value else np.empty(0, dtype=np.int32)
+        return GatherResult(matches, q_size.value, sizes)
+
+    def gather_stats(self):
+        """-> dict of this context's last gather: survivors (candidates at min_hashes or above before the walk), rounds,
+        batches (read-backs of the walk's state), row_bytes (the survivors' bit rows), round_bytes (live rows x row size summed
+        over the rounds: what the round passes streamed), overlap_ms / mark_ms / rounds_ms
+        (kernel times of the three phases, timing on)"""
+        s, r, b, rb = _c.c_int64(), _c.c_int64(), _c.c_int64(), _c.c_int64()
+        o, m, t = _c.c_double(), _c.c_double(), _c.c_double()
+        _check(self.lib.mvs_ctx_gather_stats(self._h, ctypes.byref(s), ctypes.byref(r), ctypes.byref(b), ctypes.byref(rb),
+                                             ctypes.byref(o), ctypes.byref(m), ctypes.byref(t)))
+        streamed = _c.c_int64()
+        _check(self.lib.mvs_ctx_gather_round_bytes(self._h, ctypes.byref(streamed)))
+        return {"survivors": s.value, "rounds": r.value, "batches": b.value, "row_bytes": rb.value, "overlap_ms": o.value,
+                "mark_ms": m.value, "rounds_ms": t.value, "round_bytes": streamed.value}
 
     def pairwise_dots(self, sset, r0, r1, c0, c1, algo=0, out=None):
         if out is None:

@@ -1,0 +1,189 @@
+// gather_sketches -- which samples of a hash file make up each query, and how much of the query each explains that the ones
+// before it did not: the greedy minimum-set-cover walk (the rule of sourmash `gather`) on the exact hash lists, on the MI355X
+// (mvs_gather, include/mvs_hip.h "gather").  The reference has no such tool: its search (src/jaccard.py) ranks pairs, and ten
+// strains that all contain the same third of a query are reported ten times there.
+//
+//   gather_sketches --hashes <file> --query <file> --output <gather.tsv> [--min_hashes <k>] [--max_matches <r>]
+//                   [--report <file>] [--device <i>] [--help]
+//
+// --hashes is read the way `project_everything sketch` and verify_pairs read a hash file (its <file>.csr cache when valid, else
+// the text); --query holds one "name: hashes" record per line, the format of the search.  All queries go into one hash set, one
+// mvs_gather per query against every sample of --hashes.  The walk stops at the first sample that would add fewer than
+// --min_hashes hashes (default 50: sourmash's 50 kbp threshold at scaled = 1000) or after --max_matches records (default: no
+// bound).  The output is tab-separated with a header line, written under <gather.tsv>.part and renamed when complete, one line
+// per match in the order the walk found them (a query without matches writes no line):
+//   query  rank  match  intersect  unique  f_orig_query  f_match  f_unique_to_query  remaining
+// rank counts from 0; intersect = |Q n H|, unique = the hashes this match added, remaining = the query's hashes still
+// unexplained after it; f_orig_query = intersect / |Q|, f_match = intersect / |H|, f_unique_to_query = unique / |Q|, fp64 as
+// %.9g.  --report writes one line per query: its size, matches, the hashes explained and their fraction, the survivors of the
+// first phase, the rounds, and the kernel times of the three phases.
+// Exit codes: 1 bad arguments or files, 2 device errors.  One GPU (--device, else MVS_DEVICE, else 0).
+#include "mvs_host.hpp"
+#include "mvs_tool.hpp"
+
+using namespace mvs_host;
+
+namespace {
+
+constexpr const char* kProg = "gather_sketches";
+
+struct Options {
+    std::string hash_file, query_file, output, report, bad_flag;
+    long min_hashes = 50, max_matches = -1;
+    int device = -1;
+    bool show_help = false, have_hashes = false, have_query = false, have_out = false, unknown = false;
+};
+
+void print_usage(const char* argv0) {
+    std::cout << "Usage:\n"
+              << "        " << argv0
+              << " --hashes <file> --query <file> --output <file> [--min_hashes <int >= 1>] [--max_matches <int >= 0>]"
+                 " [--report <file>] [--device <int>] [--help]\n"
+              << "        --min_hashes: a match must add at least this many of the query's hashes; default 50"
+                 " (sourmash gather's 50 kbp threshold at scaled = 1000)"
+              << std::endl;
+}
+
+// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
+void parse(int argc, char* argv[], Options& o) {
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        const bool has_value = i + 1 < argc;
+        auto bad = [&](const char* flag) {
+            if (o.bad_flag.empty()) o.bad_flag = flag;
+        };
+        if (a == "--help") {
+            o.show_help = true;
+        } else if (a == "--output" || a == "--report") {
+            if (!has_value) {
+                o.unknown = true;
+                continue;
+            }
+            (a == "--output" ? o.output : o.report) = argv[++i];
+            if (a == "--output") o.have_out = true;
+        } else if (a == "--hashes" || a == "--query") {
+            const bool h = a == "--hashes";
+            (h ? o.have_hashes : o.have_query) = true;
+            const std::string v = has_value ? argv[++i] : "";
+            if (v.empty()) bad(h ? "--hashes" : "--query");
+            else (h ? o.hash_file : o.query_file) = v;
+        } else if (a == "--min_hashes") {
+            long k = 0;
+            if (!parse_integer(has_value ? argv[++i] : "", &k) || k < 1 || k > 0x7fffffffL) bad("--min_hashes");
+            else o.min_hashes = k;
+        } else if (a == "--max_matches") {
+            long r = 0;
+            if (!parse_integer(has_value ? argv[++i] : "", &r) || r < 0 || r > 0x7fffffffL) bad("--max_matches");
+            else o.max_matches = r;
+        } else if (a == "--device") {
+            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
+        } else {
+            o.unknown = true;
+        }
+    }
+}
+
+struct Gpu {
+    mvs_ctx* ctx = nullptr;
+    mvs_hash_set* hs_db = nullptr;
+    mvs_hash_set* hs_q = nullptr;
+    ~Gpu() {
+        if (hs_q) mvs_hash_set_destroy(hs_q);
+        if (hs_db) mvs_hash_set_destroy(hs_db);
+        if (ctx) mvs_ctx_destroy(ctx);
+    }
+};
+
+// a hash file: its .csr cache when `cached` and valid, else the text; 0, or 1 after a message on stderr
+int load_hashes(const std::string& file, bool cached, HashSets& sets) {
+    bool parsed = cached && load_csr_cache(file, sets);
+    if (!parsed) {
+        try {
+            parsed = read_hash_file(file, true, sets);
+        } catch (const std::exception& e) {
+            std::cerr << kProg << ": reading " << file << ": " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if (!parsed) {
+        std::cerr << "Error opening " << file << " for reading." << std::endl;
+        return 1;
+    }
+    return 0;
+}
+
+std::string ratio9(double num, double den) { return den == 0.0 ? "nan" : fmt9(num / den); }
+
+}  // namespace
+
+int main(int argc, char* argv[]) {
+    Options o;
+    parse(argc, argv, o);
+    if (o.show_help) {
+        print_usage(argv[0]);
+        return 0;
+    }
+    if (!o.have_hashes && o.bad_flag.empty()) o.bad_flag = "--hashes";
+    if (!o.have_query && o.bad_flag.empty()) o.bad_flag = "--query";
+    if (!o.bad_flag.empty()) {
+        if (o.bad_flag == "--hashes") std::cerr << kProg << ": --hashes takes the hash file of the samples to gather from" << std::endl;
+        else if (o.bad_flag == "--query") std::cerr << kProg << ": --query takes a file of 'name: hashes' lines" << std::endl;
+        else if (o.bad_flag == "--min_hashes") std::cerr << kProg << ": --min_hashes takes an integer >= 1" << std::endl;
+        else if (o.bad_flag == "--max_matches") std::cerr << kProg << ": --max_matches takes an integer >= 0" << std::endl;
+        else std::cerr << kProg << ": --device takes a device index" << std::endl;
+        return 1;
+    }
+    if (o.unknown || !o.have_out) {
+        print_usage(argv[0]);
+        return 1;
+    }
+    HashSets db, queries;
+    if (const int rc = load_hashes(o.hash_file, true, db)) return rc;
+    if (const int rc = load_hashes(o.query_file, false, queries)) return rc;
+    const int64_t n = (int64_t)db.names.size(), nq = (int64_t)queries.names.size();
+
+    std::string text = "query\trank\tmatch\tintersect\tunique\tf_orig_query\tf_match\tf_unique_to_query\tremaining\n";
+    std::string rep = "query\tsize\tmatches\texplained\tf_explained\tsurvivors\trounds\toverlap_ms\tmark_ms\trounds_ms\n";
+    int64_t written = 0;
+    if (nq > 0) {
+        Gpu g;
+        if (mvs_ctx_create(choose_device(o.device), &g.ctx) != MVS_OK) return gpu_fail(kProg, "creating context");
+        mvs_ctx_set_timing(g.ctx, 1);
+        if (mvs_hash_set_create(g.ctx, db.hashes.data(), MVS_MEM_HOST, db.offsets.data(), n, &g.hs_db) != MVS_OK ||
+            mvs_hash_set_create(g.ctx, queries.hashes.data(), MVS_MEM_HOST, queries.offsets.data(), nq, &g.hs_q) != MVS_OK)
+            return gpu_fail(kProg, "uploading the hash lists");
+        std::vector<int32_t> sizes((size_t)n);
+        if (mvs_hash_set_sizes(g.hs_db, sizes.data(), MVS_MEM_HOST) != MVS_OK) return gpu_fail(kProg, "reading the set sizes");
+        const int64_t room = o.max_matches < 0 ? n : std::min<int64_t>(o.max_matches, n);
+        std::vector<mvs_gather_match> matches((size_t)std::max<int64_t>(room, 1));
+        for (int64_t q = 0; q < nq; ++q) {
+            int64_t count = 0;
+            int32_t q_size = 0;
+            if (mvs_gather(g.ctx, g.hs_q, q, g.hs_db, nullptr, MVS_MEM_HOST, 0, (int32_t)o.min_hashes, room, matches.data(), MVS_MEM_HOST,
+                           &count, &q_size) != MVS_OK)
+                return gpu_fail(kProg, "gathering");
+            int64_t explained = 0;
+            for (int64_t r = 0; r < count; ++r) {
+                const mvs_gather_match& m = matches[(size_t)r];
+                explained += m.unique;
+                text += queries.names[(size_t)q] + '\t' + std::to_string(r) + '\t' + db.names[(size_t)m.sample] + '\t' +
+                        std::to_string(m.intersect) + '\t' + std::to_string(m.unique) + '\t' + ratio9(m.intersect, q_size) + '\t' +
+                        ratio9(m.intersect, sizes[(size_t)m.sample]) + '\t' + ratio9(m.unique, q_size) + '\t' +
+                        std::to_string(m.remaining) + '\n';
+            }
+            written += count;
+            int64_t survivors = 0, rounds = 0;
+            double overlap_ms = 0.0, mark_ms = 0.0, rounds_ms = 0.0;
+            mvs_ctx_gather_stats(g.ctx, &survivors, &rounds, nullptr, nullptr, &overlap_ms, &mark_ms, &rounds_ms);
+            rep += queries.names[(size_t)q] + '\t' + std::to_string(q_size) + '\t' + std::to_string(count) + '\t' +
+                   std::to_string(explained) + '\t' + ratio9((double)explained, q_size) + '\t' + std::to_string(survivors) + '\t' +
+                   std::to_string(rounds) + '\t' + fmt9(overlap_ms) + '\t' + fmt9(mark_ms) + '\t' + fmt9(rounds_ms) + '\n';
+        }
+    }
+    if (const int rc = write_then_rename(kProg, o.output, text)) return rc;
+    if (!o.report.empty())
+        if (const int rc = write_then_rename(kProg, o.report, rep)) return rc;
+    std::cout << "Gathered " << nq << " queries from " << n << " samples at min_hashes " << o.min_hashes << ": " << written
+              << " matches written" << std::endl;
+    return 0;
+}

@@ -209,6 +209,7 @@ const OptionSpec kOptions[] = {
     {"cluster_cells", &mvs::Options::cluster_cells, nullptr, 0, 1 << 30},
     {"cluster_block_rows", &mvs::Options::cluster_block_rows, nullptr, 0, 1 << 30},
     {"intersect_unit", &mvs::Options::intersect_unit, nullptr, 64, 1 << 30},
+    {"gather_batch", &mvs::Options::gather_batch, nullptr, 1, 1024},
     {"pairwise_block_cells", nullptr, &mvs::Options::pairwise_block_cells, 1, (1LL << 62)},
 };
 

@@ -185,6 +185,20 @@ struct mvs_ctx {
     void* ix_work = nullptr;    size_t ix_work_bytes = 0;
     double ix_kernel_ms = 0.0;
     long long ix_units = 0, ix_cut = 0, ix_bytes = 0;
+    // what the last mvs_gather did (mvs_ctx_gather_stats): survivors of phase 0, rounds run, batches (= read-backs of the
+    // walk's state), bytes of the bit rows; kernel times of the three phases (timing enabled)
+    long long ga_survivors = 0, ga_rounds = 0, ga_batches = 0, ga_row_bytes = 0, ga_round_bytes = 0;
+    double ga_overlap_ms = 0.0, ga_mark_ms = 0.0, ga_rounds_ms = 0.0;
+};
+
+// hash lists resident on the device (mvs_capi_intersect.hip builds them; mvs_capi_gather.hip reads them too)
+struct mvs_hash_set {
+    mvs_ctx* ctx = nullptr;
+    int64_t n = 0, total = 0;
+    int was_sorted = 0;
+    unsigned long long* hashes = nullptr;   // per sample strictly increasing
+    long long* offsets = nullptr;           // n + 1
+    int32_t* sizes = nullptr;               // n
 };
 
 struct mvs_sketch_set {

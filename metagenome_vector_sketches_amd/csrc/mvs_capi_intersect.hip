@@ -8,15 +8,6 @@
 
 using namespace mvs_capi;
 
-struct mvs_hash_set {
-    mvs_ctx* ctx = nullptr;
-    int64_t n = 0, total = 0;
-    int was_sorted = 0;
-    unsigned long long* hashes = nullptr;   // per sample strictly increasing
-    long long* offsets = nullptr;           // n + 1
-    int32_t* sizes = nullptr;               // n
-};
-
 namespace {
 
 constexpr int64_t kSortBatch = 1LL << 30;   // keys per segmented sort (rocprim counts them in 32 bits; a sample holds < 2^31)

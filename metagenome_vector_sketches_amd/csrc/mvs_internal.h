@@ -126,6 +126,7 @@ struct Options {
                                     // device memory (never more than the block can produce); tests lower it
     int cluster_block_rows = 0;     // mvs_pairwise_cluster: > 0 = upper bound on the rows of a block (tests); 0 = by pairwise_block_cells
     int intersect_unit = 2048;      // mvs_intersect_cells: elements of a pair's shorter hash list that one unit of work (one wave) covers
+    int gather_batch = 16;          // mvs_gather: rounds queued between two read-backs of the walk's state, 1 .. 1024
     double pairwise_block_cells = 1099511627776.0;   // row-chunk bound of mvs_pairwise_rows (2^40 cells)
 };
 
@@ -483,6 +484,27 @@ int launch_isect_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_ce
                        const unsigned long long* d_hash_r, const long long* d_off_r, const int32_t* d_size_r,
                        const unsigned long long* d_hash_c, const long long* d_off_c, const int32_t* d_size_c, int unit,
                        int32_t* d_inter);
+// the greedy decomposition of a query (mvs_gather.hip).  The walk's state lives on the device: the best bid of a round
+// ((count << 32) | (2^32 - 1 - survivor), 0 = none; consecutive rounds use alternating slots), the rows read so far, whether the
+// walk has ended, records written, live positions of the query, rounds run.  launch_gather_init: alive = the query's positions,
+// nobody retired, counts zero, a fresh state.  launch_gather_mark: the bit rows of the survivors (d_rows: n_cells x W words,
+// zeroed by the caller) over the units isect_plan laid out for d_cells = (query, survivor's sample) with `unit`, a multiple of
+// 64.  launch_gather_round: one round -- k_gather_count, k_gather_bid, k_gather_pick, all of which return at once when the walk
+// has ended --; parity = the round's number mod 2, counted over everything queued since launch_gather_init.
+struct GatherState {
+    unsigned long long best[2];
+    unsigned long long rows_read;   // live rows counted, summed over the rounds (x W x 8 = the bytes the round passes streamed)
+    int32_t done, n_records, remaining, rounds;
+};
+int launch_gather_init(hipStream_t stream, unsigned long long* d_alive, int64_t W, int32_t q_size, int32_t* d_retired, int32_t* d_count,
+                       int64_t ns, GatherState* d_state);
+int launch_gather_mark(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const long long* d_unit_start, long long n_units,
+                       const unsigned long long* d_hash_q, const long long* d_off_q, const int32_t* d_size_q,
+                       const unsigned long long* d_hash_d, const long long* d_off_d, const int32_t* d_size_d, int unit,
+                       unsigned long long* d_rows, int64_t W);
+int launch_gather_round(hipStream_t stream, const unsigned long long* d_rows, int64_t W, int64_t ns, unsigned long long* d_alive,
+                        int32_t* d_retired, int32_t min_hashes, int32_t* d_count, const int32_t* d_surv_sample,
+                        const int32_t* d_surv_orig, mvs_gather_match* d_rec, int64_t max_matches, GatherState* d_state, int parity);
 // packed cells of the streamed output: radix sort on the (row, col) bits, then CSR arrays (row_ptr over `rows` rows,
 // col, q as 8 bits -- *d_wide set if some q needs 16 -- or as 16 bits when d_q16 is given)
 int sort_packed(hipStream_t stream, unsigned long long* d_in, unsigned long long* d_out, int64_t n, int begin_bit, int end_bit,

@@ -21,6 +21,9 @@ nothing changes.
 Extension: `search ... --containment C [--slack Z]` reports, instead of the samples above -j, the database samples that CONTAIN
 each query: containment estimate (dot/d) / query_norm^2 above C by more than Z standard errors (SearchIndex.search_containment;
 the rule of mvs_pairwise_contain).  Both flags stay out of the usage text, like --hashes_db.
+
+Extension (library only, the command line does not change): `SearchIndex.gather` decomposes each query into the DB samples that
+make it up, greedily on the exact hash lists (Context.gather, the rule of sourmash `gather`); it needs hashes_db.
 """
 import os
 
@@ -170,6 +173,39 @@ class SearchIndex:
         out = []
         for q0 in range(0, len(lists), self.max_queries):
             out += self._contain_lists(lists[q0:q0 + self.max_queries], q0, float(c), float(slack), verbose)
+        return out
+
+    def gather(self, query_file, min_hashes=50, max_matches=None, prefilter=None, slack=0.0):
+        """-> one GatherResult per query (file order; .query_name and .names attached): the greedy decomposition of the query's
+        hash list into the DB's samples (Context.gather, the rule of sourmash `gather`): which samples make up the query, and
+        how many of its hashes each explains that the ones before it did not.  Needs hashes_db.  min_hashes = 50 is sourmash's
+        50 kbp threshold at scaled = 1000.
+        prefilter = c (0 < c < 1) restricts the candidates to the DB samples whose containment IN the query passes the rule of
+        mvs_pairwise_contain on the sketches (Context.pairwise_contain(..., c, slack, "row", 0, n, n, n + nq): rows are the DB,
+        columns the queries).  The walk is then exact over that list ONLY: a sample the estimate misses cannot be reported.
+        Without it every sample is a candidate, and that is cheap already: the walk's first phase retires every sample whose
+        overlap with the query is below min_hashes before anything is allocated for it."""
+        if self.hs is None:
+            raise ValueError("gather needs the DB's hash lists: SearchIndex(..., hashes_db=FILE)")
+        qnames, lists = read_queries(query_file)
+        out = []
+        for q0 in range(0, len(lists), self.max_queries):
+            part = lists[q0:q0 + self.max_queries]
+            cand = [None] * len(part)
+            if prefilter is not None:
+                n, nq = self.n, len(part)
+                qn2, n2 = self._queries_in_set(part)
+                cells = self.ctx.pairwise_contain(self.sset, n2, float(prefilter), float(slack), "row", 0, n, n, n + nq)
+                cand = [cells["row"][cells["col"] == n + qi].astype(np.int32) for qi in range(nq)]
+            offs = np.zeros(len(part) + 1, dtype=np.int64)
+            offs[1:] = np.cumsum([len(x) for x in part])
+            flat = np.concatenate(part) if offs[-1] else np.zeros(0, dtype=np.uint64)
+            with self.ctx.hash_set(flat, offs) as hq:
+                for qi in range(len(part)):
+                    res = self.ctx.gather(hq, qi, self.hs, candidates=cand[qi], min_hashes=min_hashes, max_matches=max_matches)
+                    res.query_name = qnames[q0 + qi]
+                    res.names = [self.names[s] for s in res.matches["sample"]]
+                    out.append(res)
         return out
 
     def _contain_lists(self, lists, q_first, c, slack, verbose):
