@@ -338,6 +338,12 @@ int mvs_sketch_set_info(const mvs_sketch_set* set, int64_t* n, int* d, int* limb
  * has rewritten the planes (data derived from them is rebuilt on the next comparison). */
 int mvs_sketch_set_planes(mvs_sketch_set* set, int8_t** planes);
 int mvs_sketch_set_touch(mvs_sketch_set* set);
+/* How often the context has derived data from a set's limb planes since it was created (cumulative, read-only): whole
+ * builds of the coarse plane, of its fragment-major copy and of the fragment-major copy of the limb planes, and the rows
+ * (widened to groups of 16) that were re-derived in place after mvs_sketch_set_fill rewrote a small part of a set.  Any
+ * pointer may be NULL. */
+int mvs_ctx_derived_stats(mvs_ctx* ctx, int64_t* coarse_builds, int64_t* coarse_rows_refreshed,
+                          int64_t* coarse_fm_builds, int64_t* planes_fm_builds, int64_t* planes_fm_rows_refreshed);
 int mvs_sketch_set_destroy(mvs_sketch_set* set);
 
 /* All-vs-all for the row range [row_begin, row_end) against ALL n columns -- one shard of

@@ -72,6 +72,7 @@ SYMBOLS = [
                                      _c.POINTER(_c.c_int64)]),
     ("mvs_ctx_project_stats", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int),
                                           _c.POINTER(_c.c_int)]),
+    ("mvs_ctx_derived_stats", _c.c_int, [_P] + [_c.POINTER(_c.c_int64)] * 5),
     ("mvs_sketch_sumsq", _c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_int]),
     ("mvs_sketch_stats", _c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_int, _c.POINTER(_c.c_int64)]),
     ("mvs_norms_sq_text", _c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P]),
@@ -983,6 +984,14 @@ class Context:
         a, b, t = _c.c_int64(), _c.c_int64(), _c.c_int64()
         _check(self.lib.mvs_ctx_pairwise_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(t)))
         return a.value, b.value, t.value
+
+    def derived_stats(self):
+        """mvs_ctx_derived_stats: dict of the cumulative counts of whole builds (coarse_builds, coarse_fm_builds,
+        planes_fm_builds) and of rows re-derived in place after a fill (coarse_rows_refreshed, planes_fm_rows_refreshed)"""
+        v = [_c.c_int64() for _ in range(5)]
+        _check(self.lib.mvs_ctx_derived_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("coarse_builds", "coarse_rows_refreshed", "coarse_fm_builds", "planes_fm_builds",
+                         "planes_fm_rows_refreshed"), (x.value for x in v)))
 
     # ---- projection ----
     def project_stats(self):

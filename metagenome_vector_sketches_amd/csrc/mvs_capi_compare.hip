@@ -26,6 +26,7 @@ int refresh_derived(mvs_ctx* c, const mvs_sketch_set* cs) {
             const int64_t valid = std::max<int64_t>(0, std::min<int64_t>(count, s->n - lo));
             mvs::launch_coarse_build(c->stream, s->planes + lo * 2 * dp, valid, count, s->d_pad, (int8_t*)c->pw_coarse + lo * dp,
                                      (mvs::CoarseRow*)c->pw_rows + lo, c->opt.coarse_radix);
+            c->dv_coarse_rows += count;
             int rc = check_kernel("k_coarse_build(rows)");
             if (rc) return rc;
             if (c->coarse_fm_valid) {
@@ -37,6 +38,7 @@ int refresh_derived(mvs_ctx* c, const mvs_sketch_set* cs) {
     }
     if (s->limbs == 2 && c->planes_fm_id == s->id && c->planes_fm_gen == s->gen) {
         mvs::launch_coarse_fm(c->stream, s->planes + lo * 2 * dp, count, s->d_pad, (int8_t*)c->pw_planes_fm + lo * 2 * dp, 2);
+        c->dv_planes_fm_rows += count;
         const int rc = check_kernel("k_coarse_fm(limb planes, rows)");
         if (rc) return rc;
     }
@@ -56,6 +58,7 @@ int prepare_coarse(mvs_ctx* c, const mvs_sketch_set* s) {
     if (rc) return rc;
     mvs::launch_coarse_build(c->stream, s->planes, s->n, s->n_alloc, s->d_pad, (int8_t*)c->pw_coarse,
                              (mvs::CoarseRow*)c->pw_rows, c->opt.coarse_radix);
+    ++c->dv_coarse_builds;
     rc = check_kernel("k_coarse_build");
     if (rc) return rc;
     c->coarse_id = s->id;
@@ -88,6 +91,7 @@ int prepare_coarse_fm(mvs_ctx* c, const mvs_sketch_set* s, bool* made) {
     int rc = ensure_buf(c, &c->pw_coarse_fm, &c->pw_coarse_fm_bytes, (size_t)s->n_alloc * (size_t)s->d_pad);
     if (rc) return rc;
     mvs::launch_coarse_fm(c->stream, (const int8_t*)c->pw_coarse, s->n_alloc, s->d_pad, (int8_t*)c->pw_coarse_fm);
+    ++c->dv_coarse_fm_builds;
     rc = check_kernel("k_coarse_fm");
     if (rc) return rc;
     c->coarse_fm_valid = true;
@@ -107,6 +111,7 @@ int attach_planes_fm(mvs_ctx* c, const mvs_sketch_set* s, mvs::PairwiseArgs& a, 
         int rc = ensure_buf(c, &c->pw_planes_fm, &c->pw_planes_fm_bytes, (size_t)s->n_alloc * 2 * (size_t)s->d_pad);
         if (rc) return rc;
         mvs::launch_coarse_fm(c->stream, s->planes, s->n_alloc, s->d_pad, (int8_t*)c->pw_planes_fm, 2);
+        ++c->dv_planes_fm_builds;
         rc = check_kernel("k_coarse_fm(limb planes)");
         if (rc) return rc;
         c->planes_fm_id = s->id;

@@ -129,6 +129,9 @@ struct mvs_ctx {
     void* pw_cent = nullptr;    size_t pw_cent_bytes = 0;
     unsigned long long coarse_id = 0, coarse_gen = 0;
     int coarse_mode = -1;                   // radix rule (option coarse_radix) the cached plane was built with
+    // derived data built / refreshed since the context was created (mvs_ctx_derived_stats): whole builds of the coarse plane,
+    // of its fragment-major copy and of the fragment-major limb planes, and the rows refresh_derived() re-derived in place
+    long long dv_coarse_builds = 0, dv_coarse_rows = 0, dv_coarse_fm_builds = 0, dv_planes_fm_builds = 0, dv_planes_fm_rows = 0;
     unsigned long long few_rows_id = 0, few_rows_gen = 0;   // the set whose last comparison was a block of < 1024 rows done by the
                                                             // exact kernel because no coarse plane existed (pairwise_launch)
     unsigned long long filter_off_id = 0;   // (set, coefficient) for which the filter passed too many pairs

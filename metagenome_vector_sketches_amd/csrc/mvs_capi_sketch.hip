@@ -760,6 +760,9 @@ int mvs_sketch_set_fill(mvs_sketch_set* s, const void* sketches, int elem_bytes,
     if (row_offset < 0 || n_rows < 0 || row_offset + n_rows > s->n)
         return fail(MVS_E_INVALID, "rows [%lld,%lld) outside the set", (long long)row_offset,
                     (long long)(row_offset + n_rows));
+    // (what mvs_limb_split would refuse is refused before the rows are noted: a refused call rewrites nothing)
+    if ((elem_bytes != 4 && elem_bytes != 2) || !mem_ok(mem)) return fail(MVS_E_INVALID, "bad argument");
+    if (n_rows > 0 && !sketches) return fail(MVS_E_INVALID, "sketches is NULL");
     if (n_rows > 0) note_rows_rewritten(s, row_offset, row_offset + n_rows);
     return mvs_limb_split(s->ctx, sketches, elem_bytes, mem, n_rows, s->d, s->limbs, s->owned, s->d_pad, row_offset);
 }
@@ -823,6 +826,17 @@ int mvs_sketch_set_touch(mvs_sketch_set* s) {
     if (!s) return fail(MVS_E_INVALID, "set is NULL");
     ++s->gen;
     s->dirty_lo = s->dirty_hi = 0;
+    return MVS_OK;
+}
+
+int mvs_ctx_derived_stats(mvs_ctx* c, int64_t* coarse_builds, int64_t* coarse_rows_refreshed, int64_t* coarse_fm_builds,
+                          int64_t* planes_fm_builds, int64_t* planes_fm_rows_refreshed) {
+    if (!c) return fail(MVS_E_INVALID, "ctx is NULL");
+    if (coarse_builds) *coarse_builds = c->dv_coarse_builds;
+    if (coarse_rows_refreshed) *coarse_rows_refreshed = c->dv_coarse_rows;
+    if (coarse_fm_builds) *coarse_fm_builds = c->dv_coarse_fm_builds;
+    if (planes_fm_builds) *planes_fm_builds = c->dv_planes_fm_builds;
+    if (planes_fm_rows_refreshed) *planes_fm_rows_refreshed = c->dv_planes_fm_rows;
     return MVS_OK;
 }
 
