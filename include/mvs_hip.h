@@ -37,6 +37,7 @@ extern "C" {
 #define MVS_E_NOMEM      4   /* host or device allocation failed */
 #define MVS_E_RANGE      5   /* input outside the supported numeric range */
 #define MVS_E_ABORTED    6   /* a caller's callback asked to stop */
+#define MVS_E_INTERNAL   7   /* an invariant of the library's own results does not hold; nothing was rounded or guessed */
 
 #define MVS_MEM_HOST     0
 #define MVS_MEM_DEVICE   1
@@ -144,6 +145,9 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *                         the rows of a block (0: by the device budget)
  *   pcoa_dots, pcoa_block_rows
  *                         mvs_jaccard_apply / mvs_pcoa_*: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0
+ *                         bounds the rows of a block (0: by the device budget)
+ *   groups_dots, groups_block_rows
+ *                         mvs_group_sums / mvs_permanova: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0
  *                         bounds the rows of a block (0: by the device budget)
  *   gram_slab_rows        mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536 (default
  *                         65536; rounded down to a multiple of 64)
@@ -1106,6 +1110,83 @@ int mvs_pcoa_transform(mvs_ctx* ctx, const mvs_pcoa* pcoa, const mvs_sketch_set*
 int mvs_pcoa_destroy(mvs_pcoa* pcoa);
 int mvs_ctx_pcoa_stats(const mvs_ctx* ctx, double* dots_ms, double* apply_ms, double* eigen_ms, int64_t* passes,
                        int64_t* row_blocks, int64_t* block_rows);
+
+/* ---- PERMANOVA on the Jaccard estimates, matrix-free ---------------------------------------------------
+ * Do labelled groups of samples differ in the geometry of the section above, the distance sqrt(1 - k)?  PERMANOVA (Anderson
+ * 2001; adonis2, scikit-bio's permanova) answers with a pseudo-F from within-group and total sums of squared distances and a
+ * p-value from relabelling the samples.  The n x n matrix it is defined on is never stored: the dense-dots kernels produce a
+ * block of rows, one kernel turns it into fixed-point squared distances, one folds those into per-group sums for MANY
+ * labellings at once -- the matrix is produced once and the permutations ride along.
+ *
+ * The weight of a cell.  k(i,j) is the rule of "principal coordinates" above, word for word (unit diagonal, floor, any norms).
+ * Then, fp64, ONE rounding per line:
+ *     t      = 1.0 - k(i,j)
+ *     w(i,j) = (uint32) rint(t * 1073741824.0)             2^30; 0 on the diagonal, 2^30 for k = 0
+ * w is symmetric bit for bit because k is.  Every sum of w is an INTEGER: sums do not depend on order, blocking or atomics,
+ * and two labellings that induce the same partition get EQUAL statistics -- what a permutation p-value needs, F_perm >= F_obs
+ * must hold for a tie.  The resolution of d^2 is 2^-30 = 9.3e-10, far below the estimator's own error (about 1 / sqrt(d)).
+ *
+ * mvs_group_sums      F = [row_begin, row_end) of a resident set, m = |F|; labels: HOST bytes labels[s * m + (i - row_begin)],
+ *                     `slots` labellings, every value < groups; 1 <= groups <= 255; 1 <= slots <= MVS_MAX_GROUP_SLOTS.
+ *                         sizes[s * groups + g]  = #{i in F : labels[s][i] = g}
+ *                         S[s][g]                = sum over unordered pairs {i, j} of F, i < j, labels[s][i] = labels[s][j] = g, of w(i,j)
+ *                     S is returned as 128-bit integers, sums_hi[s * groups + g] * 2^64 + sums_lo[s * groups + g] (HOST uint64
+ *                     arrays; sums_hi and sizes may be NULL).  Rows go in blocks sized as mvs_pairwise_levels sizes them
+ *                     (options groups_block_rows, groups_dots as pcoa_*); per block one dense-dots launch, the quantising
+ *                     kernel and the summing kernel.  Device memory besides the set: the dots block, slots x m bytes of labels
+ *                     twice (as given and sample-major) and slots x groups accumulators -- never n x n.
+ *                     No sum wraps: a block's partial per (slot, group) is at most block_rows * m * 2^30, so the block rows
+ *                     are clamped to block_rows * m < 2^34 and the blocks are added on the host in 128 bits; m > 2^31 - 1 is
+ *                     refused (MVS_E_INVALID).  The kernels sum over ORDERED pairs and the host halves: an odd ordered-pair
+ *                     sum is a broken invariant and returns MVS_E_INTERNAL.  An empty row range: MVS_OK, zero sums and sizes.
+ *                     MVS_E_INVALID: a label >= groups, groups outside 1 .. 255, slots outside 1 .. MVS_MAX_GROUP_SLOTS,
+ *                     floor outside [0, 1) or NaN, a range outside the set, a NULL buffer that is needed.
+ * mvs_permutation_labels  pure host.  out[(permutations + 1) * m]: slot 0 is `labels`; slot p >= 1 is a Fisher-Yates shuffle
+ *                     of it.  With mix(x): x += 0x9e3779b97f4a7c15; x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9;
+ *                     x = (x ^ (x >> 27)) * 0x94d049bb133111eb; return x ^ (x >> 31)  (uint64 arithmetic, splitmix64):
+ *                         state = mix(seed ^ mix(p))
+ *                         for i = m - 1 down to 1:  r = mix(state) % (i + 1);  state += 0x9e3779b97f4a7c15;  swap(out[i], out[r])
+ *                     (the bias of `%` is at most (i + 1) / 2^64 and accepted).  m >= 0, permutations >= 0.
+ * mvs_permanova_stats pure host: from the sums and sizes of slots = permutations + 2 labellings -- slot 0 observed, slots
+ *                     1 .. permutations relabelled, the LAST slot all zeros (its group 0 holds S_all) -- to the numbers.  All
+ *                     fp64, each line one rounding:
+ *                         term_g     = (double)S_g / (double)n_g            for n_g > 0   (128 bits -> double, to nearest even)
+ *                         ss_within  = (sum of the term_g taken in ASCENDING order of value) * 2^-30
+ *                         ss_total   = ((double)S_all / (double)m) * 2^-30
+ *                         ss_between = ss_total - ss_within
+ *                         F          = (ss_between / (G - 1)) / (ss_within / (m - G))     G = non-empty groups of slot 0
+ *                         R2         = ss_between / ss_total
+ *                         p_value    = (1 + #{p >= 1 : ss_within(p) <= ss_within(0)}) / (permutations + 1)
+ *                     The ascending order makes equal multisets of (S_g, n_g) give equal doubles: swapping the ids of two
+ *                     groups ties.  The p-value compares ss_within, equivalent to F_p >= F_0 because ss_total is shared,
+ *                     which sidesteps ss_within = 0 (there F is +inf or NaN as IEEE gives it).  group_mean_d2[g] (NULL: not
+ *                     wanted) = ((double)S_g / (double)(n_g (n_g - 1) / 2)) * 2^-30 of slot 0, 0 for n_g < 2; perm_f[p - 1]
+ *                     (NULL: not wanted) is the F of slot p.  MVS_E_INVALID: G < 2 or G >= m, sizes of slot 0 that do not add
+ *                     up to m, permutations < 0, groups outside 1 .. 255, a NULL buffer that is needed.
+ * mvs_permanova       generates the labellings (mvs_permutation_labels), appends the all-zero slot, calls mvs_group_sums and
+ *                     mvs_permanova_stats.  labels: m HOST bytes < groups; 0 <= permutations <= MVS_MAX_GROUP_SLOTS - 2 (0 gives
+ *                     p_value = 1).  group_sizes[groups], group_mean_d2[groups], perm_f[permutations]: HOST, any may be NULL.
+ *                     G < 2 or G >= m is refused before any launch.
+ * mvs_ctx_groups_stats  of the context's last mvs_group_sums / mvs_permanova: kernel times of the dots, the quantising and the
+ *                     summing summed over the row blocks (0 unless mvs_ctx_set_timing is on), row blocks, rows per block,
+ *                     slots.  Any pointer may be NULL.
+ * All synchronous.  The kernels are in csrc/mvs_groups.hip. */
+#define MVS_MAX_GROUP_SLOTS 16384
+typedef struct {
+    double f, r2, p_value, ss_total, ss_within, ss_between;
+    int64_t df_between, df_within, samples, groups, permutations;   /* groups: the non-empty ones, G */
+} mvs_permanova_result;
+int mvs_group_sums(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double floor, int64_t row_begin,
+                   int64_t row_end, const uint8_t* labels, int64_t slots, int groups, uint64_t* sums_lo, uint64_t* sums_hi,
+                   int64_t* sizes);
+int mvs_permutation_labels(const uint8_t* labels, int64_t m, int64_t permutations, uint64_t seed, uint8_t* out);
+int mvs_permanova_stats(const uint64_t* sums_lo, const uint64_t* sums_hi, const int64_t* sizes, int64_t permutations, int groups,
+                        int64_t m, mvs_permanova_result* result, double* group_mean_d2, double* perm_f);
+int mvs_permanova(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double floor, int64_t row_begin,
+                  int64_t row_end, const uint8_t* labels, int groups, int64_t permutations, uint64_t seed,
+                  mvs_permanova_result* result, int64_t* group_sizes, double* group_mean_d2, double* perm_f);
+int mvs_ctx_groups_stats(const mvs_ctx* ctx, double* dots_ms, double* quantise_ms, double* sums_ms, int64_t* row_blocks,
+                         int64_t* block_rows, int64_t* slots);
 
 /* ---- multi-GPU exchange ---------------------------------------------------------------------------
  * One process per GPU; shard k of src/pairwise_comp_optimized.cpp:938-940 is rank k.  Where the reference's shard

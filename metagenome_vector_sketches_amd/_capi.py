@@ -13,12 +13,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVS_HIP_LIBRARY: profiling tools point this at the ablation build (make -C csrc ablations); nothing else should
 LIB_PATH = os.environ.get("MVS_HIP_LIBRARY") or os.path.join(_HERE, "libmvs_hip.so")
 
-MVS_OK, MVS_E_INVALID, MVS_E_HIP, MVS_E_CAPACITY, MVS_E_NOMEM, MVS_E_RANGE, MVS_E_ABORTED = 0, 1, 2, 3, 4, 5, 6
+MVS_OK, MVS_E_INVALID, MVS_E_HIP, MVS_E_CAPACITY, MVS_E_NOMEM, MVS_E_RANGE, MVS_E_ABORTED, MVS_E_INTERNAL = 0, 1, 2, 3, 4, 5, 6, 7
 MEM_HOST, MEM_DEVICE = 0, 1
 KEEP_INT32, KEEP_INT16 = 0, 1
 TOPK_EXCLUDE_SELF = 1
 CONTAIN_ROW, CONTAIN_MAX = 0, 1
 LIMBS_K3 = 0x103
+MAX_GROUP_SLOTS = 16384
 BLOCK_SYMMETRIC, BLOCK_MIRROR_ALL = 1, 2
 
 CELL_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("dot", "<i4"), ("q", "<i4")])
@@ -49,6 +50,15 @@ class EncodedRows(ctypes.Structure):
 
 
 ENCODED_ROWS_CB = ctypes.CFUNCTYPE(_c.c_int, _P, _c.POINTER(EncodedRows))
+
+
+class PermanovaResult(ctypes.Structure):
+    """mvs_permanova_result"""
+    _fields_ = [("f", _c.c_double), ("r2", _c.c_double), ("p_value", _c.c_double), ("ss_total", _c.c_double),
+                ("ss_within", _c.c_double), ("ss_between", _c.c_double), ("df_between", _c.c_int64), ("df_within", _c.c_int64),
+                ("samples", _c.c_int64), ("groups", _c.c_int64), ("permutations", _c.c_int64)]
+
+
 SYMBOLS = [
     ("mvs_version", _c.c_char_p, []),
     ("mvs_last_error", _c.c_char_p, []),
@@ -138,6 +148,13 @@ SYMBOLS = [
     ("mvs_pcoa_destroy", _c.c_int, [_P]),
     ("mvs_ctx_pcoa_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                                        _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_group_sums", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _c.c_int64, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _P, _P]),
+    ("mvs_permutation_labels", _c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_uint64, _P]),
+    ("mvs_permanova_stats", _c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int64, _c.POINTER(PermanovaResult), _P, _P]),
+    ("mvs_permanova", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _c.c_int64, _c.c_int64, _P, _c.c_int, _c.c_int64, _c.c_uint64,
+                                  _c.POINTER(PermanovaResult), _P, _P, _P]),
+    ("mvs_ctx_groups_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
+                                         _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     ("mvs_cluster_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_cluster_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
     ("mvs_pairwise_cluster", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
@@ -717,6 +734,44 @@ class Pca(_Handle):
         out = np.empty((rows, self.components), dtype=np.float64)
         _check(self.ctx.lib.mvs_pca_transform(self.ctx._h, self._h, sset._h, int(row_begin), int(row_end), out.ctypes.data, MEM_HOST))
         return out
+
+
+class Permanova:
+    """The result of Context.permanova (mvs_permanova): f, p_value, r2, ss_total, ss_within, ss_between, df_between, df_within,
+    samples, groups (the non-empty ones), permutations; group_sizes int64 and group_mean_d2 float64 per group id (the mean
+    squared distance inside the group, 0 for a singleton); perm_f float64 [permutations], the pseudo-F of every relabelling"""
+
+    def __init__(self, res, group_sizes, group_mean_d2, perm_f):
+        for name, _ in PermanovaResult._fields_:
+            setattr(self, name, getattr(res, name))
+        self.group_sizes, self.group_mean_d2, self.perm_f = group_sizes, group_mean_d2, perm_f
+
+
+def permutation_labels(labels, permutations, seed=0):
+    """mvs_permutation_labels: labels uint8 [m] -> uint8 [permutations + 1, m]; row 0 is `labels`, row p a shuffle of it that is
+    a function of (seed, p) alone.  Needs no device."""
+    lab = np.ascontiguousarray(labels, dtype=np.uint8)
+    if lab.ndim != 1:
+        raise ValueError("labels must be one-dimensional")
+    out = np.zeros((max(0, int(permutations)) + 1, len(lab)), dtype=np.uint8)
+    _check(load_library().mvs_permutation_labels(lab.ctypes.data, len(lab), int(permutations), int(seed) & (2 ** 64 - 1), out.ctypes.data))
+    return out
+
+
+def permanova_stats(sums, sizes, m):
+    """mvs_permanova_stats: sums [permutations + 2, groups] of Python ints and sizes int64 of the same shape, the last slot the
+    all-zero labelling -> Permanova (group_sizes: those of slot 0).  Needs no device."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    slots, groups = sizes.shape
+    flat = [int(v) for v in np.asarray(sums, dtype=object).reshape(-1)]
+    lo = np.array([v & (2 ** 64 - 1) for v in flat], dtype=np.uint64)
+    hi = np.array([v >> 64 for v in flat], dtype=np.uint64)
+    res = PermanovaResult()
+    mean = np.zeros(groups, dtype=np.float64)
+    perm_f = np.zeros(max(0, slots - 2), dtype=np.float64)
+    _check(load_library().mvs_permanova_stats(lo.ctypes.data, hi.ctypes.data, sizes.ctypes.data, slots - 2, groups, int(m), ctypes.byref(res),
+                                              mean.ctypes.data, perm_f.ctypes.data))
+    return Permanova(res, sizes[0].copy(), mean, perm_f)
 
 
 class Pcoa(_Handle):
@@ -1574,6 +1629,55 @@ class Context:
         _check(self.lib.mvs_ctx_pcoa_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n), ctypes.byref(r),
                                            ctypes.byref(k)))
         return {"dots_ms": a.value, "apply_ms": b.value, "eigen_ms": e.value, "passes": n.value, "row_blocks": r.value, "block_rows": k.value}
+
+    # ---- PERMANOVA on the Jaccard estimates (include/mvs_hip.h "PERMANOVA") ----
+    def group_sums(self, sset, norms_sq, labels, groups, rows=None, floor=0.0):
+        """mvs_group_sums: labels uint8 [slots, m] (or [m]), every value < groups, m the size of `rows` = (begin, end) of `sset`
+        (default all) -> (sums, sizes): sums an object array [slots, groups] of Python ints, the within-group sums of the
+        quantised squared distances w over unordered pairs; sizes int64 [slots, groups]."""
+        rb, re = (0, sset.n) if rows is None else rows
+        m = max(0, int(re) - int(rb))
+        lab = np.ascontiguousarray(labels, dtype=np.uint8)
+        if lab.ndim == 1:
+            lab = lab.reshape(1, -1)
+        if lab.ndim != 2 or lab.shape[1] != m:
+            raise ValueError("labels must have one column per row of the range")
+        slots, groups = lab.shape[0], int(groups)
+        np_, nm, nk = _norms(norms_sq)
+        cells = max(0, slots) * max(0, groups)
+        lo, hi = np.zeros(cells, dtype=np.uint64), np.zeros(cells, dtype=np.uint64)
+        sizes = np.zeros(cells, dtype=np.int64)
+        _check(self.lib.mvs_group_sums(self._h, sset._h, np_, nm, float(floor), int(rb), int(re), lab.ctypes.data, slots, groups,
+                                       lo.ctypes.data, hi.ctypes.data, sizes.ctypes.data))
+        sums = np.array([(int(h) << 64) | int(l) for l, h in zip(lo.tolist(), hi.tolist())], dtype=object)
+        return sums.reshape(slots, groups), sizes.reshape(slots, groups)
+
+    def permanova(self, sset, norms_sq, labels, permutations=999, seed=0, rows=None, floor=0.0):
+        """mvs_permanova: labels uint8 [m], one group id per sample of `rows` = (begin, end) of `sset` (default all); the
+        number of group ids is max(labels) + 1 -> Permanova"""
+        rb, re = (0, sset.n) if rows is None else rows
+        m = max(0, int(re) - int(rb))
+        lab = np.ascontiguousarray(labels, dtype=np.uint8)
+        if lab.ndim != 1 or len(lab) != m:
+            raise ValueError("labels must have one entry per row of the range")
+        groups = int(lab.max()) + 1 if m else 1
+        np_, nm, nk = _norms(norms_sq)
+        res = PermanovaResult()
+        sizes = np.zeros(groups, dtype=np.int64)
+        mean = np.zeros(groups, dtype=np.float64)
+        perm_f = np.zeros(max(0, int(permutations)), dtype=np.float64)
+        _check(self.lib.mvs_permanova(self._h, sset._h, np_, nm, float(floor), int(rb), int(re), lab.ctypes.data, groups, int(permutations),
+                                      int(seed) & (2 ** 64 - 1), ctypes.byref(res), sizes.ctypes.data, mean.ctypes.data, perm_f.ctypes.data))
+        return Permanova(res, sizes, mean, perm_f)
+
+    def groups_stats(self):
+        """-> dict of the last group_sums / permanova: dots_ms, quantise_ms, sums_ms (kernel times over its row blocks, timing
+        on), row_blocks, block_rows, slots"""
+        a, b, e = _c.c_double(), _c.c_double(), _c.c_double()
+        n, r, k = _c.c_int64(), _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_groups_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n), ctypes.byref(r),
+                                             ctypes.byref(k)))
+        return {"dots_ms": a.value, "quantise_ms": b.value, "sums_ms": e.value, "row_blocks": n.value, "block_rows": r.value, "slots": k.value}
 
     def _consumer_stats(self, fn, work_key):
         """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time

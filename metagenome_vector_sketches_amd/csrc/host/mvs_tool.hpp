@@ -1,5 +1,5 @@
 // mvs_tool.hpp -- what the tools over a sketch DB share (cluster_sketches, linkage_sketches, dereplicate_sketches, verify_pairs,
-// pca_sketches, pcoa_sketches, gather_sketches, and pairwise_comp_optimized for the loader): opening the DB folder, loading vectors.bin into a sketch set, reporting a
+// pca_sketches, pcoa_sketches, gather_sketches, permanova_sketches, and pairwise_comp_optimized for the loader): opening the DB folder, loading vectors.bin into a sketch set, reporting a
 // device error, writing an output file under <file>.part, the hash file a DB was sketched from, and the parsing of flag values.  Header-only; include it after
 // mvs_host.hpp.  Each tool keeps its own parse() chain, usage text, Gpu holder and output format.
 #ifndef MVS_TOOL_HPP
@@ -183,7 +183,7 @@ inline int load_sketch_db(const char* prog, mvs_ctx* ctx, const SketchDb& db, mv
     return load_sketch_dbs(prog, ctx, {&db}, set);
 }
 
-// ---- what the ordination tools share (pca_sketches, pcoa_sketches) ----
+// ---- what the ordination tools share (pca_sketches, pcoa_sketches; permanova_sketches for the norms and its report) ----
 inline std::string fmt9(double v) {
     char buf[64];
     snprintf(buf, sizeof buf, "%.9g", v);

@@ -204,6 +204,8 @@ const OptionSpec kOptions[] = {
     {"levels_block_rows", &mvs::Options::levels_block_rows, nullptr, 0, 1 << 30},
     {"pcoa_dots", &mvs::Options::pcoa_dots, nullptr, 0, 1},
     {"pcoa_block_rows", &mvs::Options::pcoa_block_rows, nullptr, 0, 1 << 30},
+    {"groups_dots", &mvs::Options::groups_dots, nullptr, 0, 1},
+    {"groups_block_rows", &mvs::Options::groups_block_rows, nullptr, 0, 1 << 30},
     {"gram_slab_rows", &mvs::Options::gram_slab_rows, nullptr, 64, 65536},
     {"gram_variant", &mvs::Options::gram_variant, nullptr, 0, 1},
     {"cluster_cells", &mvs::Options::cluster_cells, nullptr, 0, 1 << 30},

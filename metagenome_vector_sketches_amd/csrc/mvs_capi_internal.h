@@ -44,6 +44,13 @@ struct ConsumerStats {
     long long edges = 0, blocks = 0, rounds = 0;
     void reset() { *this = ConsumerStats(); }
 };
+// what the last mvs_group_sums / mvs_permanova did on a context (mvs_ctx_groups_stats): kernel times summed over the row blocks
+// (timing enabled), row blocks, rows per block, labellings
+struct GroupsStats {
+    double dots_ms = 0.0, quantise_ms = 0.0, sums_ms = 0.0;
+    long long blocks = 0, block_rows = 0, slots = 0;
+    void reset() { *this = GroupsStats(); }
+};
 }  // namespace mvs_capi
 
 struct mvs_ctx {
@@ -183,6 +190,7 @@ struct mvs_ctx {
     // what the clustering, linkage and dereplication calls did since the last mvs_cluster_create / mvs_linkage_create /
     // mvs_derep_create on this context (mvs_ctx_cluster_stats, mvs_ctx_linkage_stats, mvs_ctx_derep_stats)
     mvs_capi::ConsumerStats cl, lk, dr;
+    mvs_capi::GroupsStats gs;
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
     // did (mvs_ctx_intersect_stats)
     void* ix_work = nullptr;    size_t ix_work_bytes = 0;

@@ -118,6 +118,9 @@ struct Options {
     int pcoa_dots = 0;              // mvs_jaccard_apply / mvs_pcoa_*: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU
                                     // kernel (A/B, tests); same result
     int pcoa_block_rows = 0;        // mvs_jaccard_apply / mvs_pcoa_*: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
+    int groups_dots = 0;            // mvs_group_sums / mvs_permanova: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU
+                                    // kernel (A/B, tests); same sums
+    int groups_block_rows = 0;      // mvs_group_sums / mvs_permanova: > 0 = upper bound on the rows of a block (tests); 0 = by the device budget
     int gram_slab_rows = 65536;     // mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536
                                     // (rounded down to a multiple of 64; tests lower it to force several slabs)
     int gram_variant = 0;           // k_gram_tiles: 0 = by shape (128 x 128 tiles for one or two limbs and d >= 128, else 64 x 64),
@@ -338,6 +341,16 @@ int64_t apply_padded_cols(int64_t cols);
 int apply_padded_b(int b);
 int launch_jaccard_apply(hipStream_t stream, const int32_t* d_dots, int64_t rows, int64_t ld, int64_t row0, int64_t c0,
                          const double* d_norms_sq, int d, double floor_, const double* d_Xp, int b, double* d_Y);
+// within-group sums of quantised squared distances for many labellings at once (mvs_groups.hip; the rule is stated there and in
+// include/mvs_hip.h).  quantise: a block of dense dots becomes uint32 weights in place.  transpose: labels (slots x m bytes) ->
+// d_packed, m x group_label_quads(slots) dwords.  sums: the block's ORDERED-pair sums are added to d_acc (slots x groups);
+// rows x ld must stay below 2^34 (MVS_E_INVALID otherwise) and the caller clears d_acc between blocks
+int64_t group_label_quads(int64_t slots);
+int launch_dist_quantise(hipStream_t stream, int32_t* d_cells, int64_t rows, int64_t ld, int64_t row0, int64_t c0, const double* d_norms_sq,
+                         int d, double floor_);
+int launch_labels_transpose(hipStream_t stream, const uint8_t* d_labels, int64_t slots, int64_t m, uint32_t* d_packed);
+int launch_group_sums(hipStream_t stream, const uint32_t* d_w, int64_t rows, int64_t ld, int64_t f0, const uint32_t* d_packed, int64_t slots,
+                      int groups, unsigned long long* d_acc);
 // single-linkage clustering over device cell lists (mvs_cluster.hip): union-find rounds over parent[n] -- d_counters: [0] cells
 // with row != col, [1] cells with an index outside [0, n), [2] cells whose endpoints still have different roots -- and the
 // finish passes (cluster ids by ascending root, sizes, representatives)
