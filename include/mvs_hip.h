@@ -432,6 +432,15 @@ int mvs_pairwise_stream_encoded(mvs_ctx* ctx, const mvs_sketch_set* set, const d
 int mvs_ctx_stream_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* bytes_out, int64_t* row_blocks, int64_t* pieces,
                          int* two_stage);
 
+/* Which route the row blocks of the most recent stream call took (counters only): blocks delivered out of the dense byte
+ * matrix (dense_blocks); of the encoded ones, those whose row passes were queued with buffers sized from the blocks before
+ * them (spec_blocks, option stream_spec) and, among these, the ones whose sizes did not hold, so that the block was done
+ * again with its own counts read back first (spec_redone); dense blocks that held a q a byte cannot store -- 0, or beyond
+ * 255 -- after which that block and the rest of the rows went through packed lists (list_fallbacks).  Any pointer may be
+ * NULL. */
+int mvs_ctx_stream_dense_stats(const mvs_ctx* ctx, int64_t* dense_blocks, int64_t* spec_blocks, int64_t* spec_redone,
+                               int64_t* list_fallbacks);
+
 /* One rectangular block of the comparison -- rows [row_begin,row_end) x columns [col_begin,col_end) -- for
  * schedules that split a shard's work by column block (metagenome_vector_sketches_amd/parallel.py: with G
  * shards every unordered pair of row blocks is compared ONCE and the mirrored cells are exchanged).

@@ -110,6 +110,7 @@ SYMBOLS = [
                                                 ENCODED_ROWS_CB, _P, _c.POINTER(_c.c_int64)]),
     ("mvs_ctx_stream_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
                                          _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int)]),
+    ("mvs_ctx_stream_dense_stats", _c.c_int, [_P] + [_c.POINTER(_c.c_int64)] * 4),
     ("mvs_pairwise_block", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int,
                                        _P, _c.c_int64, _c.POINTER(_c.c_int64)]),
     ("mvs_cells_sort", _c.c_int, [_P, _P, _c.c_int64, _P]),
@@ -1291,6 +1292,15 @@ class Context:
         _check(self.lib.mvs_ctx_stream_stats(self._h, ctypes.byref(k), ctypes.byref(b), ctypes.byref(r), ctypes.byref(p_),
                                              ctypes.byref(t)))
         return {"kernel_ms": k.value, "bytes": b.value, "row_blocks": r.value, "pieces": p_.value, "two_stage": int(t.value)}
+
+    def stream_dense_stats(self):
+        """mvs_ctx_stream_dense_stats: the route the last stream call's row blocks took -- dict(dense_blocks: delivered out
+        of the dense byte matrix, spec_blocks: row passes queued with buffers sized from the blocks before, spec_redone: of
+        those, done again because the sizes did not hold, list_fallbacks: dense blocks with a q a byte cannot hold, after
+        which the rows went through packed lists)"""
+        v = [_c.c_int64() for _ in range(4)]
+        _check(self.lib.mvs_ctx_stream_dense_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("dense_blocks", "spec_blocks", "spec_redone", "list_fallbacks"), (x.value for x in v)))
 
     def pairwise_block(self, sset, norms_sq, row_begin, row_end, col_begin, col_end, flags, cells, n_cells,
                        keep_mode=KEEP_INT32):

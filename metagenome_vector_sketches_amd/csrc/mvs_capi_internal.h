@@ -123,6 +123,10 @@ struct mvs_ctx {
     // what the last mvs_pairwise_stream did (mvs_ctx_stream_stats)
     double st_kernel_ms = 0.0;                    // comparison kernels, summed over the row blocks (timing enabled)
     long long st_bytes = 0, st_blocks = 0, st_pieces = 0, st_two_stage = 0;
+    // ... and the route its row blocks took (mvs_ctx_stream_dense_stats): delivered out of the dense byte matrix, row passes
+    // queued with buffers sized from the blocks before, of those the ones whose sizes did not hold (done again), dense
+    // blocks with a q a byte cannot hold (that block and the rest became lists)
+    long long st_dense_blocks = 0, st_spec_blocks = 0, st_spec_redone = 0, st_list_fallbacks = 0;
     // tile-granular two-stage comparison: tile flags, flagged tiles per tile row, their row-major list (entry 0 = total),
     // the candidate list without the pairs of flagged tiles
     void* pw_tflag = nullptr;   size_t pw_tflag_bytes = 0;

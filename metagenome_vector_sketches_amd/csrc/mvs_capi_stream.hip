@@ -859,6 +859,7 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
     if (rc) return rc;
     c->st_kernel_ms = 0.0;
     c->st_bytes = c->st_blocks = c->st_pieces = c->st_two_stage = 0;
+    c->st_dense_blocks = c->st_spec_blocks = c->st_spec_redone = c->st_list_fallbacks = 0;
     bool tiles_phase = false;   // the launches being timed are runs of flagged tiles (ev[6] .. ev[3]), not whole comparisons
     auto add_kernel_ms = [&]() {
         float ms = 0.0f;
@@ -1299,13 +1300,17 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
                 rc = rows_from_dense_spec(c, rb, re, s->n, whole ? row_begin : rb, ld, (int64_t)k, blk, &odd, ps, active, cap_cells, cap_bytes,
                                           lopt.encode_stage_words, &held);
                 if (rc) return finish(rc);
+                ++c->st_spec_blocks;
+                if (!held) ++c->st_spec_redone;
                 if (!held) blk = BlockCsr();          // the sizes did not hold (or a 16-bit q): the careful way below
             }
             if (!held) rc = csr_from_dense(c, rb, re, s->n, whole ? row_begin : rb, ld, (int64_t)k, blk, &odd, ps, active, ecb != nullptr);
             if (rc) return finish(rc);
             mark("csr", (long)k);
             if (!side) add_kernel_ms();
+            if (!odd) ++c->st_dense_blocks;
             if (odd) {
+                ++c->st_list_fallbacks;
                 if (side) {                 // back to one stream; a launch already queued for block k + 1 is wasted, not wrong
                     (void)hipStreamSynchronize(c->stream);
                     side = false;
@@ -1378,6 +1383,16 @@ int mvs_ctx_stream_stats(const mvs_ctx* c, double* kernel_ms, int64_t* bytes_out
     return MVS_OK;
 }
 
+int mvs_ctx_stream_dense_stats(const mvs_ctx* c, int64_t* dense_blocks, int64_t* spec_blocks, int64_t* spec_redone,
+                               int64_t* list_fallbacks) {
+    if (!c) return fail(MVS_E_INVALID, "ctx is NULL");
+    if (dense_blocks) *dense_blocks = c->st_dense_blocks;
+    if (spec_blocks) *spec_blocks = c->st_spec_blocks;
+    if (spec_redone) *spec_redone = c->st_spec_redone;
+    if (list_fallbacks) *list_fallbacks = c->st_list_fallbacks;
+    return MVS_OK;
+}
+
 
 }  // extern "C"
 
@@ -1396,6 +1411,7 @@ int cells_stream_impl(mvs_ctx* c, const mvs_cell* cells, int64_t n, int64_t rb, 
     if (rc) return rc;
     c->st_kernel_ms = 0.0;
     c->st_bytes = c->st_blocks = c->st_pieces = c->st_two_stage = 0;
+    c->st_dense_blocks = c->st_spec_blocks = c->st_spec_redone = c->st_list_fallbacks = 0;
     const int64_t rows = re - rb;
     const size_t piece_bytes = (size_t)c->opt.stream_piece_mib << 20;
     BlockCsr blk;

@@ -28,6 +28,11 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert b"gfx950" in lib.mvs_version()
 
 
+def test_stream_dense_stats_refuses_a_null_context():
+    lib = _capi.load_library()
+    assert lib.mvs_ctx_stream_dense_stats(None, None, None, None, None) == _capi.MVS_E_INVALID
+
+
 def test_pure_host_helpers_match_reference_formulas():
     # src/pairwise_comp_optimized.cpp:903-906, :938-940
     assert _capi.chunk_size(12, 2048) == 192
