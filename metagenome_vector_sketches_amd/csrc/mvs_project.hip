@@ -19,8 +19,12 @@
 //     2 xors + 2 bitop3 were 4.  Hot loop of the default variant (24): 19.38 VALU per (hash, block)
 //     (tools/check_project_isa.py);
 //   * one wave owns BPW 64-dim blocks of one (sample, hash-chunk) unit; at the end the 64 lanes'
-//     bit-sliced counters are summed by a butterfly of bit-sliced ripple adders (ds_bpermute) and
-//     lane k extracts count_k;
+//     bit-sliced counters are summed by a butterfly of bit-sliced ripple adders.  The default variant (24) does it
+//     inside the VALU (v_permlane*_swap and DPP moves, no LDS) and for its four blocks together: the stages hand
+//     different lanes different blocks, a lane ends with the total of one block's half, extracts four consecutive
+//     counts and writes them with one 16-byte store (reduce_counts_wave4: 10 LV0 + 16 digit additions per wave where
+//     an all-reduce per block did 24 LV0 + 60).  The other variants reduce block by block through ds_bpermute and
+//     lane k extracts count_k (reduce_counts);
 //   * samples are cut into units of <= 65536 hashes so that long samples spread over many
 //     workgroups, and the units that would run past the launch's ideal end into smaller pieces
 //     (mvs_project_plan); units of one sample combine with int32 atomics (order independent => exact).
@@ -351,14 +355,11 @@ __device__ __forceinline__ int32_t reduce_counts(const uint32_t (&lo_in)[kLV], c
     return cnt;
 }
 
-// The same sums without LDS: every cross-lane move is a DPP move or a v_permlane*_swap, all inside the VALU.  Lane k only
-// needs the digits of its own word (lo for k < 32, hi for k >= 32), so the first step adds the two 32-lane halves AND
+// The same sums without LDS (DEEP): every cross-lane move is a DPP move or a v_permlane*_swap, all inside the VALU.  A lane
+// only needs the digits of one word (lo: positions 0-31, hi: 32-63), so the first step adds the two 32-lane halves AND
 // merges lo with hi: v_permlane32_swap(lo, hi) hands lanes 0-31 the pair (lo[k], lo[k + 32]) and lanes 32-63 the pair
-// (hi[k - 32], hi[k]).  From there on one word per digit is reduced instead of two, over the 32 lanes of each half:
-// quad_perm [1,0,3,2] / [2,3,0,1] (pairs within a quad), row_half_mirror (lane i <-> 7 - i: quad 0 <-> quad 1),
-// row_mirror (i <-> 15 - i: half-rows), v_permlane16_swap (rows 0 <-> 1 and 2 <-> 3).  A swap leaves {own, partner}
-// in its two outputs in some order, and the sum of the two is the same either way.  Every lane ends up with its half's
-// total.  6 stages, (LV0 + 1) + ... + (LV0 + 5) digit additions of one word each.
+// (hi[k - 32], hi[k]).  From there on one word per digit is reduced instead of two.  A swap leaves {own, partner} in its two
+// outputs in some order, and the sum of the two is the same either way.
 __device__ __forceinline__ void add_digit(uint32_t& w, uint32_t a, uint32_t b, uint32_t& c) {
     w = xor3(a, b, c);
     c = maj3(a, b, c);
@@ -381,37 +382,82 @@ __device__ __forceinline__ void reduce_stage_dpp(uint32_t (&w)[N]) {
     w[LIVE] = c;
 }
 
+// The four blocks of a BPW = 4 wave reduced TOGETHER.  An all-reduce per block (five more stages over the 32 lanes of a
+// half behind the first) leaves all 32 lanes of a half with the same total, of which each extracts one position: (LV0 + 1)
+// + ... + (LV0 + 5) additions behind the first LV0, per block.  Here every stage that can hands different lanes
+// different blocks, so the words halve as the lanes to add do, and a lane ends with the total of ONE block's half and
+// extracts four positions of it:
+//   stage 0  per block as above: v_permlane32_swap(lo, hi), lanes 0-31 hold the lo word (positions 0-31), 32-63 the hi word;
+//   stage 1  v_permlane16_swap(W_a, W_b) exchanges rows 1, 3 of W_a with rows 0, 2 of W_b: the sum of its two outputs is
+//            block a over both rows of the half in rows 0, 2 and block b in rows 1, 3.  One addition serves two blocks
+//            (a, b) = (0, 1) -> X and (2, 3) -> Y;
+//   stage 2  lanes i and i ^ 1: even lanes keep X and get the neighbour's X, odd lanes keep Y and get the neighbour's Y
+//            (two selects, one DPP move);
+//   stages 3-5  all-reduce over the 8 lanes of a row with the same parity: quad_perm [2,3,0,1], row_ror:4, row_ror:8.
+// Row r = lane >> 4 then holds half r >> 1 of block (r & 1) + 2 * (lane & 1), and lane j = (lane & 15) >> 1 of the eight
+// holders extracts positions 4j .. 4j + 3 of that half into cnt.  Digit additions: 4 LV0 + 2 (LV0 + 1) + (LV0 + 2) + ... +
+// (LV0 + 5) = 10 LV0 + 16 where four all-reduces do 24 LV0 + 60.
+//
+// The extraction takes the lane's four bits of a digit at once: n * 0x00204081 spreads the nibble n over the low bits of
+// four bytes (n, n << 7, n << 14, n << 21 do not overlap), and with the digit's shift inside the constant three
+// instructions per digit (bfe, mul, and_or) build byte-packed counts, eight digits per accumulator.
 template <int LV0>
-__device__ __forceinline__ int32_t reduce_counts_valu(const uint32_t (&lo_in)[kLV], const uint32_t (&hi_in)[kLV],
-                                                      int lane) {
-    static_assert(LV0 >= 1 && LV0 <= kLV, "live digits");
-    constexpr int kOut = LV0 + 6;
-    uint32_t w[kOut];
-    uint32_t c = 0;
+__device__ __forceinline__ void reduce_pair_stage01(const uint32_t (&lo_a)[kLV], const uint32_t (&hi_a)[kLV],
+                                                    const uint32_t (&lo_b)[kLV], const uint32_t (&hi_b)[kLV],
+                                                    uint32_t (&x)[LV0 + 6]) {
+    uint32_t wa[LV0 + 1], wb[LV0 + 1];
+    uint32_t ca = 0, cb = 0;
 #pragma unroll
     for (int l = 0; l < LV0; ++l) {
-        const auto r = __builtin_amdgcn_permlane32_swap(lo_in[l], hi_in[l], false, false);
-        add_digit(w[l], r[0], r[1], c);
+        const auto ra = __builtin_amdgcn_permlane32_swap(lo_a[l], hi_a[l], false, false);
+        add_digit(wa[l], ra[0], ra[1], ca);
+        const auto rb = __builtin_amdgcn_permlane32_swap(lo_b[l], hi_b[l], false, false);
+        add_digit(wb[l], rb[0], rb[1], cb);
     }
-    w[LV0] = c;
+    wa[LV0] = ca;
+    wb[LV0] = cb;
+    uint32_t c = 0;
 #pragma unroll
-    for (int l = LV0 + 1; l < kOut; ++l) w[l] = 0u;
-    reduce_stage_dpp<0xb1, LV0 + 1>(w);     // quad_perm [1,0,3,2]
-    reduce_stage_dpp<0x4e, LV0 + 2>(w);     // quad_perm [2,3,0,1]
-    reduce_stage_dpp<0x141, LV0 + 3>(w);    // row_half_mirror
-    reduce_stage_dpp<0x140, LV0 + 4>(w);    // row_mirror
-    c = 0;
-#pragma unroll
-    for (int l = 0; l < LV0 + 5; ++l) {
-        const auto r = __builtin_amdgcn_permlane16_swap(w[l], w[l], false, false);
-        add_digit(w[l], r[0], r[1], c);
+    for (int l = 0; l < LV0 + 1; ++l) {
+        const auto r = __builtin_amdgcn_permlane16_swap(wa[l], wb[l], false, false);
+        add_digit(x[l], r[0], r[1], c);
     }
-    w[LV0 + 5] = c;
-    int32_t cnt = 0;
-    const int sh = lane & 31;
+    x[LV0 + 1] = c;
+}
+
+template <int LV0>
+__device__ __forceinline__ void reduce_counts_wave4(const Acc<4>& s, int lane, int32_t (&cnt)[4]) {
+    static_assert(LV0 >= 1 && LV0 <= kLV, "live digits");
+    constexpr int kOut = LV0 + 6;
+    uint32_t x[kOut], y[kOut];
+    reduce_pair_stage01<LV0>(s.lo[0], s.hi[0], s.lo[1], s.hi[1], x);
+    reduce_pair_stage01<LV0>(s.lo[2], s.hi[2], s.lo[3], s.hi[3], y);
+    const bool odd = (lane & 1) != 0;
+    uint32_t c = 0;
 #pragma unroll
-    for (int l = 0; l < kOut; ++l) cnt += (int32_t)((w[l] >> sh) & 1u) << l;
-    return cnt;
+    for (int l = 0; l < LV0 + 2; ++l) {
+        const uint32_t send = odd ? x[l] : y[l], keep = odd ? y[l] : x[l];
+        add_digit(x[l], keep, dpp_mov<0xb1>(send), c);   // quad_perm [1,0,3,2]
+    }
+    x[LV0 + 2] = c;
+    reduce_stage_dpp<0x4e, LV0 + 3>(x);     // quad_perm [2,3,0,1]
+    reduce_stage_dpp<0x124, LV0 + 4>(x);    // row_ror:4
+    reduce_stage_dpp<0x128, LV0 + 5>(x);    // row_ror:8
+    const uint32_t sh = ((uint32_t)lane & 14u) << 1;
+    uint32_t v[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int g = 0; g < (kOut + 7) / 8; ++g) {   // digits 8g .. 8g + 7: byte p of acc = those bits of position p's count
+        uint32_t acc = 0u;
+#pragma unroll
+        for (int l = 8 * g; l < 8 * g + 8 && l < kOut; ++l) {
+            const uint32_t n = (x[l] >> sh) & 15u;
+            acc |= (n * (0x00204081u << (l & 7))) & (0x01010101u << (l & 7));
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) v[p] |= ((acc >> (8 * p)) & 0xffu) << (8 * g);
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) cnt[p] = (int32_t)v[p];
 }
 
 // the STATS all-reduce (sum of squares, max |v|) over the wave with the same moves: every lane gets the totals
@@ -456,12 +502,12 @@ __device__ __forceinline__ void wave_sum_max_valu(unsigned long long& ss, uint32
 // digits 7..10) follows once per 128 hashes instead of through 5..10 once per 32, so counting costs ~2.05 bitop3 per
 // input word instead of ~2.45; the level-1 adder that also does the hash's last xor (absorb) adds 0.5 to either figure and
 // takes the v_xor_b32 per input word of that xorshift away.  The branches on the iteration number are wave-uniform.  The
-// epilogue is reduce_counts_valu.
+// epilogue is reduce_counts_wave4, which takes the four blocks of a wave: DEEP exists for BPW = 4 only.
 //
 // Main loop, VALU instructions per (hash, 64-dim block) as compiled (tools/check_project_isa.py): variant 24 19.38,
 // 14 20.04, 12 21.27, 2 21.94, 1 22.12 (20.63 / 21.29 / 22.77 / 22.94 / 23.12 with the xorshift outside the adder and the
 // shared round's 64-bit shift split in two).  The multiplies through mad64 leave these counts as they are and turn two
-// v_add3_u32 per pair into v_add_u32 in variants 24, 2 and 1 (both rounds) and one in 14 and 12 (first round).  246 / 256
+// v_add3_u32 per pair into v_add_u32 in variants 24, 2 and 1 (both rounds) and one in 14 and 12 (first round).  250 / 256
 // VGPRs for BPW 4 (variant 24 / 14: two waves per SIMD), 138 / 137 for BPW 2 (three), 103 for BPW 1 (four); no AGPRs, no
 // scratch.
 template <int BPW, bool STATS, bool SHARED = false, bool DEEP = false>
@@ -633,34 +679,71 @@ __global__ __launch_bounds__(256) void k_project(const uint64_t* __restrict__ ha
 
     long long ss = 0;
     unsigned int mx = 0;
+    static_assert(!DEEP || BPW == 4, "the DEEP epilogue reduces four blocks together");
+    if constexpr (DEEP) {
+        // one reduction over the wave's four blocks (reduce_counts_wave4): this lane holds four consecutive entries of one
+        // block.  Blocks behind nblk were hashed like the others and are dropped here: k < d implies block < nblk.
+        int32_t cnt[4];
+        if (count <= 64) reduce_counts_wave4<1>(s, lane, cnt);
+        else if (count <= 64 * 15) reduce_counts_wave4<4>(s, lane, cnt);
+        else if (count <= 64 * 127) reduce_counts_wave4<7>(s, lane, cnt);
+        else if (count <= 64 * 511) reduce_counts_wave4<9>(s, lane, cnt);
+        else if (count <= 64 * 1023) reduce_counts_wave4<10>(s, lane, cnt);
+        else reduce_counts_wave4<kLV>(s, lane, cnt);
+        const int row = lane >> 4;
+        const int k0 = (b0 + (row & 1) + 2 * (lane & 1)) * 64 + 32 * (row >> 1) + 4 * ((lane & 15) >> 1);
+        int32_t v[4];
 #pragma unroll
-    for (int b = 0; b < BPW; ++b) {
-        if (b0 + b >= nblk) break;
-        int32_t cnt;   // a lane absorbed at most ceil(count / 64) hashes
-        if constexpr (DEEP) {
-            if (count <= 64) cnt = reduce_counts_valu<1>(s.lo[b], s.hi[b], lane);
-            else if (count <= 64 * 15) cnt = reduce_counts_valu<4>(s.lo[b], s.hi[b], lane);
-            else if (count <= 64 * 127) cnt = reduce_counts_valu<7>(s.lo[b], s.hi[b], lane);
-            else if (count <= 64 * 511) cnt = reduce_counts_valu<9>(s.lo[b], s.hi[b], lane);
-            else if (count <= 64 * 1023) cnt = reduce_counts_valu<10>(s.lo[b], s.hi[b], lane);
-            else cnt = reduce_counts_valu<kLV>(s.lo[b], s.hi[b], lane);
-        } else if (count <= 64) cnt = reduce_counts<1>(s.lo[b], s.hi[b], lane);
-        else if (count <= 64 * 15) cnt = reduce_counts<4>(s.lo[b], s.hi[b], lane);
-        else if (count <= 64 * 127) cnt = reduce_counts<7>(s.lo[b], s.hi[b], lane);
-        else if (count <= 64 * 511) cnt = reduce_counts<9>(s.lo[b], s.hi[b], lane);
-        else cnt = reduce_counts<kLV>(s.lo[b], s.hi[b], lane);
-        const int k = (b0 + b) * 64 + lane;
-        if (k < d) {
-            const int32_t v = (int32_t)count - 2 * cnt;
-            int32_t* dst = out + (int64_t)u.sample * d + k;
-            if (u.single)
-                *dst = v;
-            else
-                atomicAdd(dst, v);
-            if (STATS) {   // (of a unit that is not single: never used)
-                ss += (long long)v * v;
-                const unsigned int av = (unsigned int)(v < 0 ? -v : v);
-                mx = av > mx ? av : mx;
+        for (int p = 0; p < 4; ++p) v[p] = (int32_t)count - 2 * cnt[p];
+        int32_t* dst = out + (int64_t)u.sample * d + k0;
+        // d a multiple of 4 and a 16-byte aligned base: every row is aligned and k0 .. k0 + 3 are inside the row together,
+        // so the eight lanes of a block's half write 128 contiguous bytes with one store each
+        if (u.single && (d & 3) == 0 && ((uintptr_t)out & 15) == 0) {
+            if (k0 < d) *reinterpret_cast<int4*>(dst) = make_int4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                if (k0 + p < d) {
+                    if (u.single)
+                        dst[p] = v[p];
+                    else
+                        atomicAdd(dst + p, v[p]);
+                }
+            }
+        }
+        if (STATS) {   // (of a unit that is not single: never used)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                if (k0 + p < d) {
+                    ss += (long long)v[p] * v[p];
+                    const unsigned int av = (unsigned int)(v[p] < 0 ? -v[p] : v[p]);
+                    mx = av > mx ? av : mx;
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int b = 0; b < BPW; ++b) {
+            if (b0 + b >= nblk) break;
+            int32_t cnt;   // a lane absorbed at most ceil(count / 64) hashes
+            if (count <= 64) cnt = reduce_counts<1>(s.lo[b], s.hi[b], lane);
+            else if (count <= 64 * 15) cnt = reduce_counts<4>(s.lo[b], s.hi[b], lane);
+            else if (count <= 64 * 127) cnt = reduce_counts<7>(s.lo[b], s.hi[b], lane);
+            else if (count <= 64 * 511) cnt = reduce_counts<9>(s.lo[b], s.hi[b], lane);
+            else cnt = reduce_counts<kLV>(s.lo[b], s.hi[b], lane);
+            const int k = (b0 + b) * 64 + lane;
+            if (k < d) {
+                const int32_t v = (int32_t)count - 2 * cnt;
+                int32_t* dst = out + (int64_t)u.sample * d + k;
+                if (u.single)
+                    *dst = v;
+                else
+                    atomicAdd(dst, v);
+                if (STATS) {   // (of a unit that is not single: never used)
+                    ss += (long long)v * v;
+                    const unsigned int av = (unsigned int)(v < 0 ? -v : v);
+                    mx = av > mx ? av : mx;
+                }
             }
         }
     }

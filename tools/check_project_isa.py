@@ -18,6 +18,9 @@ about:
     the table does not hold is listed as unpriced and counted at 4.4.  A second sum uses the prices the same bodies have at
     two waves per SIMD, k_project's occupancy (profiles/r10_valu_rates_microbench.txt: v_bitop3_b32 is 3.07 there, not
     2.71), and adds the s_nop at their measured 0.76 cycles;
+  * the VALU instructions outside that loop: start-up, leftover batch, tail, ripples and every digit tier of the epilogue.  A
+    static total over the laid-out code, not what one wave executes (a wave runs one tier and one tail size), so it bounds
+    the code a unit's fixed cost is made of and moves when that code does;
   * LDS instructions anywhere in the kernel (the VALU epilogue has none);
   * VGPRs and scratch, from the code object's metadata.
 
@@ -229,6 +232,7 @@ def analyse(lib, variant, stats=True, text=None):
         "ds_bpermute": sum(1 for ins in insns if ins.mnem.startswith("ds_bpermute")),
         "scratch_insts": sum(1 for ins in insns if ins.mnem.startswith("scratch_")),
         "vgprs": vgpr, "agprs": agpr, "scratch_bytes": scratch, "kernel_instructions": len(insns),
+        "valu_outside_loop": sum(1 for i, ins in enumerate(insns) if ins.mnem.startswith("v_") and not head <= i <= tail),
     }
 
 
@@ -249,9 +253,9 @@ def main():
                 print(json.dumps(r))
             else:
                 print("%-32s loop %5d insts, %d paths, %3d pairs/iter: %.2f insts, %.2f VALU per (hash, block); LDS %d; "
-                      "VGPRs %d, scratch %d B" % (r["kernel"], r["loop_instructions"], r["loop_paths"], r["pairs_per_iteration"],
-                                                  r["insts_per_pair"], r["valu_per_pair"], r["lds_insts"], r["vgprs"],
-                                                  r["scratch_bytes"]))
+                      "VGPRs %d, scratch %d B; %d VALU outside the loop"
+                      % (r["kernel"], r["loop_instructions"], r["loop_paths"], r["pairs_per_iteration"], r["insts_per_pair"],
+                         r["valu_per_pair"], r["lds_insts"], r["vgprs"], r["scratch_bytes"], r["valu_outside_loop"]))
                 print("%-32s priced %.2f SIMD cycles (%.2f with the prices at two waves per SIMD and the s_nop), %.3f s_nop per (hash, block)%s"
                       % ("", r["valu_cycles_per_pair"], r["valu_cycles_per_pair_2_waves"], r["s_nop_per_pair"],
                          "; unpriced (at %.1f): %s" % (UNPRICED_CYCLES, " ".join(r["unpriced"])) if r["unpriced"] else ""))
