@@ -149,6 +149,7 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   groups_dots, groups_block_rows
  *                         mvs_group_sums / mvs_permanova: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0
  *                         bounds the rows of a block (0: by the device budget)
+ *   core_block_rows       mvs_core_jaccard / mvs_hdbscan: > 0 bounds the rows of a top-k range (0: by the cell buffer's budget)
  *   gram_slab_rows        mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536 (default
  *                         65536; rounded down to a multiple of 64)
  *   gram_variant          tile kernel of the moments: 0 (default) by shape -- 128 x 128 tiles for one or two limbs and d >= 128, else
@@ -644,6 +645,17 @@ int mvs_ctx_cluster_stats(const mvs_ctx* ctx, double* compare_ms, double* union_
  *
  * mvs_linkage_create    an empty forest over n samples of dimension d on the context's device; norms_sq (n doubles) is copied
  *                       to the device and decides every weight.  Resets the statistics mvs_ctx_linkage_stats reports.
+ * mvs_linkage_set_core  switches the weight to the MUTUAL REACHABILITY of HDBSCAN* (section below): core (n doubles, `mem_core`) is
+ *                       copied to the device, and from then on the weight of the edge (lo, hi) is m = min(J, core[lo], core[hi]),
+ *                       the minimum taken in key order: J, unless a core value's key is strictly smaller -- then that value, lo's
+ *                       before hi's.  An edge whose J or either core value is NaN is ignored (and counted with the fed cells, as
+ *                       a NaN J is today).  The order stays (key(m) descending, lo, hi): total, so the forest is still unique,
+ *                       equal to a host Kruskal under that order, and independent of blocking, cell order and repeats -- the
+ *                       argument needs a fixed weight per edge, nothing more.  In this mode the field `jaccard` of mvs_link
+ *                       holds m, bit for bit: finish sorts by it, mvs_linkage_cells(level) returns the prefix with m > level,
+ *                       and J stays recomputable from dot and the norms.  Allowed only before the first cell is fed
+ *                       (MVS_E_INVALID afterwards: a forest built under one weight says nothing about another); may be
+ *                       called again until then.  Without it every result is bit for bit what it was.
  * mvs_linkage_add_cells replaces the forest F by the maximum spanning forest of F and the cells of a DEVICE list.  Unlike
  *                       mvs_cluster_add_cells it reads `dot`, so any producer that reports real dots may feed it
  *                       (mvs_pairwise_rows, mvs_pairwise_block, mvs_search_block, mvs_pairwise_topk).  Cells with row == col
@@ -667,10 +679,11 @@ typedef struct mvs_link {
     int32_t b;         /* the larger one */
     int32_t dot;
     int32_t q;
-    double jaccard;
+    double jaccard;    /* the weight: J, or the mutual reachability m once mvs_linkage_set_core was called */
 } mvs_link;
 typedef struct mvs_linkage mvs_linkage;
 int mvs_linkage_create(mvs_ctx* ctx, int64_t n, int d, const double* norms_sq, int mem_norms, mvs_linkage** linkage);
+int mvs_linkage_set_core(mvs_linkage* linkage, const double* core, int mem_core);
 int mvs_linkage_add_cells(mvs_linkage* linkage, const mvs_cell* d_cells, int64_t n_cells);
 int mvs_pairwise_linkage(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double min_jaccard,
                          mvs_linkage* linkage);
@@ -679,6 +692,79 @@ int mvs_linkage_cells(mvs_linkage* linkage, double level, mvs_cell* d_cells, int
 int mvs_linkage_destroy(mvs_linkage* linkage);
 int mvs_ctx_linkage_stats(const mvs_ctx* ctx, double* compare_ms, double* forest_ms, int64_t* edges, int64_t* row_blocks,
                           int64_t* rounds);
+
+/* ---- HDBSCAN* on the Jaccard estimates: clusters without a level to choose -----------------------------------------------------
+ * Every grouping call above takes one Jaccard level, and single linkage chains: a path of overlapping samples is one cluster.
+ * HDBSCAN* (Campello, Moulavi, Sander 2013; McInnes, Healy 2017) answers both.  It weighs a pair by its MUTUAL REACHABILITY
+ * m(i, j) = min(core[i], core[j], J(i, j)), core[i] the similarity of i's K-th nearest neighbour -- a thin chain between two dense
+ * groups then weighs only as much as its sparsest sample --, builds the single-linkage tree of that weight, and picks clusters
+ * by their stability over ALL levels.  The reference has nothing of the kind.  Both expensive halves are the exact device paths
+ * above (mvs_pairwise_topk, the forest of mvs_linkage_*); the selection is integer arithmetic on the host, so every output is a
+ * function of the set, the norms and the parameters alone.
+ *
+ * Core.  core[i] = the K-th best score of row i under mvs_pairwise_topk's rule, every column eligible, MVS_TOPK_EXCLUDE_SELF
+ *   set: the minimum in key order of the fp64 J of the K cells top-k returns for the row, J = inter / (n2[i] + n2[j] - inter),
+ *   inter = (double)P / d, -0.0 folded into +0.0.  A row that gets fewer than K cells (its scores are NaN) has core = NaN.
+ *   K = min_samples, 1 <= K <= 256 and K <= n - 1 (MVS_E_INVALID otherwise).
+ * Levels.  lambda(x) = llrint(min(max(x, 0), 1) * 2^30): every level below is an int64, every stability an exact int64 sum.
+ * Dendrogram.  The links with m > floor (fp64 compare), best first as mvs_linkage_finish returns them under
+ *   mvs_linkage_set_core, are Kruskal merges: merge v has lambda_v = lambda(m), two children and a size.  A forest; samples no
+ *   link touches are singleton roots.
+ * Condensed tree, top-down from every root of size >= s = min_cluster_size (smaller roots are noise).  A cluster C is born at
+ *   birth(C) (lambda(floor) for a root).  At a merge v inside C: both children >= s -- C ends, every sample under v leaves C at
+ *   lambda_v, two clusters are born at lambda_v; exactly one child >= s -- the samples of the small child leave C at lambda_v, C
+ *   continues into the large one; both < s -- every sample under v leaves at lambda_v, C ends as a leaf cluster.
+ *   stability(C) = sum over all samples ever in C of (lambda_leave(p, C) - birth(C)); death(C) = the split's lambda, for a leaf
+ *   the largest lambda_leave.
+ * Selection by excess of mass, bottom-up.  A leaf has S^ = stability.  A cluster with children A, B is selected when
+ *   stability(C) >= S^(A) + S^(B) (ties go to the parent): its descendants are deselected and S^(C) = stability(C); otherwise
+ *   S^(C) = S^(A) + S^(B).  Roots are eligible: a root is a component at the floor, what mvs_pairwise_cluster reports there.
+ *   With MVS_HDBSCAN_NO_ROOTS a root that has child clusters is never selected.
+ * Output.
+ *   clusters : one mvs_hdbscan_cluster per condensed cluster, sorted by (smallest member ascending, size descending): parent
+ *              (index into this array, -1 for a root), size at birth, selected (0 / 1), representative (the member at birth with
+ *              the largest core in key order, NaN below every number, ties to the smaller index; core == NULL: the smallest
+ *              member), birth, death, stability.  Fewer than max(n, 2) of them (leaves are disjoint and hold >= 2 samples, the rest have
+ *              two children); MVS_E_CAPACITY reports the count in *n_clusters.
+ *   labels[i]     the rank among the SELECTED clusters (in array order) of the one whose subtree holds i, -1 for noise.
+ *   strength[i]   (min(lambda_i, lmax(C)) - birth(C)) / (lmax(C) - birth(C)) for i's selected cluster C, lambda_i the level at
+ *                 which i left its last cluster and lmax(C) the largest such level under C: one fp64 division of two exactly
+ *                 converted integers; 1.0 when the denominator is 0, 0.0 for noise.
+ *   lambda_out[i] lambda_i, -1 for a sample that was never in a cluster.
+ *
+ * mvs_core_jaccard    core[] of every sample of the set -> core_out (n doubles, `mem_out`).  Top-k runs over row ranges into a
+ *                     bounded device cell buffer (option core_block_rows bounds a range); a kernel reduces each range's ragged
+ *                     list to its rows' values (mvs_core.hip); no cell list crosses the link.
+ * mvs_hdbscan_select  pure host, needs no device: n, the links best first (by (key(jaccard) descending, a, b): anything else,
+ *                     a link outside [0, n), a == b, a NaN weight or a link that closes a cycle is MVS_E_INVALID), core (n
+ *                     doubles or NULL), floor (not NaN), min_cluster_size >= 2, flags.  Any output pointer may be NULL.
+ * mvs_hdbscan         core (K = min_samples), linkage with that core at `floor` (0 < floor < 1, as mvs_pairwise_linkage), finish,
+ *                     select.  core_out, links (room for n - 1), n_links and the outputs of the selection are HOST buffers;
+ *                     any may be NULL.  cluster_capacity as above.
+ * mvs_ctx_hdbscan_stats  of the context's last mvs_core_jaccard / mvs_hdbscan: kernel times of top-k's dots and selection summed
+ *                     over the ranges and of the reduction (0 unless mvs_ctx_set_timing is on), of the comparison and the
+ *                     forest (mvs_ctx_linkage_stats), host time of the selection (always measured); top-k ranges, the most
+ *                     Boruvka rounds a list needed, links, fed cells.  Any pointer may be NULL. */
+#define MVS_HDBSCAN_NO_ROOTS 1
+typedef struct mvs_hdbscan_cluster {
+    int32_t parent;
+    int32_t size;
+    int32_t selected;
+    int32_t representative;
+    int64_t birth;
+    int64_t death;
+    int64_t stability;
+} mvs_hdbscan_cluster;
+int mvs_core_jaccard(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, int k, double* core_out,
+                     int mem_out);
+int mvs_hdbscan_select(int64_t n, const mvs_link* links, int64_t n_links, const double* core, double floor, int64_t min_cluster_size,
+                       int flags, int32_t* labels, double* strength, int64_t* lambda_out, mvs_hdbscan_cluster* clusters,
+                       int64_t cluster_capacity, int64_t* n_clusters);
+int mvs_hdbscan(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, int min_samples, double floor,
+                int64_t min_cluster_size, int flags, double* core_out, mvs_link* links, int64_t* n_links, int32_t* labels,
+                double* strength, int64_t* lambda_out, mvs_hdbscan_cluster* clusters, int64_t cluster_capacity, int64_t* n_clusters);
+int mvs_ctx_hdbscan_stats(const mvs_ctx* ctx, double* core_dots_ms, double* core_select_ms, double* core_kth_ms, double* compare_ms,
+                          double* forest_ms, double* host_ms, int64_t* ranges, int64_t* rounds, int64_t* links, int64_t* edges);
 
 /* ---- greedy dereplication: representatives with a radius guarantee -------------------------------------------------------------
  * Single linkage chains: a cluster's representative may have nothing in common with most of its members.  Dereplication wants

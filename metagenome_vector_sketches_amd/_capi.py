@@ -17,6 +17,7 @@ MVS_OK, MVS_E_INVALID, MVS_E_HIP, MVS_E_CAPACITY, MVS_E_NOMEM, MVS_E_RANGE, MVS_
 MEM_HOST, MEM_DEVICE = 0, 1
 KEEP_INT32, KEEP_INT16 = 0, 1
 TOPK_EXCLUDE_SELF = 1
+HDBSCAN_NO_ROOTS = 1
 CONTAIN_ROW, CONTAIN_MAX = 0, 1
 LIMBS_K3 = 0x103
 MAX_GROUP_SLOTS = 16384
@@ -24,6 +25,8 @@ BLOCK_SYMMETRIC, BLOCK_MIRROR_ALL = 1, 2
 
 CELL_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("dot", "<i4"), ("q", "<i4")])
 LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("dot", "<i4"), ("q", "<i4"), ("jaccard", "<f8")])      # mvs_link
+HDBSCAN_CLUSTER_DTYPE = np.dtype([("parent", "<i4"), ("size", "<i4"), ("selected", "<i4"), ("representative", "<i4"), ("birth", "<i8"),
+                                  ("death", "<i8"), ("stability", "<i8")])                                       # mvs_hdbscan_cluster
 GATHER_DTYPE = np.dtype([("sample", "<i4"), ("intersect", "<i4"), ("unique", "<i4"), ("remaining", "<i4")])  # mvs_gather_match
 
 # every symbol include/mvs_hip.h declares: (name, restype, argtypes)
@@ -164,6 +167,7 @@ SYMBOLS = [
     ("mvs_ctx_cluster_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                           _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     ("mvs_linkage_create", _c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_int, _c.POINTER(_P)]),
+    ("mvs_linkage_set_core", _c.c_int, [_P, _P, _c.c_int]),
     ("mvs_linkage_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
     ("mvs_pairwise_linkage", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
     ("mvs_linkage_finish", _c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int64)]),
@@ -171,6 +175,12 @@ SYMBOLS = [
     ("mvs_linkage_destroy", _c.c_int, [_P]),
     ("mvs_ctx_linkage_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                           _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_core_jaccard", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int]),
+    ("mvs_hdbscan_select", _c.c_int, [_c.c_int64, _P, _c.c_int64, _P, _c.c_double, _c.c_int64, _c.c_int, _P, _P, _P, _P, _c.c_int64,
+                                       _c.POINTER(_c.c_int64)]),
+    ("mvs_hdbscan", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_int, _c.c_double, _c.c_int64, _c.c_int, _P, _P, _c.POINTER(_c.c_int64), _P, _P, _P,
+                                _P, _c.c_int64, _c.POINTER(_c.c_int64)]),
+    ("mvs_ctx_hdbscan_stats", _c.c_int, [_P] + [_c.POINTER(_c.c_double)] * 6 + [_c.POINTER(_c.c_int64)] * 4),
     ("mvs_sketch_set_gather", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_derep_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_derep_add_rows", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64]),
@@ -663,6 +673,15 @@ class Linkage(_Handle):
         self._h = h
         ctx._children.add(self)
 
+    def set_core(self, core):
+        """mvs_linkage_set_core: from now on the weight of a link is the mutual reachability min(jaccard, core[a], core[b]) --
+        the `jaccard` of every result then holds that value.  core: n doubles (numpy or torch, host or device), e.g. what
+        Context.core_jaccard returns.  Only before the first cell is fed."""
+        cp, cm, ck = _norms(core)
+        if len(core) != self.n:
+            raise ValueError("core must hold n values")
+        _check(self.ctx.lib.mvs_linkage_set_core(self._h, cp, cm))
+
     def add_cells(self, cells, n_cells=None):
         """cells: torch CUDA tensor (int32 [m, 4]; the first n_cells rows, default all) or a device address (int) with n_cells.
         Feeding a list twice changes nothing."""
@@ -698,6 +717,52 @@ class Linkage(_Handle):
             raise MvsError(rc, self.ctx.lib.mvs_last_error().decode("utf-8", "replace"), needed=count.value)
         _check(rc)
         return out, count.value
+
+
+class Hdbscan:
+    """What hdbscan_select / Context.hdbscan return (include/mvs_hip.h "HDBSCAN*"): `labels` int32 [n] (the rank of the sample's
+    selected cluster, -1 noise), `strength` float64 [n], `lambda_out` int64 [n] (the level at which the sample left its last
+    cluster, -1 never in one), `clusters` (HDBSCAN_CLUSTER_DTYPE: parent, size, selected, representative, birth, death,
+    stability -- every condensed cluster, by smallest member then size descending); from Context.hdbscan also `core` float64
+    [n] and `links` (a LinkageResult whose `jaccard` is the mutual reachability).  Levels are llrint(clamp(x, 0, 1) * 2^30)."""
+
+    def __init__(self, labels, strength, lambda_out, clusters, core=None, links=None):
+        self.labels, self.strength, self.lambda_out, self.clusters, self.core, self.links = labels, strength, lambda_out, clusters, core, links
+        self.n_clusters = int(clusters["selected"].sum())
+
+    def __repr__(self):
+        return "Hdbscan(%d samples, %d clusters of %d condensed, %d noise)" % (len(self.labels), self.n_clusters, len(self.clusters),
+                                                                               int((self.labels < 0).sum()))
+
+
+def _links_array(links):
+    """a LinkageResult, a dict of arrays or a LINK_DTYPE array -> LINK_DTYPE array"""
+    if isinstance(links, np.ndarray) and links.dtype == LINK_DTYPE:
+        return np.ascontiguousarray(links)
+    get = (lambda f: links[f]) if isinstance(links, dict) else (lambda f: getattr(links, f))
+    out = np.zeros(len(get("a")), dtype=LINK_DTYPE)
+    for f in LINK_DTYPE.names:
+        out[f] = get(f)
+    return out
+
+
+def hdbscan_select(n, links, core=None, floor=0.05, min_cluster_size=5, allow_roots=True):
+    """mvs_hdbscan_select: condensed tree and selection by excess of mass over the links of a linkage built under the mutual
+    reachability (Linkage.set_core), best first -> Hdbscan.  links: a LinkageResult, a dict of arrays a / b / dot / q / jaccard or
+    a LINK_DTYPE array; core: n doubles or None (decides the representatives only).  Needs no device."""
+    arr = _links_array(links)
+    n = int(n)
+    labels, strength = np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.float64)
+    lam = np.full(n, -1, dtype=np.int64)
+    clusters = np.zeros(max(n, 1), dtype=HDBSCAN_CLUSTER_DTYPE)
+    core_a = None if core is None else np.ascontiguousarray(core, dtype=np.float64)
+    if core_a is not None and len(core_a) != n:
+        raise ValueError("core must hold n values")
+    count = _c.c_int64()
+    _check(load_library().mvs_hdbscan_select(n, arr.ctypes.data, len(arr), None if core_a is None else core_a.ctypes.data, float(floor),
+                                             int(min_cluster_size), 0 if allow_roots else HDBSCAN_NO_ROOTS, labels.ctypes.data,
+                                             strength.ctypes.data, lam.ctypes.data, clusters.ctypes.data, len(clusters), ctypes.byref(count)))
+    return Hdbscan(labels, strength, lam, clusters[:count.value].copy(), core_a)
 
 
 class Pca(_Handle):
@@ -1735,6 +1800,45 @@ class Context:
         """-> dict since this context's last Linkage was created: compare_ms / forest_ms (kernel times, timing on), edges (fed
         cells with row != col), row_blocks, rounds (most Boruvka rounds a list needed)"""
         return self._consumer_stats(self.lib.mvs_ctx_linkage_stats, "forest_ms")
+
+    # ---- HDBSCAN* (include/mvs_hip.h "HDBSCAN*") ----
+    def core_jaccard(self, sset, norms_sq, k, out=None):
+        """mvs_core_jaccard: the Jaccard estimate of every sample's k-th nearest neighbour (NaN for a sample with fewer than k
+        scored neighbours) -> float64 [n], or `out` (a torch float64 device tensor [n]) filled"""
+        np_, nm, nk = _norms(norms_sq)
+        if out is None:
+            core = np.empty(max(sset.n, 1), dtype=np.float64)
+            _check(self.lib.mvs_core_jaccard(self._h, sset._h, np_, nm, int(k), core.ctypes.data, MEM_HOST))
+            return core[:sset.n]
+        op, om, ok = _buf(out)
+        _check(self.lib.mvs_core_jaccard(self._h, sset._h, np_, nm, int(k), op, om))
+        return out
+
+    def hdbscan(self, sset, norms_sq, min_samples=5, floor=0.05, min_cluster_size=5, allow_roots=True):
+        """mvs_hdbscan: core similarities (k = min_samples), the single-linkage tree of the mutual reachability at Jaccard >
+        floor, condensed tree and selection by stability -> Hdbscan with .labels .strength .core .lambda_out .clusters .links.
+        No level to choose beyond the floor below which pairs are not compared; no cell leaves the device."""
+        n = sset.n
+        np_, nm, nk = _norms(norms_sq)
+        core, strength = np.empty(max(n, 1), dtype=np.float64), np.zeros(max(n, 1), dtype=np.float64)
+        links = np.empty(max(n - 1, 1), dtype=LINK_DTYPE)
+        labels, lam = np.full(max(n, 1), -1, dtype=np.int32), np.full(max(n, 1), -1, dtype=np.int64)
+        clusters = np.zeros(max(n, 1), dtype=HDBSCAN_CLUSTER_DTYPE)
+        n_links, count = _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_hdbscan(self._h, sset._h, np_, nm, int(min_samples), float(floor), int(min_cluster_size),
+                                    0 if allow_roots else HDBSCAN_NO_ROOTS, core.ctypes.data, links.ctypes.data, ctypes.byref(n_links),
+                                    labels.ctypes.data, strength.ctypes.data, lam.ctypes.data, clusters.ctypes.data, len(clusters),
+                                    ctypes.byref(count)))
+        return Hdbscan(labels[:n], strength[:n], lam[:n], clusters[:count.value].copy(), core[:n], LinkageResult(n, links[:n_links.value]))
+
+    def hdbscan_stats(self):
+        """-> dict of the last core_jaccard / hdbscan: core_dots_ms, core_select_ms, core_kth_ms, compare_ms, forest_ms (kernel
+        times, timing on), host_ms (the selection), ranges (top-k row ranges), rounds, links, edges"""
+        t = [_c.c_double() for _ in range(6)]
+        v = [_c.c_int64() for _ in range(4)]
+        _check(self.lib.mvs_ctx_hdbscan_stats(self._h, *[ctypes.byref(x) for x in t + v]))
+        names = ("core_dots_ms", "core_select_ms", "core_kth_ms", "compare_ms", "forest_ms", "host_ms", "ranges", "rounds", "links", "edges")
+        return dict(zip(names, (x.value for x in t + v)))
 
     # ---- greedy dereplication (include/mvs_hip.h "greedy dereplication") ----
     def derep_into(self, derep, sset, norms_sq, min_jaccard):

@@ -418,6 +418,11 @@ int mvs_ctx_set_option(mvs_ctx* c, const char* name, int64_t value) {
         c->plan_overlap = (int)value;
         return MVS_OK;
     }
+    if (std::strcmp(name, "core_block_rows") == 0) {         // host-side blocking only
+        if (value < 0 || value > (1 << 30)) return fail(MVS_E_INVALID, "option core_block_rows: 0 .. 2^30 rows");
+        c->core_block_rows = (int)value;
+        return MVS_OK;
+    }
     if (std::strcmp(name, "report_spin") == 0) {             // host-side waiting only
         if (value < 0 || value > 1000000) return fail(MVS_E_INVALID, "option report_spin: 0 .. 1000000 microseconds");
         c->report_spin = (int)value;
@@ -432,6 +437,10 @@ int mvs_ctx_get_option(const mvs_ctx* c, const char* name, int64_t* value) {
     if (!c || !name || !value) return fail(MVS_E_INVALID, "NULL argument");
     if (std::strcmp(name, "plan_overlap") == 0) {
         *value = c->plan_overlap;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "core_block_rows") == 0) {
+        *value = c->core_block_rows;
         return MVS_OK;
     }
     if (std::strcmp(name, "report_spin") == 0) {

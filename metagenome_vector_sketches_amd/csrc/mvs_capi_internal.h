@@ -51,6 +51,14 @@ struct GroupsStats {
     long long blocks = 0, block_rows = 0, slots = 0;
     void reset() { *this = GroupsStats(); }
 };
+// what the last mvs_core_jaccard / mvs_hdbscan did on a context (mvs_ctx_hdbscan_stats): kernel times of the core pass (top-k's
+// dots and selection summed over the ranges, k_core_kth), of the comparison and the forest, the host time of the selection;
+// top-k ranges, Boruvka rounds, links, fed cells
+struct HdbscanStats {
+    double core_dots_ms = 0.0, core_select_ms = 0.0, core_kth_ms = 0.0, compare_ms = 0.0, forest_ms = 0.0, host_ms = 0.0;
+    long long ranges = 0, rounds = 0, links = 0, edges = 0;
+    void reset() { *this = HdbscanStats(); }
+};
 }  // namespace mvs_capi
 
 struct mvs_ctx {
@@ -195,6 +203,9 @@ struct mvs_ctx {
     // mvs_derep_create on this context (mvs_ctx_cluster_stats, mvs_ctx_linkage_stats, mvs_ctx_derep_stats)
     mvs_capi::ConsumerStats cl, lk, dr;
     mvs_capi::GroupsStats gs;
+    mvs_capi::HdbscanStats hd;
+    int core_block_rows = 0;              // mvs_core_jaccard / mvs_hdbscan: > 0 = upper bound on the rows of a top-k range (tests); 0 = by
+                                          // the cell buffer's budget.  Host-side blocking only (option core_block_rows)
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
     // did (mvs_ctx_intersect_stats)
     void* ix_work = nullptr;    size_t ix_work_bytes = 0;

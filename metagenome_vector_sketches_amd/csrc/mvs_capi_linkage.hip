@@ -1,8 +1,9 @@
-// mvs_capi_linkage.hip -- C ABI of the single-linkage tree: mvs_linkage_create / _add_cells / _finish / _cells / _destroy (a
+// mvs_capi_linkage.hip -- C ABI of the single-linkage tree: mvs_linkage_create / _set_core / _add_cells / _finish / _cells / _destroy (a
 // consumer of DEVICE cell lists that keeps the maximum spanning forest of everything it was fed), mvs_pairwise_linkage (the
 // one-call producer: mvs_pairwise_cluster's row-block loop with this consumer) and mvs_ctx_linkage_stats.  The kernels and the
 // argument for their exactness are in mvs_linkage.hip.  What comes back is at most n - 1 links of 24 bytes.
 #include "mvs_capi_internal.h"
+#include "mvs_core.h"
 
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,8 @@ struct mvs_linkage {
     int64_t n = 0;
     int d = 0;
     double* norms_sq = nullptr;              // the linkage's own copy: every weight comes from it
+    double* core = nullptr;                  // NULL, or the core values of mvs_linkage_set_core: the weight is min(J, core, core)
+    bool fed = false;                        // a cell has been fed: the weight is fixed from here on
     mvs_cell* forest[2] = {nullptr, nullptr};   // the forest and the one the rounds build; `cur` says which is which
     int cur = 0;
     int64_t n_forest = 0;
@@ -51,6 +54,7 @@ mvs::LinkState state_of(const mvs_linkage* k) {
 int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
     mvs_ctx* c = k->ctx;
     if (n_cells == 0) return MVS_OK;
+    k->fed = true;
     StageTimer timer;
     int rc = timer.begin(c);
     if (rc) return rc;
@@ -66,7 +70,7 @@ int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
         if (!rc) rc = check_kernel("k_link_slots");
         if (rc) return rc;
         HIP_TRY(hipMemsetAsync(k->counters + 2, 0, sizeof(unsigned long long), c->stream));
-        rc = mvs::launch_link_select(c->stream, s, d_cells, n_cells, 0, round == 0);
+        rc = mvs::launch_link_select(c->stream, s, k->core, d_cells, n_cells, 0, round == 0);
         if (!rc) rc = check_kernel("k_link_select<0>");
         if (rc) return rc;
         rc = read_back(c, c->stream, {{back, k->counters, sizeof(back)}});
@@ -77,10 +81,10 @@ int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
             return fail(MVS_E_HIP, "internal: %llu edges still join different components after %d rounds", back[2], round);
         ++round;
         for (int pass = 1; pass <= 2 && !rc; ++pass) {
-            rc = mvs::launch_link_select(c->stream, s, d_cells, n_cells, pass, false);
+            rc = mvs::launch_link_select(c->stream, s, k->core, d_cells, n_cells, pass, false);
             if (!rc) rc = check_kernel("k_link_select");
         }
-        if (!rc) rc = mvs::launch_link_hook(c->stream, s, d_cells);
+        if (!rc) rc = mvs::launch_link_hook(c->stream, s, k->core, d_cells);
         if (!rc) rc = check_kernel("k_link_hook");
         if (!rc) rc = mvs::launch_link_jump(c->stream, s);
         if (!rc) rc = check_kernel("k_link_flatten");
@@ -110,14 +114,14 @@ int sort_links(mvs_linkage* k) {
     const mvs::LinkState s = state_of(k);
     DevBuf dtmp, dscratch;
     size_t need = 0;
-    int rc = mvs::link_sorted(c->stream, s, nullptr, nullptr, nullptr, 0, &need);
+    int rc = mvs::link_sorted(c->stream, s, k->core, nullptr, nullptr, nullptr, 0, &need);
     if (rc) return fail(rc, "linkage finish: sort sizing failed");
     HIP_TRY(dtmp.alloc((size_t)k->n_forest * sizeof(mvs_link)));
     HIP_TRY(dscratch.alloc(need));
     StageTimer timer;
     rc = timer.begin(c);
     if (rc) return rc;
-    rc = mvs::link_sorted(c->stream, s, (mvs_link*)dtmp.p, k->links, dscratch.p, need, nullptr);
+    rc = mvs::link_sorted(c->stream, s, k->core, (mvs_link*)dtmp.p, k->links, dscratch.p, need, nullptr);
     if (rc) return fail(rc, "linkage finish: sort failed");
     rc = check_kernel("k_link_links");
     if (rc) return rc;
@@ -167,6 +171,27 @@ int mvs_linkage_create(mvs_ctx* c, int64_t n, int d, const double* norms_sq, int
     }
     c->lk.reset();
     *out = k;
+    return MVS_OK;
+}
+
+int mvs_linkage_set_core(mvs_linkage* k, const double* core, int mem_core) {
+    if (!k) return fail(MVS_E_INVALID, "NULL linkage");
+    if (!mem_ok(mem_core)) return fail(MVS_E_INVALID, "bad argument");
+    if (k->n > 0 && !core) return fail(MVS_E_INVALID, "core is NULL");
+    if (k->fed) return fail(MVS_E_INVALID, "the linkage has been fed cells: the core values decide every weight and must come first");
+    mvs_ctx* c = k->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!k->core) {
+        if (hipMalloc((void**)&k->core, (size_t)std::max<int64_t>(k->n, 1) * 8) != hipSuccess) {
+            k->core = nullptr;
+            return fail(MVS_E_NOMEM, "hipMalloc of %lld core values failed", (long long)k->n);
+        }
+    }
+    if (k->n > 0) {
+        HIP_TRY(hipMemcpyAsync(k->core, core, (size_t)k->n * 8, mem_core == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+                               c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     return MVS_OK;
 }
 
@@ -236,7 +261,7 @@ int mvs_linkage_destroy(mvs_linkage* k) {
         (void)hipSetDevice(k->ctx->device);
         (void)hipStreamSynchronize(k->ctx->stream);
     }
-    void* bufs[] = {k->norms_sq, k->forest[0], k->forest[1], k->comp, k->next, k->slots, k->counters, k->links};
+    void* bufs[] = {k->norms_sq, k->core, k->forest[0], k->forest[1], k->comp, k->next, k->slots, k->counters, k->links};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     delete k;

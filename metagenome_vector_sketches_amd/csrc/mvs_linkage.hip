@@ -53,6 +53,16 @@
 //   back once per round; walks in flatten are bounded by n steps and report a longer one instead of spinning.
 //   Hence F after add_cells is MSF(F u L) as a SET whatever the order of the cells, the blocking or the comparison path; its
 //   order in memory is not defined, and finish sorts it (a total order: one result).
+//
+// Mutual reachability (mvs_linkage_set_core; HDBSCAN*, mvs_capi_hdbscan.hip).  With core values set, the weight of (lo, hi) is
+// m = min(J, core[lo], core[hi]) by key order instead of J, and an edge with a NaN core value is ignored like one whose J is
+// NaN.  lk_weight is the one place that decides it; select, hook and links read it through lk_edge / lk_weight, and the pointer
+// is a parameter of their launches (mvs_core.h; the declarations of mvs_internal.h pass NULL).  Nothing in
+// the argument above uses more of the weight than that it is a fixed function of the edge and the linkage's own arrays: the
+// order (key(m) descending, lo, hi) is still total, so the forest is still unique and add_cells still exact.  Ties are far
+// more common under m (every edge of a dense group may weigh its sparsest member's core value): the index rule decides them,
+// as it decides the ties among identical rows today.  core == NULL is the plain weight, bit for bit.
+#include "mvs_core.h"
 #include "mvs_internal.h"
 #include "mvs_pairwise_dev.h"
 
@@ -99,8 +109,32 @@ struct LkEdge {
 enum { kLkEdge = 0, kLkIgnored = 1, kLkSelf = 2, kLkBad = 3 };
 
 // cell e of F u L (e < n_f: F[e], else L[e - n_f]) as an edge
+// the weight of the edge (lo, hi) whose Jaccard estimate is J (not NaN).  core == NULL: J itself.  Else the mutual reachability
+// m = min(J, core[lo], core[hi]) by key order (J unless a core value's key is strictly smaller, then that value, lo before hi);
+// false if either core value is NaN: the edge is ignored
+__device__ __forceinline__ bool lk_weight(double J, const double* __restrict__ core, int32_t lo, int32_t hi, double& m,
+                                          unsigned long long& key) {
+    m = J;
+    key = lk_key(J);
+    if (core == nullptr) return true;
+    const double ca = core[lo], cb = core[hi];
+    if (!(ca == ca) || !(cb == cb)) return false;
+    const unsigned long long ka = lk_key(ca);
+    if (ka < key) {
+        key = ka;
+        m = ca;
+    }
+    const unsigned long long kb = lk_key(cb);
+    if (kb < key) {
+        key = kb;
+        m = cb;
+    }
+    return true;
+}
+
 __device__ __forceinline__ int lk_edge(const mvs_cell* __restrict__ F, int64_t n_f, const mvs_cell* __restrict__ L, int64_t e,
-                                       const double* __restrict__ norms_sq, int64_t n, int d, LkEdge& out) {
+                                       const double* __restrict__ norms_sq, const double* __restrict__ core, int64_t n, int d,
+                                       LkEdge& out) {
     const mvs_cell c = e < n_f ? F[e] : L[e - n_f];
     if (c.row < 0 || c.col < 0 || c.row >= n || c.col >= n) return kLkBad;
     if (c.row == c.col) return kLkSelf;
@@ -110,7 +144,8 @@ __device__ __forceinline__ int lk_edge(const mvs_cell* __restrict__ F, int64_t n
     out.q = c.q;
     const double J = lk_jaccard(c.dot, d, norms_sq[out.lo], norms_sq[out.hi]);
     if (!(J == J)) return kLkIgnored;
-    out.key = lk_key(J);
+    double m;
+    if (!lk_weight(J, core, out.lo, out.hi, m, out.key)) return kLkIgnored;
     out.pair = ((unsigned long long)(unsigned)out.lo << 32) | (unsigned long long)(unsigned)out.hi;
     return kLkEdge;
 }
@@ -133,7 +168,8 @@ __global__ __launch_bounds__(kLkThreads) void k_link_slots(unsigned long long* _
 // index outside [0, n) (when `first`), [2] edges whose endpoints lie in different components (pass 0)
 template <int PASS>
 __global__ __launch_bounds__(kLkThreads) void k_link_select(const mvs_cell* __restrict__ F, int64_t n_f, const mvs_cell* __restrict__ L,
-                                                            int64_t n_l, const double* __restrict__ norms_sq, int64_t n, int d,
+                                                            int64_t n_l, const double* __restrict__ norms_sq,
+                                                            const double* __restrict__ core, int64_t n, int d,
                                                             const int32_t* __restrict__ comp, unsigned long long* __restrict__ best_key,
                                                             unsigned long long* __restrict__ best_pair,
                                                             unsigned long long* __restrict__ best_idx, int first,
@@ -144,7 +180,7 @@ __global__ __launch_bounds__(kLkThreads) void k_link_select(const mvs_cell* __re
     int64_t e = (int64_t)blockIdx.x * kLkThreads + threadIdx.x;
     for (int64_t t = 0; t < trips; ++t, e += stride) {
         LkEdge g;
-        const int kind = e < total ? lk_edge(F, n_f, L, e, norms_sq, n, d, g) : kLkSelf;
+        const int kind = e < total ? lk_edge(F, n_f, L, e, norms_sq, core, n, d, g) : kLkSelf;
         bool apart = false;
         int32_t ca = 0, cb = 0;
         if (kind == kLkEdge) {
@@ -179,8 +215,9 @@ __global__ __launch_bounds__(kLkThreads) void k_link_select(const mvs_cell* __re
 
 // counters: [3] cells in the next forest, [4] set if one did not fit (cannot happen: a forest has at most n - 1 edges)
 __global__ __launch_bounds__(kLkThreads) void k_link_hook(const mvs_cell* __restrict__ F, int64_t n_f, const mvs_cell* __restrict__ L,
-                                                          const double* __restrict__ norms_sq, int64_t n, int d,
-                                                          const int32_t* __restrict__ comp, const unsigned long long* __restrict__ best_key,
+                                                          const double* __restrict__ norms_sq, const double* __restrict__ core,
+                                                          int64_t n, int d, const int32_t* __restrict__ comp,
+                                                          const unsigned long long* __restrict__ best_key,
                                                           const unsigned long long* __restrict__ best_pair,
                                                           const unsigned long long* __restrict__ best_idx, int32_t* __restrict__ next,
                                                           mvs_cell* __restrict__ F_next, int64_t capacity,
@@ -189,7 +226,7 @@ __global__ __launch_bounds__(kLkThreads) void k_link_hook(const mvs_cell* __rest
         const unsigned long long e = best_idx[c];
         if (e == kNone) continue;                                      // not a root, or a root nothing leaves
         LkEdge g;
-        if (lk_edge(F, n_f, L, (int64_t)e, norms_sq, n, d, g) != kLkEdge) continue;   // (pick wrote the index of an edge)
+        if (lk_edge(F, n_f, L, (int64_t)e, norms_sq, core, n, d, g) != kLkEdge) continue;   // (pick wrote the index of an edge)
         const int32_t ca = comp[g.lo], cb = comp[g.hi];
         const int32_t o = ca == (int32_t)c ? cb : ca;
         const bool mutual = best_key[o] == best_key[c] && best_pair[o] == best_pair[c];
@@ -234,9 +271,9 @@ __global__ __launch_bounds__(kLkThreads) void k_link_apply(int32_t* __restrict__
     for (int64_t i = (int64_t)blockIdx.x * kLkThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kLkThreads) comp[i] = next[comp[i]];
 }
 
-// the forest as links (unsorted): a = lo, b = hi, dot, q as the comparison reports it, the fp64 score
+// the forest as links (unsorted): a = lo, b = hi, dot, q as the comparison reports it, the fp64 weight (J; with core values m)
 __global__ __launch_bounds__(kLkThreads) void k_link_links(const mvs_cell* __restrict__ F, int64_t n_f, const double* __restrict__ norms_sq,
-                                                           int d, mvs_link* __restrict__ links) {
+                                                           const double* __restrict__ core, int d, mvs_link* __restrict__ links) {
     for (int64_t i = (int64_t)blockIdx.x * kLkThreads + threadIdx.x; i < n_f; i += (int64_t)gridDim.x * kLkThreads) {
         const mvs_cell c = F[i];
         mvs_link l;
@@ -244,7 +281,8 @@ __global__ __launch_bounds__(kLkThreads) void k_link_links(const mvs_cell* __res
         l.b = c.col;
         l.dot = c.dot;
         l.q = quantize_cell(c.dot, d, norms_sq[c.row], norms_sq[c.col]);
-        l.jaccard = lk_jaccard(c.dot, d, norms_sq[c.row], norms_sq[c.col]);
+        unsigned long long key;
+        (void)lk_weight(lk_jaccard(c.dot, d, norms_sq[c.row], norms_sq[c.col]), core, c.row, c.col, l.jaccard, key);
         links[i] = l;
     }
 }
@@ -302,26 +340,31 @@ int launch_link_slots(hipStream_t stream, const LinkState& s) {
     return 0;
 }
 
-int launch_link_select(hipStream_t stream, const LinkState& s, const mvs_cell* d_cells, int64_t n_cells, int pass, bool first) {
+int launch_link_select(hipStream_t stream, const LinkState& s, const double* d_core, const mvs_cell* d_cells, int64_t n_cells, int pass,
+                       bool first) {
     const int64_t total = s.n_forest + n_cells;
     if (total <= 0) return 0;
     const dim3 grid(lk_grid(total)), block(kLkThreads);
 #define MVS_LINK_SELECT(P)                                                                                                            \
-    hipLaunchKernelGGL(k_link_select<P>, grid, block, 0, stream, s.forest, s.n_forest, d_cells, n_cells, s.norms_sq, s.n, s.d, s.comp, \
-                       s.best_key, s.best_pair, s.best_idx, first ? 1 : 0, s.counters)
+    hipLaunchKernelGGL(k_link_select<P>, grid, block, 0, stream, s.forest, s.n_forest, d_cells, n_cells, s.norms_sq, d_core, s.n, s.d, \
+                       s.comp, s.best_key, s.best_pair, s.best_idx, first ? 1 : 0, s.counters)
     if (pass == 0) MVS_LINK_SELECT(0);
     else if (pass == 1) MVS_LINK_SELECT(1);
     else MVS_LINK_SELECT(2);
 #undef MVS_LINK_SELECT
     return 0;
 }
+int launch_link_select(hipStream_t stream, const LinkState& s, const mvs_cell* d_cells, int64_t n_cells, int pass, bool first) {
+    return launch_link_select(stream, s, nullptr, d_cells, n_cells, pass, first);
+}
 
-int launch_link_hook(hipStream_t stream, const LinkState& s, const mvs_cell* d_cells) {
+int launch_link_hook(hipStream_t stream, const LinkState& s, const double* d_core, const mvs_cell* d_cells) {
     if (s.n <= 0) return 0;
-    hipLaunchKernelGGL(k_link_hook, dim3(lk_grid(s.n)), dim3(kLkThreads), 0, stream, s.forest, s.n_forest, d_cells, s.norms_sq, s.n, s.d,
-                       s.comp, s.best_key, s.best_pair, s.best_idx, s.next, s.forest_next, s.capacity, s.counters);
+    hipLaunchKernelGGL(k_link_hook, dim3(lk_grid(s.n)), dim3(kLkThreads), 0, stream, s.forest, s.n_forest, d_cells, s.norms_sq, d_core, s.n,
+                       s.d, s.comp, s.best_key, s.best_pair, s.best_idx, s.next, s.forest_next, s.capacity, s.counters);
     return 0;
 }
+int launch_link_hook(hipStream_t stream, const LinkState& s, const mvs_cell* d_cells) { return launch_link_hook(stream, s, nullptr, d_cells); }
 
 int launch_link_jump(hipStream_t stream, const LinkState& s) {
     if (s.n <= 0) return 0;
@@ -332,8 +375,8 @@ int launch_link_jump(hipStream_t stream, const LinkState& s) {
 
 // the forest's links, sorted best first, into d_links (n_forest entries); d_tmp: as many again; scratch as rocprim's merge sort
 // wants it (d_scratch == NULL: *scratch_needed only)
-int link_sorted(hipStream_t stream, const LinkState& s, mvs_link* d_tmp, mvs_link* d_links, void* d_scratch, size_t scratch_bytes,
-                size_t* scratch_needed) {
+int link_sorted(hipStream_t stream, const LinkState& s, const double* d_core, mvs_link* d_tmp, mvs_link* d_links, void* d_scratch,
+                size_t scratch_bytes, size_t* scratch_needed) {
     size_t need = 0;
     hipError_t e = rocprim::merge_sort(nullptr, need, d_tmp, d_links, (size_t)s.n_forest, LinkBefore(), stream);
     if (e != hipSuccess) return MVS_E_HIP;
@@ -341,9 +384,13 @@ int link_sorted(hipStream_t stream, const LinkState& s, mvs_link* d_tmp, mvs_lin
     if (d_scratch == nullptr) return 0;
     if (scratch_bytes < need) return MVS_E_CAPACITY;
     if (s.n_forest <= 0) return 0;
-    hipLaunchKernelGGL(k_link_links, dim3(lk_grid(s.n_forest)), dim3(kLkThreads), 0, stream, s.forest, s.n_forest, s.norms_sq, s.d, d_tmp);
+    hipLaunchKernelGGL(k_link_links, dim3(lk_grid(s.n_forest)), dim3(kLkThreads), 0, stream, s.forest, s.n_forest, s.norms_sq, d_core, s.d, d_tmp);
     e = rocprim::merge_sort(d_scratch, need, d_tmp, d_links, (size_t)s.n_forest, LinkBefore(), stream);
     return e == hipSuccess ? 0 : MVS_E_HIP;
+}
+int link_sorted(hipStream_t stream, const LinkState& s, mvs_link* d_tmp, mvs_link* d_links, void* d_scratch, size_t scratch_bytes,
+                size_t* scratch_needed) {
+    return link_sorted(stream, s, nullptr, d_tmp, d_links, d_scratch, scratch_bytes, scratch_needed);
 }
 
 // counters[5] += links above `level` (the caller cleared it)
