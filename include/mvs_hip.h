@@ -149,6 +149,9 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   groups_dots, groups_block_rows
  *                         mvs_group_sums / mvs_permanova: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0
  *                         bounds the rows of a block (0: by the device budget)
+ *   labels_dots, labels_block_rows
+ *                         mvs_label_sums / mvs_silhouette: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0
+ *                         bounds the rows of a block (0: by the device budget)
  *   core_block_rows       mvs_core_jaccard / mvs_hdbscan: > 0 bounds the rows of a top-k range (0: by the cell buffer's budget)
  *   gram_slab_rows        mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536 (default
  *                         65536; rounded down to a multiple of 64)
@@ -1282,6 +1285,85 @@ int mvs_permanova(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_s
                   mvs_permanova_result* result, int64_t* group_sizes, double* group_mean_d2, double* perm_f);
 int mvs_ctx_groups_stats(const mvs_ctx* ctx, double* dots_ms, double* quantise_ms, double* sums_ms, int64_t* row_blocks,
                          int64_t* block_rows, int64_t* slots);
+
+/* ---- Labelling quality: silhouette, nearest group, medoids and dispersion, matrix-free ---------------------
+ * Five calls here write a labelling of a set (clusters at a level, a cut of the tree, representatives, HDBSCAN*, a user's
+ * metadata).  These judge one: per sample the silhouette, the nearest other group and the squared distance to the own group's
+ * centroid; per group the medoid, the mean silhouette and the dispersion (what betadisper reports).  All of it follows from
+ * the per-sample sums of distances to every group, B[i][g] = sum over j in g of w(i,j); only the own group's and the nearest
+ * other group's entry of a row are kept, so neither the n x n matrix nor the sample x group table is stored, and the number
+ * of groups is not bounded.
+ *
+ * The weight of a cell.  k(i,j) is the rule of "principal coordinates" above, word for word (unit diagonal, floor, any norms).
+ * Then, fp64, ONE rounding per line:
+ *     t      = 1.0 - k(i,j)
+ *     w(i,j) = (uint32) rint(t * 1073741824.0)             2^30; 0 on the diagonal, 2^30 for k = 0
+ * -- the weight of "PERMANOVA" above.  1 - k is the Jaccard distance, so w is that distance in units of 2^-30; it is also d^2
+ * in the geometry sqrt(1 - k) of the principal coordinates.  Every sum of w is an INTEGER.
+ *
+ * mvs_label_sums      F = [row_begin, row_end) of a resident set, m = |F|; labels: m HOST int32 in [-1, groups), labels[i -
+ *                     row_begin] the group of sample i, -1 = unlabelled (noise, or not named); groups >= 1; ids may be sparse
+ *                     (empty groups are allowed).  Per sample i of F with g = labels[i]:
+ *                         own_sum[i]    = sum of w(i,j) over j in F with labels[j] = g                  (0 for g = -1)
+ *                         B_ih          = sum of w(i,j) over j in F with labels[j] = h, for every non-empty group h != g
+ *                         mean_ih       = (double)B_ih / (double)n_h                                    one IEEE division
+ *                         near_group[i] = the h with the smallest (mean_ih, h): equal doubles go to the smaller id
+ *                         near_sum[i]   = B_ih of that group
+ *                     Without such a group near_group[i] = -1 and near_sum[i] = 0.  sizes[g] = #{i in F : labels[i] = g}
+ *                     (NULL: not wanted).  Unlabelled samples are rows, never columns: they have a nearest group and belong
+ *                     to nobody's sums.  own_sum, near_sum: HOST uint64 [m]; near_group: HOST int32 [m]; all three needed
+ *                     unless the range is empty.  The host sorts F by label (stable, unlabelled last) and gathers the set and
+ *                     the norms into that order (mvs_sketch_set_gather), so that a group is an interval of columns; rows go in
+ *                     blocks sized as mvs_group_sums sizes them without the clamp (options labels_block_rows, labels_dots);
+ *                     per block one dense-dots launch against the labelled columns and one kernel that takes the weight from
+ *                     the dot in registers and reduces the row by segments.  O(m) bytes cross the link.  Device memory besides
+ *                     the set: the gathered copy, one dots block, O(m) arrays.  No sum wraps: a row's sum is at most
+ *                     m * 2^30 < 2^61 for m <= 2^31 - 1; a larger m is refused.  The results do not depend on the row
+ *                     blocking, the dots kernel or the order of the labels.  An empty range: MVS_OK, zero sizes.
+ *                     MVS_E_INVALID: a label outside [-1, groups), groups < 1, floor outside [0, 1) or NaN, a range outside
+ *                     the set, a NULL buffer that is needed.
+ * mvs_silhouette_stats  pure host: labels, sizes and the three arrays of mvs_label_sums -> the numbers.  fp64, each line one
+ *                     rounding.  Per labelled sample, n_g the size of its group and n_near that of near_group[i]:
+ *                         a           = ((double)own_sum / (double)(n_g - 1)) * 2^-30                   0 for n_g = 1
+ *                         b           = ((double)near_sum / (double)n_near) * 2^-30
+ *                         s           = (b - a) / max(a, b)           0 for n_g = 1 or max(a, b) = 0 (scikit-learn's convention)
+ *                         centroid_d2 = ((double)own_sum / (double)n_g - ((double)W_g / (double)n_g) / (double)n_g) * 2^-30
+ *                     W_g = (sum of own_sum over the group) / 2, exact in 128 bits (an odd sum: MVS_E_INTERNAL, as in
+ *                     mvs_group_sums).  centroid_d2 is the squared distance to the group's centroid in the principal
+ *                     coordinates; it may be negative because the estimated kernel is not Euclidean, and is reported as it is.
+ *                     Per unlabelled sample s, a and centroid_d2 are NaN; b (and the nearest group) are given.  Per group g:
+ *                         medoids[g]          = the member with the smallest (own_sum, index), as an index into F (-1: empty)
+ *                         group_mean_s[g]     = (sum of s over the members in ascending index) / n_g            (NaN: empty)
+ *                         group_dispersion[g] = (sum of centroid_d2 over the members in ascending index) / n_g  (NaN: empty)
+ *                         group_within[g]     = ((double)W_g / (double)(n_g (n_g - 1) / 2)) * 2^-30, 0 for n_g < 2 -- the
+ *                                               group_mean_d2 of mvs_permanova_stats
+ *                     result: mean = (sum of s over the labelled samples in ascending index) / their number; negative = the
+ *                     labelled samples with s < 0; samples = m; labelled; groups = the non-empty ones.  Every output array but
+ *                     `result` may be NULL.  MVS_E_INVALID: fewer than 2 non-empty groups, sizes that are not those of the
+ *                     labels, a near_group that is not another non-empty group, a label outside [-1, groups), a NULL input.
+ * mvs_silhouette      mvs_label_sums, then mvs_silhouette_stats; group_sizes [groups] and nearest [m] (near_group) may be NULL
+ *                     like the arrays of the statistic.  Fewer than 2 non-empty groups is refused before any launch.
+ * mvs_ctx_label_stats of the context's last mvs_label_sums / mvs_silhouette: kernel times of the dots and of the reduction
+ *                     summed over the row blocks, the time of the gather (all 0 unless mvs_ctx_set_timing is on), row blocks,
+ *                     rows per block.  Any pointer may be NULL.
+ * All synchronous.  The kernel is in csrc/mvs_labelsum.hip. */
+typedef struct {
+    double mean;                                   /* mean silhouette of the labelled samples */
+    int64_t negative, samples, labelled, groups;   /* groups: the non-empty ones */
+} mvs_silhouette_result;
+int mvs_label_sums(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double floor, int64_t row_begin,
+                   int64_t row_end, const int32_t* labels, int groups, uint64_t* own_sum, int32_t* near_group, uint64_t* near_sum,
+                   int64_t* sizes);
+int mvs_silhouette_stats(const int32_t* labels, int64_t m, int groups, const int64_t* sizes, const uint64_t* own_sum,
+                         const int32_t* near_group, const uint64_t* near_sum, mvs_silhouette_result* result, double* s, double* a,
+                         double* b, double* centroid_d2, double* group_mean_s, double* group_within, double* group_dispersion,
+                         int64_t* medoids);
+int mvs_silhouette(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double floor, int64_t row_begin,
+                   int64_t row_end, const int32_t* labels, int groups, mvs_silhouette_result* result, int64_t* group_sizes,
+                   int32_t* nearest, double* s, double* a, double* b, double* centroid_d2, double* group_mean_s, double* group_within,
+                   double* group_dispersion, int64_t* medoids);
+int mvs_ctx_label_stats(const mvs_ctx* ctx, double* dots_ms, double* reduce_ms, double* gather_ms, int64_t* row_blocks,
+                        int64_t* block_rows);
 
 /* ---- multi-GPU exchange ---------------------------------------------------------------------------
  * One process per GPU; shard k of src/pairwise_comp_optimized.cpp:938-940 is rank k.  Where the reference's shard

@@ -62,6 +62,11 @@ class PermanovaResult(ctypes.Structure):
                 ("samples", _c.c_int64), ("groups", _c.c_int64), ("permutations", _c.c_int64)]
 
 
+class SilhouetteResult(ctypes.Structure):
+    """mvs_silhouette_result"""
+    _fields_ = [("mean", _c.c_double), ("negative", _c.c_int64), ("samples", _c.c_int64), ("labelled", _c.c_int64), ("groups", _c.c_int64)]
+
+
 SYMBOLS = [
     ("mvs_version", _c.c_char_p, []),
     ("mvs_last_error", _c.c_char_p, []),
@@ -159,6 +164,12 @@ SYMBOLS = [
                                   _c.POINTER(PermanovaResult), _P, _P, _P]),
     ("mvs_ctx_groups_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                                          _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_label_sums", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _P, _P, _P]),
+    ("mvs_silhouette_stats", _c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _P, _P, _c.POINTER(SilhouetteResult), _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("mvs_silhouette", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _c.c_int64, _c.c_int64, _P, _c.c_int, _c.POINTER(SilhouetteResult),
+                                   _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("mvs_ctx_label_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
+                                        _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     ("mvs_cluster_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_cluster_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
     ("mvs_pairwise_cluster", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
@@ -838,6 +849,49 @@ def permanova_stats(sums, sizes, m):
     _check(load_library().mvs_permanova_stats(lo.ctypes.data, hi.ctypes.data, sizes.ctypes.data, slots - 2, groups, int(m), ctypes.byref(res),
                                               mean.ctypes.data, perm_f.ctypes.data))
     return Permanova(res, sizes[0].copy(), mean, perm_f)
+
+
+class Silhouette:
+    """The result of Context.silhouette (mvs_silhouette) or silhouette_stats: per sample of the range `samples` (the silhouette s),
+    `a`, `b`, `centroid_d2` float64 and `nearest` int32 (s, a and centroid_d2 are NaN for an unlabelled sample); `mean` (of s over
+    the labelled samples), `negative` (labelled samples with s < 0), `labelled`, `groups` (the non-empty ones); per group id
+    `group_sizes` int64, `group_mean` (of s), `group_within` (mean distance inside the group), `group_dispersion` (mean
+    centroid_d2) float64 and `medoids` int64 (an index into the range, -1 for an empty group)"""
+
+    def __init__(self, res, samples, a, b, nearest, centroid_d2, group_sizes, group_mean, group_within, group_dispersion, medoids):
+        self.mean, self.negative, self.labelled, self.groups = res.mean, res.negative, res.labelled, res.groups
+        self.samples, self.a, self.b, self.nearest, self.centroid_d2 = samples, a, b, nearest, centroid_d2
+        self.group_sizes, self.group_mean, self.group_within, self.group_dispersion, self.medoids = \
+            group_sizes, group_mean, group_within, group_dispersion, medoids
+
+
+def _labels(labels, m=None):
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim != 1 or (m is not None and len(lab) != m):
+        raise ValueError("labels must have one entry per row of the range")
+    return lab
+
+
+def silhouette_stats(labels, sizes, own_sum, near_group, near_sum):
+    """mvs_silhouette_stats: labels int32 [m] (-1: unlabelled), sizes int64 [groups] and the three arrays of Context.label_sums
+    -> Silhouette.  Needs no device."""
+    lab = _labels(labels)
+    m = len(lab)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    groups = len(sizes)
+    own = np.ascontiguousarray(own_sum, dtype=np.uint64)
+    near = np.ascontiguousarray(near_group, dtype=np.int32)
+    nsum = np.ascontiguousarray(near_sum, dtype=np.uint64)
+    if not (len(own) == len(near) == len(nsum) == m):
+        raise ValueError("the arrays must have one entry per label")
+    res = SilhouetteResult()
+    s, a, b, c2 = (np.zeros(m, dtype=np.float64) for _ in range(4))
+    gm, gw, gd = (np.zeros(groups, dtype=np.float64) for _ in range(3))
+    med = np.zeros(groups, dtype=np.int64)
+    _check(load_library().mvs_silhouette_stats(lab.ctypes.data, m, groups, sizes.ctypes.data, own.ctypes.data, near.ctypes.data, nsum.ctypes.data,
+                                               ctypes.byref(res), s.ctypes.data, a.ctypes.data, b.ctypes.data, c2.ctypes.data, gm.ctypes.data,
+                                               gw.ctypes.data, gd.ctypes.data, med.ctypes.data))
+    return Silhouette(res, s, a, b, near.copy(), c2, sizes.copy(), gm, gw, gd, med)
 
 
 class Pcoa(_Handle):
@@ -1753,6 +1807,50 @@ class Context:
         _check(self.lib.mvs_ctx_groups_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n), ctypes.byref(r),
                                              ctypes.byref(k)))
         return {"dots_ms": a.value, "quantise_ms": b.value, "sums_ms": e.value, "row_blocks": n.value, "block_rows": r.value, "slots": k.value}
+
+    # ---- the quality of a labelling on the Jaccard estimates (include/mvs_hip.h "Labelling quality") ----
+    def label_sums(self, sset, norms_sq, labels, groups=None, rows=None, floor=0.0):
+        """mvs_label_sums: labels int32 [m] in [-1, groups), -1 = unlabelled, m the size of `rows` = (begin, end) of `sset` (default
+        all); groups defaults to max(labels) + 1 -> (own_sum uint64 [m], near_group int32 [m], near_sum uint64 [m], sizes int64
+        [groups]): the sum of the quantised distances w to the sample's own group, the other group with the smallest mean
+        distance (-1: none) and the sum over that group"""
+        rb, re = (0, sset.n) if rows is None else rows
+        m = max(0, int(re) - int(rb))
+        lab = _labels(labels, m)
+        groups = (max(1, int(lab.max()) + 1) if m else 1) if groups is None else int(groups)
+        np_, nm, nk = _norms(norms_sq)
+        own, nsum = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64)
+        near = np.full(m, -1, dtype=np.int32)
+        sizes = np.zeros(max(0, groups), dtype=np.int64)
+        _check(self.lib.mvs_label_sums(self._h, sset._h, np_, nm, float(floor), int(rb), int(re), lab.ctypes.data, groups, own.ctypes.data,
+                                       near.ctypes.data, nsum.ctypes.data, sizes.ctypes.data))
+        return own, near, nsum, sizes
+
+    def silhouette(self, sset, norms_sq, labels, rows=None, floor=0.0):
+        """mvs_silhouette: labels int32 [m], one group id per sample of `rows` = (begin, end) of `sset` (default all), -1 =
+        unlabelled; the number of group ids is max(labels) + 1 -> Silhouette"""
+        rb, re = (0, sset.n) if rows is None else rows
+        m = max(0, int(re) - int(rb))
+        lab = _labels(labels, m)
+        groups = max(1, int(lab.max()) + 1) if m else 1
+        np_, nm, nk = _norms(norms_sq)
+        res = SilhouetteResult()
+        s, a, b, c2 = (np.zeros(m, dtype=np.float64) for _ in range(4))
+        near = np.full(m, -1, dtype=np.int32)
+        sizes, med = np.zeros(groups, dtype=np.int64), np.zeros(groups, dtype=np.int64)
+        gm, gw, gd = (np.zeros(groups, dtype=np.float64) for _ in range(3))
+        _check(self.lib.mvs_silhouette(self._h, sset._h, np_, nm, float(floor), int(rb), int(re), lab.ctypes.data, groups, ctypes.byref(res),
+                                       sizes.ctypes.data, near.ctypes.data, s.ctypes.data, a.ctypes.data, b.ctypes.data, c2.ctypes.data,
+                                       gm.ctypes.data, gw.ctypes.data, gd.ctypes.data, med.ctypes.data))
+        return Silhouette(res, s, a, b, near, c2, sizes, gm, gw, gd, med)
+
+    def label_stats(self):
+        """-> dict of the last label_sums / silhouette: dots_ms, reduce_ms (kernel times over its row blocks), gather_ms (timing
+        on), row_blocks, block_rows"""
+        a, b, e = _c.c_double(), _c.c_double(), _c.c_double()
+        n, r = _c.c_int64(), _c.c_int64()
+        _check(self.lib.mvs_ctx_label_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n), ctypes.byref(r)))
+        return {"dots_ms": a.value, "reduce_ms": b.value, "gather_ms": e.value, "row_blocks": n.value, "block_rows": r.value}
 
     def _consumer_stats(self, fn, work_key):
         """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time

@@ -423,6 +423,16 @@ int mvs_ctx_set_option(mvs_ctx* c, const char* name, int64_t value) {
         c->core_block_rows = (int)value;
         return MVS_OK;
     }
+    if (std::strcmp(name, "labels_dots") == 0) {             // mvs_label_sums: which dense-dots kernel its blocks take
+        if (value < 0 || value > 1) return fail(MVS_E_INVALID, "option labels_dots: 0 or 1");
+        c->labels_dots = (int)value;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "labels_block_rows") == 0) {       // host-side blocking only
+        if (value < 0 || value > (1 << 30)) return fail(MVS_E_INVALID, "option labels_block_rows: 0 .. 2^30 rows");
+        c->labels_block_rows = (int)value;
+        return MVS_OK;
+    }
     if (std::strcmp(name, "report_spin") == 0) {             // host-side waiting only
         if (value < 0 || value > 1000000) return fail(MVS_E_INVALID, "option report_spin: 0 .. 1000000 microseconds");
         c->report_spin = (int)value;
@@ -441,6 +451,14 @@ int mvs_ctx_get_option(const mvs_ctx* c, const char* name, int64_t* value) {
     }
     if (std::strcmp(name, "core_block_rows") == 0) {
         *value = c->core_block_rows;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "labels_dots") == 0) {
+        *value = c->labels_dots;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "labels_block_rows") == 0) {
+        *value = c->labels_block_rows;
         return MVS_OK;
     }
     if (std::strcmp(name, "report_spin") == 0) {

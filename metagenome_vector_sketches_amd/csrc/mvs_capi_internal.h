@@ -51,6 +51,14 @@ struct GroupsStats {
     long long blocks = 0, block_rows = 0, slots = 0;
     void reset() { *this = GroupsStats(); }
 };
+// what the last mvs_label_sums / mvs_silhouette did on a context (mvs_ctx_label_stats): kernel times of the dots and of the
+// segmented reduction summed over the row blocks, the time of the gather into label order (timing enabled), row blocks, rows
+// per block
+struct LabelStats {
+    double dots_ms = 0.0, reduce_ms = 0.0, gather_ms = 0.0;
+    long long blocks = 0, block_rows = 0;
+    void reset() { *this = LabelStats(); }
+};
 // what the last mvs_core_jaccard / mvs_hdbscan did on a context (mvs_ctx_hdbscan_stats): kernel times of the core pass (top-k's
 // dots and selection summed over the ranges, k_core_kth), of the comparison and the forest, the host time of the selection;
 // top-k ranges, Boruvka rounds, links, fed cells
@@ -204,6 +212,11 @@ struct mvs_ctx {
     mvs_capi::ConsumerStats cl, lk, dr;
     mvs_capi::GroupsStats gs;
     mvs_capi::HdbscanStats hd;
+    mvs_capi::LabelStats ls;
+    int labels_dots = 0;                  // mvs_label_sums / mvs_silhouette: dots of a row block from 0 = the matrix-core kernels, 1 = the
+                                          // vector-ALU kernel (A/B, tests); same sums (option labels_dots)
+    int labels_block_rows = 0;            // ... and > 0 = upper bound on the rows of a block (tests); 0 = by the device budget.  Host-side
+                                          // blocking only (option labels_block_rows)
     int core_block_rows = 0;              // mvs_core_jaccard / mvs_hdbscan: > 0 = upper bound on the rows of a top-k range (tests); 0 = by
                                           // the cell buffer's budget.  Host-side blocking only (option core_block_rows)
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call

@@ -32,6 +32,7 @@
 // weighs 0).  Wrap: a lane's accumulator is at most cols x 2^30 and acc[slot][group] at most rows x ld x 2^30 per block; the
 // launch refuses rows x ld >= 2^34, and the caller sizes its blocks under that bound and clears acc between them.
 #include "mvs_internal.h"
+#include "mvs_weight_dev.h"      // quantised_distance: the weight of a cell, shared with mvs_labelsum.hip
 
 #include <climits>
 
@@ -43,18 +44,6 @@ constexpr int kGroupRows = 8;        // rows per wave: 8 x 4 slots x 64-bit accu
 constexpr int kGroupWaves = 4;       // waves per workgroup: consecutive row groups of one slot tile
 constexpr int kGroupTile = 256;      // slots per tile: 64 lanes x 4 packed labels
 constexpr int kGroupMinCols = 64;    // shortest column chunk of a workgroup
-
-// w of the rule for i != j; pow2: d is a power of two and inv = 1 / d
-__device__ __forceinline__ uint32_t quantised_distance(int32_t P, double n2r, double n2c, double dd, double inv, bool pow2, double floor_) {
-#pragma clang fp contract(off)
-    const double inter = pow2 ? (double)P * inv : (double)P / dd;
-    const double s = n2r + n2c;
-    const double den = s - inter;
-    const double J = inter / den;
-    const double k = !(J > floor_) ? 0.0 : (J > 1.0 ? 1.0 : J);
-    const double t = 1.0 - k;
-    return (uint32_t)rint(t * 1073741824.0);
-}
 
 // cells: rows x ld, int32 dots in, uint32 weights out (row r of the block is sample row0 + r, column j is sample c0 + j); a lane
 // takes four consecutive cells of a row, with one 16-byte load and store where every row of the block is 16-byte aligned
