@@ -152,6 +152,10 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   labels_dots, labels_block_rows
  *                         mvs_label_sums / mvs_silhouette: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0
  *                         bounds the rows of a block (0: by the device budget)
+ *   hclust_dots, hclust_block_rows, hclust_compact
+ *                         mvs_hclust: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds the rows
+ *                         of a block of the fill (0: by the device budget); the table's columns are compacted never (0), when
+ *                         at most half are alive (1, default), after every round (2).  None changes a record
  *   core_block_rows       mvs_core_jaccard / mvs_hdbscan: > 0 bounds the rows of a top-k range (0: by the cell buffer's budget)
  *   gram_slab_rows        mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536 (default
  *                         65536; rounded down to a multiple of 64)
@@ -1364,6 +1368,88 @@ int mvs_silhouette(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_
                    double* group_dispersion, int64_t* medoids);
 int mvs_ctx_label_stats(const mvs_ctx* ctx, double* dots_ms, double* reduce_ms, double* gather_ms, int64_t* row_blocks,
                         int64_t* block_rows);
+
+/* ---- Average and complete linkage: the agglomerative tree of the Jaccard distances ---------------------------
+ * Single linkage (mvs_pairwise_linkage) chains.  Average linkage (UPGMA) and complete linkage do not, but they need the
+ * distance between GROUPS, a sum (or maximum) over all cross pairs: this is the one clustering here that keeps the m x m
+ * table, 8 m^2 bytes on the device.  It keeps it in integers: with the weight w = rint((1 - k) * 2^30) of "Labelling quality"
+ * above, a merge is an addition, an average is one rational number, and no order of rounds, blocks or lanes changes a merge.
+ *
+ * State.  Slots 0 .. m-1, each alive or dead, a live slot s with a size n_s >= 1; a symmetric table S[a][b] of uint64: for
+ * MVS_HCLUST_AVERAGE the sum of w over the cross pairs of the clusters in slots a and b, for MVS_HCLUST_COMPLETE their maximum.
+ * The diagonal is never read.  A slot's index is the smallest member of its cluster.
+ *
+ * A round.  Every live row r names its nearest live column c != r: the one with the smallest (value, key).
+ *     average:   value = S[r][c] / n_c as an exact rational -- S1 / n1 < S2 / n2 iff S1 * n2 < S2 * n1, in 128 bits
+ *     complete:  value = S[r][c]
+ *     key(r, c) = splitmix64(((uint64)min(r, c) << 32) | max(r, c)), splitmix64(x): x += 0x9E3779B97F4A7C15;
+ *                 x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; return x ^ x >> 31
+ * Keys of distinct pairs are distinct, so the order is total; the key is symmetric, so the globally smallest pair is mutual
+ * and every round merges at least one pair -- and a clique of equal distances halves per round instead of losing one slot
+ * per round, as it would with "ties go to the smaller column".
+ * All mutual pairs (a, b), a < b, nearest[a] = b and nearest[b] = a, merge in that round:
+ *     first every live row r, the dying ones included:  S[r][a] = S[r][a] (+) S[r][b]          for every pair
+ *     then every pair, over the live columns c:          S[a][c] = S[a][c] (+) S[b][c]
+ *     then n_a += n_b and b dies
+ * (+) is + for average and max for complete.  Rounds repeat until one slot lives: m - 1 merges.
+ *
+ * A merge record, mvs_hmerge: a < b the two slots, round (from 0), size = n_a + n_b, sum = S[a][b] before the merge, and
+ *     average:   height = ((double)sum / ((double)n_a * (double)n_b)) * 2^-30     one IEEE division; the product is exact
+ *     complete:  height = (double)sum * 2^-30
+ * Records are in (round, a) ascending order.  Both linkages are reducible: a merge's exact value is never below that of its
+ * children (the double heights follow wherever a sum is below 2^53).
+ *
+ * Bounds.  The total of the sizes is <= 2^17 = 131072 and every entry <= n_a * n_b * 2^30, so no sum reaches 2^63; anything
+ * beyond: MVS_E_INVALID.  A table the device cannot hold: MVS_E_NOMEM, the message names the bytes asked for (8 m^2 for the
+ * table, rows padded to an even length, plus one block of dots).
+ *
+ * mvs_hclust_sums     the engine.  sums: m x m uint64, row-major, HOST or DEVICE (mem), symmetric off the diagonal (checked;
+ *                     the diagonal is ignored); sizes: m HOST int32 >= 1, NULL = all ones.  For a caller who starts from
+ *                     groups already formed (representatives with their group sizes).  merges: m - 1 HOST records; rounds
+ *                     (may be NULL): the rounds it took.  The caller's table is copied, not changed.
+ * mvs_hclust_weights  w: m x m uint32 <= 2^30, row-major, HOST or DEVICE, symmetric off the diagonal; unit sizes.
+ * mvs_hclust          F = [row_begin, row_end) of a resident set, m = |F|; slot i is sample row_begin + i.  Rows go in blocks
+ *                     (options hclust_block_rows, hclust_dots): one dense-dots launch, then a kernel that writes the
+ *                     table's rows with the weight of "Labelling quality".  The table stays on the device; the records
+ *                     cross the link.  MVS_E_INVALID: floor outside [0, 1) or NaN, a range outside the set.
+ * Per round: one workgroup per live row scans the live columns (16-byte loads; the exact comparison per lane, one reduction
+ * through the wave and LDS); one workgroup finds the mutual pairs with a prefix scan over the live rows in ascending order --
+ * which is the records' order --, writes records, sizes and the next list of live rows; the column phase and the row phase of
+ * the merge are two launches.  Option hclust_compact: 1 (default) when at most half the columns of the layout are alive, the
+ * columns of every live row are compacted in place (rows stay where they are: the table is never held twice), 2 after every
+ * round, 0 never.  Neither option changes a record.  m = 1: MVS_OK, no merges.  MVS_E_INVALID: an unknown method, m < 1, an
+ * asymmetric table, an entry or a size outside the bounds, a NULL that is needed.
+ *
+ * Pure host, no device (like mvs_hdbscan_select); merges: the m - 1 records of one of the calls above:
+ * mvs_hclust_order      Z: double [m - 1][4], SciPy's linkage matrix.  The merges sorted by (height, round, a); a leaf has
+ *                       its index as id, the t-th merge of the sorted order the id m + t; Z[t] = {the smaller id, the larger
+ *                       id, height, size} of the clusters in slots a and b.
+ * mvs_hclust_cut        labels: int32 [m] after the merges with height <= `height` (NaN: MVS_E_INVALID).
+ * mvs_hclust_cut_count  labels after the first m - k merges of the sorted order: k clusters, 1 <= k <= m.
+ *                       Labels are 0-based in ascending order of each cluster's smallest member.
+ * mvs_ctx_hclust_stats  of the context's last call: kernel times of the dots and the fill summed over the row blocks, of the
+ *                       nearest pass, the merge (pairs + both phases) and the compactions summed over the rounds (all 0
+ *                       unless mvs_ctx_set_timing is on); rounds, row scans, bytes of the table the scans read, compactions.
+ *                       Any pointer may be NULL.
+ * All synchronous.  The kernels are in csrc/mvs_hclust.hip. */
+#define MVS_HCLUST_AVERAGE 0
+#define MVS_HCLUST_COMPLETE 1
+#define MVS_HCLUST_MAX_TOTAL 131072
+typedef struct {
+    int32_t a, b, round, size;
+    uint64_t sum;
+    double height;
+} mvs_hmerge;
+int mvs_hclust_sums(mvs_ctx* ctx, const uint64_t* sums, int mem, const int32_t* sizes, int64_t m, int method, mvs_hmerge* merges,
+                    int64_t* rounds);
+int mvs_hclust_weights(mvs_ctx* ctx, const uint32_t* w, int mem, int64_t m, int method, mvs_hmerge* merges, int64_t* rounds);
+int mvs_hclust(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double floor, int64_t row_begin,
+               int64_t row_end, int method, mvs_hmerge* merges, int64_t* rounds);
+int mvs_hclust_order(int64_t m, const mvs_hmerge* merges, double* Z);
+int mvs_hclust_cut(int64_t m, const mvs_hmerge* merges, double height, int32_t* labels);
+int mvs_hclust_cut_count(int64_t m, const mvs_hmerge* merges, int64_t k, int32_t* labels);
+int mvs_ctx_hclust_stats(const mvs_ctx* ctx, double* dots_ms, double* fill_ms, double* nearest_ms, double* merge_ms, double* compact_ms,
+                         int64_t* rounds, int64_t* row_scans, int64_t* bytes_scanned, int64_t* compactions);
 
 /* ---- multi-GPU exchange ---------------------------------------------------------------------------
  * One process per GPU; shard k of src/pairwise_comp_optimized.cpp:938-940 is rank k.  Where the reference's shard

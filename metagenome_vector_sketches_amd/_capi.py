@@ -27,6 +27,9 @@ CELL_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("dot", "<i4"), ("q", "<i
 LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("dot", "<i4"), ("q", "<i4"), ("jaccard", "<f8")])      # mvs_link
 HDBSCAN_CLUSTER_DTYPE = np.dtype([("parent", "<i4"), ("size", "<i4"), ("selected", "<i4"), ("representative", "<i4"), ("birth", "<i8"),
                                   ("death", "<i8"), ("stability", "<i8")])                                       # mvs_hdbscan_cluster
+HMERGE_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("round", "<i4"), ("size", "<i4"), ("sum", "<u8"), ("height", "<f8")])            # mvs_hmerge
+HCLUST_METHODS = {"average": 0, "complete": 1}
+HCLUST_MAX_TOTAL = 131072
 GATHER_DTYPE = np.dtype([("sample", "<i4"), ("intersect", "<i4"), ("unique", "<i4"), ("remaining", "<i4")])  # mvs_gather_match
 
 # every symbol include/mvs_hip.h declares: (name, restype, argtypes)
@@ -170,6 +173,13 @@ SYMBOLS = [
                                    _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("mvs_ctx_label_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                                         _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    ("mvs_hclust_sums", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int64, _c.c_int, _P, _c.POINTER(_c.c_int64)]),
+    ("mvs_hclust_weights", _c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.POINTER(_c.c_int64)]),
+    ("mvs_hclust", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _c.c_int64, _c.c_int64, _c.c_int, _P, _c.POINTER(_c.c_int64)]),
+    ("mvs_hclust_order", _c.c_int, [_c.c_int64, _P, _P]),
+    ("mvs_hclust_cut", _c.c_int, [_c.c_int64, _P, _c.c_double, _P]),
+    ("mvs_hclust_cut_count", _c.c_int, [_c.c_int64, _P, _c.c_int64, _P]),
+    ("mvs_ctx_hclust_stats", _c.c_int, [_P] + [_c.POINTER(_c.c_double)] * 5 + [_c.POINTER(_c.c_int64)] * 4),
     ("mvs_cluster_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
     ("mvs_cluster_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
     ("mvs_pairwise_cluster", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
@@ -892,6 +902,65 @@ def silhouette_stats(labels, sizes, own_sum, near_group, near_sum):
                                                ctypes.byref(res), s.ctypes.data, a.ctypes.data, b.ctypes.data, c2.ctypes.data, gm.ctypes.data,
                                                gw.ctypes.data, gd.ctypes.data, med.ctypes.data))
     return Silhouette(res, s, a, b, near.copy(), c2, sizes.copy(), gm, gw, gd, med)
+
+
+def _hclust_method(method):
+    """'average' / 'complete' (or the ABI's number) -> MVS_HCLUST_*"""
+    if isinstance(method, str):
+        if method not in HCLUST_METHODS:
+            raise ValueError("method must be one of %s" % sorted(HCLUST_METHODS))
+        return HCLUST_METHODS[method]
+    return int(method)
+
+
+def _merges(m, merges):
+    mg = np.ascontiguousarray(merges, dtype=HMERGE_DTYPE)
+    if mg.ndim != 1 or len(mg) != max(0, int(m) - 1):
+        raise ValueError("a tree of m leaves has m - 1 merges")
+    return mg
+
+
+def hclust_order(m, merges):
+    """mvs_hclust_order: the m - 1 records of a Hclust -> SciPy's linkage matrix, float64 [m - 1, 4]: the merges sorted by
+    (height, round, a), a leaf's id its index, the t-th merge's id m + t.  Needs no device."""
+    mg = _merges(m, merges)
+    Z = np.zeros((len(mg), 4), dtype=np.float64)
+    _check(load_library().mvs_hclust_order(int(m), mg.ctypes.data, Z.ctypes.data))
+    return Z
+
+
+def hclust_cut(m, merges, height=None, clusters=None):
+    """mvs_hclust_cut (height: the merges with height <= it) or mvs_hclust_cut_count (clusters: the first m - clusters merges
+    of the sorted order) -> labels int32 [m], 0-based in ascending order of each cluster's smallest member.  Needs no device."""
+    if (height is None) == (clusters is None):
+        raise ValueError("give either height or clusters")
+    mg = _merges(m, merges)
+    labels = np.zeros(int(m), dtype=np.int32)
+    if height is not None:
+        _check(load_library().mvs_hclust_cut(int(m), mg.ctypes.data, float(height), labels.ctypes.data))
+    else:
+        _check(load_library().mvs_hclust_cut_count(int(m), mg.ctypes.data, int(clusters), labels.ctypes.data))
+    return labels
+
+
+class Hclust:
+    """The result of Context.hclust / hclust_weights / hclust_sums: `merges`, the m - 1 records (HMERGE_DTYPE: a < b the slots,
+    round, size, sum, height) in (round, a) order; `rounds`; `m`; `method` (0 average, 1 complete)"""
+
+    def __init__(self, m, method, merges, rounds):
+        self.m, self.method, self.merges, self.rounds = int(m), int(method), merges, int(rounds)
+
+    def linkage_matrix(self):
+        """-> SciPy's linkage matrix (hclust_order)"""
+        return hclust_order(self.m, self.merges)
+
+    def cut(self, height):
+        """-> labels int32 [m] after the merges with height <= `height`"""
+        return hclust_cut(self.m, self.merges, height=height)
+
+    def cut_count(self, k):
+        """-> labels int32 [m] of k clusters"""
+        return hclust_cut(self.m, self.merges, clusters=k)
 
 
 class Pcoa(_Handle):
@@ -1851,6 +1920,64 @@ class Context:
         n, r = _c.c_int64(), _c.c_int64()
         _check(self.lib.mvs_ctx_label_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(n), ctypes.byref(r)))
         return {"dots_ms": a.value, "reduce_ms": b.value, "gather_ms": e.value, "row_blocks": n.value, "block_rows": r.value}
+
+    # ---- average and complete linkage (include/mvs_hip.h "Average and complete linkage") ----
+    def hclust(self, sset, norms_sq, method="average", floor=0.0, rows=None):
+        """mvs_hclust: the agglomerative tree of the Jaccard distances of `rows` = (begin, end) of `sset` (default all), method
+        'average' (UPGMA) or 'complete' -> Hclust; slot i is sample begin + i"""
+        rb, re = (0, sset.n) if rows is None else rows
+        m = max(0, int(re) - int(rb))
+        np_, nm, nk = _norms(norms_sq)
+        merges = np.zeros(max(0, m - 1), dtype=HMERGE_DTYPE)
+        rounds = _c.c_int64()
+        meth = _hclust_method(method)
+        _check(self.lib.mvs_hclust(self._h, sset._h, np_, nm, float(floor), int(rb), int(re), meth, merges.ctypes.data, ctypes.byref(rounds)))
+        return Hclust(m, meth, merges, rounds.value)
+
+    def hclust_weights(self, w, method="average"):
+        """mvs_hclust_weights: w uint32 [m, m] <= 2^30, symmetric off the diagonal (numpy, or a torch tensor of 32-bit integers on
+        the host or the device) -> Hclust"""
+        if not _is_torch(w):
+            w = np.ascontiguousarray(w, dtype=np.uint32)
+        if w.ndim != 2 or w.shape[0] != w.shape[1]:
+            raise ValueError("w must be square")
+        m = int(w.shape[0])
+        wp, wm, wk = _buf(w)
+        merges = np.zeros(max(0, m - 1), dtype=HMERGE_DTYPE)
+        rounds = _c.c_int64()
+        meth = _hclust_method(method)
+        _check(self.lib.mvs_hclust_weights(self._h, wp, wm, m, meth, merges.ctypes.data, ctypes.byref(rounds)))
+        return Hclust(m, meth, merges, rounds.value)
+
+    def hclust_sums(self, sums, sizes=None, method="average"):
+        """mvs_hclust_sums: sums uint64 [m, m], symmetric off the diagonal, every entry <= n_a n_b 2^30 (numpy, or a torch tensor
+        of 64-bit integers); sizes int32 [m] >= 1 with a total <= 2^17, None = ones -> Hclust"""
+        if not _is_torch(sums):
+            sums = np.ascontiguousarray(sums, dtype=np.uint64)
+        if sums.ndim != 2 or sums.shape[0] != sums.shape[1]:
+            raise ValueError("sums must be square")
+        m = int(sums.shape[0])
+        sp, sm, sk = _buf(sums)
+        zp = None
+        if sizes is not None:
+            sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+            if sizes.ndim != 1 or len(sizes) != m:
+                raise ValueError("sizes must have one entry per slot")
+            zp = sizes.ctypes.data
+        merges = np.zeros(max(0, m - 1), dtype=HMERGE_DTYPE)
+        rounds = _c.c_int64()
+        meth = _hclust_method(method)
+        _check(self.lib.mvs_hclust_sums(self._h, sp, sm, zp, m, meth, merges.ctypes.data, ctypes.byref(rounds)))
+        return Hclust(m, meth, merges, rounds.value)
+
+    def hclust_stats(self):
+        """-> dict of the last hclust / hclust_weights / hclust_sums: dots_ms, fill_ms (kernel times over the row blocks),
+        nearest_ms, merge_ms, compact_ms (over the rounds; timing on), rounds, row_scans, bytes_scanned, compactions"""
+        d = [_c.c_double() for _ in range(5)]
+        n = [_c.c_int64() for _ in range(4)]
+        _check(self.lib.mvs_ctx_hclust_stats(self._h, *[ctypes.byref(x) for x in d + n]))
+        names = ("dots_ms", "fill_ms", "nearest_ms", "merge_ms", "compact_ms", "rounds", "row_scans", "bytes_scanned", "compactions")
+        return {k: x.value for k, x in zip(names, d + n)}
 
     def _consumer_stats(self, fn, work_key):
         """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time

@@ -433,6 +433,21 @@ int mvs_ctx_set_option(mvs_ctx* c, const char* name, int64_t value) {
         c->labels_block_rows = (int)value;
         return MVS_OK;
     }
+    if (std::strcmp(name, "hclust_dots") == 0) {             // mvs_hclust: which dense-dots kernel its blocks take
+        if (value < 0 || value > 1) return fail(MVS_E_INVALID, "option hclust_dots: 0 or 1");
+        c->hclust_dots = (int)value;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "hclust_block_rows") == 0) {       // host-side blocking only
+        if (value < 0 || value > (1 << 30)) return fail(MVS_E_INVALID, "option hclust_block_rows: 0 .. 2^30 rows");
+        c->hclust_block_rows = (int)value;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "hclust_compact") == 0) {          // when the table's columns are compacted: never changes a record
+        if (value < 0 || value > 2) return fail(MVS_E_INVALID, "option hclust_compact: 0, 1 or 2");
+        c->hclust_compact = (int)value;
+        return MVS_OK;
+    }
     if (std::strcmp(name, "report_spin") == 0) {             // host-side waiting only
         if (value < 0 || value > 1000000) return fail(MVS_E_INVALID, "option report_spin: 0 .. 1000000 microseconds");
         c->report_spin = (int)value;
@@ -459,6 +474,18 @@ int mvs_ctx_get_option(const mvs_ctx* c, const char* name, int64_t* value) {
     }
     if (std::strcmp(name, "labels_block_rows") == 0) {
         *value = c->labels_block_rows;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "hclust_dots") == 0) {
+        *value = c->hclust_dots;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "hclust_block_rows") == 0) {
+        *value = c->hclust_block_rows;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "hclust_compact") == 0) {
+        *value = c->hclust_compact;
         return MVS_OK;
     }
     if (std::strcmp(name, "report_spin") == 0) {

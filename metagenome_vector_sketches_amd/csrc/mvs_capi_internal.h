@@ -67,6 +67,14 @@ struct HdbscanStats {
     long long ranges = 0, rounds = 0, links = 0, edges = 0;
     void reset() { *this = HdbscanStats(); }
 };
+// what the last mvs_hclust / mvs_hclust_weights / mvs_hclust_sums did on a context (mvs_ctx_hclust_stats): kernel times of the
+// dots and of the fill summed over the row blocks, of the nearest pass, of the merge (pairs, column and row phase) and of the
+// compactions summed over the rounds (timing enabled); rounds, rows scanned, bytes of the table those scans read, compactions
+struct HclustStats {
+    double dots_ms = 0.0, fill_ms = 0.0, nearest_ms = 0.0, merge_ms = 0.0, compact_ms = 0.0;
+    long long rounds = 0, row_scans = 0, bytes_scanned = 0, compactions = 0;
+    void reset() { *this = HclustStats(); }
+};
 }  // namespace mvs_capi
 
 struct mvs_ctx {
@@ -217,6 +225,13 @@ struct mvs_ctx {
                                           // vector-ALU kernel (A/B, tests); same sums (option labels_dots)
     int labels_block_rows = 0;            // ... and > 0 = upper bound on the rows of a block (tests); 0 = by the device budget.  Host-side
                                           // blocking only (option labels_block_rows)
+    mvs_capi::HclustStats hc;
+    int hclust_dots = 0;                  // mvs_hclust: dots of a row block from 0 = the matrix-core kernels, 1 = the vector-ALU kernel (A/B,
+                                          // tests); same table (option hclust_dots)
+    int hclust_block_rows = 0;            // ... and > 0 = upper bound on the rows of a block of the fill (tests); 0 = by the device budget
+                                          // (option hclust_block_rows)
+    int hclust_compact = 1;               // the table's columns are compacted 0 = never, 1 = when at most half of them are alive, 2 = after
+                                          // every round; same records (option hclust_compact)
     int core_block_rows = 0;              // mvs_core_jaccard / mvs_hdbscan: > 0 = upper bound on the rows of a top-k range (tests); 0 = by
                                           // the cell buffer's budget.  Host-side blocking only (option core_block_rows)
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
