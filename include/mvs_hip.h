@@ -156,6 +156,8 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *                         mvs_hclust: dots from the matrix cores (0, default) or the vector-ALU kernel (1); > 0 bounds the rows
  *                         of a block of the fill (0: by the device budget); the table's columns are compacted never (0), when
  *                         at most half are alive (1, default), after every round (2).  None changes a record
+ *   community_path        mvs_community_finish: a vertex starts in the local-moving path its degree names (0, default), in the
+ *                         wave (1), workgroup (2) or global (3) path (A/B, tests).  Never changes a result
  *   core_block_rows       mvs_core_jaccard / mvs_hdbscan: > 0 bounds the rows of a top-k range (0: by the cell buffer's budget)
  *   gram_slab_rows        mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536 (default
  *                         65536; rounded down to a multiple of 64)
@@ -1450,6 +1452,113 @@ int mvs_hclust_cut(int64_t m, const mvs_hmerge* merges, double height, int32_t* 
 int mvs_hclust_cut_count(int64_t m, const mvs_hmerge* merges, int64_t k, int32_t* labels);
 int mvs_ctx_hclust_stats(const mvs_ctx* ctx, double* dots_ms, double* fill_ms, double* nearest_ms, double* merge_ms, double* compact_ms,
                          int64_t* rounds, int64_t* row_scans, int64_t* bytes_scanned, int64_t* compactions);
+
+/* ---- Communities: modularity clustering (Louvain) of the thresholded Jaccard graph --------------------------------------------
+ * Single linkage chains, dereplication fixes a radius, HDBSCAN* calls everything noise that is no density peak, average linkage
+ * needs the m x m table.  Modularity communities work on what the comparison produces anyway -- the kept cells above a floor --,
+ * need memory proportional to the edges, have one knob (the resolution) and partition every sample.  The reference has nothing
+ * of the kind.  Everything below is an integer: no order of summation, blocking, atomics or fed cells can change a result, and
+ * tests/communities_model.py is the same rule in Python integers.
+ *
+ * Graph.  n samples.  A fed cell (row, col, dot) with row != col is the edge {lo, hi} of weight a = rint(k * 2^20), k the clamped
+ *   estimate of "PERMANOVA" above: inter = (double)dot / d (dot * (1 / d) when d is a power of two); s = n2[row] + n2[col];
+ *   den = s - inter; J = inter / den; k = !(J > floor) ? 0 : (J > 1 ? 1 : J) -- fp64, one rounding per operation, the operations
+ *   of the distance w up to k.  An edge with a = 0 (a NaN estimate included) does not exist.  (r, c), (c, r) and repeated feeding
+ *   are one edge; where copies disagree the larger weight wins.  A cell that names a sample outside [0, n) is ignored and
+ *   reported as MVS_E_RANGE, the rule of mvs_cluster_add_cells.  20 fractional bits, not the 30 of w: 10^-6 in J, far below
+ *   the estimator's error, and W (below) stays under 2^55 for a clique of 100 000 and for 10^6 samples of mean degree 1 000, so
+ *   every product below fits a signed 128-bit integer.  W >= 2^55: mvs_community_finish fails with MVS_E_RANGE.
+ * Resolution.  R = 2^12, g = rint(resolution * R), 2^-12 <= resolution <= 16.
+ * Level l.  Vertices v with a self weight s_v (0 at level 0) and off-diagonal weights a_uv.  Strength k_v = s_v + sum_{u != v}
+ *   a_vu; W = sum_v k_v, the same on every level.  A level starts with c(v) = v.
+ * Round r = 0, 1, ... -- all reads are from the state at the start of the round:
+ *   v is ACTIVE iff the lowest bit of splitmix64((l << 48) ^ (r << 32) ^ v) is 1 (splitmix64 as in "Average and complete
+ *   linkage" above).  Half the vertices move per round: a synchronous sweep of all of them swaps neighbours forever.
+ *   For an active v in community A and every OTHER community C that holds a neighbour of v:
+ *       gain(C) = R W (k_vC - k_vA) - g k_v (tot(C) - tot(A) + k_v),   k_vC = sum_{u != v, c(u) = C} a_vu,  tot(C) = sum_{u in C} k_u
+ *   The best C has the largest gain, ties go to the smaller C.  v moves to it iff that gain is > 0 and not (size(A) = 1 and
+ *   size(C) = 1 and C > A).  All moves of a round are applied together.  Then
+ *       Qnum = R W sum_C in(C) - g sum_C tot(C)^2,   in(C) = sum_{v in C} s_v + sum over ordered pairs u != v in C of a_uv;
+ *   the modularity is Qnum / (R W^2).
+ * End of a level.  After a round in which no vertex moved, after 3 consecutive rounds that did not raise Qnum above the best
+ *   seen, or after max_rounds rounds.  The level's result is the best state seen (the earliest, among equals); the singleton
+ *   state counts as seen first.
+ * Aggregation.  The communities of the level's result are numbered in the order of their smallest member; if they are all
+ *   singletons the algorithm ends (that level is still reported), and it ends after MVS_COMMUNITY_MAX_LEVELS levels.  Otherwise
+ *   s'_C = in(C), a'_CD = the summed weights between C and D, and the next level starts from that graph.
+ * Finish.  A sample's community is the composition of the levels.  Every community is then split into the connected components
+ *   of its level-0 edges (the union-find of mvs_cluster_*): a split can only raise Qnum, and it removes Louvain's known defect
+ *   of disconnected communities.  Final labels are numbered by smallest member; the final Qnum is that of the final labels.
+ *
+ * mvs_community_create    an empty graph over n samples.  norms_sq (n doubles, `mem_norms`), d and floor decide the weight of a
+ *                         fed cell; norms_sq may be NULL for a graph that takes raw edges only.  floor outside [0, 1) or NaN:
+ *                         MVS_E_INVALID.  Resets the statistics mvs_ctx_community_stats reports.
+ * mvs_community_add_cells the cells of a DEVICE list (any producer's; q is not read).  The list is consumed when the call returns.
+ * mvs_community_add_edges raw integer edges (lo[i], hi[i], a[i]), 1 <= a <= 2^20, HOST or DEVICE (`mem`): the entry of crafted
+ *                         tests and of other producers.  lo == hi is ignored; an index outside [0, n) or a weight outside its
+ *                         range is ignored and reported as MVS_E_RANGE (the rest is consumed).
+ * mvs_pairwise_community  the one-call producer: the comparison of mvs_pairwise_cluster at level `floor` (its staging buffer,
+ *                         halving rule, options cluster_cells / cluster_block_rows and argument checks: floor outside (0, 1) is
+ *                         MVS_E_INVALID), every block's list fed to add_cells.  The set's d must be the graph's.
+ * mvs_community_finish    builds the graph if cells arrived since the last build (sort, one entry per edge, both directions
+ *                         sorted into a CSR) and runs the rule.  May be called again with another resolution without feeding
+ *                         again; more cells may be added in between.  `mem_out` says where labels (n int32), level_labels
+ *                         (level_capacity x n int32, row l = every sample's community after level l), degree (n int32),
+ *                         strength (n uint64, k_v of level 0), internal and total (room for n uint64 each, res->communities are
+ *                         written: in(C) and tot(C) of the final communities) live.  level_communities, level_rounds (int64) and
+ *                         level_qnum_hi / _lo are HOST arrays of level_capacity entries: a 128-bit value is hi * 2^64 + lo as in
+ *                         mvs_group_sums, in two's complement (Qnum may be negative).  Any pointer may be NULL.  More than
+ *                         level_capacity levels with a level array given: MVS_E_CAPACITY after everything else was written
+ *                         (MVS_COMMUNITY_MAX_LEVELS always suffices).  res: edges, W, levels, the final communities, the
+ *                         communities before the split, rounds of all levels, the final Qnum, g.  resolution outside
+ *                         [2^-12, 16], NaN, max_rounds < 1: MVS_E_INVALID.
+ * mvs_communities         create, mvs_pairwise_community, finish, destroy in one call.
+ * mvs_community_modularity  pure host, no device (like mvs_hdbscan_select): Qnum of `labels` (any int32 values) on the graph of
+ *                         the raw edges (the graph rule above: pairs once, the larger weight wins) at g_fixed = g.  Weights are
+ *                         int64 here, 1 <= a < 2^55, so that a coarse graph can be checked too; W >= 2^55, an index outside
+ *                         [0, n) or a weight outside its range: MVS_E_RANGE.
+ * Local moving, the hot path: a sweep of the CSR per round.  A vertex's edge weights are summed by neighbour community in a hash
+ * table, then the table is scanned for the best (gain, smaller C) with 128-bit gains.  Three paths, by the vertex's degree:
+ *     wave       degree <= 256:    one wave, 128 slots in LDS
+ *     workgroup  degree <= 16384:  256 lanes, 4096 slots in LDS
+ *     global     beyond:           256 lanes, >= 2 x degree slots in device memory
+ * A vertex that meets more neighbour communities than its table has slots is handed to the next path and done again from the
+ * start: nothing is lost or counted twice; the global table cannot fill.  Option community_path: 0 (default) by degree, 1 / 2 / 3
+ * = every vertex starts in the wave / workgroup / global path.  It never changes a result.
+ * mvs_ctx_community_stats since the context's last mvs_community_create: kernel times of the comparison, the build, the local
+ *                         moving and the numbering + aggregation, the moving of level 0 alone (all 0 unless mvs_ctx_set_timing
+ *                         is on); edges, levels and rounds of the last finish resp. all finishes, row blocks, the rounds of level
+ *                         0 and the bytes one of them reads (row_ptr, col, weight, the community gather); paths[5]: vertices
+ *                         that started in the wave / workgroup / global path (summed over the levels) and the hand-overs wave ->
+ *                         workgroup and workgroup -> global (summed over the rounds).  Any pointer may be NULL.
+ * All synchronous.  The kernels are in csrc/mvs_community.hip. */
+#define MVS_COMMUNITY_MAX_LEVELS 64
+typedef struct mvs_community mvs_community;
+typedef struct {
+    int64_t n, edges, levels, communities, composed, rounds;
+    uint64_t total_weight;          /* W */
+    uint64_t qnum_hi, qnum_lo;      /* the final Qnum */
+    int64_t g_fixed;
+} mvs_community_result;
+int mvs_community_create(mvs_ctx* ctx, int64_t n, int d, const double* norms_sq, int mem_norms, double floor, mvs_community** graph);
+int mvs_community_add_cells(mvs_community* graph, const mvs_cell* d_cells, int64_t n_cells);
+int mvs_community_add_edges(mvs_community* graph, const int32_t* lo, const int32_t* hi, const int32_t* a, int64_t n_edges, int mem);
+int mvs_pairwise_community(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double floor,
+                           mvs_community* graph);
+int mvs_community_finish(mvs_community* graph, double resolution, int64_t max_rounds, int32_t* labels, int32_t* level_labels,
+                         int64_t level_capacity, int32_t* degree, uint64_t* strength, uint64_t* internal, uint64_t* total, int mem_out,
+                         int64_t* level_communities, int64_t* level_rounds, uint64_t* level_qnum_hi, uint64_t* level_qnum_lo,
+                         mvs_community_result* res);
+int mvs_community_destroy(mvs_community* graph);
+int mvs_communities(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, double floor, double resolution,
+                    int64_t max_rounds, int32_t* labels, int32_t* level_labels, int64_t level_capacity, int32_t* degree,
+                    uint64_t* strength, uint64_t* internal, uint64_t* total, int mem_out, int64_t* level_communities,
+                    int64_t* level_rounds, uint64_t* level_qnum_hi, uint64_t* level_qnum_lo, mvs_community_result* res);
+int mvs_community_modularity(int64_t n, const int32_t* lo, const int32_t* hi, const int64_t* a, int64_t n_edges, const int32_t* labels,
+                             int64_t g_fixed, uint64_t* qnum_hi, uint64_t* qnum_lo);
+int mvs_ctx_community_stats(const mvs_ctx* ctx, double* compare_ms, double* build_ms, double* move_ms, double* aggregate_ms,
+                            double* level0_move_ms, int64_t* edges, int64_t* levels, int64_t* rounds, int64_t* row_blocks,
+                            int64_t* level0_rounds, int64_t* level0_bytes, int64_t* paths);
 
 /* ---- multi-GPU exchange ---------------------------------------------------------------------------
  * One process per GPU; shard k of src/pairwise_comp_optimized.cpp:938-940 is rank k.  Where the reference's shard

@@ -70,6 +70,13 @@ class SilhouetteResult(ctypes.Structure):
     _fields_ = [("mean", _c.c_double), ("negative", _c.c_int64), ("samples", _c.c_int64), ("labelled", _c.c_int64), ("groups", _c.c_int64)]
 
 
+class CommunityResult(ctypes.Structure):
+    """mvs_community_result"""
+    _fields_ = [("n", _c.c_int64), ("edges", _c.c_int64), ("levels", _c.c_int64), ("communities", _c.c_int64), ("composed", _c.c_int64),
+                ("rounds", _c.c_int64), ("total_weight", _c.c_uint64), ("qnum_hi", _c.c_uint64), ("qnum_lo", _c.c_uint64),
+                ("g_fixed", _c.c_int64)]
+
+
 SYMBOLS = [
     ("mvs_version", _c.c_char_p, []),
     ("mvs_last_error", _c.c_char_p, []),
@@ -270,6 +277,18 @@ SYMBOLS = [
     ("mvs_event_destroy", _c.c_int, [_P]),
     ("mvs_cells_stream", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, ROW_BLOCK_CB, _P, _c.POINTER(_c.c_int64)]),
     ("mvs_cells_stream_encoded", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, ENCODED_ROWS_CB, _P, _c.POINTER(_c.c_int64)]),
+    ("mvs_community_create", _c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_int, _c.c_double, _c.POINTER(_P)]),
+    ("mvs_community_add_cells", _c.c_int, [_P, _P, _c.c_int64]),
+    ("mvs_community_add_edges", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int]),
+    ("mvs_pairwise_community", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _P]),
+    ("mvs_community_finish", _c.c_int, [_P, _c.c_double, _c.c_int64, _P, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int, _P, _P, _P, _P,
+                                         _c.POINTER(CommunityResult)]),
+    ("mvs_community_destroy", _c.c_int, [_P]),
+    ("mvs_communities", _c.c_int, [_P, _P, _P, _c.c_int, _c.c_double, _c.c_double, _c.c_int64, _P, _P, _c.c_int64, _P, _P, _P, _P,
+                                    _c.c_int, _P, _P, _P, _P, _c.POINTER(CommunityResult)]),
+    ("mvs_community_modularity", _c.c_int, [_c.c_int64, _P, _P, _P, _c.c_int64, _P, _c.c_int64, _c.POINTER(_c.c_uint64),
+                                             _c.POINTER(_c.c_uint64)]),
+    ("mvs_ctx_community_stats", _c.c_int, [_P] + [_c.POINTER(_c.c_double)] * 5 + [_c.POINTER(_c.c_int64)] * 6 + [_P]),
     ("mvs_chunk_size", _c.c_int64, [_c.c_double, _c.c_int]),
     ("mvs_shard_rows", None, [_c.c_int64, _c.c_int, _c.c_int, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
 ]
@@ -554,6 +573,116 @@ class Cluster(_Handle):
         _check(self.ctx.lib.mvs_cluster_finish(self._h, np_, nm, labels.ctypes.data, degree.ctypes.data, reps.ctypes.data,
                                                sizes.ctypes.data, MEM_HOST, ctypes.byref(count)))
         return ClusterResult(labels, degree, reps[:count.value].copy(), sizes[:count.value].copy())
+
+
+COMMUNITY_MAX_LEVELS = 64
+COMMUNITY_R = 1 << 12
+
+
+def _i128(hi, lo):
+    """hi * 2^64 + lo in two's complement -> Python int"""
+    v = (int(hi) << 64) | int(lo)
+    return v - (1 << 128) if v >> 127 else v
+
+
+class Communities:
+    """What CommunityGraph.finish / Context.communities return.  `labels` (int32 [n]: the community of every sample, numbered by
+    smallest member), `level_labels` (int32 [levels, n]: the membership after every level, before the connected split), `qnum`
+    (the final Qnum, a Python int) and `modularity` = qnum / (R W^2), `level_qnum` / `level_modularity` / `rounds` /
+    `level_communities` per level, `sizes`, `internal` (in(C)) and `total` (tot(C)) per final community, `degree` and `strength`
+    per sample, `edges`, `total_weight` (W), `composed` (communities before the split), `g_fixed`."""
+
+    def __init__(self, res, labels, level_labels, degree, strength, internal, total, level_communities, rounds, level_qnum):
+        self.labels, self.level_labels, self.degree, self.strength = labels, level_labels, degree, strength
+        self.internal, self.total = internal, total
+        self.level_communities, self.rounds, self.level_qnum = level_communities, rounds, level_qnum
+        self.edges, self.total_weight, self.levels = int(res.edges), int(res.total_weight), int(res.levels)
+        self.composed, self.g_fixed = int(res.composed), int(res.g_fixed)
+        self.qnum = _i128(res.qnum_hi, res.qnum_lo)
+        self.sizes = np.bincount(labels, minlength=int(res.communities)).astype(np.int64)
+        self.n_communities = int(res.communities)
+
+    def _mod(self, q):
+        w = float(self.total_weight)
+        return float(q) / (float(COMMUNITY_R) * w * w) if self.total_weight else 0.0
+
+    @property
+    def modularity(self):
+        return self._mod(self.qnum)
+
+    @property
+    def level_modularity(self):
+        return [self._mod(q) for q in self.level_qnum]
+
+    def __repr__(self):
+        return "Communities(%d samples, %d edges, %d communities, modularity %.4f, %d levels)" % (
+            len(self.labels), self.edges, self.n_communities, self.modularity, self.levels)
+
+
+class CommunityGraph(_Handle):
+    """The thresholded Jaccard graph of n samples on the device and its modularity communities (mvs_community): feed it with
+    add_cells (a device cell list; needs norms_sq and d), add_edges (raw integer edges lo, hi, a with 1 <= a <= 2^20) or
+    Context.communities_into, read it with finish -- as often as wanted, at any resolution."""
+    _destroy = "mvs_community_destroy"
+
+    def __init__(self, ctx, n, d=0, norms_sq=None, floor=0.05):
+        self.ctx, self.n = ctx, int(n)
+        np_, nm, nk = _norms(norms_sq) if norms_sq is not None else (None, MEM_HOST, None)
+        h = _P()
+        _check(ctx.lib.mvs_community_create(ctx._h, self.n, int(d), np_, nm, float(floor), ctypes.byref(h)))
+        self._h = h
+        ctx._children.add(self)
+
+    def add_cells(self, cells, n_cells=None):
+        """cells: torch CUDA tensor (int32 [m, 4]; the first n_cells rows, default all) or a device address (int) with n_cells"""
+        cp, n_cells, ck = _cell_list(cells, n_cells)
+        _check(self.ctx.lib.mvs_community_add_cells(self._h, cp, n_cells))
+
+    def add_edges(self, lo, hi, a):
+        """raw edges: three int32 arrays of one length (numpy, or torch tensors that all live in the same place)"""
+        if _is_torch(lo):
+            (lp, lm, lk), (hp, hm, hk), (ap, am, ak) = _buf(lo), _buf(hi), _buf(a)
+            if not (lm == hm == am):
+                raise ValueError("lo, hi and a must live in the same place")
+        else:
+            (lp, lm, lk), (hp, hm, hk), (ap, am, ak) = _buf(lo, np.int32), _buf(hi, np.int32), _buf(a, np.int32)
+        if not (len(lo) == len(hi) == len(a)):
+            raise ValueError("lo, hi and a must have one length")
+        _check(self.ctx.lib.mvs_community_add_edges(self._h, lp, hp, ap, len(lo), lm))
+
+    def finish(self, resolution=1.0, max_rounds=100):
+        """-> Communities"""
+        return _communities_call(self.n, lambda *out: self.ctx.lib.mvs_community_finish(self._h, float(resolution), int(max_rounds), *out))
+
+
+def _communities_call(n, call):
+    """the outputs that mvs_community_finish and mvs_communities share"""
+    cap = COMMUNITY_MAX_LEVELS
+    labels, degree = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    level_labels = np.zeros((cap, n), dtype=np.int32)
+    strength, internal, total = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+    lc, lr = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64)
+    qh, ql = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+    res = CommunityResult()
+    _check(call(labels.ctypes.data, level_labels.ctypes.data, cap, degree.ctypes.data, strength.ctypes.data, internal.ctypes.data,
+                total.ctypes.data, MEM_HOST, lc.ctypes.data, lr.ctypes.data, qh.ctypes.data, ql.ctypes.data, ctypes.byref(res)))
+    lv, cc = int(res.levels), int(res.communities)
+    return Communities(res, labels, level_labels[:lv].copy(), degree, strength, internal[:cc].copy(), total[:cc].copy(),
+                       lc[:lv].tolist(), lr[:lv].tolist(), [_i128(qh[i], ql[i]) for i in range(lv)])
+
+
+def community_modularity(n, lo, hi, a, labels, resolution=1.0, g_fixed=None):
+    """mvs_community_modularity (pure host): Qnum of `labels` on the graph of the raw edges (lo, hi, a: int64 weights,
+    1 <= a < 2^55) at g = rint(resolution * 2^12), or at g_fixed -> Python int"""
+    lo, hi = np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
+    a, labels = np.ascontiguousarray(a, dtype=np.int64), np.ascontiguousarray(labels, dtype=np.int32)
+    if not (len(lo) == len(hi) == len(a)) or len(labels) != n:
+        raise ValueError("lo, hi and a must have one length, labels n entries")
+    g = int(np.rint(resolution * COMMUNITY_R)) if g_fixed is None else int(g_fixed)
+    qh, ql = _c.c_uint64(), _c.c_uint64()
+    _check(load_library().mvs_community_modularity(int(n), lo.ctypes.data, hi.ctypes.data, a.ctypes.data, len(lo), labels.ctypes.data, g,
+                                                   ctypes.byref(qh), ctypes.byref(ql)))
+    return _i128(qh.value, ql.value)
 
 
 class DerepResult:
@@ -1978,6 +2107,38 @@ class Context:
         _check(self.lib.mvs_ctx_hclust_stats(self._h, *[ctypes.byref(x) for x in d + n]))
         names = ("dots_ms", "fill_ms", "nearest_ms", "merge_ms", "compact_ms", "rounds", "row_scans", "bytes_scanned", "compactions")
         return {k: x.value for k, x in zip(names, d + n)}
+
+    # ---- modularity communities (include/mvs_hip.h "Communities") ----
+    def community_graph(self, n, d=0, norms_sq=None, floor=0.05):
+        """-> CommunityGraph: an empty graph over n samples; norms_sq, d and floor decide the weight of a fed cell (None: the graph
+        takes raw edges only)"""
+        return CommunityGraph(self, n, d, norms_sq, floor)
+
+    def communities_into(self, graph, sset, norms_sq, floor=0.05):
+        """mvs_pairwise_community: compare `sset` with itself at level `floor` and feed every kept cell into `graph`, on the device"""
+        np_, nm, nk = _norms(norms_sq)
+        _check(self.lib.mvs_pairwise_community(self._h, sset._h, np_, nm, float(floor), graph._h))
+
+    def communities(self, sset, norms_sq, floor=0.05, resolution=1.0, max_rounds=100):
+        """Modularity communities (Louvain with the connected split) of the graph of Jaccard estimates above `floor` -> Communities.
+        All integers: equal to tests/communities_model.py whatever the blocking, the options or the order of the cells."""
+        np_, nm, nk = _norms(norms_sq)
+        return _communities_call(sset.n, lambda *out: self.lib.mvs_communities(self._h, sset._h, np_, nm, float(floor), float(resolution),
+                                                                                int(max_rounds), *out))
+
+    def community_stats(self):
+        """-> dict since this context's last CommunityGraph was created: compare_ms, build_ms, move_ms, aggregate_ms, level0_move_ms
+        (timing on), edges, levels, rounds, row_blocks, level0_rounds, level0_bytes, paths (vertices that started in the wave /
+        workgroup / global path, hand-overs wave -> workgroup and workgroup -> global)"""
+        d = [_c.c_double() for _ in range(5)]
+        n = [_c.c_int64() for _ in range(6)]
+        paths = np.zeros(5, dtype=np.int64)
+        _check(self.lib.mvs_ctx_community_stats(self._h, *([ctypes.byref(x) for x in d + n] + [paths.ctypes.data])))
+        names = ("compare_ms", "build_ms", "move_ms", "aggregate_ms", "level0_move_ms", "edges", "levels", "rounds", "row_blocks",
+                 "level0_rounds", "level0_bytes")
+        out = {k: x.value for k, x in zip(names, d + n)}
+        out["paths"] = paths.tolist()
+        return out
 
     def _consumer_stats(self, fn, work_key):
         """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time

@@ -448,6 +448,11 @@ int mvs_ctx_set_option(mvs_ctx* c, const char* name, int64_t value) {
         c->hclust_compact = (int)value;
         return MVS_OK;
     }
+    if (std::strcmp(name, "community_path") == 0) {          // mvs_community_finish: where a vertex starts; never changes a result
+        if (value < 0 || value > 3) return fail(MVS_E_INVALID, "option community_path: 0 (by degree), 1 wave, 2 workgroup, 3 global");
+        c->community_path = (int)value;
+        return MVS_OK;
+    }
     if (std::strcmp(name, "report_spin") == 0) {             // host-side waiting only
         if (value < 0 || value > 1000000) return fail(MVS_E_INVALID, "option report_spin: 0 .. 1000000 microseconds");
         c->report_spin = (int)value;
@@ -486,6 +491,10 @@ int mvs_ctx_get_option(const mvs_ctx* c, const char* name, int64_t* value) {
     }
     if (std::strcmp(name, "hclust_compact") == 0) {
         *value = c->hclust_compact;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "community_path") == 0) {
+        *value = c->community_path;
         return MVS_OK;
     }
     if (std::strcmp(name, "report_spin") == 0) {

@@ -75,6 +75,17 @@ struct HclustStats {
     long long rounds = 0, row_scans = 0, bytes_scanned = 0, compactions = 0;
     void reset() { *this = HclustStats(); }
 };
+// what the community calls did on a context since its last mvs_community_create (mvs_ctx_community_stats): kernel times of the
+// comparison, of the graph's build (sort, unique, mirror, CSR), of the local moving and of the numbering + aggregation (timing
+// enabled), the moving of level 0 alone with its rounds and the bytes one of its rounds reads; edges, levels, rounds, row
+// blocks; vertices that started in the wave / workgroup / global path (summed over the levels) and hand-overs wave ->
+// workgroup and workgroup -> global (summed over the rounds)
+struct CommunityStats {
+    double compare_ms = 0.0, build_ms = 0.0, move_ms = 0.0, aggregate_ms = 0.0, level0_move_ms = 0.0;
+    long long edges = 0, levels = 0, rounds = 0, blocks = 0, level0_rounds = 0, level0_bytes = 0;
+    long long paths[5] = {0, 0, 0, 0, 0};
+    void reset() { *this = CommunityStats(); }
+};
 }  // namespace mvs_capi
 
 struct mvs_ctx {
@@ -232,6 +243,9 @@ struct mvs_ctx {
                                           // (option hclust_block_rows)
     int hclust_compact = 1;               // the table's columns are compacted 0 = never, 1 = when at most half of them are alive, 2 = after
                                           // every round; same records (option hclust_compact)
+    mvs_capi::CommunityStats cm;
+    int community_path = 0;               // mvs_community_finish: a vertex starts in 0 = the path its degree names, 1 = the wave path, 2 = the
+                                          // workgroup path, 3 = the global path (tests); same result (option community_path)
     int core_block_rows = 0;              // mvs_core_jaccard / mvs_hdbscan: > 0 = upper bound on the rows of a top-k range (tests); 0 = by
                                           // the cell buffer's budget.  Host-side blocking only (option core_block_rows)
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call

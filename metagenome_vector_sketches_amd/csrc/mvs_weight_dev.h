@@ -23,6 +23,18 @@ __device__ __forceinline__ uint32_t quantised_distance(int32_t P, double n2r, do
     return (uint32_t)rint(t * 1073741824.0);
 }
 
+// a = rint(k * 2^20), the similarity of the same cell: the operations of quantised_distance up to k, in its order, with its floor
+// (include/mvs_hip.h "Communities")
+__device__ __forceinline__ uint32_t quantised_similarity(int32_t P, double n2r, double n2c, double dd, double inv, bool pow2, double floor_) {
+#pragma clang fp contract(off)
+    const double inter = pow2 ? (double)P * inv : (double)P / dd;
+    const double s = n2r + n2c;
+    const double den = s - inter;
+    const double J = inter / den;
+    const double k = !(J > floor_) ? 0.0 : (J > 1.0 ? 1.0 : J);
+    return (uint32_t)rint(k * 1048576.0);
+}
+
 }  // namespace mvs
 
 #endif
