@@ -158,6 +158,8 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *                         at most half are alive (1, default), after every round (2).  None changes a record
  *   community_path        mvs_community_finish: a vertex starts in the local-moving path its degree names (0, default), in the
  *                         wave (1), workgroup (2) or global (3) path (A/B, tests).  Never changes a result
+ *   tsne_slice_cols       mvs_tsne_gradient / _run / _kl: columns of a repulsion unit, 16 .. 1024 (default 1024; tests).  Never
+ *                         changes a result
  *   core_block_rows       mvs_core_jaccard / mvs_hdbscan: > 0 bounds the rows of a top-k range (0: by the cell buffer's budget)
  *   gram_slab_rows        mvs_sketch_moments / mvs_pca_fit: samples per slab of the transposed scratch copy, 64 .. 65536 (default
  *                         65536; rounded down to a multiple of 64)
@@ -1559,6 +1561,109 @@ int mvs_community_modularity(int64_t n, const int32_t* lo, const int32_t* hi, co
 int mvs_ctx_community_stats(const mvs_ctx* ctx, double* compare_ms, double* build_ms, double* move_ms, double* aggregate_ms,
                             double* level0_move_ms, int64_t* edges, int64_t* levels, int64_t* rounds, int64_t* row_blocks,
                             int64_t* level0_rounds, int64_t* level0_bytes, int64_t* paths);
+
+/* ---- t-SNE: the exact map of the Jaccard kNN graph ---------------------------------------------------------------------------
+ * The two ordinations above are linear; at 10^5 .. 10^6 samples in hundreds of groups two leading axes show a blob.  What one
+ * draws of such a collection is its neighbour graph: t-SNE on the K best Jaccard estimates of every sample.  Both expensive inputs
+ * exist here exactly -- mvs_pairwise_topk's cells and the community graph's sort + sum-by-key --, and the gradient's all-pairs
+ * repulsion is n^2 rational terms per iteration, which the device evaluates exactly: no Barnes-Hut tree, no FFT grid, no n x n
+ * buffer.  A pair's term is a fixed sequence of IEEE fp64 operations, each rounded once and never fused (the precedent of
+ * "PERMANOVA" and "Communities"), and is QUANTISED before it is added: every sum over more than one term is a sum of integers.
+ * No tiling, atomic or order of lanes can change a coordinate, and tests/tsne_model.py -- the same rule in numpy -- equals the
+ * device bit for bit over hundreds of iterations.  Two quantities pass through exp / log and are not bit-stable: beta, which the
+ * stopping rule pins, and the KL divergence, which is reported once.
+ *
+ * Affinities.  Row i has the neighbours j_1 .. j_m of a cell list sorted by row (mvs_pairwise_topk's, MVS_TOPK_EXCLUDE_SELF):
+ *   m <= 256; m < K where n - 1 < K.  Per cell, in fp64, one rounding per operation, top-k's order:
+ *       inter = (double)dot / d;  s = n2[i] + n2[j];  den = s - inter;  J = inter / den;  J = !(J > 0) ? 0 : (J > 1 ? 1 : J)
+ *       delta = 1.0 - J                                   (the squared distance of "principal coordinates")
+ *   x_j = delta_j - min_j delta_j;  w_j = exp(-beta x_j);  p_j = w_j / sum w;  H = log(sum w) + beta (sum w x) / (sum w).
+ *   beta: 0 if m <= perplexity or all delta of the row are equal (p is uniform); else bisection from beta = 1 with lo = 0 and no
+ *   upper bound: stop when |H - log(perplexity)| <= 1e-5 or after 200 steps; H too large: lo = beta, beta = beta * 2 while no upper
+ *   bound is known, else (beta + hi) / 2; H too small: hi = beta, beta = (lo + beta) / 2.  The two sums are wave reductions, so
+ *   beta may differ from another implementation's in its last bits.  Everything after beta is exact:
+ *       c_ij = rint(p_j * 2^30)                           (int, a cell's value)
+ *       s_ij = c_ij + c_ji, summed by key; both directions (i, j) and (j, i) are stored with the same s
+ *       S = the sum of all stored s;  P_ij = (double)s_ij / (double)S
+ *   Raw edges (lo, hi, s >= 1) enter the same sum: each adds s to (lo, hi) and to (hi, lo); duplicates and reversed copies add
+ *   up; lo == hi is ignored.
+ * One evaluation at the state y (n x 2 doubles).  Per ordered pair i != j:
+ *       dx = y_i0 - y_j0;  dy = y_i1 - y_j1;  r = dx * dx + dy * dy;  q = 1.0 / (1.0 + r);  u = q * q
+ *   Row sums, int64:  Z_i = sum_j rint(q * 2^40);  Rx_i = sum_j rint((u * dx) * 2^40), Ry_i likewise  (|u dx| < 0.33: a row fits
+ *   for n < 2^23).  Z = sum_i (Z_i >> 20) fits int64 for n <= 2^21: a larger n is MVS_E_INVALID.  Zd = (double)Z * 2^-20.
+ *   Attraction over the stored entries of row i:  Ax_i = sum_j rint(((P_ij * q) * dx) * 2^40), Ay_i likewise.
+ *       g_x = 4.0 * (e * ((double)Ax_i * 2^-40) - ((double)Rx_i * 2^-40) / Zd),   e the exaggeration;
+ *   the quotient counts as 0.0 where Z = 0 (n = 1).
+ * One iteration, per coordinate, all reads from the state before it:
+ *       gain = ((g > 0) == (vel > 0)) ? gain * 0.8 : gain + 0.2;  gain < 0.01: gain = 0.01
+ *       vel  = momentum * vel - learning_rate * (gain * g);   y = y + vel
+ *   A new handle's state is y = 0, vel = 0, gain = 1.  Nothing is recentred while the optimiser runs.  The state must stay finite.
+ * mvs_tsne, the whole path.  K = params->neighbours, or ceil(3 * perplexity) where that is 0; 1 <= perplexity <= K <= 256 (so the
+ *   default K allows a perplexity of 85), else MVS_E_INVALID.  Initial y: MVS_TSNE_INIT_PCOA -- the two leading coordinates of
+ *   mvs_pcoa_fit(rows [0, n), floor 0, tol 1e-10, 300 iterations), times 1e-4 / sd, sd the population standard deviation of
+ *   coordinate 1 with mean and squares summed in index order (n >= 3, sd > 0, else MVS_E_INVALID) -- or MVS_TSNE_INIT_RANDOM:
+ *   u = (splitmix64(splitmix64(seed) ^ (2 i + axis)) >> 11) * 2^-53, y = (2 u - 1) * 1e-4.  Schedule: min(iterations,
+ *   exaggeration_iters) iterations at e = exaggeration, momentum 0.5, the rest at e = 1, momentum 0.8; learning_rate <= 0 means
+ *   max(n / 12 / 4, 50).  Output: Y = y - mean per axis, mean = ((double)sum_i rint(y_i * 2^30) * 2^-30) / n, an integer sum.
+ *   KL = sum over the stored entries with s > 0 of P log(P / (q / Zd)), summed on the device with fp64 atomics.
+ *
+ * mvs_tsne_create         an empty graph and a fresh state over 1 <= n <= 2^21 samples.  Resets mvs_ctx_tsne_stats.
+ * mvs_tsne_add_edges      raw integer edges, HOST or DEVICE (`mem`).  An index outside [0, n) or s < 1: MVS_E_RANGE, and NOTHING of
+ *                         the list is added.
+ * mvs_tsne_add_neighbours calibrates a cell list (HOST or DEVICE; sorted by row, <= 256 cells per row, row != col, indices in
+ *                         [0, n): else MVS_E_RANGE / MVS_E_INVALID and nothing is added).  norms_sq: n doubles.  beta_out (HOST, n
+ *                         doubles, may be NULL) is written for the rows between the list's first and last row; c_out (HOST, n_cells
+ *                         int32, may be NULL) receives c per cell.  perplexity outside [1, 256]: MVS_E_INVALID.
+ * mvs_tsne_finish_graph   sort, sum by key, CSR, S and P.  More may be added afterwards; finish again then.
+ * mvs_tsne_edges          the stored directed entries sorted by (row, col): HOST arrays of `capacity`, any may be NULL; *n_entries
+ *                         and *S are always written; MVS_E_CAPACITY if an array is given and too small.
+ * mvs_tsne_set_state / _get_state   y, velocity, gain: HOST, n x 2 doubles each, any may be NULL (left as it is / not wanted).
+ * mvs_tsne_gradient       one evaluation, state untouched: grad (n x 2), z_rows (n int64), *z -- HOST, any may be NULL.
+ * mvs_tsne_run            `iterations` iterations at one (exaggeration, momentum, learning_rate); the host reads nothing back
+ *                         while they run.
+ * mvs_tsne_kl             KL at the present state.
+ * _edges, _gradient, _run and _kl before mvs_tsne_finish_graph (or after feeding more): MVS_E_INVALID.  Every refusal leaves the
+ * handle as it was.
+ * mvs_tsne                top-k over row ranges (option cluster_block_rows bounds their rows), each range calibrated on the
+ *                         device, the graph, the initial state, the schedule, the centring.  Y (n x 2), Y0 (the initial state),
+ *                         beta (n): HOST, any may be NULL.  graph_out: NULL, or receives the handle with the final state (the
+ *                         caller destroys it).
+ * mvs_ctx_tsne_stats      since the context's last mvs_tsne_create: kernel times of top-k, calibration, graph build, and of the
+ *                         repulsion, attraction and update summed over the iterations (0 unless mvs_ctx_set_timing is on: with
+ *                         it every iteration is waited for); iterations, stored entries, units of one repulsion, top-k ranges.
+ * The repulsion, the hot path: a unit is 256 rows x one slice of columns (option tsne_slice_cols, 16 .. 1024, default 1024;
+ * never changes a result).  A lane owns a row; the slice's y is staged in LDS and read as broadcasts.  The quantised terms are
+ * integer-valued doubles <= 2^40, at most 1024 of them per unit, so a lane's fp64 partial sums are exact below 2^53: one
+ * conversion to int64 and one 64-bit atomic per accumulator and unit.  All synchronous.  The kernels are in csrc/mvs_tsne.hip. */
+#define MVS_TSNE_INIT_PCOA   0
+#define MVS_TSNE_INIT_RANDOM 1
+typedef struct mvs_tsne_graph mvs_tsne_graph;
+typedef struct {
+    double perplexity, exaggeration, learning_rate;
+    int64_t neighbours, iterations, exaggeration_iters, init;
+    uint64_t seed;
+} mvs_tsne_params;
+typedef struct {
+    int64_t n, neighbours, entries, beta_zero_rows, iterations;
+    uint64_t S;
+    double learning_rate, kl;
+} mvs_tsne_result;
+int mvs_tsne_create(mvs_ctx* ctx, int64_t n, mvs_tsne_graph** graph);
+int mvs_tsne_destroy(mvs_tsne_graph* graph);
+int mvs_tsne_add_edges(mvs_tsne_graph* graph, const int32_t* lo, const int32_t* hi, const int32_t* s, int64_t n_edges, int mem);
+int mvs_tsne_add_neighbours(mvs_tsne_graph* graph, const mvs_cell* cells, int64_t n_cells, int mem_cells, const double* norms_sq,
+                            int mem_norms, int d, double perplexity, double* beta_out, int32_t* c_out);
+int mvs_tsne_finish_graph(mvs_tsne_graph* graph);
+int mvs_tsne_edges(mvs_tsne_graph* graph, int32_t* row, int32_t* col, int64_t* s, int64_t capacity, int64_t* n_entries, uint64_t* S);
+int mvs_tsne_set_state(mvs_tsne_graph* graph, const double* y, const double* velocity, const double* gain);
+int mvs_tsne_get_state(mvs_tsne_graph* graph, double* y, double* velocity, double* gain);
+int mvs_tsne_gradient(mvs_tsne_graph* graph, double exaggeration, double* grad, int64_t* z_rows, int64_t* z);
+int mvs_tsne_run(mvs_tsne_graph* graph, int64_t iterations, double exaggeration, double momentum, double learning_rate);
+int mvs_tsne_kl(mvs_tsne_graph* graph, double* kl);
+int mvs_tsne(mvs_ctx* ctx, const mvs_sketch_set* set, const double* norms_sq, int mem_norms, const mvs_tsne_params* params, double* Y,
+             double* Y0, double* beta, mvs_tsne_result* result, mvs_tsne_graph** graph_out);
+int mvs_ctx_tsne_stats(const mvs_ctx* ctx, double* topk_ms, double* calibrate_ms, double* graph_ms, double* repulse_ms,
+                       double* attract_ms, double* update_ms, int64_t* iterations, int64_t* entries, int64_t* units, int64_t* row_blocks);
 
 /* ---- multi-GPU exchange ---------------------------------------------------------------------------
  * One process per GPU; shard k of src/pairwise_comp_optimized.cpp:938-940 is rank k.  Where the reference's shard

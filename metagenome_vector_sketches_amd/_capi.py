@@ -77,6 +77,18 @@ class CommunityResult(ctypes.Structure):
                 ("g_fixed", _c.c_int64)]
 
 
+class TsneParams(ctypes.Structure):
+    """mvs_tsne_params"""
+    _fields_ = [("perplexity", _c.c_double), ("exaggeration", _c.c_double), ("learning_rate", _c.c_double), ("neighbours", _c.c_int64),
+                ("iterations", _c.c_int64), ("exaggeration_iters", _c.c_int64), ("init", _c.c_int64), ("seed", _c.c_uint64)]
+
+
+class TsneResult(ctypes.Structure):
+    """mvs_tsne_result"""
+    _fields_ = [("n", _c.c_int64), ("neighbours", _c.c_int64), ("entries", _c.c_int64), ("beta_zero_rows", _c.c_int64),
+                ("iterations", _c.c_int64), ("S", _c.c_uint64), ("learning_rate", _c.c_double), ("kl", _c.c_double)]
+
+
 SYMBOLS = [
     ("mvs_version", _c.c_char_p, []),
     ("mvs_last_error", _c.c_char_p, []),
@@ -289,6 +301,19 @@ SYMBOLS = [
     ("mvs_community_modularity", _c.c_int, [_c.c_int64, _P, _P, _P, _c.c_int64, _P, _c.c_int64, _c.POINTER(_c.c_uint64),
                                              _c.POINTER(_c.c_uint64)]),
     ("mvs_ctx_community_stats", _c.c_int, [_P] + [_c.POINTER(_c.c_double)] * 5 + [_c.POINTER(_c.c_int64)] * 6 + [_P]),
+    ("mvs_tsne_create", _c.c_int, [_P, _c.c_int64, _c.POINTER(_P)]),
+    ("mvs_tsne_destroy", _c.c_int, [_P]),
+    ("mvs_tsne_add_edges", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int]),
+    ("mvs_tsne_add_neighbours", _c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_double, _P, _P]),
+    ("mvs_tsne_finish_graph", _c.c_int, [_P]),
+    ("mvs_tsne_edges", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_uint64)]),
+    ("mvs_tsne_set_state", _c.c_int, [_P, _P, _P, _P]),
+    ("mvs_tsne_get_state", _c.c_int, [_P, _P, _P, _P]),
+    ("mvs_tsne_gradient", _c.c_int, [_P, _c.c_double, _P, _P, _c.POINTER(_c.c_int64)]),
+    ("mvs_tsne_run", _c.c_int, [_P, _c.c_int64, _c.c_double, _c.c_double, _c.c_double]),
+    ("mvs_tsne_kl", _c.c_int, [_P, _c.POINTER(_c.c_double)]),
+    ("mvs_tsne", _c.c_int, [_P, _P, _P, _c.c_int, _c.POINTER(TsneParams), _P, _P, _P, _c.POINTER(TsneResult), _c.POINTER(_P)]),
+    ("mvs_ctx_tsne_stats", _c.c_int, [_P] + [_c.POINTER(_c.c_double)] * 6 + [_c.POINTER(_c.c_int64)] * 4),
     ("mvs_chunk_size", _c.c_int64, [_c.c_double, _c.c_int]),
     ("mvs_shard_rows", None, [_c.c_int64, _c.c_int, _c.c_int, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
 ]
@@ -683,6 +708,112 @@ def community_modularity(n, lo, hi, a, labels, resolution=1.0, g_fixed=None):
     _check(load_library().mvs_community_modularity(int(n), lo.ctypes.data, hi.ctypes.data, a.ctypes.data, len(lo), labels.ctypes.data, g,
                                                    ctypes.byref(qh), ctypes.byref(ql)))
     return _i128(qh.value, ql.value)
+
+
+TSNE_INIT = {"pcoa": 0, "random": 1}
+
+
+class TsneGraph(_Handle):
+    """The symmetric graph of integer affinities of n samples and the optimiser's state (y, velocity, gain) on the device
+    (mvs_tsne_graph; include/mvs_hip.h "t-SNE"): feed it with add_neighbours (a top-k cell list, calibrated on the device) or
+    add_edges (raw integer edges), finish_graph, then set_state / gradient / run / kl."""
+    _destroy = "mvs_tsne_destroy"
+
+    def __init__(self, ctx, n, _handle=None):
+        self.ctx, self.n = ctx, int(n)
+        if _handle is None:
+            _handle = _P()
+            _check(ctx.lib.mvs_tsne_create(ctx._h, self.n, ctypes.byref(_handle)))
+        self._h = _handle
+        ctx._children.add(self)
+
+    def add_edges(self, lo, hi, s):
+        """raw edges: three int32 arrays of one length (numpy, or torch tensors that all live in the same place), s >= 1"""
+        if _is_torch(lo):
+            (lp, lm, lk), (hp, hm, hk), (sp, sm, sk) = _buf(lo), _buf(hi), _buf(s)
+            if not (lm == hm == sm):
+                raise ValueError("lo, hi and s must live in the same place")
+        else:
+            (lp, lm, lk), (hp, hm, hk), (sp, sm, sk) = _buf(lo, np.int32), _buf(hi, np.int32), _buf(s, np.int32)
+        if not (len(lo) == len(hi) == len(s)):
+            raise ValueError("lo, hi and s must have one length")
+        _check(self.ctx.lib.mvs_tsne_add_edges(self._h, lp, hp, sp, len(lo), lm))
+
+    def add_neighbours(self, cells, norms_sq, d, perplexity, n_cells=None):
+        """cells: a CELL_DTYPE array (host) or a torch CUDA int32 tensor [m, 4], sorted by row as pairwise_topk returns them
+        -> (beta float64 [n]: written between the list's first and last row, c int32 per cell)"""
+        if _is_torch(cells):
+            cp, n_cells, ck = _cell_list(cells, n_cells)
+            cm = MEM_DEVICE
+        else:
+            ck = np.ascontiguousarray(cells, dtype=CELL_DTYPE)
+            cp, cm, n_cells = ck.ctypes.data, MEM_HOST, len(ck)
+        np_, nm, nk = _norms(norms_sq)
+        beta = np.zeros(self.n, dtype=np.float64)
+        c = np.zeros(max(1, n_cells), dtype=np.int32)
+        _check(self.ctx.lib.mvs_tsne_add_neighbours(self._h, cp, n_cells, cm, np_, nm, int(d), float(perplexity), beta.ctypes.data,
+                                                    c.ctypes.data))
+        return beta, c[:n_cells]
+
+    def finish_graph(self):
+        _check(self.ctx.lib.mvs_tsne_finish_graph(self._h))
+
+    def edges(self):
+        """-> (row, col, s, S): the stored directed entries sorted by (row, col) as int32 / int32 / int64 arrays, and their sum"""
+        m, S = _c.c_int64(), _c.c_uint64()
+        _check(self.ctx.lib.mvs_tsne_edges(self._h, None, None, None, 0, ctypes.byref(m), ctypes.byref(S)))
+        row, col = np.zeros(max(1, m.value), dtype=np.int32), np.zeros(max(1, m.value), dtype=np.int32)
+        s = np.zeros(max(1, m.value), dtype=np.int64)
+        _check(self.ctx.lib.mvs_tsne_edges(self._h, row.ctypes.data, col.ctypes.data, s.ctypes.data, len(s), ctypes.byref(m), ctypes.byref(S)))
+        return row[:m.value], col[:m.value], s[:m.value], int(S.value)
+
+    def set_state(self, y=None, velocity=None, gain=None):
+        """float64 [n, 2] each; None leaves that part as it is"""
+        bufs = []
+        for a in (y, velocity, gain):
+            if a is None:
+                bufs.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (self.n, 2):
+                raise ValueError("state arrays are [n, 2]")
+            bufs.append(a)
+        _check(self.ctx.lib.mvs_tsne_set_state(self._h, *[None if a is None else a.ctypes.data for a in bufs]))
+
+    def get_state(self):
+        """-> (y, velocity, gain), float64 [n, 2] each"""
+        out = [np.zeros((self.n, 2), dtype=np.float64) for _ in range(3)]
+        _check(self.ctx.lib.mvs_tsne_get_state(self._h, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def gradient(self, exaggeration=1.0):
+        """one evaluation, state untouched -> (grad float64 [n, 2], Z_rows int64 [n], Z int)"""
+        grad, zr, z = np.zeros((self.n, 2), dtype=np.float64), np.zeros(self.n, dtype=np.int64), _c.c_int64()
+        _check(self.ctx.lib.mvs_tsne_gradient(self._h, float(exaggeration), grad.ctypes.data, zr.ctypes.data, ctypes.byref(z)))
+        return grad, zr, int(z.value)
+
+    def run(self, iterations, exaggeration, momentum, learning_rate):
+        _check(self.ctx.lib.mvs_tsne_run(self._h, int(iterations), float(exaggeration), float(momentum), float(learning_rate)))
+
+    def kl(self):
+        v = _c.c_double()
+        _check(self.ctx.lib.mvs_tsne_kl(self._h, ctypes.byref(v)))
+        return v.value
+
+
+class Tsne:
+    """What Context.tsne returns: `coordinates` (float64 [n, 2], centred), `initial` (the state the optimiser started from),
+    `beta` (float64 [n]; 0 = a uniform row), `kl`, `edges` (row, col, s, S of the symmetric graph), `iterations`,
+    `learning_rate`, `neighbours`, `beta_zero_rows`."""
+
+    def __init__(self, res, coordinates, initial, beta, edges):
+        self.coordinates, self.initial, self.beta, self.edges = coordinates, initial, beta, edges
+        self.kl, self.iterations, self.learning_rate = float(res.kl), int(res.iterations), float(res.learning_rate)
+        self.neighbours, self.beta_zero_rows = int(res.neighbours), int(res.beta_zero_rows)
+
+    def __repr__(self):
+        return "Tsne(%d samples, %d neighbours, %d entries, %d iterations, KL %.4f)" % (
+            len(self.coordinates), self.neighbours, len(self.edges[0]), self.iterations, self.kl)
 
 
 class DerepResult:
@@ -2139,6 +2270,38 @@ class Context:
         out = {k: x.value for k, x in zip(names, d + n)}
         out["paths"] = paths.tolist()
         return out
+
+    # ---- t-SNE (include/mvs_hip.h "t-SNE") ----
+    def tsne_graph(self, n):
+        """-> TsneGraph: an empty graph of affinities and a fresh optimiser state over n samples"""
+        return TsneGraph(self, n)
+
+    def tsne(self, sset, norms_sq, perplexity=30, neighbours=None, iterations=750, exaggeration=12, exaggeration_iters=250,
+             learning_rate=None, init="pcoa", seed=0):
+        """The exact t-SNE map of the Jaccard kNN graph -> Tsne.  Equal to tests/tsne_model.py bit for bit from the same graph and
+        initial state, whatever the blocking or the options."""
+        if init not in TSNE_INIT:
+            raise ValueError("init is 'pcoa' or 'random'")
+        p = TsneParams(float(perplexity), float(exaggeration), float(learning_rate or 0.0), int(neighbours or 0), int(iterations),
+                       int(exaggeration_iters), TSNE_INIT[init], int(seed))
+        np_, nm, nk = _norms(norms_sq)
+        n = sset.n
+        Y, Y0, beta = np.zeros((n, 2), dtype=np.float64), np.zeros((n, 2), dtype=np.float64), np.zeros(n, dtype=np.float64)
+        res, h = TsneResult(), _P()
+        _check(self.lib.mvs_tsne(self._h, sset._h, np_, nm, ctypes.byref(p), Y.ctypes.data, Y0.ctypes.data, beta.ctypes.data,
+                                 ctypes.byref(res), ctypes.byref(h)))
+        with TsneGraph(self, n, _handle=h) as g:
+            edges = g.edges()
+        return Tsne(res, Y, Y0, beta, edges)
+
+    def tsne_stats(self):
+        """-> dict since this context's last TsneGraph was created: topk_ms, calibrate_ms, graph_ms, repulse_ms, attract_ms,
+        update_ms (timing on), iterations, entries, units, row_blocks"""
+        d = [_c.c_double() for _ in range(6)]
+        n = [_c.c_int64() for _ in range(4)]
+        _check(self.lib.mvs_ctx_tsne_stats(self._h, *[ctypes.byref(x) for x in d + n]))
+        names = ("topk_ms", "calibrate_ms", "graph_ms", "repulse_ms", "attract_ms", "update_ms", "iterations", "entries", "units", "row_blocks")
+        return {k: x.value for k, x in zip(names, d + n)}
 
     def _consumer_stats(self, fn, work_key):
         """what cluster_stats, linkage_stats and derep_stats share: fn is the context's mvs_ctx_*_stats, work_key names the time

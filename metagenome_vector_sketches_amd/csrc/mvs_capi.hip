@@ -453,6 +453,11 @@ int mvs_ctx_set_option(mvs_ctx* c, const char* name, int64_t value) {
         c->community_path = (int)value;
         return MVS_OK;
     }
+    if (std::strcmp(name, "tsne_slice_cols") == 0) {         // the repulsion's column slice; never changes a result
+        if (value < 16 || value > 1024) return fail(MVS_E_INVALID, "option tsne_slice_cols: 16 .. 1024 columns");
+        c->tsne_slice_cols = (int)value;
+        return MVS_OK;
+    }
     if (std::strcmp(name, "report_spin") == 0) {             // host-side waiting only
         if (value < 0 || value > 1000000) return fail(MVS_E_INVALID, "option report_spin: 0 .. 1000000 microseconds");
         c->report_spin = (int)value;
@@ -495,6 +500,10 @@ int mvs_ctx_get_option(const mvs_ctx* c, const char* name, int64_t* value) {
     }
     if (std::strcmp(name, "community_path") == 0) {
         *value = c->community_path;
+        return MVS_OK;
+    }
+    if (std::strcmp(name, "tsne_slice_cols") == 0) {
+        *value = c->tsne_slice_cols;
         return MVS_OK;
     }
     if (std::strcmp(name, "report_spin") == 0) {

@@ -86,6 +86,14 @@ struct CommunityStats {
     long long paths[5] = {0, 0, 0, 0, 0};
     void reset() { *this = CommunityStats(); }
 };
+// what the t-SNE calls did on a context since its last mvs_tsne_create (mvs_ctx_tsne_stats): kernel times of top-k, of the
+// calibration, of the graph's build (sort, sum by key, CSR, P), of the repulsion, the attraction and the update summed over the
+// iterations (timing enabled); iterations run, directed entries of the graph, units of one repulsion, top-k row ranges
+struct TsneStats {
+    double topk_ms = 0.0, calibrate_ms = 0.0, graph_ms = 0.0, repulse_ms = 0.0, attract_ms = 0.0, update_ms = 0.0;
+    long long iterations = 0, edges = 0, units = 0, blocks = 0;
+    void reset() { *this = TsneStats(); }
+};
 }  // namespace mvs_capi
 
 struct mvs_ctx {
@@ -246,6 +254,9 @@ struct mvs_ctx {
     mvs_capi::CommunityStats cm;
     int community_path = 0;               // mvs_community_finish: a vertex starts in 0 = the path its degree names, 1 = the wave path, 2 = the
                                           // workgroup path, 3 = the global path (tests); same result (option community_path)
+    mvs_capi::TsneStats ts;
+    int tsne_slice_cols = 1024;           // mvs_tsne_gradient / _run / _kl: columns of a repulsion unit, 16 .. 1024 (tests force small inputs
+                                          // through many slices); same sums (option tsne_slice_cols)
     int core_block_rows = 0;              // mvs_core_jaccard / mvs_hdbscan: > 0 = upper bound on the rows of a top-k range (tests); 0 = by
                                           // the cell buffer's budget.  Host-side blocking only (option core_block_rows)
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
