@@ -751,7 +751,8 @@ int mvs_ctx_linkage_stats(const mvs_ctx* ctx, double* compare_ms, double* forest
  *                     doubles or NULL), floor (not NaN), min_cluster_size >= 2, flags.  Any output pointer may be NULL.
  * mvs_hdbscan         core (K = min_samples), linkage with that core at `floor` (0 < floor < 1, as mvs_pairwise_linkage), finish,
  *                     select.  core_out, links (room for n - 1), n_links and the outputs of the selection are HOST buffers;
- *                     any may be NULL.  cluster_capacity as above.
+ *                     any may be NULL.  cluster_capacity as above.  The pairs that arrive are those of the comparison's keep
+ *                     test at `floor` (the cut property's caveat above applies); the selection's m > floor only removes links.
  * mvs_ctx_hdbscan_stats  of the context's last mvs_core_jaccard / mvs_hdbscan: kernel times of top-k's dots and selection summed
  *                     over the ranges and of the reduction (0 unless mvs_ctx_set_timing is on), of the comparison and the
  *                     forest (mvs_ctx_linkage_stats), host time of the selection (always measured); top-k ranges, the most
@@ -1499,9 +1500,17 @@ int mvs_ctx_hclust_stats(const mvs_ctx* ctx, double* dots_ms, double* fill_ms, d
  * mvs_community_add_edges raw integer edges (lo[i], hi[i], a[i]), 1 <= a <= 2^20, HOST or DEVICE (`mem`): the entry of crafted
  *                         tests and of other producers.  lo == hi is ignored; an index outside [0, n) or a weight outside its
  *                         range is ignored and reported as MVS_E_RANGE (the rest is consumed).
- * mvs_pairwise_community  the one-call producer: the comparison of mvs_pairwise_cluster at level `floor` (its staging buffer,
- *                         halving rule, options cluster_cells / cluster_block_rows and argument checks: floor outside (0, 1) is
- *                         MVS_E_INVALID), every block's list fed to add_cells.  The set's d must be the graph's.
+ * mvs_pairwise_community  the one-call producer: the comparison of mvs_pairwise_cluster (its staging buffer, halving rule, options
+ *                         cluster_cells / cluster_block_rows and argument checks on `floor`: outside (0, 1) is MVS_E_INVALID),
+ *                         every block's list fed to add_cells.  The set's d must be the graph's.  The comparison runs at the
+ *                         level floor * (1 - 2^-40), not at floor: its keep test, (double)dot / d > t / (1 + t) * s, and the
+ *                         rule's J > floor are one inequality in algebra and differ in fp64 within a few doubles of the boundary
+ *                         (at floor 0.1 and d = 384 the keep test drops pairs whose J exceeds the floor).  2^-40 is 2^12 times
+ *                         that disagreement, so every pair with J > floor is kept and add_cells decides it: the edge set is the
+ *                         graph rule's alone wherever s = n2[row] + n2[col] > 0.  (A pair with s < inter < 0 -- negative norms
+ *                         and a negative dot -- has J > 0 and fails the keep test at every level: it is never fed.)  So
+ *                         mvs_pairwise_cluster at level t and the communities at floor t may differ, in degree and in who is
+ *                         linked, on pairs whose J is within an ulp of t.
  * mvs_community_finish    builds the graph if cells arrived since the last build (sort, one entry per edge, both directions
  *                         sorted into a CSR) and runs the rule.  May be called again with another resolution without feeding
  *                         again; more cells may be added in between.  `mem_out` says where labels (n int32), level_labels

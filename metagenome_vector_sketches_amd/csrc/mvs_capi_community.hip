@@ -269,8 +269,13 @@ int mvs_pairwise_community(mvs_ctx* c, const mvs_sketch_set* s, const double* no
     const int rc = consumer_checks("community graph", c, s, k, mem_norms, floor_);
     if (rc) return rc;
     if (s->d != k->d) return fail(MVS_E_INVALID, "the graph was created for dimension %d, the sketch set has %d", k->d, s->d);
+    // The comparison's keep test, double(P)/d > t/(1+t) * (n2r + n2c), and the rule's J > floor are one inequality in algebra and
+    // differ in fp64 within a few doubles of the boundary (at floor 0.1, d = 384 the keep test drops pairs the rule calls edges:
+    // tests/rule_edges_model.py).  The graph's edge set is the rule's alone: the comparison runs at a level 2^-40 (relative) below
+    // the floor -- 2^12 times the disagreement -- so it keeps a superset, and k_comm_cells decides every kept cell with J > floor.
+    const double feed_level = floor_ * (1.0 - 1.0 / 1099511627776.0);                    // (1 - 2^-40)
     ConsumerStats st;
-    const int rf = feed_consumer("mvs_pairwise_community", c, s, norms_sq, mem_norms, floor_, st,
+    const int rf = feed_consumer("mvs_pairwise_community", c, s, norms_sq, mem_norms, feed_level, st,
                                  [k](const mvs_cell* d_cells, int64_t n_cells, int64_t, int64_t) { return consume_cells(k, d_cells, n_cells); });
     c->cm.compare_ms += st.compare_ms;
     c->cm.blocks += st.blocks;
