@@ -585,7 +585,10 @@ int mvs_ctx_levels_stats(const mvs_ctx* ctx, double* dots_ms, double* count_ms, 
  *   (double)dot / (double)d > (t / (1.0 + t)) * (n2[i] + n2[j])        (fp64, in that order; t = min_jaccard, 0 < t < 1)
  * -- "the Jaccard estimate of src/pairwise_comp_optimized.cpp:661-662 exceeds t", the rule and the kernels of mvs_search_block
  * (the floating keep test with the coefficient t/(1+t) in place of 0.05); `dot` is the wrapped int32 dot every path reports.
- * A sample whose norm is NaN or +inf is linked to nothing.  A CLUSTER is a connected component of that graph.  The reference
+ * A sample whose norm is NaN or +inf is linked to nothing; every other double is held to the test as written, on every comparison
+ * path: a negative norm lowers the threshold, and a sample whose norm is -inf is linked to every sample whose norm is neither NaN
+ * nor +inf.  (The single-linkage tree and the greedy dereplication take their pairs from the same comparison.)  A CLUSTER is a
+ * connected component of that graph.  The reference
  * has no clustering: it writes the thresholded matrix (:645-817) and leaves the grouping to its readers; here the kept cells
  * never leave the device and the answer is four int32 arrays:
  *   labels[i]          cluster of sample i; clusters are numbered 0 .. C-1 by ascending smallest member

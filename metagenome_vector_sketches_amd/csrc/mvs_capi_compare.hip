@@ -377,7 +377,7 @@ int two_stage_filter(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, do
             a.cand_counter = c->d_counter + 6;
         }
         // the exact kernel's integer pre-test constants
-        rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, (size_t)s->n_alloc * 4);
+        rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
         if (rc) return rc;
         mvs::launch_cand_thr(c->stream, d_n2, s->n, s->n_alloc, s->d, keep_coeff, (int32_t*)c->pw_thr);
         rc = check_kernel("k_cand_thr");
@@ -529,7 +529,7 @@ int pairwise_launch(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int
     }
     c->last_candidates = 0;
     if (po && po->two_stage_only) return kNeedExact;
-    rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, (size_t)s->n_alloc * 4);
+    rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
     if (rc) return rc;
     mvs::launch_cand_thr(c->stream, d_n2, s->n, s->n_alloc, s->d, keep_coeff, (int32_t*)c->pw_thr);
     rc = check_kernel("k_cand_thr");

@@ -593,7 +593,7 @@ int mvs_plan_finish(mvs_ctx* c, const uint64_t** d_count) {
             a.cand = (int2*)c->pw_cand2;
             a.cand_capacity = c->pw_cand2_bytes / sizeof(int2);
             a.cand_counter = c->d_counter + 6;
-            rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, (size_t)s->n_alloc * 4);
+            rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
             if (rc) return rc;
             mvs::launch_cand_thr(c->stream, st.d_n2, s->n, s->n_alloc, s->d, a.keep_coeff, (int32_t*)c->pw_thr);
             rc = check_kernel("k_cand_thr");
@@ -684,7 +684,7 @@ int mvs_plan_finish(mvs_ctx* c, const uint64_t** d_count) {
             a.cand_capacity = c->pw_cand2_bytes / sizeof(int2);
             a.cand_counter = c->d_counter + 6;
         }
-        rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, (size_t)s->n_alloc * 4);
+        rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
         if (rc) return rc;
         mvs::launch_cand_thr(c->stream, st.d_n2, s->n, s->n_alloc, s->d, a.keep_coeff, (int32_t*)c->pw_thr);
         rc = check_kernel("k_cand_thr");

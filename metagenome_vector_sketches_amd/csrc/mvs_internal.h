@@ -155,7 +155,7 @@ struct PairwiseArgs {
     int64_t col_begin, col_end;   // column range (dots) / [0,n) for the comparison
     // comparison outputs
     const double* norms_sq;       // n
-    const int32_t* cand_thr;      // n_alloc: conservative integer per-sample threshold part
+    const int32_t* cand_thr;      // n_alloc (+ 1, launch_cand_thr's mark): conservative integer per-sample threshold part
     int keep_mode;
     double keep_coeff;            // 0.05 in the reference's keep test; j/(1+j) for a Jaccard > j search
     mvs_cell* cells;

@@ -82,7 +82,10 @@ __global__ __launch_bounds__(256) void k_limb_split(const T* __restrict__ sk, in
     }
 }
 
-// conservative integer part of the keep threshold: keep(i,j) implies P >= thr[i] + thr[j]
+// conservative integer part of the keep threshold: keep(i,j) implies P >= thr[i] + thr[j] -- as long as no norm is negative.
+// A negative norm (never produced by the reference's loader, but callers pass arbitrary doubles) pulls a pair's threshold
+// below what one int32 per sample can state -- with -inf every dot passes the keep test, INT32_MIN included -- so it raises
+// the word behind the thresholds, thr[n_alloc] (cleared by the launcher), and k_cand_thr_open opens the test for the call.
 __global__ __launch_bounds__(256) void k_cand_thr(const double* __restrict__ n2, int64_t n, int64_t n_alloc,
                                                   int d, double coeff, int32_t* __restrict__ thr) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -94,9 +97,18 @@ __global__ __launch_bounds__(256) void k_cand_thr(const double* __restrict__ n2,
         if (x >= 0.0) {
             const double f = floor(coeff * (double)d * x * (1.0 - 1.0 / 1048576.0)) - 1.0;
             t = f >= 1073741823.0 ? (1 << 30) - 1 : (f < -1.0 ? -1 : (int32_t)f);
+        } else if (x < 0.0) {
+            thr[n_alloc] = 1;    // (every writer stores the same value)
         }
     }
     thr[i] = t;
+}
+
+// a launch of its own, so that the word is final: if a norm was negative every sample gets -2^30 -- the sum of two is -2^31, below
+// or at every int32 dot, and the keep test alone decides each cell (slow, and exact; the two-stage filter does the same per row)
+__global__ __launch_bounds__(256) void k_cand_thr_open(int64_t n, int64_t n_alloc, int32_t* __restrict__ thr) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && thr[n_alloc] != 0) thr[i] = -(1 << 30);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -554,8 +566,11 @@ int launch_limb_split(hipStream_t stream, const void* d_sk, int elem_bytes, int6
 
 int launch_cand_thr(hipStream_t stream, const double* d_norms_sq, int64_t n, int64_t n_alloc, int d,
                     double coeff, int32_t* d_thr) {
-    hipLaunchKernelGGL(k_cand_thr, dim3((unsigned)((n_alloc + 255) / 256)), dim3(256), 0, stream, d_norms_sq, n,
-                       n_alloc, d, coeff, d_thr);
+    // d_thr: n_alloc + 1 words, the last one the "a norm is negative" mark
+    if (hipMemsetAsync(d_thr + n_alloc, 0, sizeof(int32_t), stream) != hipSuccess) return MVS_E_HIP;
+    const dim3 grid((unsigned)((n_alloc + 255) / 256));
+    hipLaunchKernelGGL(k_cand_thr, grid, dim3(256), 0, stream, d_norms_sq, n, n_alloc, d, coeff, d_thr);
+    hipLaunchKernelGGL(k_cand_thr_open, grid, dim3(256), 0, stream, n, n_alloc, d_thr);
     return 0;
 }
 
