@@ -172,6 +172,10 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   intersect_unit        mvs_intersect_cells: elements of a pair's SHORTER hash list that one unit of work (one wave) covers,
  *                         64 .. 2^30 (default 2048); a pair with a longer one is cut into several units
  *   gather_batch          mvs_gather: rounds of the walk queued between two read-backs of its state, 1 .. 1024 (default 16)
+ *   kmer_unit             mvs_hash_set_from_sequences: k-mer positions of one sample that one unit of work (one workgroup)
+ *                         covers, 64 .. 32768 (default 17408); a longer sample is cut into several units
+ *   kmer_capacity         mvs_hash_set_from_sequences: > 0 = the values the staging list of the first hashing pass holds (tests
+ *                         lower it to force the second pass); 0 (default) = the expected number of kept values plus a margin
  *   stream_block_rows, encode_stage_words, pairwise_map, coarse_radix, cand_regions, recheck_mode, recheck_blocks
  *                         test / experiment switches (DESIGN.md, appendix "switches"; encode_stage_words below 64 also keeps
  *                         every row on the device encoder's general loop)
@@ -891,6 +895,62 @@ int mvs_hash_set_destroy(mvs_hash_set* set);
 int mvs_intersect_cells(mvs_ctx* ctx, const mvs_hash_set* hs_rows, const mvs_hash_set* hs_cols, const mvs_cell* cells,
                         int mem_cells, int64_t n_cells, int32_t* inter, int mem_out);
 int mvs_ctx_intersect_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* units, int64_t* cut_pairs, int64_t* bytes);
+
+/* ---- sketches from sequences: FracMinHash values of DNA bytes ------------------------------------------------------------------
+ * Every path of this library starts from hash lists.  These calls make them from sequences, on the device, as a mvs_hash_set:
+ * mvs_intersect_cells and mvs_gather take it as it is, mvs_project_csr takes its device pointer (mvs_hash_set_device).  The
+ * reference has no hashing of sequences (only its unused extract_31mers hints at the need), so nothing of it is replaced.
+ *
+ * A SAMPLE is a byte string.  Its sketch for (ksize, seed, max_hash) is the ascending list of the distinct values h below.
+ *   Bases and breaks: the bytes A C G T a c g t are bases, lower case counting as upper case; every other byte (N, IUPAC codes,
+ *     '\n', 0, 255, ...) is a break.  No k-mer contains a break; a caller joins the records of one sample with one break byte,
+ *     so that no k-mer spans two records.
+ *   Per k-mer: for every position i such that bytes i .. i + ksize - 1 are all bases, fw = those bytes upper-cased, rc = the
+ *     reverse complement (A<->T, C<->G), canon = the bytewise-lexicographically smaller of the two,
+ *         h = the FIRST 64-bit word of MurmurHash3_x64_128(canon, ksize bytes, seed)       (Appleby, public domain)
+ *     and h is kept iff h <= max_hash.  1 <= ksize <= 32 (a k-mer is then one 64-bit word of 2-bit codes, whose integer order is
+ *     the string order); ksize > 32 is refused.
+ *   max_hash(scaled) = (uint64)(2^64 / (double)scaled) for scaled >= 2 and 2^64 - 1 for scaled = 1 (keep everything): 1000 gives
+ *     18446744073709552, 2000 gives 9223372036854776.
+ * Exact and deterministic whatever the options, the units of work or where the bytes lie.  Not offered: ksize > 32, protein /
+ * dayhoff / hp alphabets, abundances, sourmash .sig JSON, adding bases to a sample over several calls, several GPUs.
+ *
+ * mvs_kmer_max_hash     the formula above.  Pure host.  scaled < 1: MVS_E_INVALID.
+ * mvs_kmer_hash         the per-k-mer rule for the ksize bytes at `kmer`: *h and *valid = 1, or *valid = 0 (and *h = 0) if one
+ *                       of them is a break.  Pure host: the library's own statement of the contract.
+ * mvs_hash_set_from_sequences
+ *                       the sketches of n_samples samples -> a new hash set (destroy it with mvs_hash_set_destroy).  Sample s
+ *                       is bytes [offsets[s], offsets[s + 1]) of `bases` (`mem_bases` says where they lie; offsets: n_samples
+ *                       + 1 HOST int64, non-decreasing).  Samples may be empty or shorter than ksize: they get an empty list.
+ *                       The byte count is 64-bit; a sample keeps fewer than 2^31 values (MVS_E_RANGE otherwise).  NULL
+ *                       pointers, ksize outside 1 .. 32, decreasing offsets: MVS_E_INVALID, nothing is allocated.  Host
+ *                       bytes go up in ONE plain copy, as for mvs_hash_set_create.  Synchronous.
+ *                       How: the host cuts the samples into units of up to option kmer_unit positions, one workgroup each;
+ *                       kept values are appended to a staging list sized for the expected number (positions x (max_hash + 1)
+ *                       / 2^64, plus an eighth and 65536; option kmer_capacity > 0: exactly that many).  The counts are exact
+ *                       even when the list is too short: the hashing pass then runs a second time with a list of exactly
+ *                       the counted size -- nothing is ever truncated.  The values are moved to their samples' ranges and
+ *                       mvs_hash_set_create's segmented sort and unique compaction finish the set.
+ * mvs_hash_set_export   what a set (however it was made) holds: `hashes` (total values where `mem_out` says, per sample
+ *                       strictly increasing) and `offsets` (n_samples + 1 HOST int64).  Either may be NULL.  Synchronous.
+ * mvs_hash_set_device   the device address of the set's values, valid until the set is destroyed: with the exported offsets,
+ *                       mvs_project_csr(..., MVS_MEM_DEVICE, offsets, ...) projects the set where it lies.
+ * mvs_ctx_kmer_stats    the context's last mvs_hash_set_from_sequences: time of its hashing passes and of the move into sample
+ *                       order (0 unless mvs_ctx_set_timing is on), bytes given, valid positions (k-mers), values kept before
+ *                       the unique compaction, units of work, hashing passes repeated for a longer staging list.  Any
+ *                       pointer may be NULL.
+ * mvs_ctx_kmer_sample_stats
+ *                       ... and per sample: valid positions and values kept before the unique compaction, n_samples int64
+ *                       each on the host (n_samples must be the last call's: MVS_E_INVALID otherwise).  Either may be NULL. */
+int mvs_kmer_max_hash(int64_t scaled, uint64_t* max_hash);
+int mvs_kmer_hash(const char* kmer, int ksize, uint32_t seed, uint64_t* h, int* valid);
+int mvs_hash_set_from_sequences(mvs_ctx* ctx, const uint8_t* bases, int mem_bases, const int64_t* offsets, int64_t n_samples,
+                                int ksize, uint32_t seed, uint64_t max_hash, mvs_hash_set** set);
+int mvs_hash_set_export(const mvs_hash_set* set, uint64_t* hashes, int mem_out, int64_t* offsets);
+int mvs_hash_set_device(const mvs_hash_set* set, const uint64_t** d_hashes);
+int mvs_ctx_kmer_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* bases, int64_t* kmers, int64_t* kept, int64_t* units,
+                       int64_t* second_trips);
+int mvs_ctx_kmer_sample_stats(const mvs_ctx* ctx, int64_t n_samples, int64_t* kmers, int64_t* kept);
 
 /* ---- gather: the greedy decomposition of a query into samples of a hash set -------------------------------------------------
  * Everything above asks about a PAIR of samples.  This call answers the set question "which DB samples make up my sample, and

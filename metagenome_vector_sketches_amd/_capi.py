@@ -234,6 +234,13 @@ SYMBOLS = [
     ("mvs_hash_set_info", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int)]),
     ("mvs_hash_set_sizes", _c.c_int, [_P, _P, _c.c_int]),
     ("mvs_hash_set_destroy", _c.c_int, [_P]),
+    ("mvs_kmer_max_hash", _c.c_int, [_c.c_int64, _c.POINTER(_c.c_uint64)]),
+    ("mvs_kmer_hash", _c.c_int, [_c.c_char_p, _c.c_int, _c.c_uint32, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
+    ("mvs_hash_set_from_sequences", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int64, _c.c_int, _c.c_uint32, _c.c_uint64, _c.POINTER(_P)]),
+    ("mvs_hash_set_export", _c.c_int, [_P, _P, _c.c_int, _P]),
+    ("mvs_hash_set_device", _c.c_int, [_P, _c.POINTER(_P)]),
+    ("mvs_ctx_kmer_stats", _c.c_int, [_P, _c.POINTER(_c.c_double)] + [_c.POINTER(_c.c_int64)] * 5),
+    ("mvs_ctx_kmer_sample_stats", _c.c_int, [_P, _c.c_int64, _P, _P]),
     ("mvs_intersect_cells", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _P, _c.c_int]),
     ("mvs_ctx_intersect_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
                                             _c.POINTER(_c.c_int64)]),
@@ -364,6 +371,8 @@ def _buf(x, dtype=None, writable=False):
     """-> (pointer, mem flag, keepalive).  numpy arrays are host buffers, torch CUDA tensors device."""
     if x is None:
         return None, MEM_HOST, None
+    if isinstance(x, DeviceArray):
+        return x.ptr, MEM_DEVICE, x
     if _is_torch(x):
         if not x.is_contiguous():
             raise ValueError("tensor must be contiguous")
@@ -372,6 +381,35 @@ def _buf(x, dtype=None, writable=False):
     if writable and (not a.flags["C_CONTIGUOUS"] or (dtype is not None and a.dtype != np.dtype(dtype))):
         raise ValueError("output array must be C-contiguous %s" % dtype)
     return a.ctypes.data, MEM_HOST, a
+
+
+class DeviceArray:
+    """`count` values of `dtype` at the device address `ptr`, owned by `owner` (which this object keeps alive): what
+    HashSet.device_hashes returns, accepted wherever a device buffer of hashes is (Context.project_csr, Context.hash_set)."""
+
+    def __init__(self, ptr, count, dtype, owner):
+        self.ptr, self.count, self.dtype, self.owner = ptr, int(count), np.dtype(dtype), owner
+
+    def __len__(self):
+        return self.count
+
+
+def kmer_max_hash(scaled):
+    """mvs_kmer_max_hash: the largest hash a FracMinHash sketch of this `scaled` keeps (scaled = 1: 2^64 - 1)"""
+    out = _c.c_uint64()
+    _check(load_library().mvs_kmer_max_hash(int(scaled), ctypes.byref(out)))
+    return out.value
+
+
+def kmer_hash(kmer, seed=42):
+    """mvs_kmer_hash: the hash of one k-mer (bytes or str, 1 .. 32 letters) under the sketching rule -- canonical form,
+    MurmurHash3_x64_128's first word --, or None if one of its bytes is not a base"""
+    if isinstance(kmer, str):
+        kmer = kmer.encode("latin-1")
+    kmer = bytes(kmer)
+    h, valid = _c.c_uint64(), _c.c_int()
+    _check(load_library().mvs_kmer_hash(kmer, len(kmer), int(seed) & 0xFFFFFFFF, ctypes.byref(h), ctypes.byref(valid)))
+    return h.value if valid.value else None
 
 
 def _norms(norms_sq):
@@ -1287,6 +1325,28 @@ class HashSet(_Handle):
         op, om, ok = _buf(out, np.int32, writable=True) if not _is_torch(out) else _buf(out)
         _check(self.ctx.lib.mvs_hash_set_sizes(self._h, op, om))
         return out
+
+    def export(self):
+        """-> (hashes uint64 [total], offsets int64 [n + 1]) as numpy arrays: every sample's values, strictly increasing
+        (mvs_hash_set_export)"""
+        hashes, offsets = np.empty(self.total, dtype=np.uint64), np.empty(self.n + 1, dtype=np.int64)
+        _check(self.ctx.lib.mvs_hash_set_export(self._h, hashes.ctypes.data, MEM_HOST, offsets.ctypes.data))
+        return hashes, offsets
+
+    def device_hashes(self):
+        """-> DeviceArray of the set's values where they lie (mvs_hash_set_device), valid while the set is open: with
+        export()'s offsets (or offsets()), Context.project_csr projects the set without a copy over the link"""
+        if self._h is None:
+            raise ValueError("the hash set is closed")
+        p = _P()
+        _check(self.ctx.lib.mvs_hash_set_device(self._h, ctypes.byref(p)))
+        return DeviceArray(p.value, self.total, np.uint64, self)
+
+    def offsets(self):
+        """-> int64 [n + 1]: where every sample's values start in export()'s / device_hashes()'s array"""
+        offsets = np.empty(self.n + 1, dtype=np.int64)
+        _check(self.ctx.lib.mvs_hash_set_export(self._h, None, MEM_HOST, offsets.ctypes.data))
+        return offsets
 
 
 class GatherResult:
@@ -2433,6 +2493,51 @@ class Context:
         h = _P()
         _check(self.lib.mvs_hash_set_create(self._h, hp, hm, offsets.ctypes.data, n, ctypes.byref(h)))
         return HashSet(self, h)
+
+    # ---- sketches from sequences (include/mvs_hip.h "sketches from sequences") ----
+    def sketch_sequences(self, seqs, ksize=31, scaled=1000, seed=42, max_hash=None):
+        """mvs_hash_set_from_sequences: the FracMinHash sketches of DNA samples -> HashSet.  seqs: a list of bytes / str, one
+        sample each (join the records of a sample with one non-base byte such as b"\\n"), or a pair (bases, offsets) with bases
+        a uint8 numpy array or torch tensor (host or device) and offsets host int64 [n + 1].  A value is kept iff it is
+        <= max_hash (default: kmer_max_hash(scaled))."""
+        if isinstance(seqs, tuple) and len(seqs) == 2 and not isinstance(seqs[0], (bytes, bytearray, str)):
+            bases, offsets = seqs
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            if _is_torch(bases):
+                if str(bases.dtype) != "torch.uint8":
+                    raise ValueError("bases must be uint8")
+                bp, bm, bk = _buf(bases)
+            else:
+                bp, bm, bk = _buf(bases, np.uint8)
+        else:
+            parts = [x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in seqs]
+            offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+            if parts:
+                np.cumsum([len(x) for x in parts], out=offsets[1:])
+            bp, bm, bk = _buf(np.frombuffer(b"".join(parts), dtype=np.uint8), np.uint8)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("offsets must hold n + 1 entries")
+        if max_hash is None:
+            max_hash = kmer_max_hash(scaled)
+        h = _P()
+        _check(self.lib.mvs_hash_set_from_sequences(self._h, bp, bm, offsets.ctypes.data, len(offsets) - 1, int(ksize),
+                                                     int(seed) & 0xFFFFFFFF, int(max_hash), ctypes.byref(h)))
+        return HashSet(self, h)
+
+    def kmer_stats(self):
+        """-> dict of this context's last sketch_sequences: kernel_ms (timing on), bases, kmers (valid positions), kept (values
+        <= max_hash before the unique compaction), units of work, second_trips (hashing passes repeated for a longer list)"""
+        ms = _c.c_double()
+        v = [_c.c_int64() for _ in range(5)]
+        _check(self.lib.mvs_ctx_kmer_stats(self._h, ctypes.byref(ms), *[ctypes.byref(x) for x in v]))
+        return dict(zip(("kernel_ms", "bases", "kmers", "kept", "units", "second_trips"), [ms.value] + [x.value for x in v]))
+
+    def kmer_sample_stats(self, n_samples):
+        """-> (kmers, kept): int64 [n_samples] each, per sample of this context's last sketch_sequences: valid positions and
+        the values <= max_hash before the unique compaction"""
+        kmers, kept = np.empty(n_samples, dtype=np.int64), np.empty(n_samples, dtype=np.int64)
+        _check(self.lib.mvs_ctx_kmer_sample_stats(self._h, int(n_samples), kmers.ctypes.data, kept.ctypes.data))
+        return kmers, kept
 
     def intersect_cells(self, hs, cells, n_cells=None, hs_cols=None, out=None):
         """inter[i] = |H_rows(cells[i].row) n H_cols(cells[i].col)|, exact (mvs_intersect_cells).  cells: numpy structured

@@ -1,5 +1,5 @@
 // mvs_tool.hpp -- what the tools over a sketch DB share (cluster_sketches, linkage_sketches, dereplicate_sketches, verify_pairs,
-// pca_sketches, pcoa_sketches, gather_sketches, permanova_sketches, hdbscan_sketches, silhouette_sketches, hclust_sketches, communities_sketches, tsne_sketches, and pairwise_comp_optimized for the loader): opening the DB folder, loading vectors.bin into a sketch set, reporting a
+// pca_sketches, pcoa_sketches, gather_sketches, permanova_sketches, hdbscan_sketches, silhouette_sketches, hclust_sketches, communities_sketches, tsne_sketches, pairwise_comp_optimized for the loader, and sketch_sequences for the flag values and the output file): opening the DB folder, loading vectors.bin into a sketch set, reporting a
 // device error, writing an output file under <file>.part, the hash file a DB was sketched from, and the parsing of flag values.  Header-only; include it after
 // mvs_host.hpp.  Each tool keeps its own parse() chain, usage text, Gpu holder and output format.
 #ifndef MVS_TOOL_HPP

@@ -212,6 +212,8 @@ const OptionSpec kOptions[] = {
     {"cluster_block_rows", &mvs::Options::cluster_block_rows, nullptr, 0, 1 << 30},
     {"intersect_unit", &mvs::Options::intersect_unit, nullptr, 64, 1 << 30},
     {"gather_batch", &mvs::Options::gather_batch, nullptr, 1, 1024},
+    {"kmer_unit", &mvs::Options::kmer_unit, nullptr, 64, mvs::kKmerUnitMax},
+    {"kmer_capacity", &mvs::Options::kmer_capacity, nullptr, 0, 1 << 30},
     {"pairwise_block_cells", nullptr, &mvs::Options::pairwise_block_cells, 1, (1LL << 62)},
 };
 

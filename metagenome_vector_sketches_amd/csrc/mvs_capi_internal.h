@@ -268,6 +268,12 @@ struct mvs_ctx {
     // walk's state), bytes of the bit rows; kernel times of the three phases (timing enabled)
     long long ga_survivors = 0, ga_rounds = 0, ga_batches = 0, ga_row_bytes = 0, ga_round_bytes = 0;
     double ga_overlap_ms = 0.0, ga_mark_ms = 0.0, ga_rounds_ms = 0.0;
+    // what the last mvs_hash_set_from_sequences did (mvs_ctx_kmer_stats): time of the hashing passes and the scatter (timing
+    // enabled), bytes read, valid positions, kept values before the unique compaction, units of work, hashing passes repeated
+    // because the staging list was too short
+    double km_kernel_ms = 0.0;
+    long long km_bases = 0, km_kmers = 0, km_kept = 0, km_units = 0, km_second_trips = 0;
+    std::vector<long long> km_sample_kmers, km_sample_kept;   // ... and per sample (mvs_ctx_kmer_sample_stats)
 };
 
 // hash lists resident on the device (mvs_capi_intersect.hip builds them; mvs_capi_gather.hip reads them too)

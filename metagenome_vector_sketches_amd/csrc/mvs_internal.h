@@ -130,6 +130,10 @@ struct Options {
     int cluster_block_rows = 0;     // mvs_pairwise_cluster: > 0 = upper bound on the rows of a block (tests); 0 = by pairwise_block_cells
     int intersect_unit = 2048;      // mvs_intersect_cells: elements of a pair's shorter hash list that one unit of work (one wave) covers
     int gather_batch = 16;          // mvs_gather: rounds queued between two read-backs of the walk's state, 1 .. 1024
+    int kmer_unit = 17408;          // mvs_hash_set_from_sequences: k-mer positions of one sample that one unit of work (one workgroup)
+                                    // covers, 64 .. 32768 (the default is 256 threads x 68 positions: LDS reads 17 dwords apart)
+    int kmer_capacity = 0;          // mvs_hash_set_from_sequences: > 0 = values the staging list of the first trip holds (tests force
+                                    // the second trip with it); 0 = the expected number of kept values plus a margin
     double pairwise_block_cells = 1099511627776.0;   // row-chunk bound of mvs_pairwise_rows (2^40 cells)
 };
 
@@ -497,6 +501,24 @@ int launch_isect_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_ce
                        const unsigned long long* d_hash_r, const long long* d_off_r, const int32_t* d_size_r,
                        const unsigned long long* d_hash_c, const long long* d_off_c, const int32_t* d_size_c, int unit,
                        int32_t* d_inter);
+// FracMinHash values of DNA bytes (mvs_kmer.hip).  A unit is npos <= `unit` consecutive k-mer positions of one sample, the first
+// at byte `byte0` of the buffer; launch_kmer_hash gives every unit to one workgroup (kmer_lds_bytes(unit, ksize) of LDS), which
+// appends (value, sample) of the kept positions to a staging list of `cap` entries -- what does not fit is dropped but
+// counted: d_counters[0] = kept values, d_sample_counts[s] / d_sample_valid[s] = kept values / valid positions of sample s
+// (all zeroed by the caller).  launch_kmer_scatter moves n staged entries to d_out[d_offsets[sample] + ...] (d_cursors: one zeroed counter per
+// sample), in arbitrary order inside a sample.
+struct KmerUnit {
+    long long byte0;
+    int32_t sample, npos;
+};
+constexpr int kKmerUnitMax = 32768;
+size_t kmer_lds_bytes(int unit, int ksize);
+int launch_kmer_hash(hipStream_t stream, const uint8_t* d_bases, long long total_bytes, const KmerUnit* d_units, long long n_units,
+                     int unit, int ksize, uint32_t seed, uint64_t max_hash, unsigned long long* d_vals, int32_t* d_sample,
+                     unsigned long long cap, unsigned long long* d_counters, unsigned long long* d_sample_counts,
+                     unsigned long long* d_sample_valid);
+int launch_kmer_scatter(hipStream_t stream, const unsigned long long* d_vals, const int32_t* d_sample, long long n,
+                        const long long* d_offsets, unsigned long long* d_cursors, unsigned long long* d_out);
 // the greedy decomposition of a query (mvs_gather.hip).  The walk's state lives on the device: the best bid of a round
 // ((count << 32) | (2^32 - 1 - survivor), 0 = none; consecutive rounds use alternating slots), the rows read so far, whether the
 // walk has ended, records written, live positions of the query, rounds run.  launch_gather_init: alive = the query's positions,
