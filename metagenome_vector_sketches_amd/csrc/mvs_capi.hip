@@ -217,6 +217,26 @@ const OptionSpec kOptions[] = {
     {"pairwise_block_cells", nullptr, &mvs::Options::pairwise_block_cells, 1, (1LL << 62)},
 };
 
+// ... and the options that are fields of the context: host-side scheduling, blocking and path choices that never change a
+// result.  No environment default; mvs_ctx_set_option / _get_option look here first.
+struct CtxOptionSpec {
+    const char* name;
+    int mvs_ctx::*field;
+    long long lo, hi;
+};
+const CtxOptionSpec kCtxOptions[] = {
+    {"plan_overlap", &mvs_ctx::plan_overlap, 0, 1},
+    {"core_block_rows", &mvs_ctx::core_block_rows, 0, 1 << 30},
+    {"labels_dots", &mvs_ctx::labels_dots, 0, 1},
+    {"labels_block_rows", &mvs_ctx::labels_block_rows, 0, 1 << 30},
+    {"hclust_dots", &mvs_ctx::hclust_dots, 0, 1},
+    {"hclust_block_rows", &mvs_ctx::hclust_block_rows, 0, 1 << 30},
+    {"hclust_compact", &mvs_ctx::hclust_compact, 0, 2},
+    {"community_path", &mvs_ctx::community_path, 0, 3},
+    {"tsne_slice_cols", &mvs_ctx::tsne_slice_cols, 16, 1024},
+    {"report_spin", &mvs_ctx::report_spin, 0, 1000000},
+};
+
 int apply_option(mvs::Options& o, const OptionSpec& sp, long long v) {
 #ifndef MVS_ABLATIONS
     if (sp.ifield == &mvs::Options::pairwise_debug && v != 0)
@@ -415,56 +435,13 @@ int mvs_ctx_destroy(mvs_ctx* c) {
 
 int mvs_ctx_set_option(mvs_ctx* c, const char* name, int64_t value) {
     if (!c || !name) return fail(MVS_E_INVALID, "NULL argument");
-    if (std::strcmp(name, "plan_overlap") == 0) {            // host-side scheduling only: not one of the kernels' options
-        if (value < 0 || value > 1) return fail(MVS_E_INVALID, "option plan_overlap: 0 or 1");
-        c->plan_overlap = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "core_block_rows") == 0) {         // host-side blocking only
-        if (value < 0 || value > (1 << 30)) return fail(MVS_E_INVALID, "option core_block_rows: 0 .. 2^30 rows");
-        c->core_block_rows = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "labels_dots") == 0) {             // mvs_label_sums: which dense-dots kernel its blocks take
-        if (value < 0 || value > 1) return fail(MVS_E_INVALID, "option labels_dots: 0 or 1");
-        c->labels_dots = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "labels_block_rows") == 0) {       // host-side blocking only
-        if (value < 0 || value > (1 << 30)) return fail(MVS_E_INVALID, "option labels_block_rows: 0 .. 2^30 rows");
-        c->labels_block_rows = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "hclust_dots") == 0) {             // mvs_hclust: which dense-dots kernel its blocks take
-        if (value < 0 || value > 1) return fail(MVS_E_INVALID, "option hclust_dots: 0 or 1");
-        c->hclust_dots = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "hclust_block_rows") == 0) {       // host-side blocking only
-        if (value < 0 || value > (1 << 30)) return fail(MVS_E_INVALID, "option hclust_block_rows: 0 .. 2^30 rows");
-        c->hclust_block_rows = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "hclust_compact") == 0) {          // when the table's columns are compacted: never changes a record
-        if (value < 0 || value > 2) return fail(MVS_E_INVALID, "option hclust_compact: 0, 1 or 2");
-        c->hclust_compact = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "community_path") == 0) {          // mvs_community_finish: where a vertex starts; never changes a result
-        if (value < 0 || value > 3) return fail(MVS_E_INVALID, "option community_path: 0 (by degree), 1 wave, 2 workgroup, 3 global");
-        c->community_path = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "tsne_slice_cols") == 0) {         // the repulsion's column slice; never changes a result
-        if (value < 16 || value > 1024) return fail(MVS_E_INVALID, "option tsne_slice_cols: 16 .. 1024 columns");
-        c->tsne_slice_cols = (int)value;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "report_spin") == 0) {             // host-side waiting only
-        if (value < 0 || value > 1000000) return fail(MVS_E_INVALID, "option report_spin: 0 .. 1000000 microseconds");
-        c->report_spin = (int)value;
-        return MVS_OK;
-    }
+    for (const CtxOptionSpec& sp : kCtxOptions)
+        if (std::strcmp(sp.name, name) == 0) {
+            if (value < sp.lo || value > sp.hi)
+                return fail(MVS_E_INVALID, "option %s: %lld outside [%lld, %lld]", sp.name, (long long)value, sp.lo, sp.hi);
+            c->*(sp.field) = (int)value;
+            return MVS_OK;
+        }
     for (const OptionSpec& sp : kOptions)
         if (std::strcmp(sp.name, name) == 0) return apply_option(c->opt, sp, (long long)value);
     return fail(MVS_E_INVALID, "unknown option '%s'", name);
@@ -472,46 +449,11 @@ int mvs_ctx_set_option(mvs_ctx* c, const char* name, int64_t value) {
 
 int mvs_ctx_get_option(const mvs_ctx* c, const char* name, int64_t* value) {
     if (!c || !name || !value) return fail(MVS_E_INVALID, "NULL argument");
-    if (std::strcmp(name, "plan_overlap") == 0) {
-        *value = c->plan_overlap;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "core_block_rows") == 0) {
-        *value = c->core_block_rows;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "labels_dots") == 0) {
-        *value = c->labels_dots;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "labels_block_rows") == 0) {
-        *value = c->labels_block_rows;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "hclust_dots") == 0) {
-        *value = c->hclust_dots;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "hclust_block_rows") == 0) {
-        *value = c->hclust_block_rows;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "hclust_compact") == 0) {
-        *value = c->hclust_compact;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "community_path") == 0) {
-        *value = c->community_path;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "tsne_slice_cols") == 0) {
-        *value = c->tsne_slice_cols;
-        return MVS_OK;
-    }
-    if (std::strcmp(name, "report_spin") == 0) {
-        *value = c->report_spin;
-        return MVS_OK;
-    }
+    for (const CtxOptionSpec& sp : kCtxOptions)
+        if (std::strcmp(sp.name, name) == 0) {
+            *value = c->*(sp.field);
+            return MVS_OK;
+        }
     for (const OptionSpec& sp : kOptions)
         if (std::strcmp(sp.name, name) == 0) {
             *value = sp.ifield ? (int64_t)(c->opt.*(sp.ifield)) : (int64_t)(c->opt.*(sp.dfield));

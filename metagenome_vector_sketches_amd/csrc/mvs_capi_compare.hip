@@ -195,6 +195,39 @@ void fill_args(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int keep
     a.symmetric = (symmetric && opt.pairwise_symmetric) ? 1 : 0;   // the launcher checks the alignment
 }
 
+mvs::PairwiseArgs dots_args(const mvs_sketch_set* s, int64_t r0, int64_t r1, int64_t cb, int64_t ce, int32_t* out) {
+    mvs::PairwiseArgs a{};
+    a.planes = s->planes;
+    a.n = s->n;
+    a.n_alloc = s->n_alloc;
+    a.d = s->d;
+    a.d_pad = s->d_pad;
+    a.limbs = s->limbs;
+    a.row_begin = r0;
+    a.row_end = r1;
+    a.col_begin = cb;
+    a.col_end = ce;
+    a.dots = out;
+    return a;
+}
+
+int64_t dots_block_rows(size_t budget_bytes, size_t row_bytes, int cap_option, int64_t max_rows) {
+    int64_t R = (int64_t)std::max<size_t>(1, budget_bytes / row_bytes);
+    R = std::min<int64_t>(R, 8192);
+    if (cap_option > 0) R = std::min<int64_t>(R, cap_option);
+    return std::min(R, max_rows);
+}
+
+int dots_stats_out(const mvs_ctx* c, DotsStats mvs_ctx::*which, double* dots_ms, double* work_ms, int64_t* row_blocks, int64_t* block_rows) {
+    if (!c) return fail(MVS_E_INVALID, "NULL context");
+    const DotsStats& st = c->*which;
+    if (dots_ms) *dots_ms = st.dots_ms;
+    if (work_ms) *work_ms = st.work_ms;
+    if (row_blocks) *row_blocks = st.blocks;
+    if (block_rows) *block_rows = st.block_rows;
+    return MVS_OK;
+}
+
 // the running cell count starts at `start` (appending calls); kKeepCount: it stays what the device counter holds (a block
 // plan appends block after block without the host ever learning the count in between)
 int set_cell_count(mvs_ctx* c, unsigned long long start) {
@@ -730,19 +763,7 @@ int mvs_pairwise_dots(mvs_ctx* c, const mvs_sketch_set* s, int64_t r0, int64_t r
         HIP_TRY(dout.alloc(bytes));
         d_out = (int32_t*)dout.p;
     }
-    mvs::PairwiseArgs a{};
-    a.planes = s->planes;
-    a.n = s->n;
-    a.n_alloc = s->n_alloc;
-    a.d = s->d;
-    a.d_pad = s->d_pad;
-    a.limbs = s->limbs;
-    a.row_begin = r0;
-    a.row_end = r1;
-    a.col_begin = c0;
-    a.col_end = c1;
-    a.dots = d_out;
-    int rc = mvs::launch_pairwise(c->stream, a, 1, algo, c->opt);
+    int rc = mvs::launch_pairwise(c->stream, dots_args(s, r0, r1, c0, c1, d_out), 1, algo, c->opt);
     if (rc) return fail(rc, "pairwise launch rejected");
     rc = check_kernel("k_pairwise(dots)");
     if (rc) return rc;

@@ -2,7 +2,7 @@
 // mvs_group_sums, mvs_permutation_labels, mvs_permanova_stats, mvs_permanova, mvs_ctx_groups_stats.  The kernels and the weight
 // of a cell are in mvs_groups.hip.
 //
-// Sums.  Rows are taken in blocks of R, sized as mvs_pairwise_levels sizes them and clamped to R x m < 2^34: a block's partial
+// Sums.  Rows are taken in blocks of R (dots_block_rows), clamped to R x m < 2^34: a block's partial
 // per (slot, group) is at most R x m x 2^30 < 2^64.  Per block: the dense-dots kernels fill an R x m int32 block, k_dist_quantise
 // turns it into weights in place, k_group_sums adds the block's ordered-pair sums to the cleared slots x groups accumulators,
 // which come back and are added on the host in unsigned __int128.  The host halves at the end (the diagonal weighs 0 and w is
@@ -82,7 +82,7 @@ int mvs_group_sums(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, 
     Range mark(c, "mvs_group_sums");
     HIP_TRY(hipSetDevice(c->device));
 
-    DevBuf dnorms, dlabels, dpacked, dacc, ddots;
+    DevBuf dnorms, dlabels, dpacked, dacc;
     const double* d_n2 = nullptr;
     if (const int rc = norms_on_device(c, norms_sq, mem_norms, s->n, dnorms, &d_n2)) return rc;
     const int64_t quads = mvs::group_label_quads(slots);
@@ -96,50 +96,26 @@ int mvs_group_sums(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, 
         rc = check_kernel("k_labels_transpose");
         if (rc) return rc;
     }
-    // rows per block: the dots block takes a quarter of the free memory (as mvs_pairwise_levels sizes its blocks), and
     // R x m < 2^34 keeps a block's partial per (slot, group), at most R x m x 2^30, inside 64 bits
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const size_t row_bytes = (size_t)m * 4;
-    int64_t R = (int64_t)std::max<size_t>(1, (free_b / 4) / row_bytes);
-    R = std::min<int64_t>(R, 8192);
-    R = std::min<int64_t>(R, ((1LL << 34) - 1) / m);
-    if (c->opt.groups_block_rows > 0) R = std::min<int64_t>(R, c->opt.groups_block_rows);
-    R = std::min(R, m);
-    HIP_TRY(ddots.alloc((size_t)R * row_bytes));
+    const int64_t R = std::min<int64_t>(dots_block_rows(free_b / 4, (size_t)m * 4, c->opt.groups_block_rows, m), ((1LL << 34) - 1) / m);
+    DotsBlocks blocks;
+    if (const int rc = blocks.init(c, s, rb, re, R, c->opt.groups_dots,
+                                   {"k_group_sums dots", "group sums: dots launch rejected", "k_pairwise(group sums dots)"}))
+        return rc;
     c->gs.block_rows = R;
 
     std::vector<u128> total(cells, 0);
     std::vector<unsigned long long> part(cells);
     bool sized = !sizes;
-    for (int64_t r0 = rb; r0 < re; r0 += R) {
-        const int64_t r1 = std::min(r0 + R, re);
-        mvs::PairwiseArgs a{};
-        a.planes = s->planes;
-        a.n = s->n;
-        a.n_alloc = s->n_alloc;
-        a.d = s->d;
-        a.d_pad = s->d_pad;
-        a.limbs = s->limbs;
-        a.row_begin = r0;
-        a.row_end = r1;
-        a.col_begin = rb;
-        a.col_end = re;
-        a.dots = (int32_t*)ddots.p;
-        StageTimer t_dots, t_quant, t_sums;
-        if (const int rc = t_dots.begin(c)) return rc;
-        {
-            Range rd(c, "k_group_sums dots");
-            int rc = mvs::launch_pairwise(c->stream, a, 1, c->opt.groups_dots, c->opt);
-            if (rc) return fail(rc, "group sums: dots launch rejected");
-            rc = check_kernel("k_pairwise(group sums dots)");
-            if (rc) return rc;
-        }
-        if (const int rc = t_dots.mark_end()) return rc;
+    // per block: the dots become weights in place, their sums come back (the one wait of a block) and are added
+    const auto sum = [&](int64_t r0, int64_t r1, int32_t* dots) -> int {
+        StageTimer t_quant, t_sums;
         if (const int rc = t_quant.begin(c)) return rc;
         {
             Range rq(c, "k_dist_quantise");
-            int rc = mvs::launch_dist_quantise(c->stream, (int32_t*)ddots.p, r1 - r0, m, r0, rb, d_n2, s->d, floor);
+            int rc = mvs::launch_dist_quantise(c->stream, dots, r1 - r0, m, r0, rb, d_n2, s->d, floor);
             if (rc) return fail(rc, "group sums: quantise launch rejected");
             rc = check_kernel("k_dist_quantise");
             if (rc) return rc;
@@ -149,7 +125,7 @@ int mvs_group_sums(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, 
         if (const int rc = t_sums.begin(c)) return rc;
         {
             Range rs(c, "k_group_sums");
-            int rc = mvs::launch_group_sums(c->stream, (const uint32_t*)ddots.p, r1 - r0, m, r0 - rb, (const uint32_t*)dpacked.p, slots, groups,
+            int rc = mvs::launch_group_sums(c->stream, (const uint32_t*)dots, r1 - r0, m, r0 - rb, (const uint32_t*)dpacked.p, slots, groups,
                                             (unsigned long long*)dacc.p);
             if (rc) return fail(rc, "group sums: launch rejected");
             rc = check_kernel("k_group_sums");
@@ -164,11 +140,10 @@ int mvs_group_sums(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, 
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < cells; ++i) total[i] += part[i];
-        if (const int rc = t_dots.add_to(&c->gs.dots_ms)) return rc;
         if (const int rc = t_quant.add_to(&c->gs.quantise_ms)) return rc;
-        if (const int rc = t_sums.add_to(&c->gs.sums_ms)) return rc;
-        ++c->gs.blocks;
-    }
+        return t_sums.add_to(&c->gs.sums_ms);
+    };
+    if (const int rc = blocks.run(rb, re, &c->gs.dots_ms, nullptr, &c->gs.blocks, sum)) return rc;
     for (size_t i = 0; i < cells; ++i) {
         if (total[i] & 1) return fail(MVS_E_INTERNAL, "the ordered-pair sum of slot %lld, group %lld is odd", (long long)(i / groups), (long long)(i % groups));
         const u128 half = total[i] >> 1;

@@ -286,50 +286,22 @@ int mvs_hclust(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, int 
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const size_t left = free_b > table_bytes ? free_b - table_bytes : 0;
-    int64_t R = (int64_t)std::max<size_t>(1, (left / 2) / row_bytes);
-    R = std::min<int64_t>(R, 8192);
-    if (c->hclust_block_rows > 0) R = std::min<int64_t>(R, c->hclust_block_rows);
-    R = std::min(R, m);
+    const int64_t R = dots_block_rows(left / 2, row_bytes, c->hclust_block_rows, m);
     Engine e;
     if (const int rc = engine_alloc(c, m, (size_t)R * row_bytes, e)) return rc;
-    DevBuf dnorms, ddots;
+    DevBuf dnorms;
     const double* d_n2 = nullptr;
     if (const int rc = norms_on_device(c, norms_sq, mem_norms, s->n, dnorms, &d_n2)) return rc;
-    HIP_TRY(ddots.alloc((size_t)R * row_bytes));
-
-    for (int64_t r0 = rb; r0 < re; r0 += R) {
-        const int64_t r1 = std::min(r0 + R, re);
-        mvs::PairwiseArgs a{};
-        a.planes = s->planes;
-        a.n = s->n;
-        a.n_alloc = s->n_alloc;
-        a.d = s->d;
-        a.d_pad = s->d_pad;
-        a.limbs = s->limbs;
-        a.row_begin = r0;
-        a.row_end = r1;
-        a.col_begin = rb;
-        a.col_end = re;
-        a.dots = (int32_t*)ddots.p;
-        StageTimer t_dots, t_fill;
-        if (const int rc = t_dots.begin(c)) return rc;
-        {
-            Range rd(c, "k_hclust_fill dots");
-            int rc = mvs::launch_pairwise(c->stream, a, 1, c->hclust_dots, c->opt);
-            if (rc) return fail(rc, "hclust: dots launch rejected");
-            rc = check_kernel("k_pairwise(hclust dots)");
-            if (rc) return rc;
-        }
-        if (const int rc = t_dots.mark_end()) return rc;
-        if (const int rc = t_fill.begin(c)) return rc;
-        HCLUST_LAUNCH(mvs::launch_hclust_fill(c->stream, (const int32_t*)ddots.p, r1 - r0, m, r0, rb, d_n2, s->d, floor,
-                                              e.st.table + (r0 - rb) * e.st.ld, e.st.ld),
+    DotsBlocks blocks;
+    if (const int rc = blocks.init(c, s, rb, re, R, c->hclust_dots, {"k_hclust_fill dots", "hclust: dots launch rejected", "k_pairwise(hclust dots)"}))
+        return rc;
+    const auto fill = [&](int64_t r0, int64_t r1, const int32_t* dots) -> int {
+        HCLUST_LAUNCH(mvs::launch_hclust_fill(c->stream, dots, r1 - r0, m, r0, rb, d_n2, s->d, floor, e.st.table + (r0 - rb) * e.st.ld, e.st.ld),
                       "k_hclust_fill");
-        if (const int rc = t_fill.mark_end()) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (const int rc = t_dots.add_to(&c->hc.dots_ms)) return rc;
-        if (const int rc = t_fill.add_to(&c->hc.fill_ms)) return rc;
-    }
+        return MVS_OK;
+    };
+    if (const int rc = blocks.run(rb, re, &c->hc.dots_ms, &c->hc.fill_ms, nullptr, fill)) return rc;
     return engine_run(c, e, nullptr, method, false, merges, rounds);     // (a table of this fill is symmetric and bounded)
 }
 

@@ -31,8 +31,8 @@ int core_pass(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int k, do
         int64_t m = 0;
         int rc = mvs_pairwise_topk(c, s, d_n2, MVS_MEM_DEVICE, k, r0, r1, 0, n, MVS_TOPK_EXCLUDE_SELF, (mvs_cell*)dcells.p, MVS_MEM_DEVICE, &m);
         if (rc) return rc;
-        c->hd.core_dots_ms += c->tk_dots_ms;
-        c->hd.core_select_ms += c->tk_select_ms;
+        c->hd.core_dots_ms += c->tk.dots_ms;
+        c->hd.core_select_ms += c->tk.work_ms;
         if (m > (r1 - r0) * (int64_t)k) return fail(MVS_E_INTERNAL, "top-k returned %lld cells for %lld rows at k = %d", (long long)m, (long long)(r1 - r0), k);
         StageTimer timer;
         rc = timer.begin(c);

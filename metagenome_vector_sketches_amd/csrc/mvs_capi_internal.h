@@ -44,6 +44,13 @@ struct ConsumerStats {
     long long edges = 0, blocks = 0, rounds = 0;
     void reset() { *this = ConsumerStats(); }
 };
+// what the last call of one consumer of dense dots (top-k, containment, level counts, the Jaccard operator) did on a context:
+// kernel times of the dots and of the consumer's own work summed over the row blocks (timing enabled), row blocks, rows per block
+struct DotsStats {
+    double dots_ms = 0.0, work_ms = 0.0;
+    long long blocks = 0, block_rows = 0;
+    void reset() { *this = DotsStats(); }
+};
 // what the last mvs_group_sums / mvs_permanova did on a context (mvs_ctx_groups_stats): kernel times summed over the row blocks
 // (timing enabled), row blocks, rows per block, labellings
 struct GroupsStats {
@@ -218,22 +225,16 @@ struct mvs_ctx {
     struct PlanState* plan = nullptr;
     void* plan_tmp = nullptr;   size_t plan_tmp_bytes = 0;
     const void* rows_max_done = nullptr;   // state block whose widest row mvs_cells_sort_rows_ahead has already computed
-    // what the last mvs_pairwise_topk did (mvs_ctx_topk_stats): kernel times summed over its row blocks (timing enabled)
-    double tk_dots_ms = 0.0, tk_select_ms = 0.0;
-    long long tk_blocks = 0, tk_block_rows = 0;
-    // what the last mvs_pairwise_contain did (mvs_ctx_contain_stats): kernel times summed over its row blocks (timing enabled)
-    double ct_dots_ms = 0.0, ct_select_ms = 0.0;
-    long long ct_blocks = 0, ct_block_rows = 0;
-    // what the last mvs_pairwise_levels did (mvs_ctx_levels_stats): kernel times summed over its row blocks (timing enabled)
-    double lv_dots_ms = 0.0, lv_count_ms = 0.0;
-    long long lv_blocks = 0, lv_block_rows = 0;
+    // what the last mvs_pairwise_topk / _contain / _levels did (mvs_ctx_topk_stats, mvs_ctx_contain_stats, mvs_ctx_levels_stats)
+    mvs_capi::DotsStats tk, ct, lv;
     // what the last mvs_sketch_moments / mvs_pca_fit / mvs_pca_transform did (mvs_ctx_pca_stats): times with timing enabled
     double pc_gram_ms = 0.0, pc_eigen_ms = 0.0, pc_scores_ms = 0.0;
     long long pc_slabs = 0, pc_iters = 0;
     // what the last mvs_jaccard_apply / mvs_pcoa_fit / mvs_pcoa_transform did (mvs_ctx_pcoa_stats): kernel times summed over its
     // passes and row blocks, the solver's whole time (timing enabled)
-    double po_dots_ms = 0.0, po_apply_ms = 0.0, po_eigen_ms = 0.0;
-    long long po_passes = 0, po_blocks = 0, po_block_rows = 0;
+    mvs_capi::DotsStats po;
+    double po_eigen_ms = 0.0;
+    long long po_passes = 0;
     // what the clustering, linkage and dereplication calls did since the last mvs_cluster_create / mvs_linkage_create /
     // mvs_derep_create on this context (mvs_ctx_cluster_stats, mvs_ctx_linkage_stats, mvs_ctx_derep_stats)
     mvs_capi::ConsumerStats cl, lk, dr;
@@ -473,6 +474,75 @@ int feed_consumer(const char* entry, mvs_ctx* c, const mvs_sketch_set* s, const 
 // the body of mvs_ctx_cluster_stats / _linkage_stats / _derep_stats
 int consumer_stats_out(const mvs_ctx* c, ConsumerStats mvs_ctx::*which, double* compare_ms, double* work_ms, int64_t* edges,
                        int64_t* row_blocks, int64_t* rounds);
+
+// ---- mvs_capi_compare.hip: what the consumers of dense dots share (top-k, containment, level counts, the Jaccard operator,
+// group sums, label sums, hclust's fill) ----
+// the arguments of a dense-dots launch of set `s` over [r0, r1) x [cb, ce) into `out`
+mvs::PairwiseArgs dots_args(const mvs_sketch_set* s, int64_t r0, int64_t r1, int64_t cb, int64_t ce, int32_t* out);
+// Rows per block of such a consumer.  Its dots block (row_bytes per row) may take budget_bytes, which the caller derives from
+// the device's free memory where its own allocations stand (a quarter of it, as mvs_pairwise_stream sizes its blocks).  A block
+// has at least 1 row and at most 8192, at most cap_option where that is > 0 (the consumer's *_block_rows), at most max_rows.
+int64_t dots_block_rows(size_t budget_bytes, size_t row_bytes, int cap_option, int64_t max_rows);
+// the marker range of a consumer's dots launch, the refusal when the launcher rejects it, the kernel's name for check_kernel
+struct DotsTexts {
+    const char *marker, *rejected, *kernel;
+};
+// A consumer's walk over rows in blocks of R: the dense-dots kernel (option value `algo`) fills the R x (ce - cb) int32 block
+// this object owns, then work(r0, r1, dots) queues the consumer's own launches over it.  With timing off nothing is recorded
+// and nothing waits: a consumer synchronises where its `work` does.  With timing on run() waits once per block and adds the
+// two stretches' times to *dots_ms and *work_ms.
+struct DotsBlocks {
+    mvs_ctx* c = nullptr;
+    const mvs_sketch_set* s = nullptr;
+    int64_t cb = 0, ce = 0, R = 0;
+    int algo = 0;
+    DotsTexts txt{};
+    DevBuf dots;
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~DotsBlocks() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    int init(mvs_ctx* ctx, const mvs_sketch_set* set, int64_t col_begin, int64_t col_end, int64_t block_rows, int dots_algo,
+             const DotsTexts& texts) {
+        c = ctx, s = set, cb = col_begin, ce = col_end, R = block_rows, algo = dots_algo, txt = texts;
+        HIP_TRY(dots.alloc((size_t)R * (size_t)(ce - cb) * 4));
+        if (c->timing)
+            for (hipEvent_t& x : e) HIP_TRY(hipEventCreate(&x));
+        return MVS_OK;
+    }
+    // rows [rb, re); work_ms and blocks may be NULL (a consumer that times its own stages, or keeps no count)
+    template <typename Work>
+    int run(int64_t rb, int64_t re, double* dots_ms, double* work_ms, long long* blocks, Work&& work) {
+        int32_t* const d = (int32_t*)dots.p;
+        for (int64_t r0 = rb; r0 < re; r0 += R) {
+            const int64_t r1 = std::min(r0 + R, re);
+            if (c->timing) HIP_TRY(hipEventRecord(e[0], c->stream));
+            {
+                Range rd(c, txt.marker);
+                int rc = mvs::launch_pairwise(c->stream, dots_args(s, r0, r1, cb, ce, d), 1, algo, c->opt);
+                if (rc) return fail(rc, "%s", txt.rejected);
+                rc = check_kernel(txt.kernel);
+                if (rc) return rc;
+            }
+            if (c->timing) HIP_TRY(hipEventRecord(e[1], c->stream));
+            if (const int rc = work(r0, r1, d)) return rc;
+            if (c->timing) {
+                HIP_TRY(hipEventRecord(e[2], c->stream));
+                HIP_TRY(hipEventSynchronize(e[2]));
+                float m0 = 0.f, m1 = 0.f;
+                HIP_TRY(hipEventElapsedTime(&m0, e[0], e[1]));
+                HIP_TRY(hipEventElapsedTime(&m1, e[1], e[2]));
+                *dots_ms += m0;
+                if (work_ms) *work_ms += m1;
+            }
+            if (blocks) ++*blocks;
+        }
+        return MVS_OK;
+    }
+};
+// the body of mvs_ctx_topk_stats / _contain_stats / _levels_stats
+int dots_stats_out(const mvs_ctx* c, DotsStats mvs_ctx::*which, double* dots_ms, double* work_ms, int64_t* row_blocks, int64_t* block_rows);
 // ---- mvs_capi_pca.hip: the eigensolver the ordinations share (mvs_pca_fit, mvs_pcoa_fit) ----
 // Block subspace iteration with a Rayleigh-Ritz step for the leading eigenpairs of a symmetric operator of size d (the loop is
 // described at the top of mvs_capi_pca.hip).  op(q, d_Q, d_Y): q is the orthonormal block on the host and d_Q the same on the

@@ -1,6 +1,6 @@
 // mvs_capi_levels.hip -- C ABI of the level counts: mvs_pairwise_levels, mvs_ctx_levels_stats.
 //
-// Rows are taken in blocks of R, sized as mvs_pairwise_contain sizes them: the dense-dots kernels fill an R x C int32 block
+// Rows are taken in blocks of R (dots_block_rows): the dense-dots kernels fill an R x C int32 block
 // (C = the column range), k_levels_count turns every row of it into m neighbour counts (mvs_levels.hip) and adds them to the
 // m running totals, which live on the device and are read once, behind the last block.  Device memory besides the set:
 // R x C x 4 bytes of dots, R x m counts when the caller's table is on the host, one pre-test integer per sample, m
@@ -41,24 +41,20 @@ int mvs_pairwise_levels(mvs_ctx* c, const mvs_sketch_set* s, const double* norms
     if (!norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
     Range mark(c, "mvs_pairwise_levels");
     HIP_TRY(hipSetDevice(c->device));
-    c->lv_dots_ms = c->lv_count_ms = 0.0;
-    c->lv_blocks = c->lv_block_rows = 0;
+    c->lv.reset();
 
     DevBuf dnorms;
     const double* d_n2 = nullptr;
     if (const int rc = norms_on_device(c, norms_sq, mem_norms, s->n, dnorms, &d_n2)) return rc;
 
-    // rows per block: the dots block takes a quarter of the free memory (as mvs_pairwise_contain sizes its blocks)
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const size_t row_bytes = (size_t)cols * 4;
-    int64_t R = (int64_t)std::max<size_t>(1, (free_b / 4) / row_bytes);
-    R = std::min<int64_t>(R, 8192);
-    if (c->opt.levels_block_rows > 0) R = std::min<int64_t>(R, c->opt.levels_block_rows);
-    R = std::min(R, rows);
+    const int64_t R = dots_block_rows(free_b / 4, (size_t)cols * 4, c->opt.levels_block_rows, rows);
     const bool stage = degrees && mem_degrees == MVS_MEM_HOST;   // a host table is filled block by block from a device copy
-    DevBuf ddots, dcoef, dtotal, dflag, ddeg, dthr;
-    HIP_TRY(ddots.alloc((size_t)R * row_bytes));
+    DotsBlocks blocks;
+    DevBuf dcoef, dtotal, dflag, ddeg, dthr;
+    if (const int rc = blocks.init(c, s, cb, ce, R, c->opt.levels_dots, {"k_levels dots", "levels: dots launch rejected", "k_pairwise(levels dots)"}))
+        return rc;
     HIP_TRY(dcoef.alloc(sizeof coef));
     HIP_TRY(dtotal.alloc((size_t)mvs::kMaxLevels * sizeof(unsigned long long)));
     HIP_TRY(dflag.alloc(sizeof(int)));
@@ -67,69 +63,29 @@ int mvs_pairwise_levels(mvs_ctx* c, const mvs_sketch_set* s, const double* norms
     HIP_TRY(hipMemcpyAsync(dcoef.p, coef, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(dtotal.p, 0, (size_t)mvs::kMaxLevels * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipMemsetAsync(dflag.p, 0, sizeof(int), c->stream));
-    struct Events {
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } ev;
-    if (c->timing)
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
     {
         int rc = mvs::launch_levels_prep(c->stream, d_n2, s->n, cb, ce, coef[0], s->d, (int*)dthr.p, (int*)dflag.p);
         if (rc) return fail(rc, "levels: pre-test launch rejected");
         rc = check_kernel("k_levels_prep");
         if (rc) return rc;
     }
-    const int algo = c->opt.levels_dots;
-    for (int64_t r0 = rb; r0 < re; r0 += R) {
-        const int64_t r1 = std::min(r0 + R, re);
-        mvs::PairwiseArgs a{};
-        a.planes = s->planes;
-        a.n = s->n;
-        a.n_alloc = s->n_alloc;
-        a.d = s->d;
-        a.d_pad = s->d_pad;
-        a.limbs = s->limbs;
-        a.row_begin = r0;
-        a.row_end = r1;
-        a.col_begin = cb;
-        a.col_end = ce;
-        a.dots = (int32_t*)ddots.p;
-        if (c->timing) HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-        {
-            Range rd(c, "k_levels dots");
-            int rc = mvs::launch_pairwise(c->stream, a, 1, algo, c->opt);
-            if (rc) return fail(rc, "levels: dots launch rejected");
-            rc = check_kernel("k_pairwise(levels dots)");
-            if (rc) return rc;
-        }
-        if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    const auto count = [&](int64_t r0, int64_t r1, const int32_t* dots) -> int {
         int32_t* d_deg = stage ? (int32_t*)ddeg.p : degrees ? degrees + (size_t)(r0 - rb) * m : nullptr;
         {
             Range rs(c, "k_levels count");
-            int rc = mvs::launch_levels_count(c->stream, (const int32_t*)ddots.p, r1 - r0, cols, r0, cb, d_n2, (const double*)dcoef.p, m,
-                                              s->d, (const int*)dthr.p, (const int*)dflag.p, d_deg, (unsigned long long*)dtotal.p);
+            int rc = mvs::launch_levels_count(c->stream, dots, r1 - r0, cols, r0, cb, d_n2, (const double*)dcoef.p, m, s->d,
+                                              (const int*)dthr.p, (const int*)dflag.p, d_deg, (unsigned long long*)dtotal.p);
             if (rc) return fail(rc, "levels: count launch rejected");
             rc = check_kernel("k_levels_count");
             if (rc) return rc;
         }
-        if (c->timing) {
-            HIP_TRY(hipEventRecord(ev.e[2], c->stream));
-            HIP_TRY(hipEventSynchronize(ev.e[2]));
-            float m0 = 0.f, m1 = 0.f;
-            HIP_TRY(hipEventElapsedTime(&m0, ev.e[0], ev.e[1]));
-            HIP_TRY(hipEventElapsedTime(&m1, ev.e[1], ev.e[2]));
-            c->lv_dots_ms += m0;
-            c->lv_count_ms += m1;
-        }
         if (stage)                                               // (in stream order: the next block's kernel waits for the copy)
             HIP_TRY(hipMemcpyAsync(degrees + (size_t)(r0 - rb) * m, ddeg.p, (size_t)(r1 - r0) * m * sizeof(int32_t), hipMemcpyDeviceToHost,
                                    c->stream));
-        ++c->lv_blocks;
-    }
-    c->lv_block_rows = R;
+        return MVS_OK;
+    };
+    if (const int rc = blocks.run(rb, re, &c->lv.dots_ms, &c->lv.work_ms, &c->lv.blocks, count)) return rc;
+    c->lv.block_rows = R;
     unsigned long long sums[mvs::kMaxLevels];
     HIP_TRY(hipMemcpyAsync(sums, dtotal.p, (size_t)m * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                    // (also before the DevBufs free the scratch)
@@ -139,12 +95,7 @@ int mvs_pairwise_levels(mvs_ctx* c, const mvs_sketch_set* s, const double* norms
 }
 
 int mvs_ctx_levels_stats(const mvs_ctx* c, double* dots_ms, double* count_ms, int64_t* row_blocks, int64_t* block_rows) {
-    if (!c) return fail(MVS_E_INVALID, "NULL context");
-    if (dots_ms) *dots_ms = c->lv_dots_ms;
-    if (count_ms) *count_ms = c->lv_count_ms;
-    if (row_blocks) *row_blocks = c->lv_blocks;
-    if (block_rows) *block_rows = c->lv_block_rows;
-    return MVS_OK;
+    return dots_stats_out(c, &mvs_ctx::lv, dots_ms, count_ms, row_blocks, block_rows);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // mvs_capi_pcoa.hip -- C ABI of the Jaccard kernel as an operator and of the principal coordinates built on it: mvs_jaccard_apply,
 // mvs_pcoa_fit / _info / _get / _transform / _destroy, mvs_ctx_pcoa_stats.  The kernel and the rule are in mvs_kapply.hip.
 //
-// Apply.  Rows are taken in blocks of R, sized as mvs_pairwise_levels sizes them: the dense-dots kernels fill an R x C int32
+// Apply.  Rows are taken in blocks of R (dots_block_rows): the dense-dots kernels fill an R x C int32
 // block (C = the column range), k_jaccard_apply turns it into R x b sums against the zero-padded copy of X.  Device memory
 // besides the set: R x C x 4 bytes of dots, the padded X, the rows x b result -- never N x N.
 //
@@ -30,87 +30,39 @@ struct mvs_pcoa {
 
 namespace {
 
-// K over rows x [cb, ce) applied to padded operands, row block by row block; the times and counts go to the context's po_* fields
+// K over rows x [cb, ce) applied to padded operands, row block by row block; the times and counts go to the context's po fields
 struct Applier {
-    mvs_ctx* c = nullptr;
-    const mvs_sketch_set* s = nullptr;
+    DotsBlocks blocks;
     const double* d_n2 = nullptr;
     double floor = 0.0;
-    int64_t cb = 0, ce = 0, R = 0;
-    DevBuf ddots;
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Applier() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    // rows per block: the dots block takes a quarter of the free memory (as mvs_pairwise_levels sizes its blocks)
-    int init(mvs_ctx* ctx, const mvs_sketch_set* set, const double* n2, double floor_, int64_t col_begin, int64_t col_end, int64_t max_rows) {
-        c = ctx, s = set, d_n2 = n2, floor = floor_, cb = col_begin, ce = col_end;
+    int init(mvs_ctx* c, const mvs_sketch_set* s, const double* n2, double floor_, int64_t cb, int64_t ce, int64_t max_rows) {
+        d_n2 = n2, floor = floor_;
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        const size_t row_bytes = (size_t)(ce - cb) * 4;
-        R = (int64_t)std::max<size_t>(1, (free_b / 4) / row_bytes);
-        R = std::min<int64_t>(R, 8192);
-        if (c->opt.pcoa_block_rows > 0) R = std::min<int64_t>(R, c->opt.pcoa_block_rows);
-        R = std::min(R, max_rows);
-        HIP_TRY(ddots.alloc((size_t)R * row_bytes));
-        if (c->timing)
-            for (hipEvent_t& x : e) HIP_TRY(hipEventCreate(&x));
-        c->po_block_rows = R;
-        return MVS_OK;
+        c->po.block_rows = dots_block_rows(free_b / 4, (size_t)(ce - cb) * 4, c->opt.pcoa_block_rows, max_rows);
+        return blocks.init(c, s, cb, ce, c->po.block_rows, c->opt.pcoa_dots,
+                           {"k_jaccard_apply dots", "jaccard apply: dots launch rejected", "k_pairwise(apply dots)"});
     }
     // d_Y ((re - rb) x b) = K(rows [rb, re) x [cb, ce)) Xp; queued on the context's stream (with timing on it waits per block)
     int run(int64_t rb, int64_t re, const double* d_Xp, int b, double* d_Y) {
-        for (int64_t r0 = rb; r0 < re; r0 += R) {
-            const int64_t r1 = std::min(r0 + R, re);
-            mvs::PairwiseArgs a{};
-            a.planes = s->planes;
-            a.n = s->n;
-            a.n_alloc = s->n_alloc;
-            a.d = s->d;
-            a.d_pad = s->d_pad;
-            a.limbs = s->limbs;
-            a.row_begin = r0;
-            a.row_end = r1;
-            a.col_begin = cb;
-            a.col_end = ce;
-            a.dots = (int32_t*)ddots.p;
-            if (c->timing) HIP_TRY(hipEventRecord(e[0], c->stream));
-            {
-                Range rd(c, "k_jaccard_apply dots");
-                int rc = mvs::launch_pairwise(c->stream, a, 1, c->opt.pcoa_dots, c->opt);
-                if (rc) return fail(rc, "jaccard apply: dots launch rejected");
-                rc = check_kernel("k_pairwise(apply dots)");
-                if (rc) return rc;
-            }
-            if (c->timing) HIP_TRY(hipEventRecord(e[1], c->stream));
-            {
-                Range rs(c, "k_jaccard_apply");
-                int rc = mvs::launch_jaccard_apply(c->stream, (const int32_t*)ddots.p, r1 - r0, ce - cb, r0, cb, d_n2, s->d, floor, d_Xp, b,
-                                                   d_Y + (size_t)(r0 - rb) * b);
-                if (rc) return fail(rc, "jaccard apply: launch rejected");
-                rc = check_kernel("k_jaccard_apply");
-                if (rc) return rc;
-            }
-            if (c->timing) {
-                HIP_TRY(hipEventRecord(e[2], c->stream));
-                HIP_TRY(hipEventSynchronize(e[2]));
-                float m0 = 0.f, m1 = 0.f;
-                HIP_TRY(hipEventElapsedTime(&m0, e[0], e[1]));
-                HIP_TRY(hipEventElapsedTime(&m1, e[1], e[2]));
-                c->po_dots_ms += m0;
-                c->po_apply_ms += m1;
-            }
-            ++c->po_blocks;
-        }
+        mvs_ctx* c = blocks.c;
+        const auto apply = [&](int64_t r0, int64_t r1, const int32_t* dots) -> int {
+            Range rs(c, "k_jaccard_apply");
+            const int rc = mvs::launch_jaccard_apply(c->stream, dots, r1 - r0, blocks.ce - blocks.cb, r0, blocks.cb, d_n2, blocks.s->d, floor,
+                                                     d_Xp, b, d_Y + (size_t)(r0 - rb) * b);
+            if (rc) return fail(rc, "jaccard apply: launch rejected");
+            return check_kernel("k_jaccard_apply");
+        };
+        if (const int rc = blocks.run(rb, re, &c->po.dots_ms, &c->po.work_ms, &c->po.blocks, apply)) return rc;
         ++c->po_passes;
         return MVS_OK;
     }
 };
 
 void reset_stats(mvs_ctx* c) {
-    c->po_dots_ms = c->po_apply_ms = c->po_eigen_ms = 0.0;
-    c->po_passes = c->po_blocks = c->po_block_rows = 0;
+    c->po.reset();
+    c->po_eigen_ms = 0.0;
+    c->po_passes = 0;
 }
 
 inline size_t padded_doubles(int64_t cols, int b) { return (size_t)mvs::apply_padded_cols(cols) * (size_t)mvs::apply_padded_b(b); }
@@ -376,13 +328,9 @@ int mvs_pcoa_destroy(mvs_pcoa* p) {
 int mvs_ctx_pcoa_stats(const mvs_ctx* c, double* dots_ms, double* apply_ms, double* eigen_ms, int64_t* passes, int64_t* row_blocks,
                        int64_t* block_rows) {
     if (!c) return fail(MVS_E_INVALID, "NULL context");
-    if (dots_ms) *dots_ms = c->po_dots_ms;
-    if (apply_ms) *apply_ms = c->po_apply_ms;
     if (eigen_ms) *eigen_ms = c->po_eigen_ms;
     if (passes) *passes = c->po_passes;
-    if (row_blocks) *row_blocks = c->po_blocks;
-    if (block_rows) *block_rows = c->po_block_rows;
-    return MVS_OK;
+    return dots_stats_out(c, &mvs_ctx::po, dots_ms, apply_ms, row_blocks, block_rows);
 }
 
 }  // extern "C"

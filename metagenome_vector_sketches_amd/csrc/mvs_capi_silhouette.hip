@@ -4,7 +4,7 @@
 //
 // Sums.  The host sorts the samples of the range by label (stable, unlabelled last) and gathers the set and the norms into that
 // order: every non-empty group is then one interval of columns, and the columns of every dots launch are the labelled samples
-// [0, m_labelled) alone -- unlabelled samples are rows, never columns.  Rows go in blocks sized as mvs_group_sums sizes them
+// [0, m_labelled) alone -- unlabelled samples are rows, never columns.  Rows go in blocks of dots_block_rows
 // (nothing is summed across rows, so there is no R x m clamp); per block one dense-dots launch and k_segment_nearest, which
 // leaves (own_sum, near_group, near_sum) per row.  The three arrays come back once, at the end, and are scattered through the
 // permutation: O(m) bytes cross the link.  Device memory besides the set: the gathered copy, one dots block, O(m) arrays.
@@ -118,7 +118,7 @@ int mvs_label_sums(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, 
     }
     const mvs_sketch_set* o = ordered.set;
 
-    DevBuf dnorms, dcolseg, dbegin, did, down, dnear, dnsum, ddots;
+    DevBuf dnorms, dcolseg, dbegin, did, down, dnear, dnsum;
     const size_t segs = seg_id.size();
     HIP_TRY(dnorms.alloc((size_t)m * 8));
     HIP_TRY(dcolseg.alloc((size_t)m_lab * 4));
@@ -132,56 +132,24 @@ int mvs_label_sums(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, 
     HIP_TRY(hipMemcpyAsync(dbegin.p, seg_begin.data(), (segs + 1) * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(did.p, seg_id.data(), segs * 4, hipMemcpyHostToDevice, c->stream));
 
-    // rows per block: the dots block takes a quarter of the free memory, as mvs_group_sums sizes its blocks
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const size_t row_bytes = (size_t)m_lab * 4;
-    int64_t R = (int64_t)std::max<size_t>(1, (free_b / 4) / row_bytes);
-    R = std::min<int64_t>(R, 8192);
-    if (c->labels_block_rows > 0) R = std::min<int64_t>(R, c->labels_block_rows);
-    R = std::min(R, m);
-    HIP_TRY(ddots.alloc((size_t)R * row_bytes));
+    const int64_t R = dots_block_rows(free_b / 4, (size_t)m_lab * 4, c->labels_block_rows, m);
+    DotsBlocks blocks;
+    if (const int rc = blocks.init(c, o, 0, m_lab, R, c->labels_dots,
+                                   {"k_segment_nearest dots", "label sums: dots launch rejected", "k_pairwise(label sums dots)"}))
+        return rc;
     c->ls.block_rows = R;
 
-    for (int64_t r0 = 0; r0 < m; r0 += R) {
-        const int64_t r1 = std::min(r0 + R, m);
-        mvs::PairwiseArgs a{};
-        a.planes = o->planes;
-        a.n = o->n;
-        a.n_alloc = o->n_alloc;
-        a.d = o->d;
-        a.d_pad = o->d_pad;
-        a.limbs = o->limbs;
-        a.row_begin = r0;
-        a.row_end = r1;
-        a.col_begin = 0;
-        a.col_end = m_lab;
-        a.dots = (int32_t*)ddots.p;
-        StageTimer t_dots, t_reduce;
-        if (const int rc = t_dots.begin(c)) return rc;
-        {
-            Range rd(c, "k_segment_nearest dots");
-            int rc = mvs::launch_pairwise(c->stream, a, 1, c->labels_dots, c->opt);
-            if (rc) return fail(rc, "label sums: dots launch rejected");
-            rc = check_kernel("k_pairwise(label sums dots)");
-            if (rc) return rc;
-        }
-        if (const int rc = t_dots.mark_end()) return rc;
-        if (const int rc = t_reduce.begin(c)) return rc;
-        {
-            Range rs(c, "k_segment_nearest");
-            int rc = mvs::launch_segment_nearest(c->stream, (const int32_t*)ddots.p, r1 - r0, m_lab, r0, (const double*)dnorms.p, o->d, floor,
-                                                 (const int32_t*)dcolseg.p, (const int32_t*)dbegin.p, (const int32_t*)did.p,
-                                                 (unsigned long long*)down.p, (int32_t*)dnear.p, (unsigned long long*)dnsum.p);
-            if (rc) return fail(rc, "label sums: launch rejected");
-            rc = check_kernel("k_segment_nearest");
-            if (rc) return rc;
-        }
-        if (const int rc = t_reduce.mark_end()) return rc;
-        if (const int rc = t_dots.add_to(&c->ls.dots_ms)) return rc;
-        if (const int rc = t_reduce.add_to(&c->ls.reduce_ms)) return rc;
-        ++c->ls.blocks;
-    }
+    const auto reduce = [&](int64_t r0, int64_t r1, const int32_t* dots) -> int {
+        Range rs(c, "k_segment_nearest");
+        const int rc = mvs::launch_segment_nearest(c->stream, dots, r1 - r0, m_lab, r0, (const double*)dnorms.p, o->d, floor,
+                                                   (const int32_t*)dcolseg.p, (const int32_t*)dbegin.p, (const int32_t*)did.p,
+                                                   (unsigned long long*)down.p, (int32_t*)dnear.p, (unsigned long long*)dnsum.p);
+        if (rc) return fail(rc, "label sums: launch rejected");
+        return check_kernel("k_segment_nearest");
+    };
+    if (const int rc = blocks.run(0, m, &c->ls.dots_ms, &c->ls.reduce_ms, &c->ls.blocks, reduce)) return rc;
     // back, and through the permutation
     std::vector<uint64_t> h_own((size_t)m), h_nsum((size_t)m);
     std::vector<int32_t> h_near((size_t)m);

@@ -1,6 +1,6 @@
 // mvs_capi_topk.hip -- C ABI of the exact top-k comparison: mvs_pairwise_topk, mvs_ctx_topk_stats.
 //
-// Rows are taken in blocks of R: the dense-dots kernels fill an R x C int32 block (C = the column range), k_topk_select ranks
+// Rows are taken in blocks of R (dots_block_rows): the dense-dots kernels fill an R x C int32 block (C = the column range), k_topk_select ranks
 // each row of it (mvs_topk.hip), and after the last block the rows' padded lists are packed into the caller's array.  Device
 // memory besides the set: R x C x 4 bytes of dots, (rows x k) padded cells, a count and an offset per row -- never N x N.
 #include "mvs_capi_internal.h"
@@ -26,8 +26,7 @@ int mvs_pairwise_topk(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_s
     if (!norms_sq || !cells) return fail(MVS_E_INVALID, "norms_sq or cells is NULL");
     Range mark(c, "mvs_pairwise_topk");
     HIP_TRY(hipSetDevice(c->device));
-    c->tk_dots_ms = c->tk_select_ms = 0.0;
-    c->tk_blocks = c->tk_block_rows = 0;
+    c->tk.reset();
 
     DevBuf dnorms;
     const double* d_n2 = norms_sq;
@@ -36,73 +35,24 @@ int mvs_pairwise_topk(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_s
         HIP_TRY(hipMemcpyAsync(dnorms.p, norms_sq, (size_t)s->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         d_n2 = (const double*)dnorms.p;
     }
-    // rows per block: the dots block takes a quarter of the free memory (as mvs_pairwise_stream sizes its blocks)
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const size_t pad_bytes = (size_t)rows * (size_t)k * sizeof(mvs_cell);
-    const size_t row_bytes = (size_t)cols * 4;
-    int64_t R = (int64_t)std::max<size_t>(1, (free_b / 4) / row_bytes);
-    R = std::min<int64_t>(R, 8192);
-    if (c->opt.topk_block_rows > 0) R = std::min<int64_t>(R, c->opt.topk_block_rows);
-    R = std::min(R, rows);
-    DevBuf ddots, dpad, dcounts, doffs, dout;
-    HIP_TRY(ddots.alloc((size_t)R * row_bytes));
-    HIP_TRY(dpad.alloc(pad_bytes));
+    const int64_t R = dots_block_rows(free_b / 4, (size_t)cols * 4, c->opt.topk_block_rows, rows);
+    DotsBlocks blocks;
+    DevBuf dpad, dcounts, doffs, dout;
+    if (const int rc = blocks.init(c, s, cb, ce, R, c->opt.topk_dots, {"k_topk dots", "top-k: dots launch rejected", "k_pairwise(top-k dots)"}))
+        return rc;
+    HIP_TRY(dpad.alloc((size_t)rows * (size_t)k * sizeof(mvs_cell)));
     HIP_TRY(dcounts.alloc((size_t)rows * sizeof(int)));
-    struct Events {
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } ev;
-    if (c->timing)
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-    const int algo = c->opt.topk_dots;
     const int excl = (flags & MVS_TOPK_EXCLUDE_SELF) ? 1 : 0;
-    for (int64_t r0 = rb; r0 < re; r0 += R) {
-        const int64_t r1 = std::min(r0 + R, re);
-        mvs::PairwiseArgs a{};
-        a.planes = s->planes;
-        a.n = s->n;
-        a.n_alloc = s->n_alloc;
-        a.d = s->d;
-        a.d_pad = s->d_pad;
-        a.limbs = s->limbs;
-        a.row_begin = r0;
-        a.row_end = r1;
-        a.col_begin = cb;
-        a.col_end = ce;
-        a.dots = (int32_t*)ddots.p;
-        if (c->timing) HIP_TRY(hipEventRecord(ev.e[0], c->stream));
-        {
-            Range rd(c, "k_topk dots");
-            int rc = mvs::launch_pairwise(c->stream, a, 1, algo, c->opt);
-            if (rc) return fail(rc, "top-k: dots launch rejected");
-            rc = check_kernel("k_pairwise(top-k dots)");
-            if (rc) return rc;
-        }
-        if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
-        {
-            Range rs(c, "k_topk_select");
-            int rc = mvs::launch_topk_select(c->stream, (const int32_t*)ddots.p, r1 - r0, cols, r0, cb, d_n2, s->d, k, excl,
-                                             (mvs_cell*)dpad.p, (int*)dcounts.p, rb);
-            if (rc) return fail(rc, "top-k: selection launch rejected");
-            rc = check_kernel("k_topk_select");
-            if (rc) return rc;
-        }
-        if (c->timing) {
-            HIP_TRY(hipEventRecord(ev.e[2], c->stream));
-            HIP_TRY(hipEventSynchronize(ev.e[2]));
-            float m0 = 0.f, m1 = 0.f;
-            HIP_TRY(hipEventElapsedTime(&m0, ev.e[0], ev.e[1]));
-            HIP_TRY(hipEventElapsedTime(&m1, ev.e[1], ev.e[2]));
-            c->tk_dots_ms += m0;
-            c->tk_select_ms += m1;
-        }
-        ++c->tk_blocks;
-    }
-    c->tk_block_rows = R;
+    const auto select = [&](int64_t r0, int64_t r1, const int32_t* dots) -> int {
+        Range rs(c, "k_topk_select");
+        int rc = mvs::launch_topk_select(c->stream, dots, r1 - r0, cols, r0, cb, d_n2, s->d, k, excl, (mvs_cell*)dpad.p, (int*)dcounts.p, rb);
+        if (rc) return fail(rc, "top-k: selection launch rejected");
+        return check_kernel("k_topk_select");
+    };
+    if (const int rc = blocks.run(rb, re, &c->tk.dots_ms, &c->tk.work_ms, &c->tk.blocks, select)) return rc;
+    c->tk.block_rows = R;
     // per-row counts -> offsets (host scan: 4 bytes down, 8 up per row), then the padded lists packed in row order
     std::vector<int> counts((size_t)rows);
     HIP_TRY(hipMemcpyAsync(counts.data(), dcounts.p, counts.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -133,12 +83,7 @@ int mvs_pairwise_topk(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_s
 }
 
 int mvs_ctx_topk_stats(const mvs_ctx* c, double* dots_ms, double* select_ms, int64_t* row_blocks, int64_t* block_rows) {
-    if (!c) return fail(MVS_E_INVALID, "NULL context");
-    if (dots_ms) *dots_ms = c->tk_dots_ms;
-    if (select_ms) *select_ms = c->tk_select_ms;
-    if (row_blocks) *row_blocks = c->tk_blocks;
-    if (block_rows) *block_rows = c->tk_block_rows;
-    return MVS_OK;
+    return dots_stats_out(c, &mvs_ctx::tk, dots_ms, select_ms, row_blocks, block_rows);
 }
 
 }  // extern "C"

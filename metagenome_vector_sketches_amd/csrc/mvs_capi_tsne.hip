@@ -533,7 +533,7 @@ int mvs_tsne(mvs_ctx* c, const mvs_sketch_set* set, const double* norms_sq, int 
             int64_t cells = 0;
             rc = mvs_pairwise_topk(c, set, d_n2, MVS_MEM_DEVICE, (int)K, r0, r1, 0, n, MVS_TOPK_EXCLUDE_SELF, (mvs_cell*)dcells.p, MVS_MEM_DEVICE, &cells);
             if (rc) return rc;
-            c->ts.topk_ms += c->tk_dots_ms + c->tk_select_ms;
+            c->ts.topk_ms += c->tk.dots_ms + c->tk.work_ms;
             ++c->ts.blocks;
             if (cells > (r1 - r0) * K) return fail(MVS_E_INTERNAL, "top-k returned %lld cells for %lld rows at k = %lld", (long long)cells, (long long)(r1 - r0), (long long)K);
             rc = consume_neighbours(t, (const mvs_cell*)dcells.p, cells, r0, r1 - r0, d_n2, set->d, p.perplexity, nullptr, &r.beta_zero_rows);
