@@ -25,11 +25,10 @@ namespace {
 constexpr const char* kProg = "cluster_sketches";
 
 struct Options {
-    std::string db_folder, output, bad_flag;
+    std::string db_folder, output;
     double min_jaccard = 0.0;
     long min_size = 1;
     int device = -1;
-    bool show_help = false, have_db = false, have_t = false, have_out = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -38,71 +37,25 @@ void print_usage(const char* argv0) {
               << std::endl;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--db" || a == "--output") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            (a == "--db" ? o.db_folder : o.output) = argv[++i];
-            (a == "--db" ? o.have_db : o.have_out) = true;
-        } else if (a == "--min_jaccard") {
-            o.have_t = true;
-            double t = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
-            else o.min_jaccard = t;
-        } else if (a == "--min_size") {
-            long m = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &m) || m < 1) bad("--min_size");
-            else o.min_size = m;
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* set = nullptr;
-    mvs_cluster* cluster = nullptr;
-    ~Gpu() {
-        if (cluster) mvs_cluster_destroy(cluster);
-        if (set) mvs_sketch_set_destroy(set);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet set;
+    Owned<mvs_cluster, mvs_cluster_destroy> cluster;
 };
 
 }  // namespace
 
 int main(int argc, char* argv[]) {
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.have_t && o.bad_flag.empty()) o.bad_flag = "--min_jaccard";
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--min_jaccard") std::cerr << "cluster_sketches: --min_jaccard takes a number in the open range (0,1)" << std::endl;
-        else if (o.bad_flag == "--min_size") std::cerr << "cluster_sketches: --min_size takes an integer >= 1" << std::endl;
-        else std::cerr << "cluster_sketches: --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        number_flag("--min_jaccard", &o.min_jaccard, in_open_unit, "--min_jaccard takes a number in the open range (0,1)", kRefuse),
+        integer_flag("--min_size", &o.min_size, 1, LONG_MAX, "--min_size takes an integer >= 1"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const DbInfo& db = sdb.info;

@@ -33,11 +33,10 @@ namespace {
 constexpr const char* kProg = "communities_sketches";
 
 struct Options {
-    std::string db_folder, output, levels, clusters, report, bad_flag;
+    std::string db_folder, output, levels, clusters, report;
     double floor = 0.05, resolution = 1.0, min_norm = 0.0;
     long max_rounds = 100;
     int device = -1;
-    bool show_help = false, have_db = false, have_out = false, have_min_norm = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -47,57 +46,9 @@ void print_usage(const char* argv0) {
               << " [--max_rounds <int>] [--levels <file>] [--clusters <file>] [--report <file>] [--device <int>] [--help]" << std::endl;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--db" || a == "--output" || a == "--levels" || a == "--clusters" || a == "--report") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            const std::string v = argv[++i];
-            if (a == "--db") o.db_folder = v, o.have_db = true;
-            else if (a == "--output") o.output = v, o.have_out = true;
-            else if (a == "--levels") o.levels = v;
-            else if (a == "--clusters") o.clusters = v;
-            else o.report = v;
-        } else if (a == "--floor") {
-            double t = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t > 0.0) || !(t < 1.0)) bad("--floor");
-            else o.floor = t;
-        } else if (a == "--resolution") {
-            double t = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t >= 1.0 / 4096.0) || !(t <= 16.0)) bad("--resolution");
-            else o.resolution = t;
-        } else if (a == "--min_norm") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.min_norm) || std::isnan(o.min_norm)) bad("--min_norm");
-            else o.have_min_norm = true;
-        } else if (a == "--max_rounds") {
-            long m = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &m) || m < 1 || m > (1L << 30)) bad("--max_rounds");
-            else o.max_rounds = m;
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* set = nullptr;
-    ~Gpu() {
-        if (set) mvs_sketch_set_destroy(set);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet set;
 };
 
 std::string fmt17(double v) {
@@ -121,25 +72,22 @@ long double wide(uint64_t hi, uint64_t lo) {
 
 int main(int argc, char* argv[]) {
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        std::cerr << kProg << ": " << o.bad_flag;
-        if (o.bad_flag == "--floor") std::cerr << " takes a number in the open range (0, 1)";
-        else if (o.bad_flag == "--resolution") std::cerr << " takes a number in [2^-12, 16]";
-        else if (o.bad_flag == "--min_norm") std::cerr << " takes a number";
-        else if (o.bad_flag == "--max_rounds") std::cerr << " takes an integer, 1 or more";
-        else std::cerr << " takes a device index";
-        std::cerr << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--levels", &o.levels),
+        path_flag("--clusters", &o.clusters),
+        path_flag("--report", &o.report),
+        number_flag("--floor", &o.floor, in_open_unit, "--floor takes a number in the open range (0, 1)"),
+        number_flag("--resolution", &o.resolution, [](double g) { return g >= 1.0 / 4096.0 && g <= 16.0; },
+                    "--resolution takes a number in [2^-12, 16]"),
+        number_flag("--min_norm", &o.min_norm, not_nan, "--min_norm takes a number"),
+        integer_flag("--max_rounds", &o.max_rounds, 1, 1L << 30, "--max_rounds takes an integer, 1 or more"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
+    const bool have_min_norm = was_given(flags, "--min_norm");
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const DbInfo& db = sdb.info;
@@ -148,7 +96,7 @@ int main(int argc, char* argv[]) {
     std::vector<double> norms_sq = db.norms_sq;
     std::vector<char> out_of_it((size_t)n, 0);
     int64_t excluded = 0;
-    if (o.have_min_norm) {
+    if (have_min_norm) {
         const std::vector<double> norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
         for (int64_t i = 0; i < n; ++i)
             if (!(i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm)) {

@@ -32,10 +32,9 @@ namespace {
 constexpr const char* kProg = "contain_sketches";
 
 struct Options {
-    std::string db_folder, hash_file, output, report, bad_flag;
+    std::string db_folder, hash_file, output, report;
     double min_containment = 0.0, slack = 0.0, exact_min = -1.0;
     int device = -1, mode = MVS_CONTAIN_ROW;
-    bool show_help = false, have_db = false, have_c = false, have_out = false, have_hashes = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -46,72 +45,11 @@ void print_usage(const char* argv0) {
               << std::endl;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--db" || a == "--output" || a == "--report") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            (a == "--db" ? o.db_folder : a == "--output" ? o.output : o.report) = argv[++i];
-            if (a == "--db") o.have_db = true;
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--hashes") {
-            o.have_hashes = true;
-            const std::string v = has_value ? argv[++i] : "";
-            if (v.empty()) bad("--hashes");
-            else o.hash_file = v;
-        } else if (a == "--min_containment") {
-            o.have_c = true;
-            double c = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &c) || !(c > 0.0) || !(c < 1.0)) bad("--min_containment");
-            else o.min_containment = c;
-        } else if (a == "--slack") {
-            double z = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &z) || !std::isfinite(z)) bad("--slack");
-            else o.slack = z;
-        } else if (a == "--mode") {
-            const std::string v = has_value ? argv[++i] : "";
-            if (v == "row") o.mode = MVS_CONTAIN_ROW;
-            else if (v == "max") o.mode = MVS_CONTAIN_MAX;
-            else bad("--mode");
-        } else if (a == "--exact_min") {
-            double u = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &u) || !(u >= 0.0) || !(u < 1.0)) bad("--exact_min");
-            else o.exact_min = u;
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* set = nullptr;
-    mvs_hash_set* hs = nullptr;
-    void* d_norms = nullptr;
-    void* d_cells = nullptr;
-    void* d_inter = nullptr;
-    ~Gpu() {
-        if (ctx) {
-            if (d_norms) mvs_device_free(ctx, d_norms);
-            if (d_cells) mvs_device_free(ctx, d_cells);
-            if (d_inter) mvs_device_free(ctx, d_inter);
-        }
-        if (hs) mvs_hash_set_destroy(hs);
-        if (set) mvs_sketch_set_destroy(set);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet set;
+    OwnedHashSet hs;
+    DeviceMem d_inter, d_cells, d_norms;
 };
 
 struct Pair {
@@ -132,27 +70,21 @@ double ratio(double num, double den) { return den == 0.0 ? std::nan("") : num / 
 int main(int argc, char* argv[]) {
     const auto wall_begin = std::chrono::steady_clock::now();
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.have_c && o.bad_flag.empty()) o.bad_flag = "--min_containment";
-    if (o.exact_min >= 0.0 && !o.have_hashes && o.bad_flag.empty()) o.bad_flag = "--exact_min without --hashes";
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--min_containment") std::cerr << "contain_sketches: --min_containment takes a number in the open range (0,1)" << std::endl;
-        else if (o.bad_flag == "--slack") std::cerr << "contain_sketches: --slack takes a finite number" << std::endl;
-        else if (o.bad_flag == "--mode") std::cerr << "contain_sketches: --mode takes row or max" << std::endl;
-        else if (o.bad_flag == "--hashes") std::cerr << "contain_sketches: --hashes takes the hash file the DB was sketched from" << std::endl;
-        else if (o.bad_flag == "--exact_min") std::cerr << "contain_sketches: --exact_min takes a number in the range [0,1)" << std::endl;
-        else if (o.bad_flag == "--exact_min without --hashes") std::cerr << "contain_sketches: --exact_min needs --hashes" << std::endl;
-        else std::cerr << "contain_sketches: --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--report", &o.report),
+        text_flag("--hashes", &o.hash_file, "--hashes takes the hash file the DB was sketched from"),
+        number_flag("--min_containment", &o.min_containment, in_open_unit, "--min_containment takes a number in the open range (0,1)", kRefuse),
+        number_flag("--slack", &o.slack, [](double z) { return std::isfinite(z); }, "--slack takes a finite number"),
+        word_flag("--mode", &o.mode, {{"row", MVS_CONTAIN_ROW}, {"max", MVS_CONTAIN_MAX}}, "--mode takes row or max"),
+        number_flag("--exact_min", &o.exact_min, in_half_open_unit, "--exact_min takes a number in the range [0,1)"),
+        device_flag(&o.device),
+    };
+    Args args = parse_flags(argc, argv, flags);
+    const bool have_hashes = was_given(flags, "--hashes");
+    if (o.exact_min >= 0.0 && !have_hashes) args.refuse("--exact_min needs --hashes");
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const DbInfo& db = sdb.info;
@@ -162,7 +94,7 @@ int main(int argc, char* argv[]) {
     const double exact_min = o.exact_min >= 0.0 ? o.exact_min : c;
 
     HashSets sets;
-    if (o.have_hashes)
+    if (have_hashes)
         if (const int rc = load_db_hashes(kProg, o.hash_file, sdb, sets)) return rc;
 
     std::vector<Pair> pairs;
@@ -174,13 +106,13 @@ int main(int argc, char* argv[]) {
         if (mvs_ctx_create(choose_device(o.device), &g.ctx) != MVS_OK) return gpu_fail(kProg, "creating context");
         mvs_ctx_set_timing(g.ctx, 1);
         if (const int rc = load_sketch_db(kProg, g.ctx, sdb, &g.set)) return rc;
-        if (o.have_hashes) {
+        if (have_hashes) {
             if (mvs_hash_set_create(g.ctx, sets.hashes.data(), MVS_MEM_HOST, sets.offsets.data(), n, &g.hs) != MVS_OK)
                 return gpu_fail(kProg, "uploading the hash lists");
             if (mvs_hash_set_sizes(g.hs, sizes.data(), MVS_MEM_HOST) != MVS_OK) return gpu_fail(kProg, "reading the set sizes");
         }
-        if (mvs_device_alloc(g.ctx, (size_t)n * 8, 0, &g.d_norms) != MVS_OK ||
-            mvs_device_copy(g.ctx, g.d_norms, MVS_MEM_DEVICE, db.norms_sq.data(), MVS_MEM_HOST, (size_t)n * 8) != MVS_OK)
+        if (g.d_norms.alloc(g.ctx, (size_t)n * 8) != MVS_OK ||
+            mvs_device_copy(g.ctx, g.d_norms.p, MVS_MEM_DEVICE, db.norms_sq.data(), MVS_MEM_HOST, (size_t)n * 8) != MVS_OK)
             return gpu_fail(kProg, "uploading the norms");
         // row blocks; a block that keeps more than the buffer holds reports what it needs and is done again
         const int64_t block_rows = std::max<int64_t>(256, std::min<int64_t>(n, (1LL << 28) / std::max<int64_t>(n, 1) / 256 * 256));
@@ -191,25 +123,22 @@ int main(int argc, char* argv[]) {
             const int64_t re = std::min(n, rb + block_rows);
             if (capacity == 0) {
                 capacity = 1 << 20;
-                if (mvs_device_alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK ||
-                    mvs_device_alloc(g.ctx, (size_t)capacity * 4, 0, &g.d_inter) != MVS_OK)
+                if (g.d_cells.alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell)) != MVS_OK || g.d_inter.alloc(g.ctx, (size_t)capacity * 4) != MVS_OK)
                     return gpu_fail(kProg, "allocating the cell buffers");
             }
             int64_t count = 0;
-            const int src = mvs_pairwise_contain(g.ctx, g.set, (const double*)g.d_norms, MVS_MEM_DEVICE, c, o.slack, o.mode, rb, re, 0, n,
-                                                 (mvs_cell*)g.d_cells, MVS_MEM_DEVICE, capacity, &count);
+            const int src = mvs_pairwise_contain(g.ctx, g.set, (const double*)g.d_norms.p, MVS_MEM_DEVICE, c, o.slack, o.mode, rb, re, 0, n,
+                                                 (mvs_cell*)g.d_cells.p, MVS_MEM_DEVICE, capacity, &count);
             double dms = 0.0, sms = 0.0;
             if (mvs_ctx_contain_stats(g.ctx, &dms, &sms, nullptr, nullptr) == MVS_OK) {
                 dots_ms += dms;
                 select_ms += sms;
             }
             if (src == MVS_E_CAPACITY) {
-                mvs_device_free(g.ctx, g.d_cells);
-                mvs_device_free(g.ctx, g.d_inter);
-                g.d_cells = g.d_inter = nullptr;
+                g.d_cells.free();
+                g.d_inter.free();
                 capacity = count + count / 8 + 1024;
-                if (mvs_device_alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK ||
-                    mvs_device_alloc(g.ctx, (size_t)capacity * 4, 0, &g.d_inter) != MVS_OK)
+                if (g.d_cells.alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell)) != MVS_OK || g.d_inter.alloc(g.ctx, (size_t)capacity * 4) != MVS_OK)
                     return gpu_fail(kProg, "allocating the cell buffers");
                 continue;
             }
@@ -218,17 +147,17 @@ int main(int argc, char* argv[]) {
             if (count > 0) {
                 cells.resize((size_t)count);
                 inter.assign((size_t)count, 0);
-                if (o.have_hashes) {
-                    if (mvs_intersect_cells(g.ctx, g.hs, nullptr, (const mvs_cell*)g.d_cells, MVS_MEM_DEVICE, count, (int32_t*)g.d_inter,
+                if (have_hashes) {
+                    if (mvs_intersect_cells(g.ctx, g.hs, nullptr, (const mvs_cell*)g.d_cells.p, MVS_MEM_DEVICE, count, (int32_t*)g.d_inter.p,
                                             MVS_MEM_DEVICE) != MVS_OK)
                         return gpu_fail(kProg, "intersecting");
                     double kms = 0.0;
                     mvs_ctx_intersect_stats(g.ctx, &kms, nullptr, nullptr, nullptr);
                     intersect_ms += kms;
-                    if (mvs_device_copy(g.ctx, inter.data(), MVS_MEM_HOST, g.d_inter, MVS_MEM_DEVICE, (size_t)count * 4) != MVS_OK)
+                    if (mvs_device_copy(g.ctx, inter.data(), MVS_MEM_HOST, g.d_inter.p, MVS_MEM_DEVICE, (size_t)count * 4) != MVS_OK)
                         return gpu_fail(kProg, "downloading");
                 }
-                if (mvs_device_copy(g.ctx, cells.data(), MVS_MEM_HOST, g.d_cells, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_cell)) != MVS_OK)
+                if (mvs_device_copy(g.ctx, cells.data(), MVS_MEM_HOST, g.d_cells.p, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_cell)) != MVS_OK)
                     return gpu_fail(kProg, "downloading");
                 for (int64_t i = 0; i < count; ++i) {                   // sorted by (row, col) inside a block, blocks ascend
                     const mvs_cell& x = cells[(size_t)i];
@@ -256,7 +185,7 @@ int main(int argc, char* argv[]) {
         const double jac = inter_est / (n2r + n2c - inter_est);
         std::string line = db.names[(size_t)p.row] + '\t' + db.names[(size_t)p.col] + '\t' + fmt(est) + '\t' + fmt(z) + '\t' + fmt(jac) +
                            '\t' + std::to_string(p.dot);
-        if (o.have_hashes) {
+        if (have_hashes) {
             const double sa = (double)sizes[(size_t)p.row], in = (double)p.inter;
             const double exact = ratio(in, sa);
             if (exact == exact && est == est && std::isfinite(est)) {
@@ -283,7 +212,7 @@ int main(int argc, char* argv[]) {
         rep += std::string("mode\t") + mode_name + "\n";
         rep += "cells_kept\t" + std::to_string(cells_kept) + "\n";
         rep += "pairs\t" + std::to_string((int64_t)pairs.size()) + "\n";
-        if (o.have_hashes) {
+        if (have_hashes) {
             rep += "exact_min\t" + fmt(exact_min) + "\n";
             rep += "pairs_exact_above\t" + std::to_string(above) + "\n";
             rep += "estimate_rmse\t" + fmt(err_n ? std::sqrt(err_sq / (double)err_n) : 0.0) + "\n";
@@ -291,13 +220,13 @@ int main(int argc, char* argv[]) {
         rep += "pairs_written\t" + std::to_string(written) + "\n";
         rep += "dots_kernel_ms\t" + fmt(dots_ms) + "\n";
         rep += "select_kernel_ms\t" + fmt(select_ms) + "\n";
-        if (o.have_hashes) rep += "intersect_kernel_ms\t" + fmt(intersect_ms) + "\n";
+        if (have_hashes) rep += "intersect_kernel_ms\t" + fmt(intersect_ms) + "\n";
         rep += "wall_s\t" + fmt(wall_s) + "\n";
         if (const int rc = write_then_rename(kProg, o.report, rep)) return rc;
     }
     std::cout << "Kept " << cells_kept << " cells of " << n << " samples at containment > " << c << " (mode " << mode_name << ", slack "
               << o.slack << "): " << pairs.size() << " pairs";
-    if (o.have_hashes) std::cout << ", " << above << " with exact containment > " << exact_min;
+    if (have_hashes) std::cout << ", " << above << " with exact containment > " << exact_min;
     std::cout << "; " << written << " written" << std::endl;
     return 0;
 }

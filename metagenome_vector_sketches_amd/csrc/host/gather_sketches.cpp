@@ -28,10 +28,9 @@ namespace {
 constexpr const char* kProg = "gather_sketches";
 
 struct Options {
-    std::string hash_file, query_file, output, report, bad_flag;
+    std::string hash_file, query_file, output, report;
     long min_hashes = 50, max_matches = -1;
     int device = -1;
-    bool show_help = false, have_hashes = false, have_query = false, have_out = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -44,54 +43,9 @@ void print_usage(const char* argv0) {
               << std::endl;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--output" || a == "--report") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            (a == "--output" ? o.output : o.report) = argv[++i];
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--hashes" || a == "--query") {
-            const bool h = a == "--hashes";
-            (h ? o.have_hashes : o.have_query) = true;
-            const std::string v = has_value ? argv[++i] : "";
-            if (v.empty()) bad(h ? "--hashes" : "--query");
-            else (h ? o.hash_file : o.query_file) = v;
-        } else if (a == "--min_hashes") {
-            long k = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &k) || k < 1 || k > 0x7fffffffL) bad("--min_hashes");
-            else o.min_hashes = k;
-        } else if (a == "--max_matches") {
-            long r = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &r) || r < 0 || r > 0x7fffffffL) bad("--max_matches");
-            else o.max_matches = r;
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_hash_set* hs_db = nullptr;
-    mvs_hash_set* hs_q = nullptr;
-    ~Gpu() {
-        if (hs_q) mvs_hash_set_destroy(hs_q);
-        if (hs_db) mvs_hash_set_destroy(hs_db);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedHashSet hs_db, hs_q;
 };
 
 // a hash file: its .csr cache when `cached` and valid, else the text; 0, or 1 after a message on stderr
@@ -118,25 +72,17 @@ std::string ratio9(double num, double den) { return den == 0.0 ? "nan" : fmt9(nu
 
 int main(int argc, char* argv[]) {
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.have_hashes && o.bad_flag.empty()) o.bad_flag = "--hashes";
-    if (!o.have_query && o.bad_flag.empty()) o.bad_flag = "--query";
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--hashes") std::cerr << kProg << ": --hashes takes the hash file of the samples to gather from" << std::endl;
-        else if (o.bad_flag == "--query") std::cerr << kProg << ": --query takes a file of 'name: hashes' lines" << std::endl;
-        else if (o.bad_flag == "--min_hashes") std::cerr << kProg << ": --min_hashes takes an integer >= 1" << std::endl;
-        else if (o.bad_flag == "--max_matches") std::cerr << kProg << ": --max_matches takes an integer >= 0" << std::endl;
-        else std::cerr << kProg << ": --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {                                   // absent: --hashes speaks before --query
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--report", &o.report),
+        text_flag("--hashes", &o.hash_file, "--hashes takes the hash file of the samples to gather from", kRefuse),
+        text_flag("--query", &o.query_file, "--query takes a file of 'name: hashes' lines", kRefuse),
+        integer_flag("--min_hashes", &o.min_hashes, 1, 0x7fffffffL, "--min_hashes takes an integer >= 1"),
+        integer_flag("--max_matches", &o.max_matches, 0, 0x7fffffffL, "--max_matches takes an integer >= 0"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     HashSets db, queries;
     if (const int rc = load_hashes(o.hash_file, true, db)) return rc;
     if (const int rc = load_hashes(o.query_file, false, queries)) return rc;

@@ -38,11 +38,10 @@ struct Cut {
 };
 
 struct Options {
-    std::string db_folder, output, newick, report, bad_flag;
+    std::string db_folder, output, newick, report;
     std::vector<Cut> cuts;
     int method = MVS_HCLUST_AVERAGE, device = -1;
     double min_norm = 0.0, floor = 0.0;
-    bool show_help = false, have_db = false, have_out = false, have_min_norm = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -57,51 +56,6 @@ inline std::string fmt17(double v) {
     char buf[64];
     snprintf(buf, sizeof buf, "%.17g", v);
     return buf;
-}
-
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        std::string* text = a == "--db" ? &o.db_folder : a == "--output" ? &o.output : a == "--newick" ? &o.newick : a == "--report" ? &o.report : nullptr;
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (text) {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            *text = argv[++i];
-            if (a == "--db") o.have_db = true;
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--method") {
-            const std::string v = has_value ? argv[++i] : "";
-            if (v == "average") o.method = MVS_HCLUST_AVERAGE;
-            else if (v == "complete") o.method = MVS_HCLUST_COMPLETE;
-            else bad("--method");
-        } else if (a == "--cut") {
-            double u = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &u) || std::isnan(u)) bad("--cut");
-            else o.cuts.push_back({false, u, 0});
-        } else if (a == "--clusters") {
-            long k = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &k) || k < 1 || k > MVS_HCLUST_MAX_TOTAL) bad("--clusters");
-            else o.cuts.push_back({true, 0.0, k});
-        } else if (a == "--min_norm") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.min_norm) || std::isnan(o.min_norm)) bad("--min_norm");
-            else o.have_min_norm = true;
-        } else if (a == "--floor") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.floor) || !(o.floor >= 0.0) || !(o.floor < 1.0)) bad("--floor");
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
 }
 
 // a Newick label: as it is, or in single quotes (a quote doubled) where it holds a character an unquoted label may not --
@@ -148,14 +102,8 @@ std::string newick_text(int64_t m, const std::vector<double>& Z, const std::vect
 }
 
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* loaded = nullptr;
-    mvs_sketch_set* kept = nullptr;
-    ~Gpu() {
-        if (kept) mvs_sketch_set_destroy(kept);
-        if (loaded) mvs_sketch_set_destroy(loaded);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet loaded, kept;
 };
 
 }  // namespace
@@ -163,38 +111,44 @@ struct Gpu {
 int main(int argc, char* argv[]) {
     const auto wall0 = std::chrono::steady_clock::now();
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--method") std::cerr << kProg << ": --method takes average or complete" << std::endl;
-        else if (o.bad_flag == "--cut") std::cerr << kProg << ": --cut takes a height, a number" << std::endl;
-        else if (o.bad_flag == "--clusters") std::cerr << kProg << ": --clusters takes a number of clusters, 1 .. " << MVS_HCLUST_MAX_TOTAL << std::endl;
-        else if (o.bad_flag == "--min_norm") std::cerr << kProg << ": --min_norm takes a number" << std::endl;
-        else if (o.bad_flag == "--floor") std::cerr << kProg << ": --floor takes a number in [0, 1)" << std::endl;
-        else std::cerr << kProg << ": --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    // --cut and --clusters fill one list, in the order given: the cut files are numbered by it
+    auto take_cut = [&o](const std::string& v) {
+        double u = 0.0;
+        return parse_number(v, &u) && !std::isnan(u) ? (o.cuts.push_back({false, u, 0}), true) : false;
+    };
+    auto take_clusters = [&o](const std::string& v) {
+        long k = 0;
+        return parse_integer(v, &k) && k >= 1 && k <= MVS_HCLUST_MAX_TOTAL ? (o.cuts.push_back({true, 0.0, k}), true) : false;
+    };
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--newick", &o.newick),
+        path_flag("--report", &o.report),
+        word_flag("--method", &o.method, {{"average", MVS_HCLUST_AVERAGE}, {"complete", MVS_HCLUST_COMPLETE}}, "--method takes average or complete"),
+        hook_flag("--cut", take_cut, "--cut takes a height, a number"),
+        hook_flag("--clusters", take_clusters, "--clusters takes a number of clusters, 1 .. " + std::to_string(MVS_HCLUST_MAX_TOTAL)),
+        number_flag("--min_norm", &o.min_norm, not_nan, "--min_norm takes a number"),
+        number_flag("--floor", &o.floor, in_half_open_unit, "--floor takes a number in [0, 1)"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
+    const bool have_min_norm = was_given(flags, "--min_norm");
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const int64_t n = sdb.n;
 
     // who takes part
     std::vector<double> norms;
-    if (o.have_min_norm) norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
+    if (have_min_norm) norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
     std::vector<int32_t> order;
     for (int64_t i = 0; i < n; ++i)
-        if (!o.have_min_norm || (i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm)) order.push_back((int32_t)i);
+        if (!have_min_norm || (i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm)) order.push_back((int32_t)i);
     const int64_t m = (int64_t)order.size();
     if (m < 1 || m > MVS_HCLUST_MAX_TOTAL) {
         std::cerr << kProg << ": " << m << " samples take part; a tree takes 1 .. " << MVS_HCLUST_MAX_TOTAL
-                  << (o.have_min_norm ? " (see --min_norm)" : "") << std::endl;
+                  << (have_min_norm ? " (see --min_norm)" : "") << std::endl;
         return 1;
     }
     for (const Cut& c : o.cuts)
@@ -214,8 +168,7 @@ int main(int argc, char* argv[]) {
         if (mvs_sketch_set_gather(g.ctx, g.loaded, order.data(), MVS_MEM_HOST, m, &g.kept) != MVS_OK)
             return gpu_fail(kProg, "gathering the samples that take part");
         set = g.kept;
-        mvs_sketch_set_destroy(g.loaded);
-        g.loaded = nullptr;
+        g.loaded.reset();
     }
     std::vector<mvs_hmerge> merges((size_t)std::max<int64_t>(1, m - 1));
     int64_t rounds = 0;

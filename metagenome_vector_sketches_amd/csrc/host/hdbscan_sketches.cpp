@@ -28,11 +28,11 @@ namespace {
 constexpr const char* kProg = "hdbscan_sketches";
 
 struct Options {
-    std::string db_folder, output, clusters, links, report, bad_flag;
+    std::string db_folder, output, clusters, links, report;
     long min_samples = 5, min_cluster_size = 5;
     double floor = 0.05;
     int device = -1;
-    bool no_roots = false, show_help = false, have_db = false, have_out = false, unknown = false;
+    bool no_roots = false;
 };
 
 void print_usage(const char* argv0) {
@@ -43,53 +43,9 @@ void print_usage(const char* argv0) {
               << std::endl;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--no_root_clusters") {
-            o.no_roots = true;
-        } else if (a == "--db" || a == "--output" || a == "--clusters" || a == "--links" || a == "--report") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            const std::string v = argv[++i];
-            if (a == "--db") o.db_folder = v, o.have_db = true;
-            else if (a == "--output") o.output = v, o.have_out = true;
-            else if (a == "--clusters") o.clusters = v;
-            else if (a == "--links") o.links = v;
-            else o.report = v;
-        } else if (a == "--min_samples") {
-            if (!parse_integer(has_value ? argv[++i] : "", &o.min_samples) || o.min_samples < 1 || o.min_samples > 256) bad("--min_samples");
-        } else if (a == "--min_cluster_size") {
-            if (!parse_integer(has_value ? argv[++i] : "", &o.min_cluster_size) || o.min_cluster_size < 2 || o.min_cluster_size > 2147483647L)
-                bad("--min_cluster_size");
-        } else if (a == "--floor") {
-            double t = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t > 0.0) || !(t < 1.0)) bad("--floor");
-            else o.floor = t;
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* set = nullptr;
-    ~Gpu() {
-        if (set) mvs_sketch_set_destroy(set);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet set;
 };
 
 std::string g17(double v) {
@@ -102,24 +58,20 @@ std::string g17(double v) {
 
 int main(int argc, char* argv[]) {
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        std::cerr << kProg << ": " << o.bad_flag;
-        if (o.bad_flag == "--min_samples") std::cerr << " takes an integer from 1 to 256";
-        else if (o.bad_flag == "--min_cluster_size") std::cerr << " takes an integer of at least 2";
-        else if (o.bad_flag == "--floor") std::cerr << " takes a number in the open range (0,1)";
-        else std::cerr << " takes a device index";
-        std::cerr << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--clusters", &o.clusters),
+        path_flag("--links", &o.links),
+        path_flag("--report", &o.report),
+        switch_flag("--no_root_clusters", &o.no_roots),
+        integer_flag("--min_samples", &o.min_samples, 1, 256, "--min_samples takes an integer from 1 to 256"),
+        integer_flag("--min_cluster_size", &o.min_cluster_size, 2, 2147483647L, "--min_cluster_size takes an integer of at least 2"),
+        number_flag("--floor", &o.floor, in_open_unit, "--floor takes a number in the open range (0,1)"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const DbInfo& db = sdb.info;

@@ -29,10 +29,9 @@ constexpr const char* kProg = "levels_sketches";
 constexpr const char* kDefaultLevels = "0.01,0.02,0.03,0.05,0.1,0.2,0.3,0.4,0.5,0.6,0.7,0.8,0.9,0.95,0.99";
 
 struct Options {
-    std::string db_folder, output, per_sample, bad_flag;
+    std::string db_folder, output, per_sample;
     std::vector<double> levels;
     int device = -1;
-    bool show_help = false, have_db = false, have_out = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -60,41 +59,9 @@ bool parse_levels(const std::string& v, std::vector<double>& out) {
     }
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--db" || a == "--output" || a == "--per_sample") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            (a == "--db" ? o.db_folder : a == "--output" ? o.output : o.per_sample) = argv[++i];
-            if (a == "--db") o.have_db = true;
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--levels") {
-            if (!parse_levels(has_value ? argv[++i] : "", o.levels)) bad("--levels");
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* set = nullptr;
-    ~Gpu() {
-        if (set) mvs_sketch_set_destroy(set);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet set;
 };
 
 std::string fmt(double v) {
@@ -107,22 +74,16 @@ std::string fmt(double v) {
 
 int main(int argc, char* argv[]) {
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--levels")
-            std::cerr << "levels_sketches: --levels takes 1 to 64 strictly ascending numbers in the open range (0,1), separated by commas"
-                      << std::endl;
-        else std::cerr << "levels_sketches: --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--per_sample", &o.per_sample),
+        hook_flag("--levels", [&o](const std::string& v) { return parse_levels(v, o.levels); },
+                  "--levels takes 1 to 64 strictly ascending numbers in the open range (0,1), separated by commas"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     if (o.levels.empty()) parse_levels(kDefaultLevels, o.levels);
     const int m = (int)o.levels.size();
     SketchDb sdb;

@@ -26,11 +26,10 @@ namespace {
 constexpr const char* kProg = "linkage_sketches";
 
 struct Options {
-    std::string db_folder, output, bad_flag;
+    std::string db_folder, output;
     double min_jaccard = 0.0;
     std::vector<double> cuts;
     int device = -1;
-    bool show_help = false, have_db = false, have_t = false, have_out = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -39,57 +38,12 @@ void print_usage(const char* argv0) {
               << std::endl;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--db" || a == "--output") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            (a == "--db" ? o.db_folder : o.output) = argv[++i];
-            (a == "--db" ? o.have_db : o.have_out) = true;
-        } else if (a == "--min_jaccard") {
-            o.have_t = true;
-            double t = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
-            else o.min_jaccard = t;
-        } else if (a == "--cut") {
-            double u = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &u) || !(u > 0.0) || !(u < 1.0)) bad("--cut");
-            else o.cuts.push_back(u);
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-    if (!o.have_t && o.bad_flag.empty()) o.bad_flag = "--min_jaccard";
-    if (o.bad_flag.empty())
-        for (double u : o.cuts)
-            if (u < o.min_jaccard) o.bad_flag = "--cut";              // a level below the one the tree is built at
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* set = nullptr;
-    mvs_linkage* linkage = nullptr;
-    mvs_cluster* cluster = nullptr;
-    void* d_cells = nullptr;
-    ~Gpu() {
-        if (cluster) mvs_cluster_destroy(cluster);
-        if (linkage) mvs_linkage_destroy(linkage);
-        if (d_cells) mvs_device_free(ctx, d_cells);
-        if (set) mvs_sketch_set_destroy(set);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet set;
+    DeviceMem d_cells;
+    Owned<mvs_linkage, mvs_linkage_destroy> linkage;
+    Owned<mvs_cluster, mvs_cluster_destroy> cluster;
 };
 
 std::string g17(double v) {
@@ -102,21 +56,22 @@ std::string g17(double v) {
 
 int main(int argc, char* argv[]) {
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--min_jaccard") std::cerr << "linkage_sketches: --min_jaccard takes a number in the open range (0,1)" << std::endl;
-        else if (o.bad_flag == "--cut") std::cerr << "linkage_sketches: --cut takes a number in [min_jaccard,1)" << std::endl;
-        else std::cerr << "linkage_sketches: --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    const char* cut_refusal = "--cut takes a number in [min_jaccard,1)";
+    auto take_cut = [&o](const std::string& v) {
+        double u = 0.0;
+        return parse_number(v, &u) && in_open_unit(u) ? (o.cuts.push_back(u), true) : false;
+    };
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        number_flag("--min_jaccard", &o.min_jaccard, in_open_unit, "--min_jaccard takes a number in the open range (0,1)", kRefuse),
+        hook_flag("--cut", take_cut, cut_refusal),
+        device_flag(&o.device),
+    };
+    Args args = parse_flags(argc, argv, flags);
+    for (double u : o.cuts)
+        if (u < o.min_jaccard) args.refuse(cut_refusal);                 // a level below the one the tree is built at
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const DbInfo& db = sdb.info;
@@ -135,19 +90,18 @@ int main(int argc, char* argv[]) {
             return gpu_fail(kProg, "comparing");
         if (mvs_linkage_finish(g.linkage, links.data(), (int64_t)links.size(), MVS_MEM_HOST, &n_links) != MVS_OK)
             return gpu_fail(kProg, "sorting the links");
-        if (!o.cuts.empty() && mvs_device_alloc(g.ctx, (size_t)n * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK)
+        if (!o.cuts.empty() && g.d_cells.alloc(g.ctx, (size_t)n * sizeof(mvs_cell)) != MVS_OK)
             return gpu_fail(kProg, "allocating the cell buffer");
         std::vector<int32_t> labels((size_t)n), reps((size_t)n), sizes((size_t)n);
         for (double u : o.cuts) {
             int64_t m = 0, n_clusters = 0;
-            if (mvs_linkage_cells(g.linkage, u, (mvs_cell*)g.d_cells, n, &m) != MVS_OK) return gpu_fail(kProg, "listing the links above a cut");
+            if (mvs_linkage_cells(g.linkage, u, (mvs_cell*)g.d_cells.p, n, &m) != MVS_OK) return gpu_fail(kProg, "listing the links above a cut");
             if (mvs_cluster_create(g.ctx, n, &g.cluster) != MVS_OK) return gpu_fail(kProg, "allocating a cut's clusters");
-            if (mvs_cluster_add_cells(g.cluster, (const mvs_cell*)g.d_cells, m) != MVS_OK) return gpu_fail(kProg, "clustering a cut");
+            if (mvs_cluster_add_cells(g.cluster, (const mvs_cell*)g.d_cells.p, m) != MVS_OK) return gpu_fail(kProg, "clustering a cut");
             if (mvs_cluster_finish(g.cluster, db.norms_sq.data(), MVS_MEM_HOST, labels.data(), nullptr, reps.data(), sizes.data(),
                                    MVS_MEM_HOST, &n_clusters) != MVS_OK)
                 return gpu_fail(kProg, "numbering a cut's clusters");
-            mvs_cluster_destroy(g.cluster);
-            g.cluster = nullptr;
+            g.cluster.reset();
             std::ostringstream text;
             text << "#sample\tcluster\trepresentative\tsize\n";
             for (int64_t i = 0; i < n; ++i) {

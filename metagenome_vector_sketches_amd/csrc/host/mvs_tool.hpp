@@ -1,11 +1,20 @@
-// mvs_tool.hpp -- what the tools over a sketch DB share (cluster_sketches, linkage_sketches, dereplicate_sketches, verify_pairs,
-// pca_sketches, pcoa_sketches, gather_sketches, permanova_sketches, hdbscan_sketches, silhouette_sketches, hclust_sketches, communities_sketches, tsne_sketches, pairwise_comp_optimized for the loader, and sketch_sequences for the flag values and the output file): opening the DB folder, loading vectors.bin into a sketch set, reporting a
-// device error, writing an output file under <file>.part, the hash file a DB was sketched from, and the parsing of flag values.  Header-only; include it after
-// mvs_host.hpp.  Each tool keeps its own parse() chain, usage text, Gpu holder and output format.
+// mvs_tool.hpp -- what the tools over a sketch DB share: the fourteen *_sketches tools, verify_pairs, sketch_sequences (the
+// command line, the device holders and the output file) and pairwise_comp_optimized (the loader).  It holds
+//   - the command line: one Flag per flag, parse_flags() over the table, Args for what it found and for the exit;
+//   - the holders of what a tool keeps on the device (Owned, DeviceMem);
+//   - reporting a device error and writing an output file under <file>.part;
+//   - opening the DB folder and loading vectors.bin into a sketch set;
+//   - what the ordination tools share;
+//   - the hash file a DB was sketched from.
+// Header-only; include it after mvs_host.hpp.  Each tool keeps its own flag table, usage text and output format.
 #ifndef MVS_TOOL_HPP
 #define MVS_TOOL_HPP
 
 #include "mvs_host.hpp"
+
+#include <climits>
+#include <functional>
+#include <utility>
 
 namespace mvs_host {
 
@@ -30,6 +39,163 @@ inline bool parse_device(const std::string& v, int* out) {
 }
 // the device a tool works on: --device when it was given (>= 0), else MVS_DEVICE, else 0
 inline int choose_device(int device_flag) { return device_flag >= 0 ? device_flag : pick_device(); }
+
+// ---- the command line ----
+// A tool describes its flags once, as a table of Flag, and parse_flags() walks argv over it.  The rules, the same for every tool:
+// "--help" in a flag's place asks for the usage text and wins over everything.  A flag that takes a value takes the next argument
+// whatever it looks like; at the end of argv a checked flag judges the empty string and a path flag counts as an unknown argument.
+// A value that `take` refuses leaves the flag's text as the refusal, and the first refusal in argv order stands; a flag given
+// twice keeps its last good value.  After argv the absent flags speak in table order: kRefuse as if their value had been
+// refused, kUsage by asking for the usage text.  A refusal (exit 1, one line on stderr) goes before the usage text (exit 1, on
+// stdout), which is what an unknown argument, a path flag without a value or an absent kUsage flag lead to.
+enum Absent { kOptional, kRefuse, kUsage };
+
+struct Flag {
+    enum Kind { kPath, kChecked, kSwitch };
+    const char* name;
+    Kind kind;
+    std::function<bool(const std::string&)> take;    // stores a good value and says yes; a kSwitch gets ""
+    std::string refusal;                              // "<name> takes ...", printed after "<prog>: "
+    Absent absent = kOptional;
+    bool given = false;                               // parse_flags: it took a value
+};
+
+// a path or a text that is not judged: --db, --output, --report, ...
+inline Flag path_flag(const char* name, std::string* out, Absent absent = kOptional) {
+    return {name, Flag::kPath, [out](const std::string& v) { return *out = v, true; }, "", absent};
+}
+// a text that must not be empty: --hashes, --list, --query
+inline Flag text_flag(const char* name, std::string* out, std::string refusal, Absent absent = kOptional) {
+    return {name, Flag::kChecked, [out](const std::string& v) { return v.empty() ? false : (*out = v, true); }, std::move(refusal), absent};
+}
+// a number that `ok` accepts
+inline Flag number_flag(const char* name, double* out, bool (*ok)(double), std::string refusal, Absent absent = kOptional) {
+    auto take = [out, ok](const std::string& v) {
+        double x = 0.0;
+        return parse_number(v, &x) && ok(x) ? (*out = x, true) : false;
+    };
+    return {name, Flag::kChecked, take, std::move(refusal), absent};
+}
+inline bool in_open_unit(double x) { return x > 0.0 && x < 1.0; }       // (0,1)
+inline bool in_half_open_unit(double x) { return x >= 0.0 && x < 1.0; }  // [0,1)
+inline bool not_nan(double x) { return !std::isnan(x); }
+inline bool positive_finite(double x) { return x > 0.0 && !std::isinf(x); }
+// a decimal integer in lo .. hi
+template <class T>
+Flag integer_flag(const char* name, T* out, long lo, long hi, std::string refusal, Absent absent = kOptional) {
+    auto take = [out, lo, hi](const std::string& v) {
+        long x = 0;
+        return parse_integer(v, &x) && x >= lo && x <= hi ? (*out = (T)x, true) : false;
+    };
+    return {name, Flag::kChecked, take, std::move(refusal), absent};
+}
+// one word of a list, each with the value it stands for
+template <class T>
+Flag word_flag(const char* name, T* out, std::vector<std::pair<std::string, T>> words, std::string refusal) {
+    auto take = [out, words](const std::string& v) {
+        for (const auto& w : words)
+            if (v == w.first) return *out = w.second, true;
+        return false;
+    };
+    return {name, Flag::kChecked, take, std::move(refusal), kOptional};
+}
+inline Flag device_flag(int* out) {
+    return {"--device", Flag::kChecked, [out](const std::string& v) { return parse_device(v, out); }, "--device takes a device index", kOptional};
+}
+// a flag without a value
+inline Flag switch_flag(const char* name, bool* out) {
+    return {name, Flag::kSwitch, [out](const std::string&) { return *out = true; }, "", kOptional};
+}
+// a value nobody else has: `take` judges and stores it
+inline Flag hook_flag(const char* name, std::function<bool(const std::string&)> take, std::string refusal) {
+    return {name, Flag::kChecked, std::move(take), std::move(refusal), kOptional};
+}
+inline bool was_given(const std::vector<Flag>& flags, const std::string& name) {
+    for (const Flag& f : flags)
+        if (name == f.name) return f.given;
+    return false;
+}
+
+// What parse_flags() found.  A tool's own rules across flags go between the parse and exit_code(): refuse() keeps the first
+// refusal, so a rule never speaks over a flag that was refused before it, and `usage = true` asks for the usage text.
+struct Args {
+    bool help = false, usage = false;
+    std::string refusal;
+    void refuse(const std::string& text) {
+        if (refusal.empty()) refusal = text;
+    }
+    // what main returns before it touches anything, or -1: go on
+    int exit_code(const char* prog, void (*print_usage)(const char*), const char* argv0) const {
+        if (help) return print_usage(argv0), 0;
+        if (!refusal.empty()) return std::cerr << prog << ": " << refusal << std::endl, 1;
+        if (usage) return print_usage(argv0), 1;
+        return -1;
+    }
+};
+
+// files != nullptr: an argument that is no flag and does not begin with "--" is an input file (sketch_sequences)
+inline Args parse_flags(int argc, char* argv[], std::vector<Flag>& flags, std::vector<std::string>* files = nullptr) {
+    Args args;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        const bool has_value = i + 1 < argc;
+        Flag* flag = nullptr;
+        for (Flag& f : flags)
+            if (a == f.name) flag = &f;
+        if (a == "--help") args.help = true;
+        else if (!flag && files && a.compare(0, 2, "--") != 0) files->push_back(a);
+        else if (!flag || (flag->kind == Flag::kPath && !has_value)) args.usage = true;
+        else if (flag->take(flag->kind != Flag::kSwitch && has_value ? argv[++i] : "")) flag->given = true;
+        else args.refuse(flag->refusal);
+    }
+    for (const Flag& f : flags) {
+        if (!f.given && f.absent == kRefuse) args.refuse(f.refusal);
+        if (!f.given && f.absent == kUsage) args.usage = true;
+    }
+    return args;
+}
+
+// ---- what a tool holds on the device ----
+// One object of the C ABI, destroyed with its holder.  A tool lists its holders as plain members of a struct and writes no
+// destructor.  THE ORDER OF THE MEMBERS MATTERS: members are destroyed in reverse order of declaration, and whatever was made on
+// a context -- device memory above all -- must go before the context does.  So the context is declared first, the sets next,
+// device memory after them, and what is built from those last.
+template <class T, int (*Destroy)(T*)>
+struct Owned {
+    T* p = nullptr;
+    Owned() = default;
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    ~Owned() { reset(); }
+    void reset() {
+        if (p) Destroy(p);
+        p = nullptr;
+    }
+    operator T*() const { return p; }
+    T** operator&() { return &p; }                    // where mvs_*_create and load_sketch_dbs put (and replace) the object
+};
+using OwnedCtx = Owned<mvs_ctx, mvs_ctx_destroy>;
+using OwnedSketchSet = Owned<mvs_sketch_set, mvs_sketch_set_destroy>;
+using OwnedHashSet = Owned<mvs_hash_set, mvs_hash_set_destroy>;
+
+// memory of mvs_device_alloc (not cleared), which is freed on the context it came from: declare it after that context
+struct DeviceMem {
+    mvs_ctx* ctx = nullptr;
+    void* p = nullptr;
+    DeviceMem() = default;
+    DeviceMem(const DeviceMem&) = delete;
+    DeviceMem& operator=(const DeviceMem&) = delete;
+    ~DeviceMem() { free(); }
+    int alloc(mvs_ctx* on, size_t bytes) {
+        free();
+        ctx = on;
+        return mvs_device_alloc(ctx, bytes, 0, &p);
+    }
+    void free() {
+        if (p) mvs_device_free(ctx, p);
+        p = nullptr;
+    }
+};
 
 // ---- errors and output ----
 inline int gpu_fail(const char* prog, const char* what) {

@@ -31,10 +31,9 @@ namespace {
 constexpr const char* kProg = "pca_sketches";
 
 struct Options {
-    std::string db_folder, output, axes, project, project_output, report, bad_flag;
+    std::string db_folder, output, axes, project, project_output, report;
     int components = 0, max_iters = 300, device = -1;
     double min_norm = 0.0, tol = 1e-10;
-    bool show_help = false, have_db = false, have_out = false, have_c = false, have_min_norm = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -46,60 +45,10 @@ void print_usage(const char* argv0) {
               << std::endl;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        std::string* text = a == "--db" ? &o.db_folder : a == "--output" ? &o.output : a == "--axes" ? &o.axes : a == "--project" ? &o.project
-                          : a == "--project_output" ? &o.project_output : a == "--report" ? &o.report : nullptr;
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (text) {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            *text = argv[++i];
-            if (a == "--db") o.have_db = true;
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--components") {
-            long v = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &v) || v < 1 || v > 64) bad("--components");
-            else o.components = (int)v, o.have_c = true;
-        } else if (a == "--max_iters") {
-            long v = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &v) || v < 1 || v > 1000000) bad("--max_iters");
-            else o.max_iters = (int)v;
-        } else if (a == "--min_norm") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.min_norm) || std::isnan(o.min_norm)) bad("--min_norm");
-            else o.have_min_norm = true;
-        } else if (a == "--tol") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.tol) || !(o.tol >= 0.0) || !(o.tol < 1.0)) bad("--tol");
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* set = nullptr;
-    mvs_sketch_set* fit = nullptr;
-    mvs_sketch_set* other = nullptr;
-    mvs_pca* pca = nullptr;
-    ~Gpu() {
-        if (pca) mvs_pca_destroy(pca);
-        if (other) mvs_sketch_set_destroy(other);
-        if (fit) mvs_sketch_set_destroy(fit);
-        if (set) mvs_sketch_set_destroy(set);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet set, fit, other;
+    Owned<mvs_pca, mvs_pca_destroy> pca;
 };
 
 }  // namespace
@@ -107,23 +56,23 @@ struct Gpu {
 int main(int argc, char* argv[]) {
     const auto wall0 = std::chrono::steady_clock::now();
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--components") std::cerr << kProg << ": --components takes an integer from 1 to 64" << std::endl;
-        else if (o.bad_flag == "--max_iters") std::cerr << kProg << ": --max_iters takes an integer of at least 1" << std::endl;
-        else if (o.bad_flag == "--min_norm") std::cerr << kProg << ": --min_norm takes a number" << std::endl;
-        else if (o.bad_flag == "--tol") std::cerr << kProg << ": --tol takes a number in [0, 1)" << std::endl;
-        else std::cerr << kProg << ": --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out || !o.have_c || o.project.empty() != o.project_output.empty()) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--axes", &o.axes),
+        path_flag("--project", &o.project),
+        path_flag("--project_output", &o.project_output),
+        path_flag("--report", &o.report),
+        integer_flag("--components", &o.components, 1, 64, "--components takes an integer from 1 to 64", kUsage),
+        integer_flag("--max_iters", &o.max_iters, 1, 1000000, "--max_iters takes an integer of at least 1"),
+        number_flag("--min_norm", &o.min_norm, not_nan, "--min_norm takes a number"),
+        number_flag("--tol", &o.tol, in_half_open_unit, "--tol takes a number in [0, 1)"),
+        device_flag(&o.device),
+    };
+    Args args = parse_flags(argc, argv, flags);
+    if (o.project.empty() != o.project_output.empty()) args.usage = true;    // both or neither
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
+    const bool have_min_norm = was_given(flags, "--min_norm");
     SketchDb sdb, pdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const int64_t n = sdb.n;
@@ -141,16 +90,16 @@ int main(int argc, char* argv[]) {
     }
     std::vector<char> fitted((size_t)n, 1);
     std::vector<int32_t> rows;
-    if (o.have_min_norm) {
+    if (have_min_norm) {
         const std::vector<double> norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
         for (int64_t i = 0; i < n; ++i) {
             fitted[(size_t)i] = i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm;
             if (fitted[(size_t)i]) rows.push_back((int32_t)i);
         }
     }
-    const int64_t n_fit = o.have_min_norm ? (int64_t)rows.size() : n;
+    const int64_t n_fit = have_min_norm ? (int64_t)rows.size() : n;
     if (n_fit < 2) {
-        std::cerr << kProg << ": " << n_fit << " samples to fit (a PCA needs at least two" << (o.have_min_norm ? "; lower --min_norm" : "") << ")"
+        std::cerr << kProg << ": " << n_fit << " samples to fit (a PCA needs at least two" << (have_min_norm ? "; lower --min_norm" : "") << ")"
                   << std::endl;
         return 1;
     }
@@ -160,7 +109,7 @@ int main(int argc, char* argv[]) {
     mvs_ctx_set_timing(g.ctx, 1);
     if (const int rc = load_sketch_db(kProg, g.ctx, sdb, &g.set)) return rc;
     const mvs_sketch_set* fit_set = g.set;
-    if (o.have_min_norm && n_fit < n) {
+    if (have_min_norm && n_fit < n) {
         if (mvs_sketch_set_gather(g.ctx, g.set, rows.data(), MVS_MEM_HOST, n_fit, &g.fit) != MVS_OK) return gpu_fail(kProg, "gathering the fitted samples");
         fit_set = g.fit;
     }

@@ -34,12 +34,11 @@ namespace {
 constexpr const char* kProg = "permanova_sketches";
 
 struct Options {
-    std::string db_folder, groups, output, perm_output, report, bad_flag;
+    std::string db_folder, groups, output, perm_output, report;
     long permutations = 999;
     unsigned long long seed = 0;
     int device = -1;
     double min_norm = 0.0, floor = 0.0;
-    bool show_help = false, have_db = false, have_out = false, have_groups = false, have_min_norm = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -56,48 +55,12 @@ inline std::string fmt17(double v) {
     return buf;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        std::string* text = a == "--db" ? &o.db_folder : a == "--groups" ? &o.groups : a == "--output" ? &o.output
-                          : a == "--perm_output" ? &o.perm_output : a == "--report" ? &o.report : nullptr;
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (text) {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            *text = argv[++i];
-            if (a == "--db") o.have_db = true;
-            if (a == "--groups") o.have_groups = true;
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--permutations") {
-            long v = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &v) || v < 0 || v > MVS_MAX_GROUP_SLOTS - 2) bad("--permutations");
-            else o.permutations = v;
-        } else if (a == "--seed") {
-            const std::string v = has_value ? argv[++i] : "";
-            char* end = nullptr;
-            errno = 0;
-            o.seed = strtoull(v.c_str(), &end, 10);
-            if (v.empty() || v[0] == '-' || end == v.c_str() || *end || errno) bad("--seed");
-        } else if (a == "--min_norm") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.min_norm) || std::isnan(o.min_norm)) bad("--min_norm");
-            else o.have_min_norm = true;
-        } else if (a == "--floor") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.floor) || !(o.floor >= 0.0) || !(o.floor < 1.0)) bad("--floor");
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
+// --seed: the whole string is a decimal integer below 2^64 without a sign
+bool parse_seed(const std::string& v, unsigned long long* out) {
+    char* end = nullptr;
+    errno = 0;
+    *out = strtoull(v.c_str(), &end, 10);
+    return !(v.empty() || v[0] == '-' || end == v.c_str() || *end || errno);
 }
 
 // name -> group of the --groups file; 0, or 1 after a message
@@ -125,14 +88,8 @@ int read_groups(const std::string& file, std::unordered_map<std::string, std::st
 }
 
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* loaded = nullptr;
-    mvs_sketch_set* labelled = nullptr;
-    ~Gpu() {
-        if (labelled) mvs_sketch_set_destroy(labelled);
-        if (loaded) mvs_sketch_set_destroy(loaded);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet loaded, labelled;
 };
 
 }  // namespace
@@ -140,23 +97,22 @@ struct Gpu {
 int main(int argc, char* argv[]) {
     const auto wall0 = std::chrono::steady_clock::now();
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--permutations") std::cerr << kProg << ": --permutations takes an integer from 0 to " << MVS_MAX_GROUP_SLOTS - 2 << std::endl;
-        else if (o.bad_flag == "--seed") std::cerr << kProg << ": --seed takes a non-negative integer below 2^64" << std::endl;
-        else if (o.bad_flag == "--min_norm") std::cerr << kProg << ": --min_norm takes a number" << std::endl;
-        else if (o.bad_flag == "--floor") std::cerr << kProg << ": --floor takes a number in [0, 1)" << std::endl;
-        else std::cerr << kProg << ": --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out || !o.have_groups) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--groups", &o.groups, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--perm_output", &o.perm_output),
+        path_flag("--report", &o.report),
+        integer_flag("--permutations", &o.permutations, 0, MVS_MAX_GROUP_SLOTS - 2,
+                     "--permutations takes an integer from 0 to " + std::to_string(MVS_MAX_GROUP_SLOTS - 2)),
+        hook_flag("--seed", [&o](const std::string& v) { return parse_seed(v, &o.seed); }, "--seed takes a non-negative integer below 2^64"),
+        number_flag("--min_norm", &o.min_norm, not_nan, "--min_norm takes a number"),
+        number_flag("--floor", &o.floor, in_half_open_unit, "--floor takes a number in [0, 1)"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
+    const bool have_min_norm = was_given(flags, "--min_norm");
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const int64_t n = sdb.n;
@@ -165,7 +121,7 @@ int main(int argc, char* argv[]) {
 
     // who takes part, and the group ids in order of first appearance
     std::vector<double> norms;
-    if (o.have_min_norm) norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
+    if (have_min_norm) norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
     std::vector<int32_t> order;
     std::vector<uint8_t> labels;
     std::vector<std::string> group_names;
@@ -179,7 +135,7 @@ int main(int argc, char* argv[]) {
             continue;
         }
         seen.insert(it->first);
-        if (o.have_min_norm && !(i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm)) {
+        if (have_min_norm && !(i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm)) {
             ++below_norm;
             continue;
         }
@@ -198,7 +154,7 @@ int main(int argc, char* argv[]) {
     const int64_t m = (int64_t)order.size(), G = (int64_t)group_names.size();
     if (G < 2) {
         std::cerr << kProg << ": " << G << " groups among the " << m << " samples that take part (PERMANOVA needs at least two"
-                  << (o.have_min_norm ? "; lower --min_norm" : "") << ")" << std::endl;
+                  << (have_min_norm ? "; lower --min_norm" : "") << ")" << std::endl;
         return 1;
     }
     if (G >= m) {
@@ -217,8 +173,7 @@ int main(int argc, char* argv[]) {
         if (mvs_sketch_set_gather(g.ctx, g.loaded, order.data(), MVS_MEM_HOST, m, &g.labelled) != MVS_OK)
             return gpu_fail(kProg, "gathering the labelled samples");
         set = g.labelled;
-        mvs_sketch_set_destroy(g.loaded);
-        g.loaded = nullptr;
+        g.loaded.reset();
     }
     mvs_permanova_result res{};
     std::vector<int64_t> sizes((size_t)G);

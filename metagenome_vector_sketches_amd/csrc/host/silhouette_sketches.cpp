@@ -36,11 +36,10 @@ namespace {
 constexpr const char* kProg = "silhouette_sketches";
 
 struct Options {
-    std::string db_folder, labels, output, clusters, report, bad_flag, noise = "-1";
+    std::string db_folder, labels, output, clusters, report, noise = "-1";
     long column = 2;
     int device = -1;
     double min_norm = 0.0, floor = 0.0;
-    bool show_help = false, have_db = false, have_out = false, have_labels = false, have_min_norm = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -56,44 +55,6 @@ inline std::string fmt17(double v) {
     char buf[64];
     snprintf(buf, sizeof buf, "%.17g", v);
     return buf;
-}
-
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        std::string* text = a == "--db" ? &o.db_folder : a == "--labels" ? &o.labels : a == "--output" ? &o.output : a == "--clusters" ? &o.clusters
-                          : a == "--report" ? &o.report : a == "--noise" ? &o.noise : nullptr;
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (text) {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            *text = argv[++i];
-            if (a == "--db") o.have_db = true;
-            if (a == "--labels") o.have_labels = true;
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--column") {
-            long v = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &v) || v < 1 || v > 1000000) bad("--column");
-            else o.column = v;
-        } else if (a == "--min_norm") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.min_norm) || std::isnan(o.min_norm)) bad("--min_norm");
-            else o.have_min_norm = true;
-        } else if (a == "--floor") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.floor) || !(o.floor >= 0.0) || !(o.floor < 1.0)) bad("--floor");
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
 }
 
 // name -> label text of the --labels file; 0, or 1 after a message
@@ -134,14 +95,8 @@ int read_labels(const std::string& file, long column, std::unordered_map<std::st
 }
 
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* loaded = nullptr;
-    mvs_sketch_set* kept = nullptr;
-    ~Gpu() {
-        if (kept) mvs_sketch_set_destroy(kept);
-        if (loaded) mvs_sketch_set_destroy(loaded);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet loaded, kept;
 };
 
 }  // namespace
@@ -149,22 +104,21 @@ struct Gpu {
 int main(int argc, char* argv[]) {
     const auto wall0 = std::chrono::steady_clock::now();
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--column") std::cerr << kProg << ": --column takes a field number, 1 or more" << std::endl;
-        else if (o.bad_flag == "--min_norm") std::cerr << kProg << ": --min_norm takes a number" << std::endl;
-        else if (o.bad_flag == "--floor") std::cerr << kProg << ": --floor takes a number in [0, 1)" << std::endl;
-        else std::cerr << kProg << ": --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out || !o.have_labels) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--labels", &o.labels, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--clusters", &o.clusters),
+        path_flag("--report", &o.report),
+        path_flag("--noise", &o.noise),
+        integer_flag("--column", &o.column, 1, 1000000, "--column takes a field number, 1 or more"),
+        number_flag("--min_norm", &o.min_norm, not_nan, "--min_norm takes a number"),
+        number_flag("--floor", &o.floor, in_half_open_unit, "--floor takes a number in [0, 1)"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
+    const bool have_min_norm = was_given(flags, "--min_norm");
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const int64_t n = sdb.n;
@@ -173,7 +127,7 @@ int main(int argc, char* argv[]) {
 
     // who takes part, and the group ids in order of first appearance
     std::vector<double> norms;
-    if (o.have_min_norm) norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
+    if (have_min_norm) norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
     std::vector<int32_t> order, labels;
     std::vector<std::string> group_names;
     std::unordered_map<std::string, int32_t> id_of;
@@ -182,7 +136,7 @@ int main(int argc, char* argv[]) {
     for (int64_t i = 0; i < n; ++i) {
         const auto it = label_of.find(sdb.info.names[(size_t)i]);
         if (it != label_of.end()) seen.insert(it->first);
-        if (o.have_min_norm && !(i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm)) {
+        if (have_min_norm && !(i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm)) {
             ++below_norm;
             continue;
         }
@@ -203,7 +157,7 @@ int main(int argc, char* argv[]) {
     const int64_t m = (int64_t)order.size(), G = (int64_t)group_names.size();
     if (G < 2) {
         std::cerr << kProg << ": " << G << " groups among the " << m << " samples that take part (a silhouette needs at least two"
-                  << (o.have_min_norm ? "; lower --min_norm" : "") << ")" << std::endl;
+                  << (have_min_norm ? "; lower --min_norm" : "") << ")" << std::endl;
         return 1;
     }
     std::vector<double> norms_sq((size_t)m);
@@ -218,8 +172,7 @@ int main(int argc, char* argv[]) {
         if (mvs_sketch_set_gather(g.ctx, g.loaded, order.data(), MVS_MEM_HOST, m, &g.kept) != MVS_OK)
             return gpu_fail(kProg, "gathering the samples that take part");
         set = g.kept;
-        mvs_sketch_set_destroy(g.loaded);
-        g.loaded = nullptr;
+        g.loaded.reset();
     }
     mvs_silhouette_result res{};
     std::vector<int64_t> sizes((size_t)G), medoids((size_t)G);

@@ -28,11 +28,11 @@ namespace {
 constexpr const char* kProg = "sketch_sequences";
 
 struct Options {
-    std::string output, report, list, bad_flag;
+    std::string output, report, list;
     std::vector<std::string> files;
     long ksize = 31, scaled = 1000, seed = 42, batch_bytes = 1L << 30;
     int device = -1;
-    bool singleton = false, show_help = false, have_out = false, unknown = false;
+    bool singleton = false;
 };
 
 void print_usage(const char* argv0) {
@@ -48,58 +48,9 @@ void print_usage(const char* argv0) {
               << std::endl;
 }
 
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        auto integer = [&](const char* flag, long lo, long hi, long* out) {
-            long v = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &v) || v < lo || v > hi) bad(flag);
-            else *out = v;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--singleton") {
-            o.singleton = true;
-        } else if (a == "--output" || a == "--report") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            (a == "--output" ? o.output : o.report) = argv[++i];
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--list") {
-            const std::string v = has_value ? argv[++i] : "";
-            if (v.empty()) bad("--list");
-            else o.list = v;
-        } else if (a == "--ksize") {
-            integer("--ksize", 1, 32, &o.ksize);
-        } else if (a == "--scaled") {
-            integer("--scaled", 1, 0x7fffffffffffffffL, &o.scaled);
-        } else if (a == "--seed") {
-            integer("--seed", 0, 4294967295L, &o.seed);
-        } else if (a == "--batch_bytes") {
-            integer("--batch_bytes", 1, 0x7fffffffffffffffL, &o.batch_bytes);
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else if (a.size() > 1 && a[0] == '-' && a[1] == '-') {
-            o.unknown = true;
-        } else {
-            o.files.push_back(a);
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_hash_set* hs = nullptr;
-    ~Gpu() {
-        if (hs) mvs_hash_set_destroy(hs);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedHashSet hs;
 };
 
 struct Sample {
@@ -116,24 +67,20 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 
 int main(int argc, char* argv[]) {
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--ksize") std::cerr << kProg << ": --ksize takes an integer from 1 to 32" << std::endl;
-        else if (o.bad_flag == "--scaled") std::cerr << kProg << ": --scaled takes an integer >= 1" << std::endl;
-        else if (o.bad_flag == "--seed") std::cerr << kProg << ": --seed takes an integer from 0 to 4294967295" << std::endl;
-        else if (o.bad_flag == "--batch_bytes") std::cerr << kProg << ": --batch_bytes takes an integer >= 1" << std::endl;
-        else if (o.bad_flag == "--list") std::cerr << kProg << ": --list takes a file of input paths, one per line" << std::endl;
-        else std::cerr << kProg << ": --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_out || (o.files.empty() && o.list.empty())) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--report", &o.report),
+        switch_flag("--singleton", &o.singleton),
+        text_flag("--list", &o.list, "--list takes a file of input paths, one per line"),
+        integer_flag("--ksize", &o.ksize, 1, 32, "--ksize takes an integer from 1 to 32"),
+        integer_flag("--scaled", &o.scaled, 1, LONG_MAX, "--scaled takes an integer >= 1"),
+        integer_flag("--seed", &o.seed, 0, 4294967295L, "--seed takes an integer from 0 to 4294967295"),
+        integer_flag("--batch_bytes", &o.batch_bytes, 1, LONG_MAX, "--batch_bytes takes an integer >= 1"),
+        device_flag(&o.device),
+    };
+    Args args = parse_flags(argc, argv, flags, &o.files);
+    if (o.files.empty() && o.list.empty()) args.usage = true;     // nothing to sketch
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     if (!o.list.empty()) {
         std::ifstream in(o.list);
         if (!in) {
@@ -239,8 +186,7 @@ int main(int argc, char* argv[]) {
                 sm.kept = kept[(size_t)s];
                 sm.hashes.assign(flat.begin() + off[(size_t)s], flat.begin() + off[(size_t)s + 1]);
             }
-            mvs_hash_set_destroy(g.hs);
-            g.hs = nullptr;
+            g.hs.reset();
             export_s += seconds_since(t_export);
             ++batches;
             s0 = s1;

@@ -27,12 +27,11 @@ namespace {
 constexpr const char* kProg = "tsne_sketches";
 
 struct Options {
-    std::string db_folder, output, report, bad_flag;
+    std::string db_folder, output, report;
     double perplexity = 30.0, exaggeration = 12.0, learning_rate = 0.0, min_norm = 0.0;
     long neighbours = 0, iterations = 750, exaggeration_iters = 250, init = MVS_TSNE_INIT_PCOA;
     unsigned long long seed = 0;
     int device = -1;
-    bool show_help = false, have_db = false, have_out = false, have_min_norm = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -50,70 +49,9 @@ std::string fmt17(double v) {
     return buf;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        std::string* text = a == "--db" ? &o.db_folder : a == "--output" ? &o.output : a == "--report" ? &o.report : nullptr;
-        long* count = a == "--iterations" ? &o.iterations : a == "--exaggeration_iters" ? &o.exaggeration_iters : nullptr;
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (text) {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            *text = argv[++i];
-            if (a == "--db") o.have_db = true;
-            if (a == "--output") o.have_out = true;
-        } else if (count) {
-            long v = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &v) || v < 0 || v > 1000000) bad(a == "--iterations" ? "--iterations" : "--exaggeration_iters");
-            else *count = v;
-        } else if (a == "--neighbours") {
-            long v = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &v) || v < 1 || v > 256) bad("--neighbours");
-            else o.neighbours = v;
-        } else if (a == "--seed") {
-            long v = 0;
-            if (!parse_integer(has_value ? argv[++i] : "", &v) || v < 0) bad("--seed");
-            else o.seed = (unsigned long long)v;
-        } else if (a == "--perplexity") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.perplexity) || !(o.perplexity >= 1.0) || !(o.perplexity <= 256.0)) bad("--perplexity");
-        } else if (a == "--exaggeration") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.exaggeration) || !(o.exaggeration > 0.0) || std::isinf(o.exaggeration)) bad("--exaggeration");
-        } else if (a == "--learning_rate") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.learning_rate) || !(o.learning_rate > 0.0) || std::isinf(o.learning_rate))
-                bad("--learning_rate");
-        } else if (a == "--min_norm") {
-            if (!parse_number(has_value ? argv[++i] : "", &o.min_norm) || std::isnan(o.min_norm)) bad("--min_norm");
-            else o.have_min_norm = true;
-        } else if (a == "--init") {
-            const std::string v = has_value ? argv[++i] : "";
-            if (v == "pcoa") o.init = MVS_TSNE_INIT_PCOA;
-            else if (v == "random") o.init = MVS_TSNE_INIT_RANDOM;
-            else bad("--init");
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* loaded = nullptr;
-    mvs_sketch_set* kept = nullptr;
-    ~Gpu() {
-        if (kept) mvs_sketch_set_destroy(kept);
-        if (loaded) mvs_sketch_set_destroy(loaded);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet loaded, kept;
 };
 
 }  // namespace
@@ -121,28 +59,24 @@ struct Gpu {
 int main(int argc, char* argv[]) {
     const auto wall0 = std::chrono::steady_clock::now();
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--perplexity") std::cerr << kProg << ": --perplexity takes a number from 1 to 256" << std::endl;
-        else if (o.bad_flag == "--neighbours") std::cerr << kProg << ": --neighbours takes an integer from 1 to 256" << std::endl;
-        else if (o.bad_flag == "--iterations" || o.bad_flag == "--exaggeration_iters")
-            std::cerr << kProg << ": " << o.bad_flag << " takes an integer from 0 to 1000000" << std::endl;
-        else if (o.bad_flag == "--exaggeration" || o.bad_flag == "--learning_rate")
-            std::cerr << kProg << ": " << o.bad_flag << " takes a positive number" << std::endl;
-        else if (o.bad_flag == "--seed") std::cerr << kProg << ": --seed takes a non-negative integer" << std::endl;
-        else if (o.bad_flag == "--min_norm") std::cerr << kProg << ": --min_norm takes a number" << std::endl;
-        else if (o.bad_flag == "--init") std::cerr << kProg << ": --init takes pcoa or random" << std::endl;
-        else std::cerr << kProg << ": --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--report", &o.report),
+        integer_flag("--iterations", &o.iterations, 0, 1000000, "--iterations takes an integer from 0 to 1000000"),
+        integer_flag("--exaggeration_iters", &o.exaggeration_iters, 0, 1000000, "--exaggeration_iters takes an integer from 0 to 1000000"),
+        integer_flag("--neighbours", &o.neighbours, 1, 256, "--neighbours takes an integer from 1 to 256"),
+        integer_flag("--seed", &o.seed, 0, LONG_MAX, "--seed takes a non-negative integer"),
+        number_flag("--perplexity", &o.perplexity, [](double p) { return p >= 1.0 && p <= 256.0; }, "--perplexity takes a number from 1 to 256"),
+        number_flag("--exaggeration", &o.exaggeration, positive_finite, "--exaggeration takes a positive number"),
+        number_flag("--learning_rate", &o.learning_rate, positive_finite, "--learning_rate takes a positive number"),
+        number_flag("--min_norm", &o.min_norm, not_nan, "--min_norm takes a number"),
+        word_flag("--init", &o.init, {{"pcoa", MVS_TSNE_INIT_PCOA}, {"random", MVS_TSNE_INIT_RANDOM}}, "--init takes pcoa or random"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
+    const bool have_min_norm = was_given(flags, "--min_norm");
     const long K = o.neighbours > 0 ? o.neighbours : (long)std::ceil(3.0 * o.perplexity);
     if (K > 256) {
         std::cerr << kProg << ": --perplexity " << fmt9(o.perplexity) << " asks for " << K << " neighbours, top-k holds 256 (give --neighbours)" << std::endl;
@@ -156,7 +90,7 @@ int main(int argc, char* argv[]) {
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const int64_t n = sdb.n;
     std::vector<char> fitted((size_t)n, 1);
-    if (o.have_min_norm) {
+    if (have_min_norm) {
         const std::vector<double> norms = read_plain_norms(o.db_folder + "vector_norms.txt", n);
         for (int64_t i = 0; i < n; ++i) fitted[(size_t)i] = i < (int64_t)norms.size() && norms[(size_t)i] >= o.min_norm;
     }
@@ -167,7 +101,7 @@ int main(int argc, char* argv[]) {
     const int64_t need = o.init == MVS_TSNE_INIT_PCOA ? 3 : 1;
     if (n_fit < need) {
         std::cerr << kProg << ": " << n_fit << " samples to map (--init " << (o.init == MVS_TSNE_INIT_PCOA ? "pcoa" : "random") << " needs at least " << need
-                  << (o.have_min_norm ? "; lower --min_norm" : "") << ")" << std::endl;
+                  << (have_min_norm ? "; lower --min_norm" : "") << ")" << std::endl;
         return 1;
     }
     if (n_fit > (1LL << 21)) {
@@ -185,8 +119,7 @@ int main(int argc, char* argv[]) {
     if (n_fit < n) {
         if (mvs_sketch_set_gather(g.ctx, g.loaded, order.data(), MVS_MEM_HOST, n_fit, &g.kept) != MVS_OK) return gpu_fail(kProg, "selecting the samples");
         set = g.kept;
-        mvs_sketch_set_destroy(g.loaded);
-        g.loaded = nullptr;
+        g.loaded.reset();
     }
     mvs_tsne_params p;
     p.perplexity = o.perplexity;

@@ -28,10 +28,9 @@ namespace {
 constexpr const char* kProg = "verify_pairs";
 
 struct Options {
-    std::string db_folder, hash_file, output, report, bad_flag;
+    std::string db_folder, hash_file, output, report;
     double min_jaccard = 0.0, exact_min = -1.0;
     int device = -1;
-    bool show_help = false, have_db = false, have_t = false, have_out = false, have_hashes = false, unknown = false;
 };
 
 void print_usage(const char* argv0) {
@@ -42,63 +41,11 @@ void print_usage(const char* argv0) {
               << std::endl;
 }
 
-// bad_flag: the first flag whose value is missing, unparsable or out of range (reported before anything is touched)
-void parse(int argc, char* argv[], Options& o) {
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        const bool has_value = i + 1 < argc;
-        auto bad = [&](const char* flag) {
-            if (o.bad_flag.empty()) o.bad_flag = flag;
-        };
-        if (a == "--help") {
-            o.show_help = true;
-        } else if (a == "--db" || a == "--output" || a == "--report") {
-            if (!has_value) {
-                o.unknown = true;
-                continue;
-            }
-            (a == "--db" ? o.db_folder : a == "--output" ? o.output : o.report) = argv[++i];
-            if (a == "--db") o.have_db = true;
-            if (a == "--output") o.have_out = true;
-        } else if (a == "--hashes") {
-            o.have_hashes = true;
-            const std::string v = has_value ? argv[++i] : "";
-            if (v.empty()) bad("--hashes");
-            else o.hash_file = v;
-        } else if (a == "--min_jaccard") {
-            o.have_t = true;
-            double t = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &t) || !(t > 0.0) || !(t < 1.0)) bad("--min_jaccard");
-            else o.min_jaccard = t;
-        } else if (a == "--exact_min") {
-            double u = 0.0;
-            if (!parse_number(has_value ? argv[++i] : "", &u) || !(u >= 0.0) || !(u < 1.0)) bad("--exact_min");
-            else o.exact_min = u;
-        } else if (a == "--device") {
-            if (!parse_device(has_value ? argv[++i] : "", &o.device)) bad("--device");
-        } else {
-            o.unknown = true;
-        }
-    }
-}
-
 struct Gpu {
-    mvs_ctx* ctx = nullptr;
-    mvs_sketch_set* set = nullptr;
-    mvs_hash_set* hs = nullptr;
-    void* d_norms = nullptr;
-    void* d_cells = nullptr;
-    void* d_inter = nullptr;
-    ~Gpu() {
-        if (ctx) {
-            if (d_norms) mvs_device_free(ctx, d_norms);
-            if (d_cells) mvs_device_free(ctx, d_cells);
-            if (d_inter) mvs_device_free(ctx, d_inter);
-        }
-        if (hs) mvs_hash_set_destroy(hs);
-        if (set) mvs_sketch_set_destroy(set);
-        if (ctx) mvs_ctx_destroy(ctx);
-    }
+    OwnedCtx ctx;
+    OwnedSketchSet set;
+    OwnedHashSet hs;
+    DeviceMem d_inter, d_cells, d_norms;
 };
 
 struct Pair {
@@ -119,24 +66,17 @@ double ratio(double num, double den) { return den == 0.0 ? std::nan("") : num / 
 int main(int argc, char* argv[]) {
     const auto wall_begin = std::chrono::steady_clock::now();
     Options o;
-    parse(argc, argv, o);
-    if (o.show_help) {
-        print_usage(argv[0]);
-        return 0;
-    }
-    if (!o.have_t && o.bad_flag.empty()) o.bad_flag = "--min_jaccard";
-    if (!o.have_hashes && o.bad_flag.empty()) o.bad_flag = "--hashes";
-    if (!o.bad_flag.empty()) {
-        if (o.bad_flag == "--min_jaccard") std::cerr << "verify_pairs: --min_jaccard takes a number in the open range (0,1)" << std::endl;
-        else if (o.bad_flag == "--hashes") std::cerr << "verify_pairs: --hashes takes the hash file the DB was sketched from" << std::endl;
-        else if (o.bad_flag == "--exact_min") std::cerr << "verify_pairs: --exact_min takes a number in the range [0,1)" << std::endl;
-        else std::cerr << "verify_pairs: --device takes a device index" << std::endl;
-        return 1;
-    }
-    if (o.unknown || !o.have_db || !o.have_out) {
-        print_usage(argv[0]);
-        return 1;
-    }
+    std::vector<Flag> flags = {                                   // absent: --min_jaccard speaks before --hashes
+        path_flag("--db", &o.db_folder, kUsage),
+        path_flag("--output", &o.output, kUsage),
+        path_flag("--report", &o.report),
+        number_flag("--min_jaccard", &o.min_jaccard, in_open_unit, "--min_jaccard takes a number in the open range (0,1)", kRefuse),
+        text_flag("--hashes", &o.hash_file, "--hashes takes the hash file the DB was sketched from", kRefuse),
+        number_flag("--exact_min", &o.exact_min, in_half_open_unit, "--exact_min takes a number in the range [0,1)"),
+        device_flag(&o.device),
+    };
+    const Args args = parse_flags(argc, argv, flags);
+    if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     SketchDb sdb;
     if (const int rc = open_sketch_db(o.db_folder, sdb)) return rc;
     const DbInfo& db = sdb.info;
@@ -157,8 +97,8 @@ int main(int argc, char* argv[]) {
         if (mvs_hash_set_create(g.ctx, sets.hashes.data(), MVS_MEM_HOST, sets.offsets.data(), n, &g.hs) != MVS_OK)
             return gpu_fail(kProg, "uploading the hash lists");
         if (mvs_hash_set_sizes(g.hs, sizes.data(), MVS_MEM_HOST) != MVS_OK) return gpu_fail(kProg, "reading the set sizes");
-        if (mvs_device_alloc(g.ctx, (size_t)n * 8, 0, &g.d_norms) != MVS_OK ||
-            mvs_device_copy(g.ctx, g.d_norms, MVS_MEM_DEVICE, db.norms_sq.data(), MVS_MEM_HOST, (size_t)n * 8) != MVS_OK)
+        if (g.d_norms.alloc(g.ctx, (size_t)n * 8) != MVS_OK ||
+            mvs_device_copy(g.ctx, g.d_norms.p, MVS_MEM_DEVICE, db.norms_sq.data(), MVS_MEM_HOST, (size_t)n * 8) != MVS_OK)
             return gpu_fail(kProg, "uploading the norms");
         // row blocks of the search comparison; a block that keeps more than the buffer holds reports what it needs
         const int64_t block_rows = std::max<int64_t>(256, std::min<int64_t>(n, (1LL << 28) / std::max<int64_t>(n, 1) / 256 * 256));
@@ -169,28 +109,25 @@ int main(int argc, char* argv[]) {
             const int64_t re = std::min(n, rb + block_rows);
             if (capacity == 0) {
                 capacity = 1 << 20;
-                if (mvs_device_alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK ||
-                    mvs_device_alloc(g.ctx, (size_t)capacity * 4, 0, &g.d_inter) != MVS_OK)
+                if (g.d_cells.alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell)) != MVS_OK || g.d_inter.alloc(g.ctx, (size_t)capacity * 4) != MVS_OK)
                     return gpu_fail(kProg, "allocating the cell buffers");
             }
             int64_t count = 0;
-            const int src = mvs_search_block(g.ctx, g.set, (const double*)g.d_norms, o.min_jaccard, rb, re, 0, n, (mvs_cell*)g.d_cells,
+            const int src = mvs_search_block(g.ctx, g.set, (const double*)g.d_norms.p, o.min_jaccard, rb, re, 0, n, (mvs_cell*)g.d_cells.p,
                                              capacity, &count);
             float ms = 0.f;
             if (mvs_ctx_kernel_ms(g.ctx, 1, &ms) == MVS_OK) compare_ms += ms;
             if (src == MVS_E_CAPACITY) {
-                mvs_device_free(g.ctx, g.d_cells);
-                mvs_device_free(g.ctx, g.d_inter);
-                g.d_cells = g.d_inter = nullptr;
+                g.d_cells.free();
+                g.d_inter.free();
                 capacity = count + count / 8 + 1024;
-                if (mvs_device_alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell), 0, &g.d_cells) != MVS_OK ||
-                    mvs_device_alloc(g.ctx, (size_t)capacity * 4, 0, &g.d_inter) != MVS_OK)
+                if (g.d_cells.alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell)) != MVS_OK || g.d_inter.alloc(g.ctx, (size_t)capacity * 4) != MVS_OK)
                     return gpu_fail(kProg, "allocating the cell buffers");
                 continue;
             }
             if (src != MVS_OK) return gpu_fail(kProg, "comparing");
             if (count > 0) {
-                if (mvs_intersect_cells(g.ctx, g.hs, nullptr, (const mvs_cell*)g.d_cells, MVS_MEM_DEVICE, count, (int32_t*)g.d_inter,
+                if (mvs_intersect_cells(g.ctx, g.hs, nullptr, (const mvs_cell*)g.d_cells.p, MVS_MEM_DEVICE, count, (int32_t*)g.d_inter.p,
                                         MVS_MEM_DEVICE) != MVS_OK)
                     return gpu_fail(kProg, "intersecting");
                 double kms = 0.0;
@@ -198,8 +135,8 @@ int main(int argc, char* argv[]) {
                 intersect_ms += kms;
                 cells.resize((size_t)count);
                 inter.resize((size_t)count);
-                if (mvs_device_copy(g.ctx, cells.data(), MVS_MEM_HOST, g.d_cells, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_cell)) != MVS_OK ||
-                    mvs_device_copy(g.ctx, inter.data(), MVS_MEM_HOST, g.d_inter, MVS_MEM_DEVICE, (size_t)count * 4) != MVS_OK)
+                if (mvs_device_copy(g.ctx, cells.data(), MVS_MEM_HOST, g.d_cells.p, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_cell)) != MVS_OK ||
+                    mvs_device_copy(g.ctx, inter.data(), MVS_MEM_HOST, g.d_inter.p, MVS_MEM_DEVICE, (size_t)count * 4) != MVS_OK)
                     return gpu_fail(kProg, "downloading");
                 for (int64_t i = 0; i < count; ++i)                    // sorted by (row, col) inside a block, blocks ascend
                     if (cells[(size_t)i].row < cells[(size_t)i].col)
