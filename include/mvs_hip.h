@@ -175,7 +175,12 @@ int mvs_ctx_kernel_ms(mvs_ctx* ctx, int which, float* ms);
  *   kmer_unit             mvs_hash_set_from_sequences: k-mer positions of one sample that one unit of work (one workgroup)
  *                         covers, 64 .. 32768 (default 17408); a longer sample is cut into several units
  *   kmer_capacity         mvs_hash_set_from_sequences: > 0 = the values the staging list of the first hashing pass holds (tests
- *                         lower it to force the second pass); 0 (default) = the expected number of kept values plus a margin
+ *                         lower it to force the second pass); 0 (default) = the expected number of kept values plus a margin.
+ *                         Both act per call of mvs_kmer_sketcher_add too
+ *   abund_unit            counted set build (mvs_hash_set_create_counted, mvs_kmer_sketcher_finish): sorted values that one unit
+ *                         of work (one wave) of the run-sum passes covers, 64 .. 2^20 (default 4096)
+ *   abund_big_segment     counted set build: a sample of more values than this is sorted by a device-wide radix sort of its own,
+ *                         the others by the segmented sort, 64 .. 2^30 (default 262144).  Neither has an environment default
  *   stream_block_rows, encode_stage_words, pairwise_map, coarse_radix, cand_regions, recheck_mode, recheck_blocks
  *                         test / experiment switches (DESIGN.md, appendix "switches"; encode_stage_words below 64 also keeps
  *                         every row on the device encoder's general loop)
@@ -951,6 +956,88 @@ int mvs_hash_set_device(const mvs_hash_set* set, const uint64_t** d_hashes);
 int mvs_ctx_kmer_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* bases, int64_t* kmers, int64_t* kept, int64_t* units,
                        int64_t* second_trips);
 int mvs_ctx_kmer_sample_stats(const mvs_ctx* ctx, int64_t n_samples, int64_t* kmers, int64_t* kept);
+
+/* ---- abundances: read sets, k-mer counts, a minimum count ----------------------------------------------------------------------
+ * A metagenome sample is a read set, and in raw reads most distinct k-mers are sequencing errors seen once.  These calls count
+ * how often every kept value occurs in a sample, whatever the number of calls the sample's bases arrive in, and build the set
+ * from the values whose count passes a filter.  Bases, breaks, the canonical k-mer, the hash, max_hash and 1 <= ksize <= 32 are
+ * exactly those of "sketches from sequences" above.
+ *
+ *   Pieces.  A PIECE is a byte string that belongs to a sample index.  No k-mer spans two pieces: the caller cuts at record
+ *     borders.  The pieces of a sample may arrive in any number of calls, in any order, mixed with other samples' pieces.
+ *   Abundance.  M(s) is the multiset of the kept values h <= max_hash over all valid positions of all pieces of sample s; the
+ *     abundance a_s(h) is the multiplicity of h in M(s).
+ *   Finish(min_abundance >= 1, max_abundance; 0 = no cap) returns a hash set: sample s holds, ascending, the h with
+ *     min_abundance <= a_s(h), and a_s(h) <= max_abundance if max_abundance > 0.  The set carries a uint32 abundance per value,
+ *     aligned with the values.  With min_abundance = 1 and max_abundance = 0 the values equal mvs_hash_set_from_sequences of
+ *     the same samples bit for bit.
+ *   Histogram (optional, a HOST int64[n_samples][256]): bin b counts the distinct h of sample s with min(a_s(h), 255) == b,
+ *     BEFORE the filter.  Bin 0 is always 0.
+ *   Weights.  The same rule applies to arbitrary hash lists with optional uint32 weights (mvs_hash_set_create_counted): the
+ *     abundance of a value is the sum of the weights of its occurrences in the sample, 1 each without weights.  A sum >= 2^32
+ *     is MVS_E_RANGE.  A value whose weights sum to 0 counts as absent: it is no distinct value, has no histogram bin and is
+ *     never kept.  Values are arbitrary 64-bit words: 0 and 2^64 - 1 are ordinary values, there is no sentinel.
+ *   Invariance.  Exact and deterministic: the result does not depend on the options, the units of work, the cutting into pieces
+ *     and calls, the arrival order, or where the bytes lie.
+ *
+ * mvs_kmer_sketcher_create   a sketcher for n_samples samples (all empty).  ksize outside 1 .. 32, n_samples < 0: MVS_E_INVALID.
+ * mvs_kmer_sketcher_add      n_pieces pieces: piece i is bytes [offsets[i], offsets[i + 1]) of `bases` (`mem_bases` says where
+ *                       they lie; offsets: n_pieces + 1 HOST int64, non-decreasing) and belongs to sample samples[i] (HOST
+ *                       int32).  n_pieces = 0, empty pieces and pieces shorter than ksize are fine.  The call runs the hashing
+ *                       kernel of mvs_hash_set_from_sequences over the pieces -- a piece is laid out in units of option
+ *                       kmer_unit exactly as a sample is there, options kmer_capacity and the second trip act per call -- and
+ *                       appends the kept (value, sample) pairs to a staging list on the device that lives as long as the
+ *                       sketcher and grows geometrically (by a device copy).  Synchronous: `bases` may be reused on return.
+ *                       Refused, with nothing allocated and nothing appended: NULL where a pointer is needed, decreasing
+ *                       offsets, a finished sketcher (MVS_E_INVALID); a sample index outside [0, n_samples) (MVS_E_RANGE).
+ *                       NOT a clean refusal: a sample whose |M(s)| reaches 2^31 makes that add fail with MVS_E_RANGE after
+ *                       its pairs were staged; the sketcher can then only be destroyed (every later add / finish:
+ *                       MVS_E_INVALID).
+ * mvs_kmer_sketcher_finish   the set described above (destroy it with mvs_hash_set_destroy; it outlives the sketcher) and, if
+ *                       `histogram` is not NULL, the histogram.  The pairs are moved to their samples' ranges and handed to
+ *                       the counted build below.  min_abundance = 0, 0 < max_abundance < min_abundance, NULL `set`: MVS_E_INVALID
+ *                       and the sketcher stays as it was.  A second finish, or an add after it: MVS_E_INVALID.
+ * mvs_kmer_sketcher_stats    per sample, n_samples HOST int64 each, any may be NULL: bytes given, valid positions, values kept
+ *                       (= |M(s)|), and after finish the distinct values and those that passed the filter (0 before).
+ * mvs_kmer_sketcher_info     what the sketcher's calls did so far, any pointer may be NULL: time of the hashing passes and of finish's
+ *                       move into sample order (0 unless mvs_ctx_set_timing is on), pairs staged, pairs the list has room for (0
+ *                       after finish), adds that hashed something, hashing passes repeated for more room, times the list grew.
+ *                       The sketcher keeps these itself: mvs_ctx_kmer_stats stays what the last mvs_hash_set_from_sequences left.
+ * mvs_kmer_sketcher_destroy  frees the staging list.  NULL is fine.
+ * mvs_hash_set_create_counted
+ *                       the counted build for hash lists: hashes / offsets as for mvs_hash_set_create (any order, duplicates
+ *                       welcome), weights aligned with the hashes where `mem_weights` says, or NULL.  Refusals as for
+ *                       mvs_hash_set_create plus the filter's.  How: a sort inside every sample -- samples of up to option
+ *                       abund_big_segment values (default 262144, >= 64) in batches through the segmented radix sort, each
+ *                       longer one by a device-wide radix sort of its own --, then four passes over units of option
+ *                       abund_unit sorted values (default 4096, >= 64), one wave each, whose work depends neither on the
+ *                       length of a sample nor on the length of a run of equal values: per-unit summaries, a segmented scan
+ *                       of them, count + histogram, scan, fill.  Equal values on both sides of a sample border are two runs.
+ *                       Neither option changes a result.  Synchronous.
+ * mvs_hash_set_abundances    the abundances of a counted set, aligned with mvs_hash_set_export's values, where `mem_out` says.
+ *                       MVS_E_INVALID for a set that carries none (made by mvs_hash_set_create / _from_sequences).  To
+ *                       mvs_intersect_cells, mvs_gather, mvs_hash_set_export and mvs_hash_set_device a counted set is the
+ *                       plain set it also is.
+ * mvs_ctx_abund_stats   the context's last counted build: time of its sorts and of its run-sum passes (0 unless
+ *                       mvs_ctx_set_timing is on), values given, distinct values, values that passed, units of the run-sum
+ *                       passes, samples sorted device-wide.  Any pointer may be NULL. */
+typedef struct mvs_kmer_sketcher mvs_kmer_sketcher;
+int mvs_kmer_sketcher_create(mvs_ctx* ctx, int64_t n_samples, int ksize, uint32_t seed, uint64_t max_hash, mvs_kmer_sketcher** sketcher);
+int mvs_kmer_sketcher_add(mvs_kmer_sketcher* sketcher, const uint8_t* bases, int mem_bases, const int64_t* offsets, const int32_t* samples,
+                          int64_t n_pieces);
+int mvs_kmer_sketcher_finish(mvs_kmer_sketcher* sketcher, uint32_t min_abundance, uint32_t max_abundance, int64_t* histogram,
+                             mvs_hash_set** set);
+int mvs_kmer_sketcher_stats(const mvs_kmer_sketcher* sketcher, int64_t* bases, int64_t* kmers, int64_t* kept, int64_t* distinct,
+                            int64_t* passed);
+int mvs_kmer_sketcher_info(const mvs_kmer_sketcher* sketcher, double* kernel_ms, int64_t* staged, int64_t* capacity, int64_t* adds,
+                           int64_t* second_trips, int64_t* growths);
+int mvs_kmer_sketcher_destroy(mvs_kmer_sketcher* sketcher);
+int mvs_hash_set_create_counted(mvs_ctx* ctx, const uint64_t* hashes, int mem_hashes, const uint32_t* weights, int mem_weights,
+                                const int64_t* offsets, int64_t n_samples, uint32_t min_abundance, uint32_t max_abundance,
+                                int64_t* histogram, mvs_hash_set** set);
+int mvs_hash_set_abundances(const mvs_hash_set* set, uint32_t* out, int mem_out);
+int mvs_ctx_abund_stats(const mvs_ctx* ctx, double* sort_ms, double* count_ms, int64_t* values_in, int64_t* distinct, int64_t* passed,
+                        int64_t* units, int64_t* big_segments);
 
 /* ---- gather: the greedy decomposition of a query into samples of a hash set -------------------------------------------------
  * Everything above asks about a PAIR of samples.  This call answers the set question "which DB samples make up my sample, and

@@ -241,6 +241,15 @@ SYMBOLS = [
     ("mvs_hash_set_device", _c.c_int, [_P, _c.POINTER(_P)]),
     ("mvs_ctx_kmer_stats", _c.c_int, [_P, _c.POINTER(_c.c_double)] + [_c.POINTER(_c.c_int64)] * 5),
     ("mvs_ctx_kmer_sample_stats", _c.c_int, [_P, _c.c_int64, _P, _P]),
+    ("mvs_kmer_sketcher_create", _c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_uint32, _c.c_uint64, _c.POINTER(_P)]),
+    ("mvs_kmer_sketcher_add", _c.c_int, [_P, _P, _c.c_int, _P, _P, _c.c_int64]),
+    ("mvs_kmer_sketcher_finish", _c.c_int, [_P, _c.c_uint32, _c.c_uint32, _P, _c.POINTER(_P)]),
+    ("mvs_kmer_sketcher_stats", _c.c_int, [_P, _P, _P, _P, _P, _P]),
+    ("mvs_kmer_sketcher_info", _c.c_int, [_P, _c.POINTER(_c.c_double)] + [_c.POINTER(_c.c_int64)] * 5),
+    ("mvs_kmer_sketcher_destroy", _c.c_int, [_P]),
+    ("mvs_hash_set_create_counted", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int64, _c.c_uint32, _c.c_uint32, _P, _c.POINTER(_P)]),
+    ("mvs_hash_set_abundances", _c.c_int, [_P, _P, _c.c_int]),
+    ("mvs_ctx_abund_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)] + [_c.POINTER(_c.c_int64)] * 5),
     ("mvs_intersect_cells", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _P, _c.c_int]),
     ("mvs_ctx_intersect_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
                                             _c.POINTER(_c.c_int64)]),
@@ -1347,6 +1356,88 @@ class HashSet(_Handle):
         offsets = np.empty(self.n + 1, dtype=np.int64)
         _check(self.ctx.lib.mvs_hash_set_export(self._h, None, MEM_HOST, offsets.ctypes.data))
         return offsets
+
+    def abundances(self):
+        """-> uint32 [total]: the abundance of every value, aligned with export()'s values (mvs_hash_set_abundances), or None
+        for a set that carries none: only KmerSketcher.finish and Context.hash_set_counted make sets that do"""
+        if self._h is None:
+            raise ValueError("the hash set is closed")
+        out = np.empty(self.total, dtype=np.uint32)
+        rc = self.ctx.lib.mvs_hash_set_abundances(self._h, out.ctypes.data, MEM_HOST)
+        if rc == MVS_E_INVALID:
+            return None
+        _check(rc)
+        return out
+
+
+class KmerSketcher(_Handle):
+    """The k-mer abundances of n read sets, fed over any number of calls (mvs_kmer_sketcher, include/mvs_hip.h "abundances").
+    add() takes pieces -- byte strings no k-mer may span, each with its sample's index --, finish() returns the HashSet of the
+    values whose abundance passes the filter; that set carries the abundances (HashSet.abundances) and outlives the sketcher."""
+    _destroy = "mvs_kmer_sketcher_destroy"
+
+    def __init__(self, ctx, n_samples, ksize=31, scaled=1000, seed=42, max_hash=None):
+        if max_hash is None:
+            max_hash = kmer_max_hash(scaled)
+        h = _P()
+        _check(ctx.lib.mvs_kmer_sketcher_create(ctx._h, int(n_samples), int(ksize), int(seed) & 0xFFFFFFFF, int(max_hash), ctypes.byref(h)))
+        self.ctx, self._h, self.n = ctx, h, int(n_samples)
+        self.histogram = None
+        ctx._children.add(self)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the sketcher is closed")
+        return self._h
+
+    def add(self, pieces, samples):
+        """pieces: a list of bytes / str, or a pair (bases, offsets) as Context.sketch_sequences takes it; samples: the sample
+        index of every piece"""
+        samples = np.ascontiguousarray(samples, dtype=np.int32)
+        if isinstance(pieces, tuple) and len(pieces) == 2 and not isinstance(pieces[0], (bytes, bytearray, str)):
+            bases, offsets = pieces
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            if _is_torch(bases):
+                if str(bases.dtype) != "torch.uint8":
+                    raise ValueError("bases must be uint8")
+                bp, bm, bk = _buf(bases)
+            else:
+                bp, bm, bk = _buf(bases, np.uint8)
+        else:
+            parts = [x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in pieces]
+            offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+            if parts:
+                np.cumsum([len(x) for x in parts], out=offsets[1:])
+            bp, bm, bk = _buf(np.frombuffer(b"".join(parts), dtype=np.uint8), np.uint8)
+        if offsets.ndim != 1 or len(offsets) != len(samples) + 1:
+            raise ValueError("offsets must hold one entry more than samples")
+        _check(self.ctx.lib.mvs_kmer_sketcher_add(self._handle(), bp, bm, offsets.ctypes.data, samples.ctypes.data, len(samples)))
+
+    def finish(self, min_abundance=1, max_abundance=0, histogram=False):
+        """-> HashSet of the values v with min_abundance <= abundance(v) (<= max_abundance if that is > 0).  histogram=True also
+        leaves int64 [n, 256] in self.histogram: distinct values per min(abundance, 255), before the filter"""
+        hist = np.zeros((self.n, 256), dtype=np.int64) if histogram else None
+        h = _P()
+        _check(self.ctx.lib.mvs_kmer_sketcher_finish(self._handle(), int(min_abundance), int(max_abundance),
+                                                      hist.ctypes.data if histogram else None, ctypes.byref(h)))
+        self.histogram = hist
+        return HashSet(self.ctx, h)
+
+    def info(self):
+        """-> dict of what this sketcher's calls did so far: kernel_ms (hashing passes and finish's scatter, timing on), staged
+        pairs, capacity of the staging list (0 after finish), adds that hashed something, second_trips, growths of the list"""
+        ms = _c.c_double()
+        v = [_c.c_int64() for _ in range(5)]
+        _check(self.ctx.lib.mvs_kmer_sketcher_info(self._handle(), ctypes.byref(ms), *[ctypes.byref(x) for x in v]))
+        return dict(zip(("kernel_ms", "staged", "capacity", "adds", "second_trips", "growths"), [ms.value] + [x.value for x in v]))
+
+    def stats(self):
+        """-> dict of int64 [n] arrays: bases given, kmers (valid positions), kept (values <= max_hash, duplicates included), and
+        after finish distinct values and those that passed the filter (zeros before)"""
+        names = ("bases", "kmers", "kept", "distinct", "passed")
+        out = {k: np.zeros(self.n, dtype=np.int64) for k in names}
+        _check(self.ctx.lib.mvs_kmer_sketcher_stats(self._handle(), *[out[k].ctypes.data for k in names]))
+        return out
 
 
 class GatherResult:
@@ -2523,6 +2614,51 @@ class Context:
         _check(self.lib.mvs_hash_set_from_sequences(self._h, bp, bm, offsets.ctypes.data, len(offsets) - 1, int(ksize),
                                                      int(seed) & 0xFFFFFFFF, int(max_hash), ctypes.byref(h)))
         return HashSet(self, h)
+
+    # ---- abundances (include/mvs_hip.h "abundances") ----
+    def kmer_sketcher(self, n_samples, ksize=31, scaled=1000, seed=42, max_hash=None):
+        """mvs_kmer_sketcher_create -> KmerSketcher for n_samples read sets"""
+        return KmerSketcher(self, n_samples, ksize=ksize, scaled=scaled, seed=seed, max_hash=max_hash)
+
+    def hash_set_counted(self, lists, weights=None, min_abundance=1, max_abundance=0, histogram=False):
+        """mvs_hash_set_create_counted: lists = one sequence of 64-bit values per sample (any order, duplicates welcome), or a
+        pair (hashes, offsets) as hash_set takes it (hashes ONE flat numpy array or uint64 / int64 tensor, never a list); weights = uint32 aligned with the values (same form as lists), default 1
+        each.  -> HashSet with abundances (the sums of the weights of equal values) of the values that pass the filter; with
+        histogram=True -> (HashSet, int64 [n, 256])"""
+        def flat(x, dtype):
+            # (array, offsets): the first entry is ONE flat numpy array / tensor / DeviceArray; anything else is a sequence of samples
+            if isinstance(x, tuple) and len(x) == 2 and (_is_torch(x[0]) or isinstance(x[0], (np.ndarray, DeviceArray))):
+                if _is_torch(x[0]) and str(x[0].dtype) not in (("torch.uint64", "torch.int64") if dtype == np.uint64 else ("torch.uint32", "torch.int32")):
+                    raise ValueError("a tensor of %s is needed (the signed view of the bits is accepted)" % np.dtype(dtype).name)
+                return x[0], np.ascontiguousarray(x[1], dtype=np.int64)
+            parts = [np.asarray(v, dtype=dtype).reshape(-1) for v in x]
+            offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+            if parts:
+                np.cumsum([len(v) for v in parts], out=offsets[1:])
+            return (np.concatenate(parts) if parts else np.empty(0, dtype=dtype)), offsets
+        hashes, offsets = flat(lists, np.uint64)
+        hp, hm, hk = _buf(hashes) if _is_torch(hashes) else _buf(hashes, np.uint64)
+        wp, wm, wk = None, MEM_HOST, None
+        if weights is not None:
+            w, woff = flat((weights, offsets) if _is_torch(weights) or isinstance(weights, np.ndarray) else weights, np.uint32)
+            if woff.tolist() != offsets.tolist():
+                raise ValueError("weights must be aligned with the values")
+            wp, wm, wk = _buf(w) if _is_torch(w) else _buf(w, np.uint32)
+        n = len(offsets) - 1
+        hist = np.zeros((n, 256), dtype=np.int64) if histogram else None
+        h = _P()
+        _check(self.lib.mvs_hash_set_create_counted(self._h, hp, hm, wp, wm, offsets.ctypes.data, n, int(min_abundance), int(max_abundance),
+                                                     hist.ctypes.data if histogram else None, ctypes.byref(h)))
+        hs = HashSet(self, h)
+        return (hs, hist) if histogram else hs
+
+    def abund_stats(self):
+        """-> dict of this context's last counted build (KmerSketcher.finish, hash_set_counted): sort_ms, count_ms (kernel times,
+        timing on), values_in, distinct, passed, units of the run-sum passes, big_segments (samples sorted device-wide)"""
+        t = [_c.c_double(), _c.c_double()]
+        v = [_c.c_int64() for _ in range(5)]
+        _check(self.lib.mvs_ctx_abund_stats(self._h, *[ctypes.byref(x) for x in t + v]))
+        return dict(zip(("sort_ms", "count_ms", "values_in", "distinct", "passed", "units", "big_segments"), (x.value for x in t + v)))
 
     def kmer_stats(self):
         """-> dict of this context's last sketch_sequences: kernel_ms (timing on), bases, kmers (valid positions), kept (values

@@ -159,6 +159,7 @@ struct OptionSpec {
     int mvs::Options::*ifield;
     double mvs::Options::*dfield;
     long long lo, hi;
+    bool no_env = false;   // the option has no environment default
 };
 const OptionSpec kOptions[] = {
     {"pairwise_filter", &mvs::Options::pairwise_filter, nullptr, 0, 2},
@@ -214,6 +215,8 @@ const OptionSpec kOptions[] = {
     {"gather_batch", &mvs::Options::gather_batch, nullptr, 1, 1024},
     {"kmer_unit", &mvs::Options::kmer_unit, nullptr, 64, mvs::kKmerUnitMax},
     {"kmer_capacity", &mvs::Options::kmer_capacity, nullptr, 0, 1 << 30},
+    {"abund_unit", &mvs::Options::abund_unit, nullptr, 64, 1 << 20, true},
+    {"abund_big_segment", &mvs::Options::abund_big_segment, nullptr, 64, 1 << 30, true},
     {"pairwise_block_cells", nullptr, &mvs::Options::pairwise_block_cells, 1, (1LL << 62)},
 };
 
@@ -254,6 +257,7 @@ int apply_option(mvs::Options& o, const OptionSpec& sp, long long v) {
 // values the setter would reject are ignored
 void options_from_env(mvs::Options& o) {
     for (const OptionSpec& sp : kOptions) {
+        if (sp.no_env) continue;
         std::string env = "MVS_";
         for (const char* p = sp.name; *p; ++p) env += (char)toupper((unsigned char)*p);
         const char* e = getenv(env.c_str());

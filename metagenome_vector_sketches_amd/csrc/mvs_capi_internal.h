@@ -275,6 +275,10 @@ struct mvs_ctx {
     double km_kernel_ms = 0.0;
     long long km_bases = 0, km_kmers = 0, km_kept = 0, km_units = 0, km_second_trips = 0;
     std::vector<long long> km_sample_kmers, km_sample_kept;   // ... and per sample (mvs_ctx_kmer_sample_stats)
+    // what the last counted set build did (mvs_ctx_abund_stats): time of the sorts and of the run-sum passes (timing enabled),
+    // values given, distinct values, values that passed the filter, units of the run-sum passes, samples sorted device-wide
+    double ab_sort_ms = 0.0, ab_count_ms = 0.0;
+    long long ab_values = 0, ab_distinct = 0, ab_passed = 0, ab_units = 0, ab_big = 0;
 };
 
 // hash lists resident on the device (mvs_capi_intersect.hip builds them; mvs_capi_gather.hip reads them too)
@@ -285,6 +289,7 @@ struct mvs_hash_set {
     unsigned long long* hashes = nullptr;   // per sample strictly increasing
     long long* offsets = nullptr;           // n + 1
     int32_t* sizes = nullptr;               // n
+    uint32_t* abund = nullptr;              // aligned with hashes: the counted builds' abundances; NULL for every other set
 };
 
 struct mvs_sketch_set {
@@ -387,6 +392,13 @@ constexpr size_t kUploadPiece = 32u << 20;    // bytes per staging buffer (pinni
 int ensure_upload_pipeline(mvs_ctx* c);
 int check_kernel(const char* what);
 void plan_state_free(mvs_ctx* c);      // mvs_capi_plan.hip
+
+// ---- mvs_capi_reads.hip: the counted set build (mvs_hash_set_create_counted, mvs_kmer_sketcher_finish) ----
+// d_in (and d_w, or NULL: weight 1) hold the samples' values on the device, sample s at [off[s], off[s + 1]) with off[0] = 0,
+// in any order.  -> a new set with abundances; histogram (host, n x 256, or NULL); distinct / passed per sample (or NULL).
+int counted_build(mvs_ctx* c, const unsigned long long* d_in, const uint32_t* d_w, const std::vector<long long>& off, int64_t n,
+                  uint32_t min_abundance, uint32_t max_abundance, int64_t* histogram, std::vector<long long>* distinct,
+                  std::vector<long long>* passed, mvs_hash_set** out);
 
 // ---- mvs_capi_sketch.hip ----
 void note_rows_rewritten(mvs_sketch_set* s, int64_t lo, int64_t hi);

@@ -187,6 +187,7 @@ int mvs_hash_set_destroy(mvs_hash_set* h) {
     if (h->hashes) (void)hipFree(h->hashes);
     if (h->offsets) (void)hipFree(h->offsets);
     if (h->sizes) (void)hipFree(h->sizes);
+    if (h->abund) (void)hipFree(h->abund);
     delete h;
     return MVS_OK;
 }

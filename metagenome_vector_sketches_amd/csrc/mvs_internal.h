@@ -134,6 +134,12 @@ struct Options {
                                     // covers, 64 .. 32768 (the default is 256 threads x 68 positions: LDS reads 17 dwords apart)
     int kmer_capacity = 0;          // mvs_hash_set_from_sequences: > 0 = values the staging list of the first trip holds (tests force
                                     // the second trip with it); 0 = the expected number of kept values plus a margin
+    int abund_unit = 4096;          // counted set build: sorted values that one unit of work (one wave) of the run-sum passes covers,
+                                    // 64 .. 2^20; never changes a result (tests lower it to put borders everywhere)
+    int abund_big_segment = 1 << 18;   // counted set build: a sample of more values than this is sorted by a device-wide radix sort
+                                    // of its own, the others by the segmented sort (one workgroup per sample there); >= 64.  The
+                                    // largest size at which the segmented sort still wins in bulk (2^26 values as samples
+                                    // of 2^18: 9.1 against 26.4 ms; of 2^20: 34.7 against 11.9 ms)
     double pairwise_block_cells = 1099511627776.0;   // row-chunk bound of mvs_pairwise_rows (2^40 cells)
 };
 
@@ -519,6 +525,36 @@ int launch_kmer_hash(hipStream_t stream, const uint8_t* d_bases, long long total
                      unsigned long long* d_sample_valid);
 int launch_kmer_scatter(hipStream_t stream, const unsigned long long* d_vals, const int32_t* d_sample, long long n,
                         const long long* d_offsets, unsigned long long* d_cursors, unsigned long long* d_out);
+// the counted set build (mvs_abund.hip).  ab_sort_segments / ab_sort_whole: the segmented sort of hs_sort_segments, or a
+// device-wide radix sort of ONE sample, with the weights travelling along where d_win is not NULL.  launch_ab_borders sets
+// bit off[s] of the (zeroed) bit map for every sample that starts in front of `total`.  ab_count queues passes A, B, C and the
+// two scans over the sorted values (d_scratch: ab_work_bytes(n_units)); ab_fill the offsets' tail, pass D and the sizes.
+struct AbCarry {
+    unsigned long long v, f;
+};
+struct AbArgs {
+    const unsigned long long* keys;      // sorted inside every sample
+    const uint32_t* weights;             // aligned with the keys, or NULL: 1 each
+    const unsigned int* borders;         // bit map of the samples' first positions: (total + 31) / 32 + 1 words
+    const long long* off;                // n + 1
+    long long n, total, n_units;
+    int unit;
+    unsigned long long min_ab, max_ab;   // the filter (max_ab 0: no cap)
+    AbCarry *summary, *tails;            // n_units each
+    long long *head_counts, *pass_counts, *head_start, *pass_start;   // n_units + 1 each, the counts' last entry zero
+    unsigned int* flags;                 // [0] != 0: an abundance reached 2^32 (zeroed by the caller)
+    unsigned long long* hist;            // n x 256, zeroed by the caller, or NULL
+};
+int ab_sort_segments(hipStream_t stream, const unsigned long long* d_in, unsigned long long* d_out, const uint32_t* d_win,
+                     uint32_t* d_wout, unsigned int count, unsigned int segments, const unsigned int* d_begin,
+                     const unsigned int* d_end, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed);
+int ab_sort_whole(hipStream_t stream, const unsigned long long* d_in, unsigned long long* d_out, const uint32_t* d_win,
+                  uint32_t* d_wout, unsigned int count, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed);
+size_t ab_work_bytes(long long n_units);
+int launch_ab_borders(hipStream_t stream, const long long* d_off, long long n, long long total, unsigned int* d_borders);
+int ab_count(hipStream_t stream, const AbArgs& a, void* d_scratch, size_t scratch_bytes);
+int ab_fill(hipStream_t stream, const AbArgs& a, unsigned long long* d_out_vals, uint32_t* d_out_ab, long long* d_new_off,
+            long long* d_distinct_off, int32_t* d_sizes);
 // the greedy decomposition of a query (mvs_gather.hip).  The walk's state lives on the device: the best bid of a round
 // ((count << 32) | (2^32 - 1 - survivor), 0 = none; consecutive rounds use alternating slots), the rows read so far, whether the
 // walk has ended, records written, live positions of the query, rounds run.  launch_gather_init: alive = the query's positions,
