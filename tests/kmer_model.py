@@ -71,13 +71,15 @@ def kmer_hash(kmer, seed=42):
     return None if c is None else murmur3_h1(c, seed)
 
 
-def kept_values(sample, ksize=31, seed=42, maxh=M64):
-    """-> (valid positions, the kept values in position order, duplicates included)"""
+def kept_values(sample, ksize=31, seed=42, maxh=M64, memo=None):
+    """-> (valid positions, the kept values in position order, duplicates included).  memo: a dict the caller keeps for ONE
+    (ksize, seed), upper-cased k-mer -> value, so that samples which share most of their k-mers are hashed once"""
     sample = bytes(sample)
     is_base = [b in _BASES for b in sample]
     up = sample.upper()
     run, valid, kept = 0, 0, []
-    memo = {}
+    if memo is None:
+        memo = {}
     for i in range(len(sample)):
         run = run + 1 if is_base[i] else 0
         if run >= ksize:

@@ -41,6 +41,19 @@ def counted(lists, weights=None, min_abundance=1, max_abundance=0):
     return vals, abund, hist
 
 
+def sorted_layout(lists):
+    """what the run-sum passes walk: -> (keys, borders, heads) of the samples' values sorted inside every sample and laid end
+    to end: the value of every position, the positions that start a (non-empty) sample, the positions that start a run"""
+    keys, borders = [], []
+    for x in lists:
+        if len(x):
+            borders.append(len(keys))
+            keys.extend(sorted(int(v) for v in x))
+    starts = set(borders)
+    heads = [p for p in range(len(keys)) if p == 0 or p in starts or keys[p] != keys[p - 1]]
+    return keys, borders, heads
+
+
 def kept_lists(pieces, samples, n_samples, ksize=31, seed=42, maxh=km.M64):
     """M(s) per sample: the kept values of all its pieces, duplicates included; plus bases, valid positions per sample"""
     lists = [[] for _ in range(n_samples)]
