@@ -76,17 +76,10 @@ Range::~Range() {
     if (on) roctx().pop();
 }
 
-int ensure_buf(mvs_ctx* c, void** p, size_t* have, size_t bytes) {
-    if (*have >= bytes) return MVS_OK;
-    if (*p) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipFree(*p));
-        *p = nullptr;
-        *have = 0;
-    }
-    const size_t want = bytes + std::min<size_t>(bytes / 4, (size_t)256 << 20) + 4096;   // head room: avoid regrowing on small changes
-    if (hipMalloc(p, want) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %zu bytes failed", want);
-    *have = want;
+int ensure_buf(mvs_ctx* c, DevBuf& b, size_t bytes) {
+    if (b.bytes >= bytes) return MVS_OK;
+    if (b.p) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (b.grow(bytes) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %zu bytes failed", DevBuf::grown(bytes));
     return MVS_OK;
 }
 
@@ -94,13 +87,8 @@ int ensure_buf(mvs_ctx* c, void** p, size_t* have, size_t bytes) {
 // into pageable memory is staged by the runtime and blocks the host once per copy), the stream is synchronised once, then
 // the values are copied out.  Only the thread that drives the context's comparison calls this.
 int ensure_read_back(mvs_ctx* c, size_t total) {
-    if (c->rb_pinned && c->rb_bytes >= total) return MVS_OK;
-    if (c->rb_pinned) HIP_TRY(hipHostFree(c->rb_pinned));
-    c->rb_pinned = nullptr;
-    c->rb_bytes = 0;
-    const size_t want = std::max<size_t>(total * 2, (size_t)1 << 20);
-    HIP_TRY(hipHostMalloc(&c->rb_pinned, want, hipHostMallocDefault));
-    c->rb_bytes = want;
+    if (c->rb_pinned.p && c->rb_pinned.bytes >= total) return MVS_OK;
+    HIP_TRY(c->rb_pinned.alloc(std::max<size_t>(total * 2, (size_t)1 << 20)));
     return MVS_OK;
 }
 int read_back(mvs_ctx* c, hipStream_t st, std::initializer_list<ReadBack> items) {
@@ -110,28 +98,22 @@ int read_back(mvs_ctx* c, hipStream_t st, std::initializer_list<ReadBack> items)
     if (rc_rb) return rc_rb;
     size_t at = 0;
     for (const ReadBack& it : items) {
-        if (it.bytes) HIP_TRY(hipMemcpyAsync((char*)c->rb_pinned + at, it.src, it.bytes, hipMemcpyDeviceToHost, st));
+        if (it.bytes) HIP_TRY(hipMemcpyAsync((char*)c->rb_pinned.p + at, it.src, it.bytes, hipMemcpyDeviceToHost, st));
         at += (it.bytes + 63) & ~(size_t)63;
     }
     HIP_TRY(hipStreamSynchronize(st));
     at = 0;
     for (const ReadBack& it : items) {
-        if (it.bytes) memcpy(it.dst, (const char*)c->rb_pinned + at, it.bytes);
+        if (it.bytes) memcpy(it.dst, (const char*)c->rb_pinned.p + at, it.bytes);
         at += (it.bytes + 63) & ~(size_t)63;
     }
     return MVS_OK;
 }
 
 int ensure_scratch(mvs_ctx* c, size_t bytes) {
-    if (c->scratch_bytes >= bytes) return MVS_OK;
-    if (c->scratch) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&c->scratch, bytes));
-    c->scratch_bytes = bytes;
+    if (c->scratch.bytes >= bytes) return MVS_OK;
+    if (c->scratch.p) HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(c->scratch.alloc(bytes));
     return MVS_OK;
 }
 
@@ -141,15 +123,8 @@ int acquire_pinned(mvs_ctx* c, size_t bytes) {
         HIP_TRY(hipEventSynchronize(c->pinned_ev));
         c->pinned_busy = false;
     }
-    if (c->pinned_bytes >= bytes) return MVS_OK;
-    if (c->pinned) {
-        HIP_TRY(hipHostFree(c->pinned));
-        c->pinned = nullptr;
-        c->pinned_bytes = 0;
-    }
-    const size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    HIP_TRY(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
-    c->pinned_bytes = want;
+    if (c->pinned.bytes >= bytes) return MVS_OK;
+    HIP_TRY(c->pinned.alloc(bytes < (1u << 20) ? (1u << 20) : bytes));
     return MVS_OK;
 }
 
@@ -293,13 +268,12 @@ void parallel_copy(void* dst, const void* src, size_t bytes) {
 }
 
 int ensure_upload_pipeline(mvs_ctx* c) {
-    if (c->up_bytes) return MVS_OK;
-    HIP_TRY(hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
+    if (c->up_done[1]) return MVS_OK;
+    HIP_TRY(c->up_stream.create(hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
-        HIP_TRY(hipHostMalloc(&c->up_pinned[i], kUploadPiece, hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&c->up_done[i], hipEventDisableTiming));
+        HIP_TRY(c->up_pinned[i].alloc(kUploadPiece));
+        HIP_TRY(c->up_done[i].create(hipEventDisableTiming));
     }
-    c->up_bytes = kUploadPiece;
     return MVS_OK;
 }
 
@@ -310,6 +284,12 @@ int check_kernel(const char* what) {
 }
 
 }  // namespace mvs_capi
+
+mvs_ctx::~mvs_ctx() {
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    plan_state_free(this);
+}
 
 extern "C" {
 
@@ -355,24 +335,20 @@ int mvs_ctx_create(int device, mvs_ctx** out) {
     c->opt.pairwise_bdirect = 0;
 #endif
     options_from_env(c->opt);
-    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    if (c->own_stream.create(hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return fail(MVS_E_HIP, "hipStreamCreate failed");
     }
     c->stream = c->own_stream;
-    for (auto& ev : c->ev) {
-        if (hipEventCreate(&ev) != hipSuccess) {
-            mvs_ctx_destroy(c);
-            return fail(MVS_E_HIP, "hipEventCreate failed");
-        }
-    }
-    if (hipEventCreateWithFlags(&c->pinned_ev, hipEventDisableTiming) != hipSuccess) {
-        mvs_ctx_destroy(c);
+    bool events = true;
+    for (Event& ev : c->ev) events = events && ev.create() == hipSuccess;
+    if (!events || c->pinned_ev.create(hipEventDisableTiming) != hipSuccess) {
+        delete c;
         return fail(MVS_E_HIP, "hipEventCreate failed");
     }
     // 8 counter slots; +256 B: the filter's stop flag; +1024 B: the re-check's eight round counters, 64 B apart
-    if (hipMalloc((void**)&c->d_counter, 2048) != hipSuccess) {
-        mvs_ctx_destroy(c);
+    if (c->d_counter.alloc(2048) != hipSuccess) {
+        delete c;
         return fail(MVS_E_HIP, "hipMalloc failed");
     }
     *out = c;
@@ -381,58 +357,6 @@ int mvs_ctx_create(int device, mvs_ctx** out) {
 
 int mvs_ctx_destroy(mvs_ctx* c) {
     if (!c) return MVS_OK;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->d_counter) (void)hipFree(c->d_counter);
-    if (c->pw_thr) (void)hipFree(c->pw_thr);
-    if (c->pw_tmp) (void)hipFree(c->pw_tmp);
-    if (c->pw_sort) (void)hipFree(c->pw_sort);
-    if (c->pw_out) (void)hipFree(c->pw_out);
-    if (c->stage) (void)hipFree(c->stage);
-    if (c->pw_coarse) (void)hipFree(c->pw_coarse);
-    if (c->pw_coarse_fm) (void)hipFree(c->pw_coarse_fm);
-    if (c->pw_planes_fm) (void)hipFree(c->pw_planes_fm);
-    if (c->pw_need) (void)hipFree(c->pw_need);
-    if (c->ix_work) (void)hipFree(c->ix_work);
-    if (c->st_tlist) (void)hipFree(c->st_tlist);
-    if (c->st_tlist_n) (void)hipFree(c->st_tlist_n);
-    if (c->st_ends) (void)hipFree(c->st_ends);
-    if (c->pw_rows) (void)hipFree(c->pw_rows);
-    if (c->pw_fmeta) (void)hipFree(c->pw_fmeta);
-    if (c->pw_cand) (void)hipFree(c->pw_cand);
-    for (void* p : {c->st_raw, c->st_sorted, c->st_col[0], c->st_col[1], c->st_q[0], c->st_q[1], c->st_rowptr, c->st_counts,
-                    c->st_dense, c->en_size, c->en_off, c->en_jac, c->en_first, c->en_par, c->st_enc[0], c->st_enc[1]})
-        if (p) (void)hipFree(p);
-    for (int i = 0; i < 2; ++i) {
-        if (c->dl_pinned[i]) (void)hipHostFree(c->dl_pinned[i]);
-        if (c->dl_done[i]) (void)hipEventDestroy(c->dl_done[i]);
-        if (c->dl_block[i]) (void)hipEventDestroy(c->dl_block[i]);
-    }
-    for (hipEvent_t ev : c->dl_ready) if (ev) (void)hipEventDestroy(ev);
-    if (c->dl_stream) (void)hipStreamDestroy(c->dl_stream);
-    if (c->dl_hsa && c->dl_hsa_free) c->dl_hsa_free(c->dl_hsa);
-    for (mvs_tile_order& o : c->tile_orders)
-        if (o.d) (void)hipFree(o.d);
-    if (c->post_stream) (void)hipStreamDestroy(c->post_stream);
-    if (c->cmp_done) (void)hipEventDestroy(c->cmp_done);
-    if (c->pw_chdr) (void)hipFree(c->pw_chdr);
-    if (c->pw_cent) (void)hipFree(c->pw_cent);
-    for (void* p : {c->pw_tflag, c->pw_trow, c->pw_tlist, c->pw_cand2, c->pw_ttouch, c->pw_tnew})
-        if (p) (void)hipFree(p);
-    if (c->rb_pinned) (void)hipHostFree(c->rb_pinned);
-    for (int i = 0; i < 2; ++i) {
-        if (c->up_pinned[i]) (void)hipHostFree(c->up_pinned[i]);
-        if (c->up_done[i]) (void)hipEventDestroy(c->up_done[i]);
-    }
-    if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->pinned_ev) (void)hipEventDestroy(c->pinned_ev);
-    for (auto& ev : c->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    plan_state_free(c);
-    if (c->plan_tmp) (void)hipFree(c->plan_tmp);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return MVS_OK;
 }
@@ -524,7 +448,7 @@ int mvs_ctx_kernel_ms(mvs_ctx* c, int which, float* ms) {
 // -------------------------------------------------------------------------------------------------
 struct mvs_event {
     int device = 0;
-    hipEvent_t ev = nullptr;
+    Event ev;
     bool timing = false, recorded = false;
 };
 
@@ -532,16 +456,13 @@ int mvs_device_alloc(mvs_ctx* c, size_t bytes, int zero, void** ptr) {
     if (!c || !ptr) return fail(MVS_E_INVALID, "NULL argument");
     *ptr = nullptr;
     HIP_TRY(hipSetDevice(c->device));
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %zu bytes failed", bytes);
+    DevBuf b;
+    if (b.alloc(bytes) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %zu bytes failed", bytes);
     if (zero && bytes) {
-        const hipError_t e = hipMemsetAsync(p, 0, bytes, c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return fail(MVS_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-        }
+        const hipError_t e = hipMemsetAsync(b.p, 0, bytes, c->stream);
+        if (e != hipSuccess) return fail(MVS_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
-    *ptr = p;
+    *ptr = std::exchange(b.p, nullptr);   // the caller's from here on (mvs_device_free)
     return MVS_OK;
 }
 
@@ -586,7 +507,7 @@ int mvs_event_create(mvs_ctx* c, int timing, mvs_event** out) {
     if (!e) return fail(MVS_E_NOMEM, "out of host memory");
     e->device = c->device;
     e->timing = timing != 0;
-    const hipError_t rc = hipEventCreateWithFlags(&e->ev, timing ? hipEventDefault : hipEventDisableTiming);
+    const hipError_t rc = e->ev.create(timing ? hipEventDefault : hipEventDisableTiming);
     if (rc != hipSuccess) {
         delete e;
         return fail(MVS_E_HIP, "hipEventCreate: %s", hipGetErrorString(rc));
@@ -633,7 +554,6 @@ int mvs_event_elapsed_ms(mvs_event* b, mvs_event* e, float* ms) {
 int mvs_event_destroy(mvs_event* e) {
     if (!e) return MVS_OK;
     (void)hipSetDevice(e->device);
-    if (e->ev) (void)hipEventDestroy(e->ev);
     delete e;
     return MVS_OK;
 }

@@ -12,9 +12,9 @@ using namespace mvs_capi;
 struct mvs_cluster {
     mvs_ctx* ctx = nullptr;
     int64_t n = 0;
-    int32_t* parent = nullptr;              // the forest: parent[x] <= x
-    int32_t* degree = nullptr;
-    unsigned long long* counters = nullptr;  // mvs_cluster.hip: edges, cells out of range, cells whose endpoints are apart
+    DevBuf parent;     // int32_t, the forest: parent[x] <= x
+    DevBuf degree;     // int32_t
+    DevBuf counters;   // unsigned long long (mvs_cluster.hip): edges, cells out of range, cells whose endpoints are apart
 };
 
 namespace {
@@ -28,22 +28,23 @@ int consume_cells(mvs_cluster* k, const mvs_cell* d_cells, int64_t n_cells) {
     StageTimer timer;
     int rc = timer.begin(c);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(k->counters, 0, 3 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(k->counters.as<unsigned long long>(), 0, 3 * sizeof(unsigned long long), c->stream));
     unsigned long long back[3] = {0, 0, 0};
     int round = 0;
     for (;;) {
         ++round;
-        rc = mvs::launch_cluster_hook(c->stream, d_cells, n_cells, k->parent, k->degree, k->n, round == 1, k->counters);
+        rc = mvs::launch_cluster_hook(c->stream, d_cells, n_cells, k->parent.as<int32_t>(), k->degree.as<int32_t>(), k->n, round == 1,
+                                      k->counters.as<unsigned long long>());
         if (!rc) rc = check_kernel("k_cluster_hook");
         if (rc) return rc;
-        rc = mvs::launch_cluster_flatten(c->stream, k->parent, k->n);
+        rc = mvs::launch_cluster_flatten(c->stream, k->parent.as<int32_t>(), k->n);
         if (!rc) rc = check_kernel("k_cluster_flatten");
         if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(k->counters + 2, 0, sizeof(unsigned long long), c->stream));
-        rc = mvs::launch_cluster_verify(c->stream, d_cells, n_cells, k->parent, k->n, k->counters);
+        HIP_TRY(hipMemsetAsync(k->counters.as<unsigned long long>() + 2, 0, sizeof(unsigned long long), c->stream));
+        rc = mvs::launch_cluster_verify(c->stream, d_cells, n_cells, k->parent.as<int32_t>(), k->n, k->counters.as<unsigned long long>());
         if (!rc) rc = check_kernel("k_cluster_verify");
         if (rc) return rc;
-        rc = read_back(c, c->stream, {{back, k->counters, sizeof(back)}});
+        rc = read_back(c, c->stream, {{back, k->counters.as<unsigned long long>(), sizeof(back)}});
         if (rc) return rc;
         if (back[1] != 0) break;
         if (back[2] == 0) break;
@@ -84,21 +85,21 @@ int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, doubl
     if (capacity <= 0) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        const size_t have = free_b + c->pw_tmp_bytes;               // (the buffer below is the context's own, counted as free)
+        const size_t have = free_b + c->pw_tmp.bytes;               // (the buffer below is the context's own, counted as free)
         capacity = (int64_t)std::min<size_t>(std::max<size_t>(4096, have / 4 / sizeof(mvs_cell)), (size_t)1 << 30);   // (the option's range)
         const double block = (double)std::min(R, n) * (double)n;
         if (block < (double)capacity) capacity = (int64_t)block;
     }
     capacity = std::max<int64_t>(capacity, 1);
-    int rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)capacity * sizeof(mvs_cell));
+    int rc = ensure_buf(c, c->pw_tmp, (size_t)capacity * sizeof(mvs_cell));
     if (rc) return rc;
     for (int64_t rb = 0; rb < n;) {
         const int64_t re = std::min(n, rb + R);
         unsigned long long count = 0;
-        rc = pairwise_launch(c, s, d_n2, MVS_KEEP_INT16, rb, re, 0, n, true, false, (mvs_cell*)c->pw_tmp, capacity, 0, &count, coeff);
+        rc = pairwise_launch(c, s, d_n2, MVS_KEEP_INT16, rb, re, 0, n, true, false, (mvs_cell*)c->pw_tmp.p, capacity, 0, &count, coeff);
         if (rc) return rc;
         if (count == ~0ULL) {
-            rc = read_back(c, c->stream, {{&count, c->d_counter, 8}});
+            rc = read_back(c, c->stream, {{&count, c->counters(), 8}});
             if (rc) return rc;
         }
         if (c->timing && c->ev_valid[1]) {
@@ -113,11 +114,11 @@ int pairwise_feed(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, doubl
                 continue;
             }
             capacity = (int64_t)count;
-            rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)capacity * sizeof(mvs_cell));
+            rc = ensure_buf(c, c->pw_tmp, (size_t)capacity * sizeof(mvs_cell));
             if (rc) return rc;
             continue;
         }
-        rc = consume((const mvs_cell*)c->pw_tmp, (int64_t)count, rb, re);
+        rc = consume((const mvs_cell*)c->pw_tmp.p, (int64_t)count, rb, re);
         if (rc) return rc;
         ++*row_blocks;
         rb = re;
@@ -171,24 +172,18 @@ int mvs_cluster_create(mvs_ctx* c, int64_t n, mvs_cluster** out) {
     if (n < 0) return fail(MVS_E_INVALID, "n = %lld is negative", (long long)n);
     if (n >= (1LL << 31) - 256) return fail(MVS_E_RANGE, "n too large for int32 sample indices");
     HIP_TRY(hipSetDevice(c->device));
-    mvs_cluster* k = new (std::nothrow) mvs_cluster();
+    std::unique_ptr<mvs_cluster> k(new (std::nothrow) mvs_cluster());
     if (!k) return fail(MVS_E_NOMEM, "out of host memory");
     k->ctx = c;
     k->n = n;
     const size_t words = (size_t)std::max<int64_t>(n, 1);
-    if (hipMalloc((void**)&k->parent, words * 4) != hipSuccess || hipMalloc((void**)&k->degree, words * 4) != hipSuccess ||
-        hipMalloc((void**)&k->counters, 64) != hipSuccess) {
-        mvs_cluster_destroy(k);
+    if (k->parent.alloc(words * 4) != hipSuccess || k->degree.alloc(words * 4) != hipSuccess || k->counters.alloc(64) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of the forest of %lld samples failed", (long long)n);
-    }
-    int rc = mvs::launch_cluster_init(c->stream, k->parent, k->degree, n);
+    int rc = mvs::launch_cluster_init(c->stream, k->parent.as<int32_t>(), k->degree.as<int32_t>(), n);
     if (!rc) rc = check_kernel("k_cluster_init");
-    if (rc) {
-        mvs_cluster_destroy(k);
-        return rc;
-    }
+    if (rc) return rc;
     c->cl.reset();
-    *out = k;
+    *out = k.release();
     return MVS_OK;
 }
 
@@ -233,18 +228,18 @@ int mvs_cluster_finish(mvs_cluster* k, const double* norms_sq, int mem_norms, in
     int32_t* d_sizes = d_labels + np1;
     int32_t* d_rep = d_sizes + np1;
     size_t need = 0;
-    rc = mvs::cluster_finish(c->stream, k->parent, d_n2, n, d_is_root, d_ids, d_labels, d_sizes, d_rep, (unsigned long long*)dbest.p,
-                             nullptr, 0, &need);
+    rc = mvs::cluster_finish(c->stream, k->parent.as<int32_t>(), d_n2, n, d_is_root, d_ids, d_labels, d_sizes, d_rep,
+                             (unsigned long long*)dbest.p, nullptr, 0, &need);
     if (rc) return fail(rc, "cluster finish: scan sizing failed");
     HIP_TRY(dscan.alloc(need));
     StageTimer timer;
     rc = timer.begin(c);
     if (rc) return rc;
-    rc = mvs::launch_cluster_flatten(c->stream, k->parent, n);
+    rc = mvs::launch_cluster_flatten(c->stream, k->parent.as<int32_t>(), n);
     if (!rc) rc = check_kernel("k_cluster_flatten");
     if (rc) return rc;
-    rc = mvs::cluster_finish(c->stream, k->parent, d_n2, n, d_is_root, d_ids, d_labels, d_sizes, d_rep, (unsigned long long*)dbest.p,
-                             dscan.p, need, nullptr);
+    rc = mvs::cluster_finish(c->stream, k->parent.as<int32_t>(), d_n2, n, d_is_root, d_ids, d_labels, d_sizes, d_rep,
+                             (unsigned long long*)dbest.p, dscan.p, need, nullptr);
     if (rc) return fail(rc, "cluster finish failed");
     rc = check_kernel("k_cluster_label");
     if (rc) return rc;
@@ -256,7 +251,7 @@ int mvs_cluster_finish(mvs_cluster* k, const double* norms_sq, int mem_norms, in
     if (rc) return rc;
     if (n_clusters) *n_clusters = total;
     rc = give_out(c, labels, d_labels, n, mem_out);
-    if (!rc) rc = give_out(c, degree, k->degree, n, mem_out);
+    if (!rc) rc = give_out(c, degree, k->degree.as<int32_t>(), n, mem_out);
     if (!rc) rc = give_out(c, representatives, d_rep, total, mem_out);
     if (!rc) rc = give_out(c, sizes, d_sizes, total, mem_out);
     if (rc) return rc;
@@ -270,9 +265,6 @@ int mvs_cluster_destroy(mvs_cluster* k) {
         (void)hipSetDevice(k->ctx->device);
         (void)hipStreamSynchronize(k->ctx->stream);
     }
-    if (k->parent) (void)hipFree(k->parent);
-    if (k->degree) (void)hipFree(k->degree);
-    if (k->counters) (void)hipFree(k->counters);
     delete k;
     return MVS_OK;
 }

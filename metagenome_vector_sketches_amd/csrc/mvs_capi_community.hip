@@ -22,22 +22,20 @@ struct mvs_community {
     int64_t n = 0;
     int d = 0;
     double floor_ = 0.0;
-    double* d_n2 = nullptr;
+    DevBuf d_n2;                             // double, or empty
     // the fed entries (lo << 32 | hi, a): `count` of them; `unique`: sorted, one per edge
-    u64* keys = nullptr;
-    uint32_t* w = nullptr;
+    DevBuf keys;                             // u64
+    DevBuf w;                                // uint32_t
     int64_t cap = 0, count = 0;
     bool unique = true;
-    u64* counters = nullptr;                 // mvs_community.hip: [0] entries, [1] out of range, [2] bad weights; [4..7] scratch words
+    DevBuf counters;                         // u64 (mvs_community.hip): [0] entries, [1] out of range, [2] bad weights; [4..7] scratch words
     // level 0 (built by the first finish after a feed)
     bool built = false;
     int64_t m = 0;
-    long long* row_ptr = nullptr;
-    int32_t* src = nullptr;
-    int32_t* col = nullptr;
-    uint32_t* w32 = nullptr;
-    u64* self0 = nullptr;
-    u64* k0 = nullptr;
+    DevBuf row_ptr;                          // long long
+    DevBuf src, col;                         // int32_t
+    DevBuf w32;                              // uint32_t
+    DevBuf self0, k0;                        // u64
     u64 W = 0;
 };
 
@@ -48,19 +46,8 @@ constexpr int kPatience = 3;
 constexpr int kMaxUnionRounds = 64;
 constexpr int64_t kSplitChunk = 1LL << 22;   // cells of the connected split per union-find pass
 
-template <typename T>
-void free_dev(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 void drop_level0(mvs_community* k) {
-    free_dev(k->row_ptr);
-    free_dev(k->src);
-    free_dev(k->col);
-    free_dev(k->w32);
-    free_dev(k->self0);
-    free_dev(k->k0);
+    for (DevBuf* b : {&k->row_ptr, &k->src, &k->col, &k->w32, &k->self0, &k->k0}) b->reset();
     k->built = false;
     k->m = 0;
 }
@@ -68,22 +55,17 @@ void drop_level0(mvs_community* k) {
 int ensure_room(mvs_community* k, int64_t extra) {
     if (k->count + extra <= k->cap) return MVS_OK;
     const int64_t cap = std::max<int64_t>({2 * k->cap, k->count + extra, 1024});
-    u64* nk = nullptr;
-    uint32_t* nw = nullptr;
-    if (hipMalloc((void**)&nk, (size_t)cap * 8) != hipSuccess || hipMalloc((void**)&nw, (size_t)cap * 4) != hipSuccess) {
-        free_dev(nk);
+    DevBuf nk, nw;
+    if (nk.alloc((size_t)cap * 8) != hipSuccess || nw.alloc((size_t)cap * 4) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of %lld graph entries failed", (long long)cap);
-    }
     mvs_ctx* c = k->ctx;
     if (k->count > 0) {
-        HIP_TRY(hipMemcpyAsync(nk, k->keys, (size_t)k->count * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(nw, k->w, (size_t)k->count * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(nk.p, k->keys.p, (size_t)k->count * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(nw.p, k->w.p, (size_t)k->count * 4, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    free_dev(k->keys);
-    free_dev(k->w);
-    k->keys = nk;
-    k->w = nw;
+    k->keys = std::move(nk);
+    k->w = std::move(nw);
     k->cap = cap;
     return MVS_OK;
 }
@@ -92,7 +74,7 @@ int ensure_room(mvs_community* k, int64_t extra) {
 int after_feed(mvs_community* k, const char* what) {
     mvs_ctx* c = k->ctx;
     u64 back[3] = {0, 0, 0};
-    const int rc = read_back(c, c->stream, {{back, k->counters, sizeof(back)}});
+    const int rc = read_back(c, c->stream, {{back, k->counters.as<u64>(), sizeof(back)}});
     if (rc) return rc;
     if ((int64_t)back[0] != k->count) {
         k->unique = false;
@@ -108,14 +90,15 @@ int after_feed(mvs_community* k, const char* what) {
 int consume_cells(mvs_community* k, const mvs_cell* d_cells, int64_t n_cells) {
     mvs_ctx* c = k->ctx;
     if (n_cells == 0) return MVS_OK;
-    if (!k->d_n2) return fail(MVS_E_INVALID, "the graph was created without norms: it takes raw edges only");
+    if (!k->d_n2.as<double>()) return fail(MVS_E_INVALID, "the graph was created without norms: it takes raw edges only");
     int rc = ensure_room(k, n_cells);
     if (rc) return rc;
     StageTimer timer;
     rc = timer.begin(c);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(k->counters + 1, 0, 2 * sizeof(u64), c->stream));
-    rc = mvs::launch_comm_cells(c->stream, d_cells, n_cells, k->n, k->d_n2, k->d, k->floor_, k->keys, k->w, k->counters);
+    HIP_TRY(hipMemsetAsync(k->counters.as<u64>() + 1, 0, 2 * sizeof(u64), c->stream));
+    rc = mvs::launch_comm_cells(c->stream, d_cells, n_cells, k->n, k->d_n2.as<double>(), k->d, k->floor_, k->keys.as<u64>(),
+                                k->w.as<uint32_t>(), k->counters.as<u64>());
     if (!rc) rc = check_kernel("k_comm_cells");
     if (!rc) rc = timer.mark_end();
     if (rc) return rc;
@@ -136,19 +119,19 @@ int build_level0(mvs_community* k) {
         DevBuf tk, tw;
         HIP_TRY(tk.alloc((size_t)k->count * 8));
         HIP_TRY(tw.alloc((size_t)k->count * 4));
-        rc = mvs::comm_unique_max(c->stream, k->keys, k->w, k->count, (u64*)tk.p, (uint32_t*)tw.p, k->counters);
+        rc = mvs::comm_unique_max(c->stream, k->keys.as<u64>(), k->w.as<uint32_t>(), k->count, (u64*)tk.p, (uint32_t*)tw.p,
+                                  k->counters.as<u64>());
         if (rc) return fail(rc, "communities: sorting the fed cells failed");
         u64 left = 0;
-        rc = read_back(c, c->stream, {{&left, k->counters, 8}});
+        rc = read_back(c, c->stream, {{&left, k->counters.as<u64>(), 8}});
         if (rc) return rc;
         k->count = (int64_t)left;
     }
     k->unique = true;
     const int64_t n = k->n, e = k->count, m = 2 * e;
     const size_t mm = (size_t)std::max<int64_t>(m, 1), nn = (size_t)std::max<int64_t>(n, 1);
-    if (hipMalloc((void**)&k->row_ptr, (nn + 1) * 8) != hipSuccess || hipMalloc((void**)&k->src, mm * 4) != hipSuccess ||
-        hipMalloc((void**)&k->col, mm * 4) != hipSuccess || hipMalloc((void**)&k->w32, mm * 4) != hipSuccess ||
-        hipMalloc((void**)&k->self0, nn * 8) != hipSuccess || hipMalloc((void**)&k->k0, nn * 8) != hipSuccess) {
+    if (k->row_ptr.alloc((nn + 1) * 8) != hipSuccess || k->src.alloc(mm * 4) != hipSuccess || k->col.alloc(mm * 4) != hipSuccess ||
+        k->w32.alloc(mm * 4) != hipSuccess || k->self0.alloc(nn * 8) != hipSuccess || k->k0.alloc(nn * 8) != hipSuccess) {
         drop_level0(k);
         return fail(MVS_E_NOMEM, "hipMalloc of the graph of %lld edges failed", (long long)e);
     }
@@ -157,28 +140,29 @@ int build_level0(mvs_community* k) {
         HIP_TRY(dk.alloc(mm * 8));
         HIP_TRY(tk.alloc(mm * 8));
         HIP_TRY(tw.alloc(mm * 4));
-        rc = mvs::comm_mirror(c->stream, k->keys, k->w, e, (u64*)dk.p, k->w32, (u64*)tk.p, (uint32_t*)tw.p);
+        rc = mvs::comm_mirror(c->stream, k->keys.as<u64>(), k->w.as<uint32_t>(), e, (u64*)dk.p, k->w32.as<uint32_t>(), (u64*)tk.p,
+                              (uint32_t*)tw.p);
         if (rc) return fail(rc, "communities: sorting the directed entries failed");
-        rc = mvs::launch_comm_csr(c->stream, (const u64*)dk.p, m, n, k->row_ptr, k->src, k->col);
+        rc = mvs::launch_comm_csr(c->stream, (const u64*)dk.p, m, n, k->row_ptr.as<long long>(), k->src.as<int32_t>(), k->col.as<int32_t>());
         if (!rc) rc = check_kernel("k_comm_csr");
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    HIP_TRY(hipMemsetAsync(k->self0, 0, nn * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(k->counters + 4, 0, 8, c->stream));
+    HIP_TRY(hipMemsetAsync(k->self0.as<u64>(), 0, nn * 8, c->stream));
+    HIP_TRY(hipMemsetAsync(k->counters.as<u64>() + 4, 0, 8, c->stream));
     mvs::CommLevel g;
     g.n = n;
     g.m = m;
-    g.row_ptr = k->row_ptr;
-    g.src = k->src;
-    g.col = k->col;
-    g.w32 = k->w32;
-    g.self = k->self0;
-    rc = mvs::launch_comm_strength(c->stream, g, k->k0, k->counters + 4);
+    g.row_ptr = k->row_ptr.as<long long>();
+    g.src = k->src.as<int32_t>();
+    g.col = k->col.as<int32_t>();
+    g.w32 = k->w32.as<uint32_t>();
+    g.self = k->self0.as<u64>();
+    rc = mvs::launch_comm_strength(c->stream, g, k->k0.as<u64>(), k->counters.as<u64>() + 4);
     if (!rc) rc = check_kernel("k_comm_strength");
     if (!rc) rc = timer.mark_end();
     if (rc) return rc;
-    rc = read_back(c, c->stream, {{&k->W, k->counters + 4, 8}});
+    rc = read_back(c, c->stream, {{&k->W, k->counters.as<u64>() + 4, 8}});
     if (!rc) rc = timer.add_to(&c->cm.build_ms);
     if (rc) return rc;
     k->m = m;
@@ -208,24 +192,21 @@ int mvs_community_create(mvs_ctx* c, int64_t n, int d, const double* norms_sq, i
     if (!(floor_ >= 0.0) || !(floor_ < 1.0)) return fail(MVS_E_INVALID, "floor = %g outside [0, 1)", floor_);
     if (norms_sq && (d < 1 || !mem_ok(mem_norms))) return fail(MVS_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    mvs_community* k = new (std::nothrow) mvs_community();
+    std::unique_ptr<mvs_community> k(new (std::nothrow) mvs_community());
     if (!k) return fail(MVS_E_NOMEM, "out of host memory");
     k->ctx = c;
     k->n = n;
     k->d = d;
     k->floor_ = floor_;
-    bool ok = hipMalloc((void**)&k->counters, 64) == hipSuccess && hipMemsetAsync(k->counters, 0, 64, c->stream) == hipSuccess;
+    bool ok = k->counters.alloc(64) == hipSuccess && hipMemsetAsync(k->counters.p, 0, 64, c->stream) == hipSuccess;
     if (ok && norms_sq && n > 0)
-        ok = hipMalloc((void**)&k->d_n2, (size_t)n * 8) == hipSuccess &&
-             hipMemcpyAsync(k->d_n2, norms_sq, (size_t)n * 8, mem_norms == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+        ok = k->d_n2.alloc((size_t)n * 8) == hipSuccess &&
+             hipMemcpyAsync(k->d_n2.p, norms_sq, (size_t)n * 8, mem_norms == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                             c->stream) == hipSuccess;
     if (ok) ok = hipStreamSynchronize(c->stream) == hipSuccess;
-    if (!ok) {
-        mvs_community_destroy(k);
-        return fail(MVS_E_NOMEM, "hipMalloc of the graph of %lld samples failed", (long long)n);
-    }
+    if (!ok) return fail(MVS_E_NOMEM, "hipMalloc of the graph of %lld samples failed", (long long)n);
     c->cm.reset();
-    *out = k;
+    *out = k.release();
     return MVS_OK;
 }
 
@@ -258,8 +239,8 @@ int mvs_community_add_edges(mvs_community* k, const int32_t* lo, const int32_t* 
     }
     int rc = ensure_room(k, n_edges);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(k->counters + 1, 0, 2 * sizeof(u64), c->stream));
-    rc = mvs::launch_comm_edges(c->stream, dlo, dhi, da, n_edges, k->n, k->keys, k->w, k->counters);
+    HIP_TRY(hipMemsetAsync(k->counters.as<u64>() + 1, 0, 2 * sizeof(u64), c->stream));
+    rc = mvs::launch_comm_edges(c->stream, dlo, dhi, da, n_edges, k->n, k->keys.as<u64>(), k->w.as<uint32_t>(), k->counters.as<u64>());
     if (!rc) rc = check_kernel("k_comm_edges");
     if (rc) return rc;
     return after_feed(k, "edges");
@@ -327,12 +308,12 @@ int mvs_community_finish(mvs_community* k, double resolution, int64_t max_rounds
     mvs::CommLevel g;
     g.n = n;
     g.m = k->m;
-    g.row_ptr = k->row_ptr;
-    g.src = k->src;
-    g.col = k->col;
-    g.w32 = k->w32;
-    g.self = k->self0;
-    g.k = k->k0;
+    g.row_ptr = k->row_ptr.as<long long>();
+    g.src = k->src.as<int32_t>();
+    g.col = k->col.as<int32_t>();
+    g.w32 = k->w32.as<uint32_t>();
+    g.self = k->self0.as<u64>();
+    g.k = k->k0.as<u64>();
     const mvs::CommLevel g0 = g;
     std::unique_ptr<LevelBufs> cur;
 
@@ -364,11 +345,7 @@ int mvs_community_finish(mvs_community* k, double resolution, int64_t max_rounds
         if (c2 > 0 || hand2) {
             while (slots < 2 * maxdeg) slots <<= 1;
             groups = (int)std::min<int64_t>(mvs::kCommGlobalGroups, std::max<int64_t>(c2, hand2 ? c0 + c1 : 0));
-            if (dtab.p) {
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                (void)hipFree(dtab.p);
-                dtab.p = nullptr;
-            }
+            if (dtab.p) HIP_TRY(hipStreamSynchronize(c->stream));
             if (dtab.alloc((size_t)groups * (size_t)slots * 12) != hipSuccess)
                 return fail(MVS_E_NOMEM, "hipMalloc of %d tables of %lld slots failed", groups, (long long)slots);
         }
@@ -593,7 +570,7 @@ int mvs_community_finish(mvs_community* k, double resolution, int64_t max_rounds
         r.communities = final_count;
         rc = give_out(c, labels, d_new, n, mem_out);
         if (!rc) rc = give_out(c, degree, d_size, n, mem_out);
-        if (!rc) rc = give_out(c, strength, k->k0, n, mem_out);
+        if (!rc) rc = give_out(c, strength, k->k0.as<u64>(), n, mem_out);
         if (!rc) rc = give_out(c, internal, d_out_a, final_count, mem_out);
         if (!rc) rc = give_out(c, total, d_out_b, final_count, mem_out);
         if (rc) return rc;
@@ -611,11 +588,6 @@ int mvs_community_destroy(mvs_community* k) {
         (void)hipSetDevice(k->ctx->device);
         (void)hipStreamSynchronize(k->ctx->stream);
     }
-    drop_level0(k);
-    free_dev(k->keys);
-    free_dev(k->w);
-    free_dev(k->d_n2);
-    free_dev(k->counters);
     delete k;
     return MVS_OK;
 }

@@ -24,20 +24,20 @@ int refresh_derived(mvs_ctx* c, const mvs_sketch_set* cs) {
             c->coarse_id = 0;                                  // another radix rule was asked for: rebuilt as a whole anyway
         } else {
             const int64_t valid = std::max<int64_t>(0, std::min<int64_t>(count, s->n - lo));
-            mvs::launch_coarse_build(c->stream, s->planes + lo * 2 * dp, valid, count, s->d_pad, (int8_t*)c->pw_coarse + lo * dp,
-                                     (mvs::CoarseRow*)c->pw_rows + lo, c->opt.coarse_radix);
+            mvs::launch_coarse_build(c->stream, s->planes + lo * 2 * dp, valid, count, s->d_pad, (int8_t*)c->pw_coarse.p + lo * dp,
+                                     (mvs::CoarseRow*)c->pw_rows.p + lo, c->opt.coarse_radix);
             c->dv_coarse_rows += count;
             int rc = check_kernel("k_coarse_build(rows)");
             if (rc) return rc;
             if (c->coarse_fm_valid) {
-                mvs::launch_coarse_fm(c->stream, (const int8_t*)c->pw_coarse + lo * dp, count, s->d_pad, (int8_t*)c->pw_coarse_fm + lo * dp);
+                mvs::launch_coarse_fm(c->stream, (const int8_t*)c->pw_coarse.p + lo * dp, count, s->d_pad, (int8_t*)c->pw_coarse_fm.p + lo * dp);
                 rc = check_kernel("k_coarse_fm(rows)");
                 if (rc) return rc;
             }
         }
     }
     if (s->limbs == 2 && c->planes_fm_id == s->id && c->planes_fm_gen == s->gen) {
-        mvs::launch_coarse_fm(c->stream, s->planes + lo * 2 * dp, count, s->d_pad, (int8_t*)c->pw_planes_fm + lo * 2 * dp, 2);
+        mvs::launch_coarse_fm(c->stream, s->planes + lo * 2 * dp, count, s->d_pad, (int8_t*)c->pw_planes_fm.p + lo * 2 * dp, 2);
         c->dv_planes_fm_rows += count;
         const int rc = check_kernel("k_coarse_fm(limb planes, rows)");
         if (rc) return rc;
@@ -52,12 +52,12 @@ int prepare_coarse(mvs_ctx* c, const mvs_sketch_set* s) {
     if (c->coarse_id == s->id && c->coarse_gen == s->gen && c->coarse_mode == c->opt.coarse_radix) return MVS_OK;
     c->coarse_id = 0;
     c->coarse_fm_valid = false;
-    int rc = ensure_buf(c, &c->pw_coarse, &c->pw_coarse_bytes, (size_t)s->n_alloc * (size_t)s->d_pad);
+    int rc = ensure_buf(c, c->pw_coarse, (size_t)s->n_alloc * (size_t)s->d_pad);
     if (rc) return rc;
-    rc = ensure_buf(c, &c->pw_rows, &c->pw_rows_bytes, (size_t)s->n_alloc * sizeof(mvs::CoarseRow));
+    rc = ensure_buf(c, c->pw_rows, (size_t)s->n_alloc * sizeof(mvs::CoarseRow));
     if (rc) return rc;
-    mvs::launch_coarse_build(c->stream, s->planes, s->n, s->n_alloc, s->d_pad, (int8_t*)c->pw_coarse,
-                             (mvs::CoarseRow*)c->pw_rows, c->opt.coarse_radix);
+    mvs::launch_coarse_build(c->stream, s->planes, s->n, s->n_alloc, s->d_pad, (int8_t*)c->pw_coarse.p,
+                             (mvs::CoarseRow*)c->pw_rows.p, c->opt.coarse_radix);
     ++c->dv_coarse_builds;
     rc = check_kernel("k_coarse_build");
     if (rc) return rc;
@@ -84,13 +84,13 @@ bool fm_copy_fits(size_t have_bytes, size_t want_bytes) {
 int prepare_coarse_fm(mvs_ctx* c, const mvs_sketch_set* s, bool* made) {
     *made = true;
     if (c->coarse_fm_valid) return MVS_OK;
-    if (!fm_copy_fits(c->pw_coarse_fm_bytes, (size_t)s->n_alloc * (size_t)s->d_pad)) {
+    if (!fm_copy_fits(c->pw_coarse_fm.bytes, (size_t)s->n_alloc * (size_t)s->d_pad)) {
         *made = false;
         return MVS_OK;
     }
-    int rc = ensure_buf(c, &c->pw_coarse_fm, &c->pw_coarse_fm_bytes, (size_t)s->n_alloc * (size_t)s->d_pad);
+    int rc = ensure_buf(c, c->pw_coarse_fm, (size_t)s->n_alloc * (size_t)s->d_pad);
     if (rc) return rc;
-    mvs::launch_coarse_fm(c->stream, (const int8_t*)c->pw_coarse, s->n_alloc, s->d_pad, (int8_t*)c->pw_coarse_fm);
+    mvs::launch_coarse_fm(c->stream, (const int8_t*)c->pw_coarse.p, s->n_alloc, s->d_pad, (int8_t*)c->pw_coarse_fm.p);
     ++c->dv_coarse_fm_builds;
     rc = check_kernel("k_coarse_fm");
     if (rc) return rc;
@@ -107,22 +107,22 @@ int attach_planes_fm(mvs_ctx* c, const mvs_sketch_set* s, mvs::PairwiseArgs& a, 
     if (!wanted || !c->opt.fragment_major || s->limbs != 2) return MVS_OK;
     if (!(c->planes_fm_id == s->id && c->planes_fm_gen == s->gen)) {
         c->planes_fm_id = 0;
-        if (!fm_copy_fits(c->pw_planes_fm_bytes, (size_t)s->n_alloc * 2 * (size_t)s->d_pad)) return MVS_OK;   // row-major kernels
-        int rc = ensure_buf(c, &c->pw_planes_fm, &c->pw_planes_fm_bytes, (size_t)s->n_alloc * 2 * (size_t)s->d_pad);
+        if (!fm_copy_fits(c->pw_planes_fm.bytes, (size_t)s->n_alloc * 2 * (size_t)s->d_pad)) return MVS_OK;   // row-major kernels
+        int rc = ensure_buf(c, c->pw_planes_fm, (size_t)s->n_alloc * 2 * (size_t)s->d_pad);
         if (rc) return rc;
-        mvs::launch_coarse_fm(c->stream, s->planes, s->n_alloc, s->d_pad, (int8_t*)c->pw_planes_fm, 2);
+        mvs::launch_coarse_fm(c->stream, s->planes, s->n_alloc, s->d_pad, (int8_t*)c->pw_planes_fm.p, 2);
         ++c->dv_planes_fm_builds;
         rc = check_kernel("k_coarse_fm(limb planes)");
         if (rc) return rc;
         c->planes_fm_id = s->id;
         c->planes_fm_gen = s->gen;
     }
-    a.planes_fm = (const int8_t*)c->pw_planes_fm;
+    a.planes_fm = (const int8_t*)c->pw_planes_fm.p;
     return MVS_OK;
 }
 
 // One comparison of rows [rb,re) x columns [cb,ce) appending to `raw` (device) after the first `start`
-// cells; the running count is left in c->d_counter[0].  Two-stage (filter + exact re-check of the
+// cells; the running count is left in c->counters()[0].  Two-stage (filter + exact re-check of the
 // candidates) when the set allows it, otherwise the exact MFMA / vector-ALU kernel on every cell.
 // Streamed output (mvs_pairwise_stream): kept cells as packed 64-bit words (mvs_internal.h: PairwiseArgs::packed) in a
 // grow-only buffer of the context that the launch sizes itself, so that a comparison never has to be repeated because its
@@ -144,25 +144,20 @@ int tile_order_for(mvs_ctx* c, const mvs::PairwiseArgs& a, const mvs::PlanSegs& 
     if (!hit) {
         if (c->tile_orders.size() >= 64) {                         // (other shapes every time: start over)
             HIP_TRY(hipDeviceSynchronize());
-            for (mvs_tile_order& o : c->tile_orders)
-                if (o.d) (void)hipFree(o.d);
             c->tile_orders.clear();
         }
         mvs_tile_order o;
         o.key = key;
         std::vector<unsigned> list;
-        if (mvs::plan_tile_order(a, segs, &list, &o.per)) {
-            if (hipMalloc((void**)&o.d, list.size() * 4) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of a tile order failed");
-            const hipError_t e = hipMemcpy(o.d, list.data(), list.size() * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(o.d);
-                return fail(MVS_E_HIP, "uploading a tile order: %s", hipGetErrorString(e));
-            }
+        if (mvs::plan_tile_order(a, segs, &list, &o.per) && !list.empty()) {
+            if (o.d.alloc(list.size() * 4) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of a tile order failed");
+            const hipError_t e = hipMemcpy(o.d.p, list.data(), list.size() * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) return fail(MVS_E_HIP, "uploading a tile order: %s", hipGetErrorString(e));
         }
         c->tile_orders.push_back(std::move(o));
         hit = &c->tile_orders.back();
     }
-    *d = hit->d;
+    *d = hit->d.as<unsigned>();
     *per = hit->per;
     return MVS_OK;
 }
@@ -186,7 +181,7 @@ void fill_args(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int keep
     a.norms_sq = d_n2;
     a.keep_mode = keep_mode;
     a.keep_coeff = keep_coeff;
-    a.counter = c->d_counter;
+    a.counter = c->counters();
     a.dots = nullptr;
     a.mirror_all = mirror_all ? 1 : 0;
     a.debug_flags = opt.pairwise_debug;
@@ -233,8 +228,8 @@ int dots_stats_out(const mvs_ctx* c, DotsStats mvs_ctx::*which, double* dots_ms,
 int set_cell_count(mvs_ctx* c, unsigned long long start) {
     if (start == kKeepCount) return MVS_OK;
     c->h_start = start;   // outlives the asynchronous copy
-    if (start == 0) HIP_TRY(hipMemsetAsync(c->d_counter, 0, 8, c->stream));
-    else HIP_TRY(hipMemcpyAsync(c->d_counter, &c->h_start, 8, hipMemcpyHostToDevice, c->stream));
+    if (start == 0) HIP_TRY(hipMemsetAsync(c->counters(), 0, 8, c->stream));
+    else HIP_TRY(hipMemcpyAsync(c->counters(), &c->h_start, 8, hipMemcpyHostToDevice, c->stream));
     return MVS_OK;
 }
 
@@ -249,10 +244,10 @@ int two_stage_filter(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, do
     const double block_cells = (double)(a.row_end - a.row_begin) * (double)(a.col_end - a.col_begin);
     int rc = prepare_coarse(c, s);
     if (rc) return rc;
-    rc = ensure_buf(c, &c->pw_fmeta, &c->pw_fmeta_bytes, (size_t)s->n_alloc * sizeof(float4));
+    rc = ensure_buf(c, c->pw_fmeta, (size_t)s->n_alloc * sizeof(float4));
     if (rc) return rc;
-    mvs::launch_filter_meta(c->stream, (const mvs::CoarseRow*)c->pw_rows, d_n2, s->n, s->n_alloc, s->d, keep_coeff,
-                            (float4*)c->pw_fmeta);
+    mvs::launch_filter_meta(c->stream, (const mvs::CoarseRow*)c->pw_rows.p, d_n2, s->n, s->n_alloc, s->d, keep_coeff,
+                            (float4*)c->pw_fmeta.p);
     rc = check_kernel("k_filter_meta");
     if (rc) return rc;
     const bool forced = opt.pairwise_filter == 2;
@@ -285,55 +280,55 @@ int two_stage_filter(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, do
         if (ts.tiles) cand_want = (int64_t)std::min(268435456.0, std::max(1048576.0, tiles_to_do * 8.0 * (double)opt.tile_dense_thr));
         else cand_want = (int64_t)limit;
     }
-    rc = ensure_buf(c, &c->pw_cand, &c->pw_cand_bytes, (size_t)cand_want * sizeof(int2));
+    rc = ensure_buf(c, c->pw_cand, (size_t)cand_want * sizeof(int2));
     if (rc) return rc;
-    a.coarse = (const int8_t*)c->pw_coarse;
+    a.coarse = (const int8_t*)c->pw_coarse.p;
     a.coarse_fm = nullptr;
     if (opt.fragment_major && mvs::filter_streams(a, opt)) {
         bool made = false;
         rc = prepare_coarse_fm(c, s, &made);
         if (rc) return rc;
-        if (made) a.coarse_fm = (const int8_t*)c->pw_coarse_fm;
+        if (made) a.coarse_fm = (const int8_t*)c->pw_coarse_fm.p;
     }
-    a.fmeta = (const float4*)c->pw_fmeta;
-    a.cand_counter = c->d_counter + 2;
+    a.fmeta = (const float4*)c->pw_fmeta.p;
+    a.cand_counter = c->counters() + 2;
     a.cand_limit = limit;
-    a.cand_stop = reinterpret_cast<unsigned int*>(c->d_counter + 32);
-    a.recheck_queue = c->d_counter + 128;
+    a.cand_stop = reinterpret_cast<unsigned int*>(c->counters() + 32);
+    a.recheck_queue = c->counters() + 128;
     a.recheck_mode = opt.recheck_mode;
     const int64_t n_regions = mvs::filter_region_count(a, opt);
     if (n_regions > 0) {
-        rc = ensure_buf(c, &c->pw_chdr, &c->pw_chdr_bytes, (size_t)n_regions * 4);
+        rc = ensure_buf(c, c->pw_chdr, (size_t)n_regions * 4);
         if (rc) return rc;
-        rc = ensure_buf(c, &c->pw_cent, &c->pw_cent_bytes, (size_t)n_regions * mvs::kCandRegion * sizeof(int2));
+        rc = ensure_buf(c, c->pw_cent, (size_t)n_regions * mvs::kCandRegion * sizeof(int2));
         if (rc) return rc;
-        a.cand_hdr = (unsigned int*)c->pw_chdr;
-        a.cand_ent = (int2*)c->pw_cent;
+        a.cand_hdr = (unsigned int*)c->pw_chdr.p;
+        a.cand_ent = (int2*)c->pw_cent.p;
     }
     const size_t n_tiles = (size_t)ts.n_tr * (size_t)ts.n_tc;
     if (ts.tiles) {
         if (!ts.ext_flags) {
-            rc = ensure_buf(c, &c->pw_tflag, &c->pw_tflag_bytes, n_tiles * 4);
+            rc = ensure_buf(c, c->pw_tflag, n_tiles * 4);
             if (rc) return rc;
         }
-        rc = ensure_buf(c, &c->pw_trow, &c->pw_trow_bytes, (size_t)ts.n_tr * 4);
+        rc = ensure_buf(c, c->pw_trow, (size_t)ts.n_tr * 4);
         if (rc) return rc;
-        a.tile_flag = ts.ext_flags ? ts.ext_flags : (unsigned int*)c->pw_tflag;
+        a.tile_flag = ts.ext_flags ? ts.ext_flags : (unsigned int*)c->pw_tflag.p;
         a.tile_flag_ld = ts.n_tc;
         a.tile_dense_thr = (unsigned)opt.tile_dense_thr;
-        a.tile_flag_count = reinterpret_cast<unsigned int*>(c->d_counter + 8);
+        a.tile_flag_count = reinterpret_cast<unsigned int*>(c->counters() + 8);
         a.tile_flag_limit = forced ? 0xffffffffu : (unsigned)std::min(4.0e9, std::max(64.0, 0.7 * tiles_to_do));
     }
     std::vector<int> row_count((size_t)(ts.tiles ? ts.n_tr : 0));
     unsigned long long back[33];
     for (int attempt = 0;; ++attempt) {
-        a.cand = (int2*)c->pw_cand;
-        a.cand_capacity = c->pw_cand_bytes / sizeof(int2);
+        a.cand = (int2*)c->pw_cand.p;
+        a.cand_capacity = c->pw_cand.bytes / sizeof(int2);
         // cell count, (debug), candidate count, ..., pruned count [6], flagged tiles [8] ... stop flag [32]; NOT words 3
         // and 4 (the streamed output's "wide q" and "q beyond a byte" flags: a block's flag must survive the next block's
         // filter pass, which is queued before the block's rows are read)
-        HIP_TRY(hipMemsetAsync(c->d_counter + 1, 0, 16, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_counter + 5, 0, 224, c->stream));
+        HIP_TRY(hipMemsetAsync(c->counters() + 1, 0, 16, c->stream));
+        HIP_TRY(hipMemsetAsync(c->counters() + 5, 0, 224, c->stream));
         rc = set_cell_count(c, start);
         if (rc) return rc;
         HIP_TRY(hipMemsetAsync(a.recheck_queue, 0, 512, c->stream));
@@ -362,13 +357,13 @@ int two_stage_filter(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, do
             if (rc) return rc;
         }
         if (ts.tiles) {
-            mvs::launch_tile_count(c->stream, a.tile_flag, ts.n_tr, ts.n_tc, (int*)c->pw_trow);
+            mvs::launch_tile_count(c->stream, a.tile_flag, ts.n_tr, ts.n_tc, (int*)c->pw_trow.p);
             rc = check_kernel("k_tile_count");
             if (rc) return rc;
         }
         // one host synchronisation between the stages: the later launches are sized from these counts
-        rc = read_back(c, c->stream, {{back, c->d_counter, sizeof(back)},
-                                      {row_count.data(), c->pw_trow, ts.tiles ? (size_t)ts.n_tr * 4 : 0}});
+        rc = read_back(c, c->stream, {{back, c->counters(), sizeof(back)},
+                                      {row_count.data(), c->pw_trow.p, ts.tiles ? (size_t)ts.n_tr * 4 : 0}});
         if (rc) return rc;
         ts.n_cand = back[2];
         c->last_candidates = ts.n_cand;
@@ -382,7 +377,7 @@ int two_stage_filter(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, do
         }
         if (ts.n_cand <= a.cand_capacity) break;
         if (attempt >= 2) return fail(MVS_E_HIP, "internal: the candidate list keeps outgrowing its buffer");
-        rc = ensure_buf(c, &c->pw_cand, &c->pw_cand_bytes, (size_t)ts.n_cand * sizeof(int2));
+        rc = ensure_buf(c, c->pw_cand, (size_t)ts.n_cand * sizeof(int2));
         if (rc) return rc;
     }
     ts.n_flagged = 0;
@@ -393,29 +388,29 @@ int two_stage_filter(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, do
     if (ts.tiles) ts.n_flagged = ts.row_first[(size_t)ts.n_tr];
     c->last_flagged_tiles = ts.n_flagged;
     if (ts.n_flagged > 0) {
-        rc = ensure_buf(c, &c->pw_tlist, &c->pw_tlist_bytes, ((size_t)ts.n_flagged + 1) * 4);
+        rc = ensure_buf(c, c->pw_tlist, ((size_t)ts.n_flagged + 1) * 4);
         if (rc) return rc;
-        mvs::launch_tile_list(c->stream, a.tile_flag, ts.n_tr, ts.n_tc, (const int*)c->pw_trow, (int*)c->pw_tlist);
+        mvs::launch_tile_list(c->stream, a.tile_flag, ts.n_tr, ts.n_tc, (const int*)c->pw_trow.p, (int*)c->pw_tlist.p);
         rc = check_kernel("k_tile_list");
         if (rc) return rc;
-        ts.d_list = (const int*)c->pw_tlist + 1;
+        ts.d_list = (const int*)c->pw_tlist.p + 1;
         if (ts.n_cand > 0) {   // pairs that other waves of a flagged tile listed: those cells come from the exact kernel
-            rc = ensure_buf(c, &c->pw_cand2, &c->pw_cand2_bytes, (size_t)ts.n_cand * sizeof(int2));
+            rc = ensure_buf(c, c->pw_cand2, (size_t)ts.n_cand * sizeof(int2));
             if (rc) return rc;
-            mvs::launch_cand_prune(c->stream, a, ts.n_cand, (int2*)c->pw_cand2, c->d_counter + 6);
+            mvs::launch_cand_prune(c->stream, a, ts.n_cand, (int2*)c->pw_cand2.p, c->counters() + 6);
             rc = check_kernel("k_cand_prune");
             if (rc) return rc;
-            a.cand = (int2*)c->pw_cand2;
-            a.cand_capacity = c->pw_cand2_bytes / sizeof(int2);
-            a.cand_counter = c->d_counter + 6;
+            a.cand = (int2*)c->pw_cand2.p;
+            a.cand_capacity = c->pw_cand2.bytes / sizeof(int2);
+            a.cand_counter = c->counters() + 6;
         }
         // the exact kernel's integer pre-test constants
-        rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
+        rc = ensure_buf(c, c->pw_thr, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
         if (rc) return rc;
-        mvs::launch_cand_thr(c->stream, d_n2, s->n, s->n_alloc, s->d, keep_coeff, (int32_t*)c->pw_thr);
+        mvs::launch_cand_thr(c->stream, d_n2, s->n, s->n_alloc, s->d, keep_coeff, (int32_t*)c->pw_thr.p);
         rc = check_kernel("k_cand_thr");
         if (rc) return rc;
-        a.cand_thr = (const int32_t*)c->pw_thr;
+        a.cand_thr = (const int32_t*)c->pw_thr.p;
     }
     ts.a = a;
     return MVS_OK;
@@ -514,8 +509,8 @@ int pairwise_launch(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int
     a.capacity = (unsigned long long)capacity;
     if (po) {
         a.cells = nullptr;
-        a.packed = (unsigned long long*)*po->buf;
-        a.capacity = *po->bytes / 8;
+        a.packed = po->buf->as<unsigned long long>();
+        a.capacity = po->buf->bytes / 8;
         a.pack_row0 = po->row0;
         a.pack_shift = po->shift;
     }
@@ -548,11 +543,11 @@ int pairwise_launch(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int
             if (po) {
                 // the output is sized between the stages: a kept cell is a candidate or the mirror image of one, or a cell
                 // of a flagged tile or of its mirror image
-                rc = ensure_buf(c, po->buf, po->bytes,
+                rc = ensure_buf(c, *po->buf,
                                 (size_t)(start + 2 * ts.n_cand + (unsigned long long)ts.n_flagged * 131072ULL + 64) * 8);
                 if (rc) return rc;
-                ts.a.packed = (unsigned long long*)*po->buf;
-                ts.a.capacity = *po->bytes / 8;
+                ts.a.packed = po->buf->as<unsigned long long>();
+                ts.a.capacity = po->buf->bytes / 8;
             }
             rc = two_stage_recheck(c, ts);
             if (rc) return rc;
@@ -562,12 +557,12 @@ int pairwise_launch(mvs_ctx* c, const mvs_sketch_set* s, const double* d_n2, int
     }
     c->last_candidates = 0;
     if (po && po->two_stage_only) return kNeedExact;
-    rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
+    rc = ensure_buf(c, c->pw_thr, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
     if (rc) return rc;
-    mvs::launch_cand_thr(c->stream, d_n2, s->n, s->n_alloc, s->d, keep_coeff, (int32_t*)c->pw_thr);
+    mvs::launch_cand_thr(c->stream, d_n2, s->n, s->n_alloc, s->d, keep_coeff, (int32_t*)c->pw_thr.p);
     rc = check_kernel("k_cand_thr");
     if (rc) return rc;
-    a.cand_thr = (const int32_t*)c->pw_thr;
+    a.cand_thr = (const int32_t*)c->pw_thr.p;
     rc = set_cell_count(c, start);
     if (rc) return rc;
     rc = attach_planes_fm(c, s, a, mvs::exact_reads_fm(a, opt));
@@ -589,9 +584,9 @@ int sort_on_device(mvs_ctx* c, mvs_cell* in, int64_t n, mvs_cell* out) {
     size_t need = 0;
     int rc = mvs::sort_cells(c->stream, in, out, n, nullptr, 0, &need, c->opt);
     if (rc) return fail(rc, "sort sizing failed");
-    rc = ensure_buf(c, &c->pw_sort, &c->pw_sort_bytes, need);
+    rc = ensure_buf(c, c->pw_sort, need);
     if (rc) return rc;
-    rc = mvs::sort_cells(c->stream, in, out, n, c->pw_sort, c->pw_sort_bytes, nullptr, c->opt);
+    rc = mvs::sort_cells(c->stream, in, out, n, c->pw_sort.p, c->pw_sort.bytes, nullptr, c->opt);
     if (rc) return fail(rc, "sort failed");
     return MVS_OK;
 }
@@ -626,12 +621,12 @@ int mvs_pairwise_rows(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_s
     }
     mvs_cell* d_cells = cells;
     if (mem_cells == MVS_MEM_HOST) {   // sorted cells are staged in a grow-only device buffer of the context
-        int rc0 = ensure_buf(c, &c->pw_out, &c->pw_out_bytes, (size_t)std::max<int64_t>(capacity, 1) * sizeof(mvs_cell));
+        int rc0 = ensure_buf(c, c->pw_out, (size_t)std::max<int64_t>(capacity, 1) * sizeof(mvs_cell));
         if (rc0) return rc0;
-        d_cells = (mvs_cell*)c->pw_out;
+        d_cells = (mvs_cell*)c->pw_out.p;
     }
     // kept cells are appended (unordered) to a staging buffer and merge-sorted into the caller's
-    int rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)std::max<int64_t>(capacity, 1) * sizeof(mvs_cell));
+    int rc = ensure_buf(c, c->pw_tmp, (size_t)std::max<int64_t>(capacity, 1) * sizeof(mvs_cell));
     if (rc) return rc;
     // Very large shards go through in row chunks of at most 2^40 cells (chunk borders on multiples of 256 rows so
     // that every chunk can use the symmetric schedule): that bounds the candidate list of the two-stage
@@ -643,12 +638,12 @@ int mvs_pairwise_rows(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_s
     for (int64_t rb = row_begin; rb < row_end;) {
         const int64_t re = std::min(row_end, (rb / 256) * 256 + chunk_rows);
         unsigned long long got = 0;
-        rc = pairwise_launch(c, s, d_n2, keep_mode, rb, re, 0, s->n, true, false, (mvs_cell*)c->pw_tmp, capacity, count,
+        rc = pairwise_launch(c, s, d_n2, keep_mode, rb, re, 0, s->n, true, false, (mvs_cell*)c->pw_tmp.p, capacity, count,
                              &got);
         if (rc) return rc;
         if (got == ~0ULL) {
             {
-                const int rb_rc = read_back(c, c->stream, {{&got, c->d_counter, 8}});
+                const int rb_rc = read_back(c, c->stream, {{&got, c->counters(), 8}});
                 if (rb_rc) return rb_rc;
             }
         }
@@ -660,7 +655,7 @@ int mvs_pairwise_rows(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_s
         return fail(MVS_E_CAPACITY, "%llu cells kept but capacity is %lld", count, (long long)capacity);
     if (count == 0) return MVS_OK;
     // order by (row, col): the per-row ascending-column order of the reference's result list
-    rc = sort_on_device(c, (mvs_cell*)c->pw_tmp, (int64_t)count, d_cells);
+    rc = sort_on_device(c, (mvs_cell*)c->pw_tmp.p, (int64_t)count, d_cells);
     if (rc) return rc;
     if (mem_cells == MVS_MEM_HOST) {
         HIP_TRY(hipMemcpyAsync(cells, d_cells, (size_t)count * sizeof(mvs_cell), hipMemcpyDeviceToHost, c->stream));
@@ -694,7 +689,7 @@ int mvs_pairwise_block(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_
     if (rc) return rc;
     if (count == ~0ULL) {
         {
-            const int rb_rc = read_back(c, c->stream, {{&count, c->d_counter, 8}});
+            const int rb_rc = read_back(c, c->stream, {{&count, c->counters(), 8}});
             if (rb_rc) return rb_rc;
         }
     }
@@ -715,16 +710,16 @@ int mvs_search_block(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq
     if (row_begin == row_end || col_begin == col_end) return MVS_OK;
     if (!norms_sq || (capacity > 0 && !cells)) return fail(MVS_E_INVALID, "NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_buf(c, &c->pw_tmp, &c->pw_tmp_bytes, (size_t)std::max<int64_t>(capacity, 1) * sizeof(mvs_cell));
+    int rc = ensure_buf(c, c->pw_tmp, (size_t)std::max<int64_t>(capacity, 1) * sizeof(mvs_cell));
     if (rc) return rc;
     // J > j  <=>  (P/d) / (n2r + n2c - P/d) > j  <=>  double(P)/d > j/(1+j) * (n2r + n2c)   (for n2r + n2c > P/d >= 0)
     unsigned long long count = 0;
     rc = pairwise_launch(c, s, norms_sq, MVS_KEEP_INT16, row_begin, row_end, col_begin, col_end, false, false,
-                         (mvs_cell*)c->pw_tmp, capacity, 0, &count, jaccard_min / (1.0 + jaccard_min));
+                         (mvs_cell*)c->pw_tmp.p, capacity, 0, &count, jaccard_min / (1.0 + jaccard_min));
     if (rc) return rc;
     if (count == ~0ULL) {
         {
-            const int rb_rc = read_back(c, c->stream, {{&count, c->d_counter, 8}});
+            const int rb_rc = read_back(c, c->stream, {{&count, c->counters(), 8}});
             if (rb_rc) return rb_rc;
         }
     }
@@ -732,7 +727,7 @@ int mvs_search_block(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq
     if ((int64_t)count > capacity)
         return fail(MVS_E_CAPACITY, "%llu hits but capacity is %lld", count, (long long)capacity);
     if (count == 0) return MVS_OK;
-    rc = sort_on_device(c, (mvs_cell*)c->pw_tmp, (int64_t)count, cells);
+    rc = sort_on_device(c, (mvs_cell*)c->pw_tmp.p, (int64_t)count, cells);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));   // documented synchronous: `cells` is final on return
     return MVS_OK;

@@ -15,9 +15,9 @@ struct mvs_derep {
     mvs_ctx* ctx = nullptr;
     int64_t n = 0;
     int64_t decided = 0;                     // rows [0, decided) are final
-    int32_t* words = nullptr;                // state | assign | blocked, n each
-    int2* link = nullptr;
-    unsigned long long* counters = nullptr;  // mvs_internal.h: DerepState
+    DevBuf words;                            // int32_t: state | assign | blocked, n each
+    DevBuf link;                             // int2
+    DevBuf counters;                         // unsigned long long (mvs_internal.h: DerepState)
 };
 
 namespace {
@@ -26,11 +26,11 @@ mvs::DerepState state_of(const mvs_derep* k) {
     mvs::DerepState s;
     const size_t words = (size_t)std::max<int64_t>(k->n, 1);
     s.n = k->n;
-    s.state = k->words;
-    s.assign = k->words + words;
-    s.blocked = k->words + 2 * words;
-    s.link = k->link;
-    s.counters = k->counters;
+    s.state = k->words.as<int32_t>();
+    s.assign = k->words.as<int32_t>() + words;
+    s.blocked = k->words.as<int32_t>() + 2 * words;
+    s.link = k->link.as<int2>();
+    s.counters = k->counters.as<unsigned long long>();
     return s;
 }
 
@@ -46,7 +46,7 @@ int consume_rows(mvs_derep* k, const mvs_cell* d_cells, int64_t n_cells, int64_t
     int rc = timer.begin(c);
     if (rc) return rc;
     const mvs::DerepState s = state_of(k);
-    HIP_TRY(hipMemsetAsync(k->counters, 0, 3 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(k->counters.as<unsigned long long>(), 0, 3 * sizeof(unsigned long long), c->stream));
     rc = mvs::launch_derep_pre(c->stream, s, d_cells, n_cells, rb, re);
     if (!rc) rc = check_kernel("k_derep_pre");
     if (rc) return rc;
@@ -57,11 +57,11 @@ int consume_rows(mvs_derep* k, const mvs_cell* d_cells, int64_t n_cells, int64_t
         rc = mvs::launch_derep_scan(c->stream, s, d_cells, n_cells, rb, re, (int)round);
         if (!rc) rc = check_kernel("k_derep_scan");
         if (rc) return rc;
-        if (round > 1) HIP_TRY(hipMemsetAsync(k->counters + 2, 0, sizeof(unsigned long long), c->stream));
+        if (round > 1) HIP_TRY(hipMemsetAsync(k->counters.as<unsigned long long>() + 2, 0, sizeof(unsigned long long), c->stream));
         rc = mvs::launch_derep_decide(c->stream, s, rb, re, (int)round);
         if (!rc) rc = check_kernel("k_derep_decide");
         if (rc) return rc;
-        rc = read_back(c, c->stream, {{back, k->counters, sizeof(back)}});
+        rc = read_back(c, c->stream, {{back, k->counters.as<unsigned long long>(), sizeof(back)}});
         if (rc) return rc;
         if (back[2] == 0) break;
         // every round decides the earliest undecided row: a block of R rows is through after R rounds (a path in priority order)
@@ -128,17 +128,17 @@ int mvs_sketch_set_gather(mvs_ctx* c, const mvs_sketch_set* src, const int32_t* 
             if (e == hipSuccess) e = hipMemcpyAsync(dr.p, rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream);
             d_rows = (const int32_t*)dr.p;
         }
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_counter, 0, 8, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->counters(), 0, 8, c->stream);
         if (e != hipSuccess) {
             mvs_sketch_set_destroy(s);
             return fail(MVS_E_HIP, "staging the row list: %s", hipGetErrorString(e));
         }
         // a row is planes x d_pad contiguous bytes whatever the limb code means; d_pad is a multiple of 128
         const int64_t row_bytes = (int64_t)mvs::planes_of(src->limbs) * src->d_pad;
-        rc = mvs::launch_gather_rows(c->stream, src->planes, src->n, d_rows, n_rows, row_bytes, s->owned, c->d_counter);
+        rc = mvs::launch_gather_rows(c->stream, src->planes, src->n, d_rows, n_rows, row_bytes, s->owned.as<int8_t>(), c->counters());
         if (!rc) rc = check_kernel("k_gather_rows");
         unsigned long long bad = 0;
-        if (!rc) rc = read_back(c, c->stream, {{&bad, c->d_counter, 8}});   // (synchronises: the staged list may go)
+        if (!rc) rc = read_back(c, c->stream, {{&bad, c->counters(), 8}});   // (synchronises: the staged list may go)
         if (!rc && bad != 0)
             rc = fail(MVS_E_RANGE, "%llu of the %lld rows lie outside [0, %lld)", bad, (long long)n_rows, (long long)src->n);
         if (rc) {
@@ -156,24 +156,18 @@ int mvs_derep_create(mvs_ctx* c, int64_t n, mvs_derep** out) {
     if (n < 0) return fail(MVS_E_INVALID, "n = %lld is negative", (long long)n);
     if (n >= (1LL << 31) - 256) return fail(MVS_E_RANGE, "n too large for int32 sample indices");
     HIP_TRY(hipSetDevice(c->device));
-    mvs_derep* k = new (std::nothrow) mvs_derep();
+    std::unique_ptr<mvs_derep> k(new (std::nothrow) mvs_derep());
     if (!k) return fail(MVS_E_NOMEM, "out of host memory");
     k->ctx = c;
     k->n = n;
     const size_t words = (size_t)std::max<int64_t>(n, 1);
-    if (hipMalloc((void**)&k->words, 3 * words * 4) != hipSuccess || hipMalloc((void**)&k->link, words * sizeof(int2)) != hipSuccess ||
-        hipMalloc((void**)&k->counters, 64) != hipSuccess) {
-        mvs_derep_destroy(k);
+    if (k->words.alloc(3 * words * 4) != hipSuccess || k->link.alloc(words * sizeof(int2)) != hipSuccess || k->counters.alloc(64) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of the state of %lld samples failed", (long long)n);
-    }
-    int rc = mvs::launch_derep_init(c->stream, state_of(k));
+    int rc = mvs::launch_derep_init(c->stream, state_of(k.get()));
     if (!rc) rc = check_kernel("k_derep_init");
-    if (rc) {
-        mvs_derep_destroy(k);
-        return rc;
-    }
+    if (rc) return rc;
     c->dr.reset();
-    *out = k;
+    *out = k.release();
     return MVS_OK;
 }
 
@@ -223,13 +217,13 @@ int mvs_derep_finish(mvs_derep* k, const int32_t* order, int mem_order, int32_t*
     StageTimer timer;
     int rc = timer.begin(c);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(k->counters + 3, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(k->counters.as<unsigned long long>() + 3, 0, 2 * sizeof(unsigned long long), c->stream));
     unsigned long long back[2] = {0, 0};
     if (d_order) {
         HIP_TRY(hipMemsetAsync(d_sizes, 0, (size_t)n * 4, c->stream));
-        rc = mvs::launch_derep_order_check(c->stream, d_order, n, d_sizes, k->counters);
+        rc = mvs::launch_derep_order_check(c->stream, d_order, n, d_sizes, k->counters.as<unsigned long long>());
         if (!rc) rc = check_kernel("k_derep_order_check");
-        if (!rc) rc = read_back(c, c->stream, {{back, k->counters + 3, sizeof(back)}});
+        if (!rc) rc = read_back(c, c->stream, {{back, k->counters.as<unsigned long long>() + 3, sizeof(back)}});
         if (rc) return rc;
         if (back[1] != 0) return fail(MVS_E_INVALID, "order is not a permutation of [0, %lld): %llu bad entries", (long long)n, back[1]);
     }
@@ -239,7 +233,7 @@ int mvs_derep_finish(mvs_derep* k, const int32_t* order, int mem_order, int32_t*
     if (rc) return rc;
     rc = timer.mark_end();
     if (rc) return rc;
-    rc = read_back(c, c->stream, {{back, k->counters + 3, sizeof(back)}});
+    rc = read_back(c, c->stream, {{back, k->counters.as<unsigned long long>() + 3, sizeof(back)}});
     if (!rc) rc = timer.add_to(&c->dr.work_ms);
     if (rc) return rc;
     if (n_reps) *n_reps = (int64_t)back[0];
@@ -258,9 +252,6 @@ int mvs_derep_destroy(mvs_derep* k) {
         (void)hipSetDevice(k->ctx->device);
         (void)hipStreamSynchronize(k->ctx->stream);
     }
-    if (k->words) (void)hipFree(k->words);
-    if (k->link) (void)hipFree(k->link);
-    if (k->counters) (void)hipFree(k->counters);
     delete k;
     return MVS_OK;
 }

@@ -63,7 +63,7 @@ int mvs_gather(mvs_ctx* c, const mvs_hash_set* hs_query, int64_t query, const mv
     c->ga_survivors = c->ga_rounds = c->ga_batches = c->ga_row_bytes = c->ga_round_bytes = 0;
     c->ga_overlap_ms = c->ga_mark_ms = c->ga_rounds_ms = 0.0;
     int32_t q_size = 0;
-    HIP_TRY(hipMemcpyAsync(&q_size, hs_query->sizes + query, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&q_size, hs_query->sizes.as<int32_t>() + query, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (query_size) *query_size = q_size;
     if (max_matches == 0 || q_size == 0 || nc == 0) return MVS_OK;
@@ -115,18 +115,18 @@ int mvs_gather(mvs_ctx* c, const mvs_hash_set* hs_query, int64_t query, const mv
     const int unit = std::max(64, c->opt.intersect_unit & ~63);        // a word of a row belongs to one unit
     const size_t arr = (((size_t)ns + 1) * 8 + 255) & ~(size_t)255;
     size_t need = 0;
-    rc = mvs::isect_plan(c->stream, d_cells, ns, hs_query->sizes, hs_query->n, hs_db->sizes, hs_db->n, unit, nullptr, nullptr, d_count,
-                         false, nullptr, nullptr, 0, &need);
+    rc = mvs::isect_plan(c->stream, d_cells, ns, hs_query->sizes.as<int32_t>(), hs_query->n, hs_db->sizes.as<int32_t>(), hs_db->n, unit,
+                         nullptr, nullptr, d_count, false, nullptr, nullptr, 0, &need);
     if (rc) return fail(rc, "gather: scan sizing failed");
-    rc = ensure_buf(c, &c->ix_work, &c->ix_work_bytes, 256 + 2 * arr + need);
+    rc = ensure_buf(c, c->ix_work, 256 + 2 * arr + need);
     if (rc) return rc;
-    unsigned long long* d_counters = (unsigned long long*)c->ix_work;
-    long long* d_units = (long long*)((char*)c->ix_work + 256);
-    long long* d_start = (long long*)((char*)c->ix_work + 256 + arr);
-    void* d_scan = (char*)c->ix_work + 256 + 2 * arr;
+    unsigned long long* d_counters = (unsigned long long*)c->ix_work.p;
+    long long* d_units = (long long*)((char*)c->ix_work.p + 256);
+    long long* d_start = (long long*)((char*)c->ix_work.p + 256 + arr);
+    void* d_scan = (char*)c->ix_work.p + 256 + 2 * arr;
     HIP_TRY(hipMemsetAsync(d_counters, 0, 32, c->stream));
-    rc = mvs::isect_plan(c->stream, d_cells, ns, hs_query->sizes, hs_query->n, hs_db->sizes, hs_db->n, unit, d_units, d_start, d_count,
-                         false, d_counters, d_scan, need, nullptr);
+    rc = mvs::isect_plan(c->stream, d_cells, ns, hs_query->sizes.as<int32_t>(), hs_query->n, hs_db->sizes.as<int32_t>(), hs_db->n, unit,
+                         d_units, d_start, d_count, false, d_counters, d_scan, need, nullptr);
     if (rc) return fail(rc, "gather: planning the units failed");
     if ((rc = check_kernel("k_isect_count"))) return rc;
     long long n_units = 0;
@@ -134,8 +134,9 @@ int mvs_gather(mvs_ctx* c, const mvs_hash_set* hs_query, int64_t query, const mv
     StageTimer t_mark, t_rounds;
     if ((rc = t_mark.begin(c))) return rc;
     HIP_TRY(hipMemsetAsync(d_rows, 0, row_bytes, c->stream));
-    rc = mvs::launch_gather_mark(c->stream, d_cells, ns, d_start, n_units, hs_query->hashes, hs_query->offsets, hs_query->sizes,
-                                 hs_db->hashes, hs_db->offsets, hs_db->sizes, unit, d_rows, W);
+    rc = mvs::launch_gather_mark(c->stream, d_cells, ns, d_start, n_units, hs_query->hashes.as<unsigned long long>(),
+                                 hs_query->offsets.as<long long>(), hs_query->sizes.as<int32_t>(), hs_db->hashes.as<unsigned long long>(),
+                                 hs_db->offsets.as<long long>(), hs_db->sizes.as<int32_t>(), unit, d_rows, W);
     if (!rc) rc = check_kernel("k_gather_mark");
     if (rc) return rc;
     if ((rc = t_mark.mark_end())) return rc;

@@ -31,7 +31,7 @@ int engine_alloc(mvs_ctx* c, int64_t m, size_t extra, Engine& e) {
     const size_t table_bytes = (size_t)m * (size_t)ld * 8;
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (table_bytes + extra + (size_t)ld * 64 > free_b || hipMalloc(&e.table.p, table_bytes) != hipSuccess) {
+    if (table_bytes + extra + (size_t)ld * 64 > free_b || e.table.alloc(table_bytes) != hipSuccess) {
         (void)hipGetLastError();
         return fail(MVS_E_NOMEM, "the table of %lld slots needs %zu bytes and the dots block %zu: %zu asked for, %zu free on the device",
                     (long long)m, table_bytes, extra, table_bytes + extra, free_b);

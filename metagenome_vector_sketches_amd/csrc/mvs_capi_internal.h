@@ -26,12 +26,19 @@
 
 #include "mvs_encode.h"
 #include "mvs_internal.h"
+#include "mvs_owned.h"
+
+// the ABI's objects are declared outside the namespace (include/mvs_hip.h names them)
+using mvs_capi::DevBuf;
+using mvs_capi::Event;
+using mvs_capi::PinnedBuf;
+using mvs_capi::Stream;
 
 // a balanced tile order of a filter launch (mvs::plan_tile_order), cached by launch geometry: the comparisons of a job repeat
 // the same few shapes, so a list is built and uploaded once
 struct mvs_tile_order {
     std::vector<long long> key;
-    unsigned* d = nullptr;            // NULL: the static map serves this shape
+    DevBuf d;                         // unsigned; empty: the static map serves this shape
     unsigned per = 0;
 };
 
@@ -104,72 +111,66 @@ struct TsneStats {
 }  // namespace mvs_capi
 
 struct mvs_ctx {
+    mvs_ctx() = default;
+    ~mvs_ctx();   // waits for `stream`; the members release what they own
     int device = 0;
-    std::vector<mvs_tile_order> tile_orders;
-    mvs::Options opt;   // tuning switches: environment defaults read once at creation, then mvs_ctx_set_option
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    // timing of the dominant kernels (optional)
-    bool timing = false;
+    // the streams and events stand before every buffer, so that they are destroyed after the memory their work may use
+    Stream own_stream;
+    hipStream_t stream = nullptr;   // own_stream, or the caller's (mvs_ctx_set_stream)
     // event pairs: 0 projection kernel, 1 whole comparison (filter + re-check, or the exact kernel),
     // 2 the filter kernel alone, 3 the re-check kernel alone
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Event ev[8];
+    // streamed output (mvs_pairwise_stream): the download side
+    Stream dl_stream;
+    Event dl_done[2];    // download into pinned buffer i has completed
+    Event dl_block[2];   // the downloads out of CSR array set i have completed
+    Event dl_ready[2];   // the arrays of the row block in set i are final on the compute stream
+    Stream post_stream;  // dense row blocks -> CSR / encoded rows beside the next block's comparison
+    Event cmp_done;      // the comparison launch of the block about to be post-processed is through
+    Stream up_stream;    // host hash lists on their way to the device (below)
+    Event up_done[2];    // DMA out of staging buffer i has completed
+    Event pinned_ev;     // the upload out of `pinned` has completed
+    std::vector<mvs_tile_order> tile_orders;
+    mvs::Options opt;   // tuning switches: environment defaults read once at creation, then mvs_ctx_set_option
+    // timing of the dominant kernels (optional)
+    bool timing = false;
     bool ev_valid[5] = {false, false, false, false, false};   // [4]: exact kernel on the flagged tiles (ev[6]..ev[3])
     // reusable device scratch
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
-    unsigned long long* d_counter = nullptr;   // 8-byte slot for counters / max
+    DevBuf scratch;
+    DevBuf d_counter;                       // 8-byte slots for counters / max
+    unsigned long long* counters() const { return d_counter.as<unsigned long long>(); }
     // grow-only device buffers of mvs_pairwise_rows (no hipMalloc/hipFree on the hot path)
-    void* pw_thr = nullptr;   size_t pw_thr_bytes = 0;
-    void* pw_tmp = nullptr;   size_t pw_tmp_bytes = 0;
-    void* pw_sort = nullptr;  size_t pw_sort_bytes = 0;
-    void* pw_out = nullptr;   size_t pw_out_bytes = 0;
-    void* stage = nullptr;    size_t stage_bytes = 0;   // host sketches on their way to the limb planes
+    DevBuf pw_thr, pw_tmp, pw_sort, pw_out;
+    DevBuf stage;                           // host sketches on their way to the limb planes
     // two-stage comparison: coarse plane + row statistics of the set `coarse_id` (generation `coarse_gen`),
     // per-call filter constants, candidate list
-    void* pw_coarse = nullptr;  size_t pw_coarse_bytes = 0;
-    void* pw_coarse_fm = nullptr;  size_t pw_coarse_fm_bytes = 0;   // fragment-major copy (streaming search filters), built on demand
-    void* st_tlist = nullptr;  size_t st_tlist_bytes = 0;    // dense row passes: active tiles per tile row of the block, their counts,
-    void* st_tlist_n = nullptr;  size_t st_tlist_n_bytes = 0;  // and every row's first / last kept column
-    void* st_ends = nullptr;  size_t st_ends_bytes = 0;
-    void* pw_need = nullptr;  size_t pw_need_bytes = 0;             // block plans: rows whose limb planes are to be rebuilt (mvs_plan_wire)
-    void* pw_planes_fm = nullptr;  size_t pw_planes_fm_bytes = 0;   // fragment-major copy of the limb planes of set planes_fm_id
+    DevBuf pw_coarse;
+    DevBuf pw_coarse_fm;                    // fragment-major copy (streaming search filters), built on demand
+    DevBuf st_tlist, st_tlist_n;            // dense row passes: active tiles per tile row of the block, their counts,
+    DevBuf st_ends;                         // and every row's first / last kept column
+    DevBuf pw_need;                         // block plans: rows whose limb planes are to be rebuilt (mvs_plan_wire)
+    DevBuf pw_planes_fm;                    // fragment-major copy of the limb planes of set planes_fm_id
     unsigned long long planes_fm_id = 0, planes_fm_gen = 0;         // (generation planes_fm_gen), for the ping-pong exact kernel
     bool coarse_fm_valid = false;           // ... of the cached plane
-    void* pw_rows = nullptr;    size_t pw_rows_bytes = 0;
-    void* pw_fmeta = nullptr;   size_t pw_fmeta_bytes = 0;
-    void* pw_cand = nullptr;    size_t pw_cand_bytes = 0;
+    DevBuf pw_rows, pw_fmeta, pw_cand;
     // streamed output (mvs_pairwise_stream): packed kept cells raw / sorted, their CSR form, the download side
-    void* st_raw = nullptr;     size_t st_raw_bytes = 0;
-    void* st_sorted = nullptr;  size_t st_sorted_bytes = 0;
-    void* st_col[2] = {nullptr, nullptr};     size_t st_col_bytes[2] = {0, 0};   // CSR arrays of two row blocks: one is
-    void* st_q[2] = {nullptr, nullptr};       size_t st_q_bytes[2] = {0, 0};     // downloaded while the next is built
-    void* st_rowptr = nullptr;  size_t st_rowptr_bytes = 0;
-    void* st_counts = nullptr;  size_t st_counts_bytes = 0;
-    void* st_dense = nullptr;   size_t st_dense_bytes = 0;  // dense results: one byte per cell (mvs_internal.h)
-    void* rb_pinned = nullptr;  size_t rb_bytes = 0;        // pinned landing zone of the small per-block read-backs (row index,
+    DevBuf st_raw, st_sorted;
+    DevBuf st_col[2], st_q[2];              // CSR arrays of two row blocks: one is downloaded while the next is built
+    DevBuf st_rowptr, st_counts;
+    DevBuf st_dense;                        // dense results: one byte per cell (mvs_internal.h)
+    PinnedBuf rb_pinned;                                    // pinned landing zone of the small per-block read-backs (row index,
                                                             // record offsets, counters): a copy into pageable memory makes the
                                                             // runtime stage and block per copy -- 5 of them per row block
     size_t st_dense_zero = 0;   // the first st_dense_zero bytes of st_dense are zero once the work queued on `stream` is through:
                                 // the tile-granular dense flow needs a cleared matrix, clears it again behind its last block --
                                 // while the link still drains -- and so finds it clean the next time
     // rows encoded on the device (mvs_pairwise_stream_encoded): per-row sizes / offsets / directory, the records themselves
-    void* en_size = nullptr;    size_t en_size_bytes = 0;
-    void* en_off = nullptr;     size_t en_off_bytes = 0;
-    void* en_jac = nullptr;     size_t en_jac_bytes = 0;
-    void* en_first = nullptr;   size_t en_first_bytes = 0;
-    void* en_par = nullptr;     size_t en_par_bytes = 0;
-    void* st_enc[2] = {nullptr, nullptr};     size_t st_enc_bytes[2] = {0, 0};
-    hipStream_t dl_stream = nullptr;
-    void* dl_pinned[2] = {nullptr, nullptr};      // pinned host buffers, each allocated (and grown) when first needed:
-    size_t dl_bytes[2] = {0, 0};                  // pinning costs ~0.3 ms per MiB, a one-piece result needs only one
-    hipEvent_t dl_done[2] = {nullptr, nullptr};   // download into pinned buffer i has completed
-    hipEvent_t dl_block[2] = {nullptr, nullptr};  // the downloads out of CSR array set i have completed
-    hipEvent_t dl_ready[2] = {nullptr, nullptr};  // the arrays of the row block in set i are final on the compute stream
-    void* dl_hsa = nullptr;                       // option stream_copy = 1: agents + completion signals of the DMA copies
-    void (*dl_hsa_free)(void*) = nullptr;         // (mvs_capi_stream.hip owns the type)
-    hipStream_t post_stream = nullptr;            // dense row blocks -> CSR / encoded rows beside the next block's comparison
-    hipEvent_t cmp_done = nullptr;                // the comparison launch of the block about to be post-processed is through
+    DevBuf en_size, en_off, en_jac, en_first, en_par;
+    DevBuf st_enc[2];
+    PinnedBuf dl_pinned[2];                       // pinned host buffers, each allocated (and grown) when first needed:
+                                                  // pinning costs ~0.3 ms per MiB, a one-piece result needs only one
+    std::unique_ptr<void, void (*)(void*)> dl_hsa{nullptr, nullptr};   // option stream_copy = 1: agents + completion signals of
+                                                                       // the DMA copies (mvs_capi_stream.hip owns the type)
     // what the last mvs_pairwise_stream did (mvs_ctx_stream_stats)
     double st_kernel_ms = 0.0;                    // comparison kernels, summed over the row blocks (timing enabled)
     long long st_bytes = 0, st_blocks = 0, st_pieces = 0, st_two_stage = 0;
@@ -179,15 +180,11 @@ struct mvs_ctx {
     long long st_dense_blocks = 0, st_spec_blocks = 0, st_spec_redone = 0, st_list_fallbacks = 0;
     // tile-granular two-stage comparison: tile flags, flagged tiles per tile row, their row-major list (entry 0 = total),
     // the candidate list without the pairs of flagged tiles
-    void* pw_tflag = nullptr;   size_t pw_tflag_bytes = 0;
-    void* pw_trow = nullptr;    size_t pw_trow_bytes = 0;
-    void* pw_tlist = nullptr;   size_t pw_tlist_bytes = 0;
-    void* pw_cand2 = nullptr;   size_t pw_cand2_bytes = 0;
-    void* pw_ttouch = nullptr;  size_t pw_ttouch_bytes = 0;   // dense byte matrix: tiles the re-check's cells were scattered into,
-    void* pw_tnew = nullptr;    size_t pw_tnew_bytes = 0;     // and the list of those touched for the first time (to be cleared)
+    DevBuf pw_tflag, pw_trow, pw_tlist, pw_cand2;
+    DevBuf pw_ttouch, pw_tnew;              // dense byte matrix: tiles the re-check's cells were scattered into, and the list of
+                                            // those touched for the first time (to be cleared)
     long long last_flagged_tiles = 0, last_filter_tiles = 0;   // of the last two-stage comparison (mvs_ctx_pairwise_stats)
-    void* pw_chdr = nullptr;    size_t pw_chdr_bytes = 0;   // candidate regions of the ping-pong filter: counts, entries
-    void* pw_cent = nullptr;    size_t pw_cent_bytes = 0;
+    DevBuf pw_chdr, pw_cent;                // candidate regions of the ping-pong filter: counts, entries
     unsigned long long coarse_id = 0, coarse_gen = 0;
     int coarse_mode = -1;                   // radix rule (option coarse_radix) the cached plane was built with
     // derived data built / refreshed since the context was created (mvs_ctx_derived_stats): whole builds of the coarse plane,
@@ -201,10 +198,7 @@ struct mvs_ctx {
     unsigned long long h_start = 0;      // host copy of the starting cell count of an appending call
     // host hash lists on their way to the device: two pinned staging buffers + a copy stream, so that the host-side
     // copy into pinned memory, the DMA and the projection kernel of consecutive pieces overlap
-    void* up_pinned[2] = {nullptr, nullptr};
-    size_t up_bytes = 0;
-    hipStream_t up_stream = nullptr;
-    hipEvent_t up_done[2] = {nullptr, nullptr};   // DMA out of staging buffer i has completed
+    PinnedBuf up_pinned[2];
     // workgroups of k_project the device holds at a time, by [variant][statistics]: CUs x the occupancy of that instantiation,
     // asked for once (0: not yet) -- what mvs_project_plan balances a launch's last round against
     int cu_count = 0;
@@ -213,9 +207,7 @@ struct mvs_ctx {
     long long pj_units = 0, pj_cut_samples = 0;
     int pj_slots = 0, pj_ny = 0;
     // pinned host staging for small metadata uploads (projection unit lists)
-    void* pinned = nullptr;
-    size_t pinned_bytes = 0;
-    hipEvent_t pinned_ev = nullptr;
+    PinnedBuf pinned;
     bool pinned_busy = false;
     // block plans (mvs_plan_*): state between begin / filter / finish, scratch of mvs_sketch_set_prepare_rows, events
     int plan_overlap = 0;                 // block plans: 1 = filter launches alternate between the stream and a side stream
@@ -223,7 +215,7 @@ struct mvs_ctx {
                                           // (measured at the per-rank size of an 8-way split: filters 1.191 -> 1.164 ms, within
                                           // the box-to-box spread; off by default -- one more queue beside RCCL's for 2 %)
     struct PlanState* plan = nullptr;
-    void* plan_tmp = nullptr;   size_t plan_tmp_bytes = 0;
+    DevBuf plan_tmp;
     const void* rows_max_done = nullptr;   // state block whose widest row mvs_cells_sort_rows_ahead has already computed
     // what the last mvs_pairwise_topk / _contain / _levels did (mvs_ctx_topk_stats, mvs_ctx_contain_stats, mvs_ctx_levels_stats)
     mvs_capi::DotsStats tk, ct, lv;
@@ -262,7 +254,7 @@ struct mvs_ctx {
                                           // the cell buffer's budget.  Host-side blocking only (option core_block_rows)
     // mvs_intersect_cells: grow-only work space (unit counts, their scan, the scan's scratch, counters) and what the last call
     // did (mvs_ctx_intersect_stats)
-    void* ix_work = nullptr;    size_t ix_work_bytes = 0;
+    DevBuf ix_work;
     double ix_kernel_ms = 0.0;
     long long ix_units = 0, ix_cut = 0, ix_bytes = 0;
     // what the last mvs_gather did (mvs_ctx_gather_stats): survivors of phase 0, rounds run, batches (= read-backs of the
@@ -286,16 +278,16 @@ struct mvs_hash_set {
     mvs_ctx* ctx = nullptr;
     int64_t n = 0, total = 0;
     int was_sorted = 0;
-    unsigned long long* hashes = nullptr;   // per sample strictly increasing
-    long long* offsets = nullptr;           // n + 1
-    int32_t* sizes = nullptr;               // n
-    uint32_t* abund = nullptr;              // aligned with hashes: the counted builds' abundances; NULL for every other set
+    DevBuf hashes;    // unsigned long long, per sample strictly increasing
+    DevBuf offsets;   // long long, n + 1
+    DevBuf sizes;     // int32_t, n
+    DevBuf abund;     // uint32_t aligned with hashes: the counted builds' abundances; empty for every other set
 };
 
 struct mvs_sketch_set {
     mvs_ctx* ctx = nullptr;
     const int8_t* planes = nullptr;
-    int8_t* owned = nullptr;
+    DevBuf owned;
     int64_t n = 0, n_alloc = 0;
     int d = 0, d_pad = 0, limbs = 0;
     unsigned long long id = 0, gen = 0;   // identity of the plane contents (cache key of derived data)
@@ -328,28 +320,10 @@ struct Range {
     ~Range();
 };
 
-// RAII device buffer used for staging host inputs / outputs
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-};
-
-// a pair of events around a stretch of kernels whose time a statistic reports
-struct EventPair {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~EventPair() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
 // The time of a stretch of kernels on the context's stream, for a statistic.  With timing off every method does nothing: a
 // call site synchronises exactly where it did without the timer.
 struct StageTimer {
-    EventPair ev;
+    Event ev[2];   // around the stretch
     hipStream_t stream = nullptr;
     bool on = false;
     // the stretch begins here
@@ -357,27 +331,29 @@ struct StageTimer {
         on = c->timing;
         if (!on) return MVS_OK;
         stream = c->stream;
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], stream));
+        for (Event& x : ev) HIP_TRY(x.create());
+        HIP_TRY(hipEventRecord(ev[0], stream));
         return MVS_OK;
     }
     // ... and ends here (nothing waits)
     int mark_end() {
-        if (on) HIP_TRY(hipEventRecord(ev.e[1], stream));
+        if (on) HIP_TRY(hipEventRecord(ev[1], stream));
         return MVS_OK;
     }
     // waits for the end mark (at once where the caller has synchronised the stream since) and adds the stretch's time
     int add_to(double* ms) {
         if (!on) return MVS_OK;
-        HIP_TRY(hipEventSynchronize(ev.e[1]));
+        HIP_TRY(hipEventSynchronize(ev[1]));
         float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, ev.e[0], ev.e[1]));
+        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
         *ms += t;
         return MVS_OK;
     }
 };
 
-int ensure_buf(mvs_ctx* c, void** p, size_t* have, size_t bytes);
+// the grow-only buffers of a context: `b` holds at least `bytes` afterwards.  A smaller block is freed -- once the work queued on
+// the context's stream is through -- before the larger one is asked for; MVS_E_NOMEM leaves the buffer empty
+int ensure_buf(mvs_ctx* c, DevBuf& b, size_t bytes);
 struct ReadBack {
     void* dst;
     const void* src;
@@ -408,8 +384,7 @@ int refresh_derived(mvs_ctx* c, const mvs_sketch_set* cs);
 // the balanced order of the launch `segs` describes with the kernel arguments `a` (option plan_order; *d == NULL: use the static map)
 int tile_order_for(mvs_ctx* c, const mvs::PairwiseArgs& a, const mvs::PlanSegs& segs, const unsigned** d, unsigned* per);
 struct PackedOut {
-    void** buf;
-    size_t* bytes;
+    DevBuf* buf;               // grows as needed (ensure_buf)
     int64_t row0;              // rows are stored relative to this one
     int shift;                 // row field starts at this bit (16 bits of q, then the column)
     bool two_stage_only;       // do not fall back to the exact kernel: return kNeedExact and let the caller plan row blocks
@@ -510,23 +485,19 @@ struct DotsBlocks {
     int algo = 0;
     DotsTexts txt{};
     DevBuf dots;
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~DotsBlocks() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
+    Event e[3];
     int init(mvs_ctx* ctx, const mvs_sketch_set* set, int64_t col_begin, int64_t col_end, int64_t block_rows, int dots_algo,
              const DotsTexts& texts) {
         c = ctx, s = set, cb = col_begin, ce = col_end, R = block_rows, algo = dots_algo, txt = texts;
         HIP_TRY(dots.alloc((size_t)R * (size_t)(ce - cb) * 4));
         if (c->timing)
-            for (hipEvent_t& x : e) HIP_TRY(hipEventCreate(&x));
+            for (Event& x : e) HIP_TRY(x.create());
         return MVS_OK;
     }
     // rows [rb, re); work_ms and blocks may be NULL (a consumer that times its own stages, or keeps no count)
     template <typename Work>
     int run(int64_t rb, int64_t re, double* dots_ms, double* work_ms, long long* blocks, Work&& work) {
-        int32_t* const d = (int32_t*)dots.p;
+        int32_t* const d = dots.as<int32_t>();
         for (int64_t r0 = rb; r0 < re; r0 += R) {
             const int64_t r1 = std::min(r0 + R, re);
             if (c->timing) HIP_TRY(hipEventRecord(e[0], c->stream));

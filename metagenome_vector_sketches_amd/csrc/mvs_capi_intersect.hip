@@ -12,14 +12,6 @@ namespace {
 
 constexpr int64_t kSortBatch = 1LL << 30;   // keys per segmented sort (rocprim counts them in 32 bits; a sample holds < 2^31)
 
-struct EventQuad {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~EventQuad() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
 struct SetGuard {
     mvs_hash_set* h;
     ~SetGuard() {
@@ -49,22 +41,22 @@ int sort_and_compact(mvs_ctx* c, mvs_hash_set* h, const std::vector<long long>& 
             HIP_TRY(hipMemcpyAsync(dseg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, c->stream));
             const unsigned int* d_begin = (const unsigned int*)dseg.p;
             size_t need = 0;
-            int rc = mvs::hs_sort_segments(c->stream, h->hashes + base, (unsigned long long*)sorted.p + base, count, segments, d_begin,
-                                           d_begin + 1, nullptr, 0, &need);
+            int rc = mvs::hs_sort_segments(c->stream, h->hashes.as<unsigned long long>() + base, (unsigned long long*)sorted.p + base,
+                                           count, segments, d_begin, d_begin + 1, nullptr, 0, &need);
             if (rc) return fail(rc, "hash set: sort sizing failed");
             HIP_TRY(dtmp.alloc(need));
-            rc = mvs::hs_sort_segments(c->stream, h->hashes + base, (unsigned long long*)sorted.p + base, count, segments, d_begin,
-                                       d_begin + 1, dtmp.p, need, nullptr);
+            rc = mvs::hs_sort_segments(c->stream, h->hashes.as<unsigned long long>() + base, (unsigned long long*)sorted.p + base, count,
+                                       segments, d_begin, d_begin + 1, dtmp.p, need, nullptr);
             if (rc) return fail(rc, "hash set: segmented sort failed");
             HIP_TRY(hipStreamSynchronize(c->stream));   // (before seg is rewritten and the DevBufs free their memory)
         }
         s0 = s1;
     }
-    int rc = mvs::launch_hs_count(c->stream, (const unsigned long long*)sorted.p, h->offsets, n, h->sizes);
+    int rc = mvs::launch_hs_count(c->stream, (const unsigned long long*)sorted.p, h->offsets.as<long long>(), n, h->sizes.as<int32_t>());
     if (!rc) rc = check_kernel("k_hs_count");
     if (rc) return rc;
     std::vector<int32_t> sizes((size_t)n);
-    HIP_TRY(hipMemcpyAsync(sizes.data(), h->sizes, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(sizes.data(), h->sizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     std::vector<long long> noff((size_t)n + 1);
     noff[0] = 0;
@@ -72,22 +64,17 @@ int sort_and_compact(mvs_ctx* c, mvs_hash_set* h, const std::vector<long long>& 
     DevBuf dnoff;
     HIP_TRY(dnoff.alloc(noff.size() * 8));
     HIP_TRY(hipMemcpyAsync(dnoff.p, noff.data(), noff.size() * 8, hipMemcpyHostToDevice, c->stream));
-    unsigned long long* out = nullptr;
-    if (hipMalloc((void**)&out, (size_t)std::max<long long>(noff[(size_t)n], 1) * 8) != hipSuccess)
+    DevBuf out;
+    if (out.alloc((size_t)std::max<long long>(noff[(size_t)n], 1) * 8) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of %lld distinct hashes failed", noff[(size_t)n]);
-    rc = mvs::launch_hs_compact(c->stream, (const unsigned long long*)sorted.p, h->offsets, (const long long*)dnoff.p, n, out);
+    rc = mvs::launch_hs_compact(c->stream, (const unsigned long long*)sorted.p, h->offsets.as<long long>(), (const long long*)dnoff.p, n,
+                                out.as<unsigned long long>());
     if (!rc) rc = check_kernel("k_hs_compact");
     hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc || e != hipSuccess) {
-        (void)hipFree(out);
-        return rc ? rc : fail(MVS_E_HIP, "hash set: compaction failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(h->hashes);
-    h->hashes = out;
+    if (rc || e != hipSuccess) return rc ? rc : fail(MVS_E_HIP, "hash set: compaction failed: %s", hipGetErrorString(e));
+    h->hashes = std::move(out);
     h->total = noff[(size_t)n];
-    void* old_offsets = h->offsets;                     // the set keeps the new offsets, the DevBuf frees the old ones
-    h->offsets = (long long*)dnoff.p;
-    dnoff.p = old_offsets;
+    std::swap(h->offsets, dnoff);   // the set keeps the new offsets, dnoff frees the old ones
     return MVS_OK;
 }
 
@@ -123,19 +110,18 @@ int mvs_hash_set_create(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, cons
     h->ctx = c;
     h->n = n;
     h->total = total_in;
-    if (hipMalloc((void**)&h->hashes, (size_t)std::max<long long>(total_in, 1) * 8) != hipSuccess ||
-        hipMalloc((void**)&h->offsets, ((size_t)n + 1) * 8) != hipSuccess ||
-        hipMalloc((void**)&h->sizes, (size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess)
+    if (h->hashes.alloc((size_t)std::max<long long>(total_in, 1) * 8) != hipSuccess ||
+        h->offsets.alloc(((size_t)n + 1) * 8) != hipSuccess || h->sizes.alloc((size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of a hash set of %lld hashes failed", total_in);
     if (total_in > 0)
-        HIP_TRY(hipMemcpyAsync(h->hashes, hashes + base, (size_t)total_in * 8,
+        HIP_TRY(hipMemcpyAsync(h->hashes.p, hashes + base, (size_t)total_in * 8,
                                mem_hashes == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(h->offsets, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(h->offsets.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
     unsigned int unsorted = 0;
     if (n > 0) {
-        unsigned int* d_flag = (unsigned int*)c->d_counter;
+        unsigned int* d_flag = (unsigned int*)c->counters();
         HIP_TRY(hipMemsetAsync(d_flag, 0, 8, c->stream));
-        int rc = mvs::launch_hs_check(c->stream, h->hashes, h->offsets, n, d_flag);
+        int rc = mvs::launch_hs_check(c->stream, h->hashes.as<unsigned long long>(), h->offsets.as<long long>(), n, d_flag);
         if (!rc) rc = check_kernel("k_hs_check");
         if (rc) return rc;
         rc = read_back(c, c->stream, {{&unsorted, d_flag, 4}});
@@ -148,7 +134,7 @@ int mvs_hash_set_create(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, cons
     } else if (n > 0) {
         std::vector<int32_t> sizes((size_t)n);
         for (int64_t s = 0; s < n; ++s) sizes[(size_t)s] = (int32_t)(off[(size_t)s + 1] - off[(size_t)s]);
-        HIP_TRY(hipMemcpyAsync(h->sizes, sizes.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(h->sizes.p, sizes.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -172,7 +158,7 @@ int mvs_hash_set_sizes(const mvs_hash_set* h, int32_t* sizes, int mem_out) {
     if (!sizes) return fail(MVS_E_INVALID, "sizes is NULL");
     mvs_ctx* c = h->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(sizes, h->sizes, (size_t)h->n * 4, mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+    HIP_TRY(hipMemcpyAsync(sizes, h->sizes.p, (size_t)h->n * 4, mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MVS_OK;
@@ -184,10 +170,6 @@ int mvs_hash_set_destroy(mvs_hash_set* h) {
         (void)hipSetDevice(h->ctx->device);
         (void)hipStreamSynchronize(h->ctx->stream);
     }
-    if (h->hashes) (void)hipFree(h->hashes);
-    if (h->offsets) (void)hipFree(h->offsets);
-    if (h->sizes) (void)hipFree(h->sizes);
-    if (h->abund) (void)hipFree(h->abund);
     delete h;
     return MVS_OK;
 }
@@ -222,38 +204,39 @@ int mvs_intersect_cells(mvs_ctx* c, const mvs_hash_set* hs_rows, const mvs_hash_
     // work space: counters | units per cell | their scan | the scan's scratch
     const size_t arr = (((size_t)n_cells + 1) * 8 + 255) & ~(size_t)255;
     size_t need = 0;
-    int rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes, hs_rows->n, hs_cols->sizes, hs_cols->n, c->opt.intersect_unit,
-                             nullptr, nullptr, d_inter, false, nullptr, nullptr, 0, &need);
+    int rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes.as<int32_t>(), hs_rows->n, hs_cols->sizes.as<int32_t>(),
+                             hs_cols->n, c->opt.intersect_unit, nullptr, nullptr, d_inter, false, nullptr, nullptr, 0, &need);
     if (rc) return fail(rc, "intersect: scan sizing failed");
-    rc = ensure_buf(c, &c->ix_work, &c->ix_work_bytes, 256 + 2 * arr + need);
+    rc = ensure_buf(c, c->ix_work, 256 + 2 * arr + need);
     if (rc) return rc;
-    unsigned long long* d_counters = (unsigned long long*)c->ix_work;
-    long long* d_units = (long long*)((char*)c->ix_work + 256);
-    long long* d_start = (long long*)((char*)c->ix_work + 256 + arr);
-    void* d_scan = (char*)c->ix_work + 256 + 2 * arr;
+    unsigned long long* d_counters = (unsigned long long*)c->ix_work.p;
+    long long* d_units = (long long*)((char*)c->ix_work.p + 256);
+    long long* d_start = (long long*)((char*)c->ix_work.p + 256 + arr);
+    void* d_scan = (char*)c->ix_work.p + 256 + 2 * arr;
 
-    EventQuad ev;
+    Event ev[4];
     if (c->timing) {
-        for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+        for (Event& x : ev) HIP_TRY(x.create());
+        HIP_TRY(hipEventRecord(ev[0], c->stream));
     }
     HIP_TRY(hipMemsetAsync(d_counters, 0, 32, c->stream));
-    rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes, hs_rows->n, hs_cols->sizes, hs_cols->n, c->opt.intersect_unit,
-                         d_units, d_start, d_inter, mem_out == MVS_MEM_HOST, d_counters, d_scan, need, nullptr);
+    rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes.as<int32_t>(), hs_rows->n, hs_cols->sizes.as<int32_t>(), hs_cols->n,
+                         c->opt.intersect_unit, d_units, d_start, d_inter, mem_out == MVS_MEM_HOST, d_counters, d_scan, need, nullptr);
     if (rc) return fail(rc, "intersect: planning the units failed");
     rc = check_kernel("k_isect_count");
     if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    if (c->timing) HIP_TRY(hipEventRecord(ev[1], c->stream));
     unsigned long long back[3] = {0, 0, 0};
     long long n_units = 0;
     rc = read_back(c, c->stream, {{back, d_counters, sizeof(back)}, {&n_units, d_start + n_cells, 8}});
     if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev.e[2], c->stream));
-    rc = mvs::launch_isect_units(c->stream, d_cells, n_cells, d_start, n_units, hs_rows->hashes, hs_rows->offsets, hs_rows->sizes,
-                                 hs_cols->hashes, hs_cols->offsets, hs_cols->sizes, c->opt.intersect_unit, d_inter);
+    if (c->timing) HIP_TRY(hipEventRecord(ev[2], c->stream));
+    rc = mvs::launch_isect_units(c->stream, d_cells, n_cells, d_start, n_units, hs_rows->hashes.as<unsigned long long>(),
+                                 hs_rows->offsets.as<long long>(), hs_rows->sizes.as<int32_t>(), hs_cols->hashes.as<unsigned long long>(),
+                                 hs_cols->offsets.as<long long>(), hs_cols->sizes.as<int32_t>(), c->opt.intersect_unit, d_inter);
     if (!rc) rc = check_kernel("k_isect_units");
     if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    if (c->timing) HIP_TRY(hipEventRecord(ev[3], c->stream));
     if (mem_out == MVS_MEM_HOST) {
         if (back[0] == 0) {
             HIP_TRY(hipMemcpyAsync(inter, d_inter, (size_t)n_cells * 4, hipMemcpyDeviceToHost, c->stream));
@@ -271,8 +254,8 @@ int mvs_intersect_cells(mvs_ctx* c, const mvs_hash_set* hs_rows, const mvs_hash_
     }
     if (c->timing) {
         float a = 0.f, b = 0.f;
-        HIP_TRY(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-        HIP_TRY(hipEventElapsedTime(&b, ev.e[2], ev.e[3]));
+        HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+        HIP_TRY(hipEventElapsedTime(&b, ev[2], ev[3]));
         c->ix_kernel_ms = (double)a + (double)b;
     }
     c->ix_units = n_units;

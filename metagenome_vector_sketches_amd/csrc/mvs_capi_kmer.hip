@@ -160,8 +160,8 @@ int mvs_hash_set_from_sequences(mvs_ctx* c, const uint8_t* bases, int mem_bases,
 
     unsigned long long back[1] = {0};
     for (int trip = 0;; ++trip) {
-        if (dvals.p) { (void)hipFree(dvals.p); dvals.p = nullptr; }
-        if (dsamp.p) { (void)hipFree(dsamp.p); dsamp.p = nullptr; }
+        dvals.reset();
+        dsamp.reset();
         if (dvals.alloc((size_t)cap * 8) != hipSuccess || dsamp.alloc((size_t)cap * 4) != hipSuccess)
             return fail(MVS_E_NOMEM, "hipMalloc of a staging list of %llu values failed", cap);
         HIP_TRY(hipMemsetAsync(dcount.p, 0, count_bytes, c->stream));
@@ -223,9 +223,9 @@ int mvs_hash_set_from_sequences(mvs_ctx* c, const uint8_t* bases, int mem_bases,
         rc = tm.add_to(&c->km_kernel_ms);
         if (rc) return rc;
     }
-    (void)hipFree(dvals.p); dvals.p = nullptr;
-    (void)hipFree(dsamp.p); dsamp.p = nullptr;
-    if (dbases.p) { (void)hipFree(dbases.p); dbases.p = nullptr; }
+    dvals.reset();
+    dsamp.reset();
+    dbases.reset();
     // per-sample sort and unique compaction: the set is built from the grouped values where they lie
     return mvs_hash_set_create(c, (const uint64_t*)dgrouped.p, MVS_MEM_DEVICE, hoff.data(), n, out);
 }
@@ -235,17 +235,17 @@ int mvs_hash_set_export(const mvs_hash_set* h, uint64_t* hashes, int mem_out, in
     if (!mem_ok(mem_out)) return fail(MVS_E_INVALID, "bad argument");
     mvs_ctx* c = h->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    if (offsets) HIP_TRY(hipMemcpyAsync(offsets, h->offsets, ((size_t)h->n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (offsets) HIP_TRY(hipMemcpyAsync(offsets, h->offsets.p, ((size_t)h->n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     if (hashes && h->total > 0)
-        HIP_TRY(hipMemcpyAsync(hashes, h->hashes, (size_t)h->total * 8, mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                               c->stream));
+        HIP_TRY(hipMemcpyAsync(hashes, h->hashes.p, (size_t)h->total * 8,
+                               mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MVS_OK;
 }
 
 int mvs_hash_set_device(const mvs_hash_set* h, const uint64_t** d_hashes) {
     if (!h || !d_hashes) return fail(MVS_E_INVALID, "NULL argument");
-    *d_hashes = (const uint64_t*)h->hashes;
+    *d_hashes = h->hashes.as<const uint64_t>();
     return MVS_OK;
 }
 

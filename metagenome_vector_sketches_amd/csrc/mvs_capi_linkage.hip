@@ -13,17 +13,16 @@ struct mvs_linkage {
     mvs_ctx* ctx = nullptr;
     int64_t n = 0;
     int d = 0;
-    double* norms_sq = nullptr;              // the linkage's own copy: every weight comes from it
-    double* core = nullptr;                  // NULL, or the core values of mvs_linkage_set_core: the weight is min(J, core, core)
+    DevBuf norms_sq;                         // double, the linkage's own copy: every weight comes from it
+    DevBuf core;                             // empty, or the core values (double) of mvs_linkage_set_core: the weight is min(J, core, core)
     bool fed = false;                        // a cell has been fed: the weight is fixed from here on
-    mvs_cell* forest[2] = {nullptr, nullptr};   // the forest and the one the rounds build; `cur` says which is which
+    DevBuf forest[2];                        // mvs_cell: the forest and the one the rounds build; `cur` says which is which
     int cur = 0;
     int64_t n_forest = 0;
-    int32_t* comp = nullptr;
-    int32_t* next = nullptr;
-    unsigned long long* slots = nullptr;     // best_key | best_pair | best_idx, n words each
-    unsigned long long* counters = nullptr;  // mvs_internal.h: LinkState
-    mvs_link* links = nullptr;               // the forest sorted best first (n_forest entries) while links_valid
+    DevBuf comp, next;                       // int32_t
+    DevBuf slots;                            // unsigned long long: best_key | best_pair | best_idx, n words each
+    DevBuf counters;                         // unsigned long long (mvs_internal.h: LinkState)
+    DevBuf links;                            // mvs_link: the forest sorted best first (n_forest entries) while links_valid
     bool links_valid = false;
 };
 
@@ -36,17 +35,17 @@ mvs::LinkState state_of(const mvs_linkage* k) {
     const size_t words = (size_t)std::max<int64_t>(k->n, 1);
     s.n = k->n;
     s.d = k->d;
-    s.norms_sq = k->norms_sq;
-    s.forest = k->forest[k->cur];
+    s.norms_sq = k->norms_sq.as<double>();
+    s.forest = k->forest[k->cur].as<mvs_cell>();
     s.n_forest = k->n_forest;
-    s.forest_next = k->forest[k->cur ^ 1];
+    s.forest_next = k->forest[k->cur ^ 1].as<mvs_cell>();
     s.capacity = std::max<int64_t>(k->n - 1, 0);
-    s.comp = k->comp;
-    s.next = k->next;
-    s.best_key = k->slots;
-    s.best_pair = k->slots + words;
-    s.best_idx = k->slots + 2 * words;
-    s.counters = k->counters;
+    s.comp = k->comp.as<int32_t>();
+    s.next = k->next.as<int32_t>();
+    s.best_key = k->slots.as<unsigned long long>();
+    s.best_pair = k->slots.as<unsigned long long>() + words;
+    s.best_idx = k->slots.as<unsigned long long>() + 2 * words;
+    s.counters = k->counters.as<unsigned long long>();
     return s;
 }
 
@@ -59,8 +58,8 @@ int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
     int rc = timer.begin(c);
     if (rc) return rc;
     const mvs::LinkState s = state_of(k);
-    HIP_TRY(hipMemsetAsync(k->counters, 0, 8 * sizeof(unsigned long long), c->stream));
-    rc = mvs::launch_link_identity(c->stream, k->comp, k->n);
+    HIP_TRY(hipMemsetAsync(k->counters.as<unsigned long long>(), 0, 8 * sizeof(unsigned long long), c->stream));
+    rc = mvs::launch_link_identity(c->stream, k->comp.as<int32_t>(), k->n);
     if (!rc) rc = check_kernel("k_link_identity");
     if (rc) return rc;
     unsigned long long back[5] = {0, 0, 0, 0, 0};
@@ -69,11 +68,11 @@ int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
         rc = mvs::launch_link_slots(c->stream, s);
         if (!rc) rc = check_kernel("k_link_slots");
         if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(k->counters + 2, 0, sizeof(unsigned long long), c->stream));
-        rc = mvs::launch_link_select(c->stream, s, k->core, d_cells, n_cells, 0, round == 0);
+        HIP_TRY(hipMemsetAsync(k->counters.as<unsigned long long>() + 2, 0, sizeof(unsigned long long), c->stream));
+        rc = mvs::launch_link_select(c->stream, s, k->core.as<double>(), d_cells, n_cells, 0, round == 0);
         if (!rc) rc = check_kernel("k_link_select<0>");
         if (rc) return rc;
-        rc = read_back(c, c->stream, {{back, k->counters, sizeof(back)}});
+        rc = read_back(c, c->stream, {{back, k->counters.as<unsigned long long>(), sizeof(back)}});
         if (rc) return rc;
         if (back[4] != 0) return fail(MVS_E_HIP, "internal: the forest rounds left their bounds (flag %llu)", back[4]);
         if (back[2] == 0) break;
@@ -81,10 +80,10 @@ int consume_cells(mvs_linkage* k, const mvs_cell* d_cells, int64_t n_cells) {
             return fail(MVS_E_HIP, "internal: %llu edges still join different components after %d rounds", back[2], round);
         ++round;
         for (int pass = 1; pass <= 2 && !rc; ++pass) {
-            rc = mvs::launch_link_select(c->stream, s, k->core, d_cells, n_cells, pass, false);
+            rc = mvs::launch_link_select(c->stream, s, k->core.as<double>(), d_cells, n_cells, pass, false);
             if (!rc) rc = check_kernel("k_link_select");
         }
-        if (!rc) rc = mvs::launch_link_hook(c->stream, s, k->core, d_cells);
+        if (!rc) rc = mvs::launch_link_hook(c->stream, s, k->core.as<double>(), d_cells);
         if (!rc) rc = check_kernel("k_link_hook");
         if (!rc) rc = mvs::launch_link_jump(c->stream, s);
         if (!rc) rc = check_kernel("k_link_flatten");
@@ -114,14 +113,14 @@ int sort_links(mvs_linkage* k) {
     const mvs::LinkState s = state_of(k);
     DevBuf dtmp, dscratch;
     size_t need = 0;
-    int rc = mvs::link_sorted(c->stream, s, k->core, nullptr, nullptr, nullptr, 0, &need);
+    int rc = mvs::link_sorted(c->stream, s, k->core.as<double>(), nullptr, nullptr, nullptr, 0, &need);
     if (rc) return fail(rc, "linkage finish: sort sizing failed");
     HIP_TRY(dtmp.alloc((size_t)k->n_forest * sizeof(mvs_link)));
     HIP_TRY(dscratch.alloc(need));
     StageTimer timer;
     rc = timer.begin(c);
     if (rc) return rc;
-    rc = mvs::link_sorted(c->stream, s, k->core, (mvs_link*)dtmp.p, k->links, dscratch.p, need, nullptr);
+    rc = mvs::link_sorted(c->stream, s, k->core.as<double>(), (mvs_link*)dtmp.p, k->links.as<mvs_link>(), dscratch.p, need, nullptr);
     if (rc) return fail(rc, "linkage finish: sort failed");
     rc = check_kernel("k_link_links");
     if (rc) return rc;
@@ -147,30 +146,25 @@ int mvs_linkage_create(mvs_ctx* c, int64_t n, int d, const double* norms_sq, int
     if (n > 0 && !norms_sq) return fail(MVS_E_INVALID, "norms_sq is NULL");
     if (n >= (1LL << 31) - 256) return fail(MVS_E_RANGE, "n too large for int32 sample indices");
     HIP_TRY(hipSetDevice(c->device));
-    mvs_linkage* k = new (std::nothrow) mvs_linkage();
+    std::unique_ptr<mvs_linkage> k(new (std::nothrow) mvs_linkage());
     if (!k) return fail(MVS_E_NOMEM, "out of host memory");
     k->ctx = c;
     k->n = n;
     k->d = d;
     const size_t words = (size_t)std::max<int64_t>(n, 1);
-    if (hipMalloc((void**)&k->norms_sq, words * 8) != hipSuccess || hipMalloc((void**)&k->forest[0], words * sizeof(mvs_cell)) != hipSuccess ||
-        hipMalloc((void**)&k->forest[1], words * sizeof(mvs_cell)) != hipSuccess || hipMalloc((void**)&k->comp, words * 4) != hipSuccess ||
-        hipMalloc((void**)&k->next, words * 4) != hipSuccess || hipMalloc((void**)&k->slots, 3 * words * 8) != hipSuccess ||
-        hipMalloc((void**)&k->links, words * sizeof(mvs_link)) != hipSuccess || hipMalloc((void**)&k->counters, 64) != hipSuccess) {
-        mvs_linkage_destroy(k);
+    if (k->norms_sq.alloc(words * 8) != hipSuccess || k->forest[0].alloc(words * sizeof(mvs_cell)) != hipSuccess ||
+        k->forest[1].alloc(words * sizeof(mvs_cell)) != hipSuccess || k->comp.alloc(words * 4) != hipSuccess ||
+        k->next.alloc(words * 4) != hipSuccess || k->slots.alloc(3 * words * 8) != hipSuccess ||
+        k->links.alloc(words * sizeof(mvs_link)) != hipSuccess || k->counters.alloc(64) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of the forest of %lld samples failed", (long long)n);
-    }
     if (n > 0) {
-        const hipError_t e = hipMemcpyAsync(k->norms_sq, norms_sq, (size_t)n * 8,
+        const hipError_t e = hipMemcpyAsync(k->norms_sq.as<double>(), norms_sq, (size_t)n * 8,
                                             mem_norms == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream);
         const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
-        if (e2 != hipSuccess) {
-            mvs_linkage_destroy(k);
-            return fail(MVS_E_HIP, "copying the norms: %s", hipGetErrorString(e2));
-        }
+        if (e2 != hipSuccess) return fail(MVS_E_HIP, "copying the norms: %s", hipGetErrorString(e2));
     }
     c->lk.reset();
-    *out = k;
+    *out = k.release();
     return MVS_OK;
 }
 
@@ -181,15 +175,11 @@ int mvs_linkage_set_core(mvs_linkage* k, const double* core, int mem_core) {
     if (k->fed) return fail(MVS_E_INVALID, "the linkage has been fed cells: the core values decide every weight and must come first");
     mvs_ctx* c = k->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    if (!k->core) {
-        if (hipMalloc((void**)&k->core, (size_t)std::max<int64_t>(k->n, 1) * 8) != hipSuccess) {
-            k->core = nullptr;
-            return fail(MVS_E_NOMEM, "hipMalloc of %lld core values failed", (long long)k->n);
-        }
-    }
+    if (!k->core.p && k->core.alloc((size_t)std::max<int64_t>(k->n, 1) * 8) != hipSuccess)
+        return fail(MVS_E_NOMEM, "hipMalloc of %lld core values failed", (long long)k->n);
     if (k->n > 0) {
-        HIP_TRY(hipMemcpyAsync(k->core, core, (size_t)k->n * 8, mem_core == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
-                               c->stream));
+        HIP_TRY(hipMemcpyAsync(k->core.as<double>(), core, (size_t)k->n * 8,
+                               mem_core == MVS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return MVS_OK;
@@ -225,7 +215,7 @@ int mvs_linkage_finish(mvs_linkage* k, mvs_link* links, int64_t capacity, int me
     const Range range(c, "mvs_linkage_finish");
     const int rc = sort_links(k);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(links, k->links, (size_t)k->n_forest * sizeof(mvs_link),
+    HIP_TRY(hipMemcpyAsync(links, k->links.as<mvs_link>(), (size_t)k->n_forest * sizeof(mvs_link),
                            mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MVS_OK;
@@ -242,12 +232,12 @@ int mvs_linkage_cells(mvs_linkage* k, double level, mvs_cell* d_cells, int64_t c
     const Range range(c, "mvs_linkage_cells");
     int rc = sort_links(k);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(k->counters + 5, 0, sizeof(unsigned long long), c->stream));
-    rc = mvs::launch_link_cells(c->stream, k->links, k->n_forest, level, d_cells, capacity, k->counters);
+    HIP_TRY(hipMemsetAsync(k->counters.as<unsigned long long>() + 5, 0, sizeof(unsigned long long), c->stream));
+    rc = mvs::launch_link_cells(c->stream, k->links.as<mvs_link>(), k->n_forest, level, d_cells, capacity, k->counters.as<unsigned long long>());
     if (!rc) rc = check_kernel("k_link_cells");
     if (rc) return rc;
     unsigned long long above = 0;
-    rc = read_back(c, c->stream, {{&above, k->counters + 5, 8}});
+    rc = read_back(c, c->stream, {{&above, k->counters.as<unsigned long long>() + 5, 8}});
     if (rc) return rc;
     if (n_cells) *n_cells = (int64_t)above;
     if ((int64_t)above > capacity)
@@ -261,9 +251,6 @@ int mvs_linkage_destroy(mvs_linkage* k) {
         (void)hipSetDevice(k->ctx->device);
         (void)hipStreamSynchronize(k->ctx->stream);
     }
-    void* bufs[] = {k->norms_sq, k->core, k->forest[0], k->forest[1], k->comp, k->next, k->slots, k->counters, k->links};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
     delete k;
     return MVS_OK;
 }

@@ -29,8 +29,8 @@ struct mvs_pca {
     int iterations = 0, converged = 0;
     double total_variance = 0.0;
     std::vector<double> mean, axes, variances, residuals;   // axes: c x d, one axis per row
-    void* d_V = nullptr;     // d x c, row-major: what k_pca_scores reads
-    void* d_off = nullptr;   // c: sum_a mean[a] V[a][j]
+    DevBuf d_V;     // d x c, row-major: what k_pca_scores reads
+    DevBuf d_off;   // c: sum_a mean[a] V[a][j]
 };
 
 namespace {
@@ -364,12 +364,10 @@ int mvs_pca_fit(mvs_ctx* c, const mvs_sketch_set* s, int64_t rb, int64_t re, int
             off[(size_t)j] += p->mean[(size_t)a] * ax[a];
         }
     }
-    if (hipMalloc(&p->d_V, (size_t)d * cc * 8) != hipSuccess || hipMalloc(&p->d_off, (size_t)cc * 8) != hipSuccess) {
-        if (p->d_V) (void)hipFree(p->d_V);
+    if (p->d_V.alloc((size_t)d * cc * 8) != hipSuccess || p->d_off.alloc((size_t)cc * 8) != hipSuccess)
         return fail(MVS_E_NOMEM, "out of device memory");
-    }
-    HIP_TRY(hipMemcpyAsync(p->d_V, vc.data(), (size_t)d * cc * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_off, off.data(), (size_t)cc * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p->d_V.p, vc.data(), (size_t)d * cc * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p->d_off.p, off.data(), (size_t)cc * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *out = p.release();
     return MVS_OK;
@@ -416,7 +414,7 @@ int mvs_pca_transform(mvs_ctx* c, const mvs_pca* p, const mvs_sketch_set* s, int
     }
     StageTimer timer;
     if (const int rc = timer.begin(c)) return rc;
-    if (const int rc = mvs::launch_pca_scores(c->stream, s->planes, s->limbs, s->d, s->d_pad, rb, re, (const double*)p->d_V, (const double*)p->d_off,
+    if (const int rc = mvs::launch_pca_scores(c->stream, s->planes, s->limbs, s->d, s->d_pad, rb, re, p->d_V.as<const double>(), p->d_off.as<const double>(),
                                               p->c, d_scores))
         return fail(rc, "pca: scores launch rejected");
     if (const int ck = check_kernel("k_pca_scores")) return ck;
@@ -428,8 +426,6 @@ int mvs_pca_transform(mvs_ctx* c, const mvs_pca* p, const mvs_sketch_set* s, int
 
 int mvs_pca_destroy(mvs_pca* p) {
     if (!p) return MVS_OK;
-    if (p->d_V) (void)hipFree(p->d_V);
-    if (p->d_off) (void)hipFree(p->d_off);
     delete p;
     return MVS_OK;
 }

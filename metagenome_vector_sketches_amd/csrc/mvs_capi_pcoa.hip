@@ -25,7 +25,7 @@ struct mvs_pcoa {
     int c = 0, block = 0, iterations = 0, converged = 0, negative = 0;
     double floor = 0.0, grand = 0.0, trace = 0.0;
     std::vector<double> lambda, vectors, coords, rowmean, residuals, off;   // vectors, coords: m x c row-major; off[j] = sum_i rowmean[i] v[i][j]
-    void* d_Vp = nullptr;                                                   // the vectors, padded as k_jaccard_apply reads its operand
+    DevBuf d_Vp;                                                            // the vectors, padded as k_jaccard_apply reads its operand
 };
 
 namespace {
@@ -240,13 +240,10 @@ int mvs_pcoa_fit(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, in
         }
     }
     pad_on_host(p->vectors.data(), m, cc, padded);
-    if (hipMalloc(&p->d_Vp, padded.size() * 8) != hipSuccess) return fail(MVS_E_NOMEM, "out of device memory");
-    const hipError_t e1 = hipMemcpyAsync(p->d_Vp, padded.data(), padded.size() * 8, hipMemcpyHostToDevice, c->stream);
+    if (p->d_Vp.alloc(padded.size() * 8) != hipSuccess) return fail(MVS_E_NOMEM, "out of device memory");
+    const hipError_t e1 = hipMemcpyAsync(p->d_Vp.p, padded.data(), padded.size() * 8, hipMemcpyHostToDevice, c->stream);
     const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        (void)hipFree(p->d_Vp);
-        return fail(MVS_E_HIP, "uploading the vectors: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-    }
+    if (e1 != hipSuccess || e2 != hipSuccess) return fail(MVS_E_HIP, "uploading the vectors: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     *out = p.release();
     return MVS_OK;
 }
@@ -299,7 +296,7 @@ int mvs_pcoa_transform(mvs_ctx* c, const mvs_pcoa* p, const mvs_sketch_set* s, c
     HIP_TRY(dY.alloc(bytes));
     Applier ap;
     if (const int rc = ap.init(c, s, d_n2, p->floor, p->fb, p->fe, rows)) return rc;
-    if (const int rc = ap.run(rb, re, (const double*)p->d_Vp, cc, (double*)dY.p)) return rc;
+    if (const int rc = ap.run(rb, re, p->d_Vp.as<const double>(), cc, (double*)dY.p)) return rc;
     std::vector<double> y((size_t)rows * cc);
     HIP_TRY(hipMemcpyAsync(y.data(), dY.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -320,7 +317,6 @@ int mvs_pcoa_transform(mvs_ctx* c, const mvs_pcoa* p, const mvs_sketch_set* s, c
 
 int mvs_pcoa_destroy(mvs_pcoa* p) {
     if (!p) return MVS_OK;
-    if (p->d_Vp) (void)hipFree(p->d_Vp);
     delete p;
     return MVS_OK;
 }

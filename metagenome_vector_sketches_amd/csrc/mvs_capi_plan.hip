@@ -23,9 +23,9 @@ struct PlanState {
     int64_t capacity = 0;
     // what it did (mvs_plan_stats)
     long long tiles = 0, launches = 0, candidates = 0, flagged = 0;
-    std::vector<hipEvent_t> ev;           // start / stop per filter launch, created once and reused
+    std::vector<Event> ev;                // start / stop per filter launch, created once and reused
     size_t ev_used = 0;
-    hipEvent_t e_chk0 = nullptr, e_chk1 = nullptr, e_tiles1 = nullptr;
+    Event e_chk0, e_chk1, e_tiles1;
     bool timed = false, finished = false;
     // Running ahead of the read-backs (option plan_speculate): a plan of the same shape as the previous one sizes its second
     // half -- pruning, re-check, flagged tiles -- from THAT plan's counts and does not wait for its own; every kernel reads the
@@ -35,8 +35,8 @@ struct PlanState {
     // Filter launches alternate between the context's stream and a side stream of the plan (option plan_overlap): the last
     // round of one launch leaves CUs idle that the first round of the next can use.  A side launch waits for everything the
     // caller had put on the context's stream when it was issued (the arrival of its columns); mvs_plan_finish joins them.
-    hipStream_t side = nullptr;
-    hipEvent_t e_fork = nullptr, e_join = nullptr;
+    Stream side;
+    Event e_fork, e_join;
     bool side_busy = false;
     const int8_t* lo_wire = nullptr;      // mvs_plan_wire: the other ranks' limb planes are rebuilt from it, row by row, as needed
     bool need_clean = false;              // the row marks (pw_need) were cleared by this plan's reset and not written since
@@ -51,14 +51,7 @@ struct PlanState {
 };
 
 void mvs_capi::plan_state_free(mvs_ctx* c) {
-    PlanState* st = c->plan;
-    if (!st) return;
-    for (hipEvent_t e : st->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {st->e_chk0, st->e_chk1, st->e_tiles1, st->e_fork, st->e_join})
-        if (e) (void)hipEventDestroy(e);
-    if (st->side) (void)hipStreamDestroy(st->side);
-    delete st;
+    delete c->plan;
     c->plan = nullptr;
 }
 
@@ -98,7 +91,7 @@ int plan_resolve(mvs_ctx* c) {
     PlanState* st = c->plan;
     if (!st || !st->pending) return MVS_OK;
     unsigned long long back[33];
-    const int rc = read_back(c, c->stream, {{back, c->d_counter, sizeof(back)}});
+    const int rc = read_back(c, c->stream, {{back, c->counters(), sizeof(back)}});
     if (rc) return rc;
     plan_take_counts(c, *st, back);
     return MVS_OK;
@@ -107,14 +100,14 @@ int plan_resolve(mvs_ctx* c) {
 // counters, candidate-region headers, tile flags and the row marks of mvs_plan_wire cleared by ONE launch (six memsets were
 // nine fill kernels of 5 us each in front of every plan: 45 us of the 1.7 ms a rank of an 8-way split spends on its step)
 int plan_reset_counters(mvs_ctx* c, PlanState& st, bool cells_too) {
-    void* ptrs[7] = {cells_too ? (void*)c->d_counter : nullptr, c->d_counter + 1, c->d_counter + 5, st.a.recheck_queue,
-                     st.regions_cap ? c->pw_chdr : nullptr, st.a.tile_flag, c->pw_need};
+    void* ptrs[7] = {cells_too ? (void*)c->counters() : nullptr, c->counters() + 1, c->counters() + 5, st.a.recheck_queue,
+                     st.regions_cap ? c->pw_chdr.p : nullptr, st.a.tile_flag, c->pw_need.p};
     const size_t bytes[7] = {8, 16, 224, 512, (size_t)st.regions_cap * 4, (size_t)st.n_tr * (size_t)st.n_tc * 4,
-                             c->pw_need ? std::min((size_t)st.set->n_alloc, c->pw_need_bytes) / 4 * 4 : 0};   // (a buffer sized for an earlier, smaller set: never beyond it)
+                             c->pw_need.p ? std::min((size_t)st.set->n_alloc, c->pw_need.bytes) / 4 * 4 : 0};   // (a buffer sized for an earlier, smaller set: never beyond it)
     if (mvs::launch_zero_ranges(c->stream, ptrs, bytes, 7) != 0) return fail(MVS_E_INVALID, "plan reset: misaligned buffer");
     const int rc = check_kernel("k_zero_ranges");
     if (rc) return rc;
-    st.need_clean = c->pw_need != nullptr && st.set->n_alloc % 4 == 0 && c->pw_need_bytes >= (size_t)st.set->n_alloc;
+    st.need_clean = c->pw_need.p != nullptr && st.set->n_alloc % 4 == 0 && c->pw_need.bytes >= (size_t)st.set->n_alloc;
     st.regions_next = 0;
     return MVS_OK;
 }
@@ -124,7 +117,7 @@ int plan_meta(mvs_ctx* c, PlanState& st, int64_t r0, int64_t r1) {
     if (r1 <= r0) return MVS_OK;
     const mvs_sketch_set* s = st.set;
     mvs::launch_filter_meta(c->stream, s->ext_rows + r0, st.d_n2 + r0, r1 - r0, r1 - r0, s->d, st.a.keep_coeff,
-                            (float4*)c->pw_fmeta + r0);
+                            (float4*)c->pw_fmeta.p + r0);
     return check_kernel("k_filter_meta");
 }
 
@@ -142,11 +135,11 @@ int plan_join(mvs_ctx* c, PlanState& st) {
 int plan_rebuild_needed(mvs_ctx* c, PlanState& st) {
     if (!st.lo_wire) return MVS_OK;
     const mvs_sketch_set* s = st.set;
-    int rc = ensure_buf(c, &c->pw_need, &c->pw_need_bytes, (size_t)s->n_alloc);
+    int rc = ensure_buf(c, c->pw_need, (size_t)s->n_alloc);
     if (rc) return rc;
-    if (!st.need_clean) HIP_TRY(hipMemsetAsync(c->pw_need, 0, (size_t)s->n_alloc, c->stream));   // (the plan's reset cleared it)
+    if (!st.need_clean) HIP_TRY(hipMemsetAsync(c->pw_need.p, 0, (size_t)s->n_alloc, c->stream));   // (the plan's reset cleared it)
     st.need_clean = false;
-    mvs::launch_rows_needed(c->stream, st.a, st.n_tr, st.n_tc, st.f0, st.f1, s->n, (unsigned char*)c->pw_need);
+    mvs::launch_rows_needed(c->stream, st.a, st.n_tr, st.n_tc, st.f0, st.f1, s->n, (unsigned char*)c->pw_need.p);
     rc = check_kernel("k_rows_needed");
     if (rc) return rc;
     // ONE launch over the rows on both sides of the frame (its 16-row groups are skipped inside the kernel)
@@ -155,7 +148,7 @@ int plan_rebuild_needed(mvs_ctx* c, PlanState& st) {
     const int64_t count = std::max(hi_end, lo_end);                                             // rows [0, count) but [lo_end, hi_begin)
     const int64_t skip_first = lo_end, skip_count = std::max<int64_t>(0, std::min(hi_begin, count) - lo_end);
     mvs::launch_planes_from_wire(c->stream, st.lo_wire, s->ext_coarse_fm, s->ext_rows, count, s->d_pad, const_cast<int8_t*>(s->planes),
-                                 (const unsigned char*)c->pw_need, skip_first, skip_count);
+                                 (const unsigned char*)c->pw_need.p, skip_first, skip_count);
     return check_kernel("k_planes_from_wire(needed rows)");
 }
 
@@ -188,9 +181,9 @@ int plan_launch(mvs_ctx* c, PlanState& st, size_t first, int count) {
     hipStream_t on = c->stream;
     if (c->plan_overlap != 0 && (st.launches & 1) != 0) {          // every second launch of a plan: the side stream
         if (!st.side) {
-            HIP_TRY(hipStreamCreateWithFlags(&st.side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&st.e_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&st.e_join, hipEventDisableTiming));
+            HIP_TRY(st.side.create(hipStreamNonBlocking));
+            HIP_TRY(st.e_fork.create(hipEventDisableTiming));
+            HIP_TRY(st.e_join.create(hipEventDisableTiming));
         }
         HIP_TRY(hipEventRecord(st.e_fork, c->stream));
         HIP_TRY(hipStreamWaitEvent(st.side, st.e_fork, 0));
@@ -199,9 +192,9 @@ int plan_launch(mvs_ctx* c, PlanState& st, size_t first, int count) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing) {
         while (st.ev.size() < st.ev_used + 2) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e));
-            st.ev.push_back(e);
+            Event e;
+            HIP_TRY(e.create());
+            st.ev.push_back(std::move(e));
         }
         e0 = st.ev[st.ev_used];
         e1 = st.ev[st.ev_used + 1];
@@ -248,13 +241,13 @@ int mvs_sketch_set_prepare_rows(mvs_ctx* c, mvs_sketch_set* s, int64_t row_first
                     (long long)row_count, (long long)s->n_alloc);
     if (row_count == 0 || s->limbs != 2 || s->d_pad > 32768 || !s->ext_coarse_fm) return MVS_OK;   // nothing the filter could use
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_buf(c, &c->plan_tmp, &c->plan_tmp_bytes, (size_t)row_count * (size_t)s->d_pad);
+    int rc = ensure_buf(c, c->plan_tmp, (size_t)row_count * (size_t)s->d_pad);
     if (rc) return rc;
     mvs::launch_coarse_build(c->stream, s->planes + row_first * 2 * (int64_t)s->d_pad, row_count, row_count, s->d_pad,
-                             (int8_t*)c->plan_tmp, s->ext_rows + row_first, c->opt.coarse_radix);
+                             (int8_t*)c->plan_tmp.p, s->ext_rows + row_first, c->opt.coarse_radix);
     rc = check_kernel("k_coarse_build(rows)");
     if (rc) return rc;
-    mvs::launch_coarse_fm(c->stream, (const int8_t*)c->plan_tmp, row_count, s->d_pad, s->ext_coarse_fm + row_first * (int64_t)s->d_pad);
+    mvs::launch_coarse_fm(c->stream, (const int8_t*)c->plan_tmp.p, row_count, s->d_pad, s->ext_coarse_fm + row_first * (int64_t)s->d_pad);
     return check_kernel("k_coarse_fm(rows)");
 }
 
@@ -376,16 +369,16 @@ int mvs_plan_begin(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, 
     c->last_flagged_tiles = 0;
     c->last_filter_tiles = 0;
     if (!st.two_stage) {
-        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 8, c->stream));
+        HIP_TRY(hipMemsetAsync(c->counters(), 0, 8, c->stream));
         st.active = true;
         return MVS_OK;
     }
     mvs::filter_tile_grid(a, &st.n_tr, &st.n_tc);
-    int rc = ensure_buf(c, &c->pw_fmeta, &c->pw_fmeta_bytes, (size_t)s->n_alloc * sizeof(float4));
+    int rc = ensure_buf(c, c->pw_fmeta, (size_t)s->n_alloc * sizeof(float4));
     if (rc) return rc;
     const double frame_cells = (double)(f1 - f0) * (double)s->n;
     const int64_t cand_want = std::max<int64_t>(1 << 20, (int64_t)(frame_cells / 4096.0));
-    rc = ensure_buf(c, &c->pw_cand, &c->pw_cand_bytes, (size_t)cand_want * sizeof(int2));
+    rc = ensure_buf(c, c->pw_cand, (size_t)cand_want * sizeof(int2));
     if (rc) return rc;
     // candidate regions: 8 per workgroup of every launch; a launch pads each rectangle to whole super-patches, so the sum
     // over a plan is a little more than the frame's own padded grid -- a launch that no longer fits appends with atomics
@@ -393,35 +386,35 @@ int mvs_plan_begin(mvs_ctx* c, const mvs_sketch_set* s, const double* norms_sq, 
     st.regions_cap = c->opt.cand_regions ? n_spr * (n_spc + 8) * 2048ull : 0;
     if (st.regions_cap > (8ull << 20)) st.regions_cap = 0;
     if (st.regions_cap) {
-        rc = ensure_buf(c, &c->pw_chdr, &c->pw_chdr_bytes, (size_t)st.regions_cap * 4);
+        rc = ensure_buf(c, c->pw_chdr, (size_t)st.regions_cap * 4);
         if (rc) return rc;
-        rc = ensure_buf(c, &c->pw_cent, &c->pw_cent_bytes, (size_t)st.regions_cap * mvs::kCandRegion * sizeof(int2));
+        rc = ensure_buf(c, c->pw_cent, (size_t)st.regions_cap * mvs::kCandRegion * sizeof(int2));
         if (rc) return rc;
     }
-    rc = ensure_buf(c, &c->pw_tflag, &c->pw_tflag_bytes, (size_t)st.n_tr * (size_t)st.n_tc * 4);
+    rc = ensure_buf(c, c->pw_tflag, (size_t)st.n_tr * (size_t)st.n_tc * 4);
     if (rc) return rc;
-    rc = ensure_buf(c, &c->pw_trow, &c->pw_trow_bytes, (size_t)st.n_tr * 4);
+    rc = ensure_buf(c, c->pw_trow, (size_t)st.n_tr * 4);
     if (rc) return rc;
     a.coarse = nullptr;                   // plans read the fragment-major plane only
     a.coarse_fm = s->ext_coarse_fm;
     a.planes_fm = nullptr;                // flagged tiles: the exact kernel copies from the row-major limb planes
-    a.fmeta = (const float4*)c->pw_fmeta;
-    a.cand = (int2*)c->pw_cand;
-    a.cand_capacity = c->pw_cand_bytes / sizeof(int2);
-    a.cand_counter = c->d_counter + 2;
+    a.fmeta = (const float4*)c->pw_fmeta.p;
+    a.cand = (int2*)c->pw_cand.p;
+    a.cand_capacity = c->pw_cand.bytes / sizeof(int2);
+    a.cand_counter = c->counters() + 2;
     a.cand_limit = ~0ULL;
-    a.cand_stop = reinterpret_cast<unsigned int*>(c->d_counter + 32);
-    a.recheck_queue = c->d_counter + 128;
+    a.cand_stop = reinterpret_cast<unsigned int*>(c->counters() + 32);
+    a.recheck_queue = c->counters() + 128;
     a.recheck_mode = c->opt.recheck_mode;
-    a.cand_hdr = st.regions_cap ? (unsigned int*)c->pw_chdr : nullptr;
-    a.cand_ent = st.regions_cap ? (int2*)c->pw_cent : nullptr;
-    a.tile_flag = (unsigned int*)c->pw_tflag;
+    a.cand_hdr = st.regions_cap ? (unsigned int*)c->pw_chdr.p : nullptr;
+    a.cand_ent = st.regions_cap ? (int2*)c->pw_cent.p : nullptr;
+    a.tile_flag = (unsigned int*)c->pw_tflag.p;
     a.tile_flag_ld = st.n_tc;
     a.tile_dense_thr = c->opt.tile_dense_thr > 0 ? (unsigned)c->opt.tile_dense_thr : 0xffffffffu;
-    a.tile_flag_count = reinterpret_cast<unsigned int*>(c->d_counter + 8);
+    a.tile_flag_count = reinterpret_cast<unsigned int*>(c->counters() + 8);
     a.tile_flag_limit = 0xffffffffu;      // a plan never gives up on its filter: dense tiles go to the exact kernel one by one
     if (s->n_alloc % 4 == 0) {            // the row marks of mvs_plan_wire: cleared with the counters (one launch)
-        rc = ensure_buf(c, &c->pw_need, &c->pw_need_bytes, (size_t)s->n_alloc);
+        rc = ensure_buf(c, c->pw_need, (size_t)s->n_alloc);
         if (rc) return rc;
     }
     rc = plan_reset_counters(c, st, true);
@@ -543,7 +536,7 @@ int mvs_plan_finish(mvs_ctx* c, const uint64_t** d_count) {
     PlanState& st = *c->plan;
     const mvs_sketch_set* s = st.set;
     HIP_TRY(hipSetDevice(c->device));
-    if (d_count) *d_count = reinterpret_cast<const uint64_t*>(c->d_counter);
+    if (d_count) *d_count = reinterpret_cast<const uint64_t*>(c->counters());
     st.finished = true;
     st.active = false;
     if (!st.two_stage || st.blocks.empty()) return MVS_OK;
@@ -551,8 +544,8 @@ int mvs_plan_finish(mvs_ctx* c, const uint64_t** d_count) {
         const int rj = plan_join(c, st);
         if (rj) return rj;
     }
-    auto lazy_event = [&](hipEvent_t& e) -> int {
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    auto lazy_event = [&](Event& e) -> int {
+        if (!e) HIP_TRY(e.create());
         return MVS_OK;
     };
     if (st.timed) {
@@ -571,34 +564,34 @@ int mvs_plan_finish(mvs_ctx* c, const uint64_t** d_count) {
             const int rc = check_kernel("k_cand_gather");
             if (rc) return rc;
         }
-        mvs::launch_tile_count(c->stream, st.a.tile_flag, st.n_tr, st.n_tc, (int*)c->pw_trow);
+        mvs::launch_tile_count(c->stream, st.a.tile_flag, st.n_tr, st.n_tc, (int*)c->pw_trow.p);
         int rc = check_kernel("k_tile_count");
         if (rc) return rc;
         rc = plan_rebuild_needed(c, st);
         if (rc) return rc;
         const bool tiles_pass = st.hint_flagged > 0;
         const int tile_cap = tiles_pass ? (int)std::min<long long>((long long)st.n_tr * st.n_tc, 2 * st.hint_flagged + 64) : 0;
-        rc = ensure_buf(c, &c->pw_tlist, &c->pw_tlist_bytes, ((size_t)tile_cap + 1) * 4);
+        rc = ensure_buf(c, c->pw_tlist, ((size_t)tile_cap + 1) * 4);
         if (rc) return rc;
         mvs::PairwiseArgs a = st.a;
-        mvs::launch_tile_list(c->stream, a.tile_flag, st.n_tr, st.n_tc, (const int*)c->pw_trow, (int*)c->pw_tlist, tile_cap);
+        mvs::launch_tile_list(c->stream, a.tile_flag, st.n_tr, st.n_tc, (const int*)c->pw_trow.p, (int*)c->pw_tlist.p, tile_cap);
         rc = check_kernel("k_tile_list");
         if (rc) return rc;
         if (tiles_pass) {
-            rc = ensure_buf(c, &c->pw_cand2, &c->pw_cand2_bytes, c->pw_cand_bytes);      // whatever the list holds fits
+            rc = ensure_buf(c, c->pw_cand2, c->pw_cand.bytes);      // whatever the list holds fits
             if (rc) return rc;
-            mvs::launch_cand_prune(c->stream, a, 0, (int2*)c->pw_cand2, c->d_counter + 6, st.hint_cand + st.hint_cand / 4);
+            mvs::launch_cand_prune(c->stream, a, 0, (int2*)c->pw_cand2.p, c->counters() + 6, st.hint_cand + st.hint_cand / 4);
             rc = check_kernel("k_cand_prune");
             if (rc) return rc;
-            a.cand = (int2*)c->pw_cand2;
-            a.cand_capacity = c->pw_cand2_bytes / sizeof(int2);
-            a.cand_counter = c->d_counter + 6;
-            rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
+            a.cand = (int2*)c->pw_cand2.p;
+            a.cand_capacity = c->pw_cand2.bytes / sizeof(int2);
+            a.cand_counter = c->counters() + 6;
+            rc = ensure_buf(c, c->pw_thr, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
             if (rc) return rc;
-            mvs::launch_cand_thr(c->stream, st.d_n2, s->n, s->n_alloc, s->d, a.keep_coeff, (int32_t*)c->pw_thr);
+            mvs::launch_cand_thr(c->stream, st.d_n2, s->n, s->n_alloc, s->d, a.keep_coeff, (int32_t*)c->pw_thr.p);
             rc = check_kernel("k_cand_thr");
             if (rc) return rc;
-            a.cand_thr = (const int32_t*)c->pw_thr;
+            a.cand_thr = (const int32_t*)c->pw_thr.p;
         }
         rc = mvs::launch_exact_pairs(c->stream, a, c->opt, st.hint_cand + st.hint_cand / 4);
         if (rc) return fail(rc, "exact re-check launch rejected");
@@ -606,13 +599,13 @@ int mvs_plan_finish(mvs_ctx* c, const uint64_t** d_count) {
         if (rc) return rc;
         if (st.timed) HIP_TRY(hipEventRecord(st.e_chk1, c->stream));
         if (tiles_pass) {
-            rc = mvs::launch_exact_tiles(c->stream, a, (const int*)c->pw_tlist + 1, tile_cap, c->opt, true);
+            rc = mvs::launch_exact_tiles(c->stream, a, (const int*)c->pw_tlist.p + 1, tile_cap, c->opt, true);
             if (rc) return fail(rc, "exact tile launch rejected");
             rc = check_kernel("k_pairwise_pp(tiles)");
             if (rc) return rc;
         }
         if (st.timed) HIP_TRY(hipEventRecord(st.e_tiles1, c->stream));
-        mvs::launch_plan_verdict(c->stream, c->d_counter, st.a.cand_capacity, (const int*)c->pw_tlist, tile_cap, !tiles_pass);
+        mvs::launch_plan_verdict(c->stream, c->counters(), st.a.cand_capacity, (const int*)c->pw_tlist.p, tile_cap, !tiles_pass);
         rc = check_kernel("k_plan_verdict");
         if (rc) return rc;
         st.pending = true;
@@ -626,20 +619,20 @@ int mvs_plan_finish(mvs_ctx* c, const uint64_t** d_count) {
             const int rc = check_kernel("k_cand_gather");
             if (rc) return rc;
         }
-        mvs::launch_tile_count(c->stream, st.a.tile_flag, st.n_tr, st.n_tc, (int*)c->pw_trow);
+        mvs::launch_tile_count(c->stream, st.a.tile_flag, st.n_tr, st.n_tc, (int*)c->pw_trow.p);
         int rc = check_kernel("k_tile_count");
         if (rc) return rc;
         // the plan's ONE host synchronisation: the later launches are sized from these counts
-        rc = read_back(c, c->stream, {{back, c->d_counter, sizeof(back)}, {row_count.data(), c->pw_trow, (size_t)st.n_tr * 4}});
+        rc = read_back(c, c->stream, {{back, c->counters(), sizeof(back)}, {row_count.data(), c->pw_trow.p, (size_t)st.n_tr * 4}});
         if (rc) return rc;
         st.candidates = (long long)back[2];
         if (back[2] <= st.a.cand_capacity) break;
         if (attempt >= 2) return fail(MVS_E_HIP, "internal: the candidate list keeps outgrowing its buffer");
         // the list did not hold the candidates: grow it and run the plan's filter launches again (their inputs are resident)
-        rc = ensure_buf(c, &c->pw_cand, &c->pw_cand_bytes, (size_t)(back[2] + back[2] / 4) * sizeof(int2));
+        rc = ensure_buf(c, c->pw_cand, (size_t)(back[2] + back[2] / 4) * sizeof(int2));
         if (rc) return rc;
-        st.a.cand = (int2*)c->pw_cand;
-        st.a.cand_capacity = c->pw_cand_bytes / sizeof(int2);
+        st.a.cand = (int2*)c->pw_cand.p;
+        st.a.cand_capacity = c->pw_cand.bytes / sizeof(int2);
         rc = plan_reset_counters(c, st, true);
         if (rc) return rc;
         st.launches = 0;
@@ -668,28 +661,28 @@ int mvs_plan_finish(mvs_ctx* c, const uint64_t** d_count) {
     mvs::PairwiseArgs a = st.a;
     const int* d_list = nullptr;
     if (n_flagged > 0) {
-        int rc = ensure_buf(c, &c->pw_tlist, &c->pw_tlist_bytes, ((size_t)n_flagged + 1) * 4);
+        int rc = ensure_buf(c, c->pw_tlist, ((size_t)n_flagged + 1) * 4);
         if (rc) return rc;
-        mvs::launch_tile_list(c->stream, a.tile_flag, st.n_tr, st.n_tc, (const int*)c->pw_trow, (int*)c->pw_tlist);
+        mvs::launch_tile_list(c->stream, a.tile_flag, st.n_tr, st.n_tc, (const int*)c->pw_trow.p, (int*)c->pw_tlist.p);
         rc = check_kernel("k_tile_list");
         if (rc) return rc;
-        d_list = (const int*)c->pw_tlist + 1;
+        d_list = (const int*)c->pw_tlist.p + 1;
         if (st.candidates > 0) {
-            rc = ensure_buf(c, &c->pw_cand2, &c->pw_cand2_bytes, (size_t)st.candidates * sizeof(int2));
+            rc = ensure_buf(c, c->pw_cand2, (size_t)st.candidates * sizeof(int2));
             if (rc) return rc;
-            mvs::launch_cand_prune(c->stream, a, (unsigned long long)st.candidates, (int2*)c->pw_cand2, c->d_counter + 6);
+            mvs::launch_cand_prune(c->stream, a, (unsigned long long)st.candidates, (int2*)c->pw_cand2.p, c->counters() + 6);
             rc = check_kernel("k_cand_prune");
             if (rc) return rc;
-            a.cand = (int2*)c->pw_cand2;
-            a.cand_capacity = c->pw_cand2_bytes / sizeof(int2);
-            a.cand_counter = c->d_counter + 6;
+            a.cand = (int2*)c->pw_cand2.p;
+            a.cand_capacity = c->pw_cand2.bytes / sizeof(int2);
+            a.cand_counter = c->counters() + 6;
         }
-        rc = ensure_buf(c, &c->pw_thr, &c->pw_thr_bytes, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
+        rc = ensure_buf(c, c->pw_thr, ((size_t)s->n_alloc + 1) * 4);   // (+ the mark of launch_cand_thr)
         if (rc) return rc;
-        mvs::launch_cand_thr(c->stream, st.d_n2, s->n, s->n_alloc, s->d, a.keep_coeff, (int32_t*)c->pw_thr);
+        mvs::launch_cand_thr(c->stream, st.d_n2, s->n, s->n_alloc, s->d, a.keep_coeff, (int32_t*)c->pw_thr.p);
         rc = check_kernel("k_cand_thr");
         if (rc) return rc;
-        a.cand_thr = (const int32_t*)c->pw_thr;
+        a.cand_thr = (const int32_t*)c->pw_thr.p;
     }
     if (st.candidates > 0) {
         int rc = mvs::launch_exact_pairs(c->stream, a, c->opt, st.candidates);
@@ -808,10 +801,10 @@ int mvs_cells_sort_rows(mvs_ctx* c, const mvs_cell* cells_in, int64_t n, int64_t
     int rc = mvs::sort_cells_rows(c->stream, cells_in, cells_out, n, (int)own_begin, (int)(own_end - own_begin),
                                   reinterpret_cast<const unsigned long long*>(d_own_state), nullptr, 0, &need);
     if (rc) return fail(rc, "row sort sizing failed");
-    rc = ensure_buf(c, &c->pw_sort, &c->pw_sort_bytes, need);
+    rc = ensure_buf(c, c->pw_sort, need);
     if (rc) return rc;
     rc = mvs::sort_cells_rows(c->stream, cells_in, cells_out, n, (int)own_begin, (int)(own_end - own_begin),
-                              reinterpret_cast<const unsigned long long*>(d_own_state), c->pw_sort, c->pw_sort_bytes, nullptr);
+                              reinterpret_cast<const unsigned long long*>(d_own_state), c->pw_sort.p, c->pw_sort.bytes, nullptr);
     if (rc) return fail(rc, "row sort failed");
     return check_kernel("k_rows_sort");
 }
@@ -829,10 +822,10 @@ int mvs_cells_sort_rows_ahead(mvs_ctx* c, const mvs_cell* cells_in, int64_t in_c
     int rc = mvs::sort_cells_rows(c->stream, cells_in, cells_out, 0, (int)own_begin, (int)(own_end - own_begin),
                                   reinterpret_cast<const unsigned long long*>(d_own_state), nullptr, 0, &need, in_capacity, out_capacity);
     if (rc) return fail(rc, "row sort sizing failed");
-    rc = ensure_buf(c, &c->pw_sort, &c->pw_sort_bytes, need);
+    rc = ensure_buf(c, c->pw_sort, need);
     if (rc) return rc;
     rc = mvs::sort_cells_rows(c->stream, cells_in, cells_out, 0, (int)own_begin, (int)(own_end - own_begin),
-                              reinterpret_cast<const unsigned long long*>(d_own_state), c->pw_sort, c->pw_sort_bytes, nullptr, in_capacity,
+                              reinterpret_cast<const unsigned long long*>(d_own_state), c->pw_sort.p, c->pw_sort.bytes, nullptr, in_capacity,
                               out_capacity);
     if (rc) return fail(rc, "row sort failed");
     c->rows_max_done = d_own_state;        // the scan left the widest row in the state block: the report need not look again
@@ -848,13 +841,13 @@ int mvs_cells_report(mvs_ctx* c, const void* recv, int world, int64_t foreign_ca
     const size_t hdr_bytes = (size_t)world * MVS_CELLS_HEADER_BYTES;
     const int rc = ensure_read_back(c, 64 + hdr_bytes + 33 * 8);
     if (rc) return rc;
-    unsigned long long* own = static_cast<unsigned long long*>(c->rb_pinned);
+    unsigned long long* own = static_cast<unsigned long long*>(c->rb_pinned.p);
     unsigned long long* hdr = own + 8;
     unsigned long long* plan_back = hdr + (size_t)world * 8;
-    memset(c->rb_pinned, 0, 64 + hdr_bytes);
+    memset(c->rb_pinned.p, 0, 64 + hdr_bytes);
     // a plan that ran ahead of its read-backs: its counts come along with this one
     const bool with_plan = c->plan && c->plan->pending;
-    if (with_plan) HIP_TRY(hipMemcpyAsync(plan_back, c->d_counter, 33 * 8, hipMemcpyDeviceToHost, c->stream));
+    if (with_plan) HIP_TRY(hipMemcpyAsync(plan_back, c->counters(), 33 * 8, hipMemcpyDeviceToHost, c->stream));
     if (c->rows_max_done != d_own_count)
         mvs::launch_rows_max(c->stream, reinterpret_cast<unsigned long long*>(d_own_count), (int)own_rows);
     HIP_TRY(hipMemcpyAsync(own, d_own_count, 16, hipMemcpyDeviceToHost, c->stream));

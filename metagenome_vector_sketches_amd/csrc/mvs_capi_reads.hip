@@ -16,8 +16,8 @@ struct mvs_kmer_sketcher {
     uint64_t max_hash = 0;
     bool finished = false, broken = false;
     // the staging list of (value, sample) pairs: `len` of `cap` entries are filled
-    unsigned long long* vals = nullptr;
-    int32_t* samp = nullptr;
+    DevBuf vals;   // unsigned long long
+    DevBuf samp;   // int32_t
     long long cap = 0, len = 0;
     // what the adds did (mvs_kmer_sketcher_info): hashing time (timing enabled), second trips, times the list grew
     double hash_ms = 0.0;
@@ -105,40 +105,24 @@ int sort_samples(mvs_ctx* c, const unsigned long long* d_in, const uint32_t* d_w
     return tm.add_to(&c->ab_sort_ms);
 }
 
-void sketcher_free_staging(mvs_kmer_sketcher* k) {
-    if (k->vals) (void)hipFree(k->vals);
-    if (k->samp) (void)hipFree(k->samp);
-    k->vals = nullptr;
-    k->samp = nullptr;
-    k->cap = 0;
-}
-
 // the staging list holds at least `want` entries; what it held is kept (a device copy into a list at least twice as long)
 int sketcher_reserve(mvs_kmer_sketcher* k, long long want) {
     if (want <= k->cap) return MVS_OK;
     mvs_ctx* c = k->ctx;
     const long long cap = std::max(want, 2 * k->cap);
-    unsigned long long* nv = nullptr;
-    int32_t* ns = nullptr;
-    if (hipMalloc((void**)&nv, (size_t)cap * 8) != hipSuccess || hipMalloc((void**)&ns, (size_t)cap * 4) != hipSuccess) {
-        if (nv) (void)hipFree(nv);
+    DevBuf nv, ns;
+    if (nv.alloc((size_t)cap * 8) != hipSuccess || ns.alloc((size_t)cap * 4) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of a staging list of %lld values failed", cap);
-    }
     hipError_t e = hipSuccess;
     if (k->len > 0) {
-        e = hipMemcpyAsync(nv, k->vals, (size_t)k->len * 8, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ns, k->samp, (size_t)k->len * 4, hipMemcpyDeviceToDevice, c->stream);
+        e = hipMemcpyAsync(nv.p, k->vals.p, (size_t)k->len * 8, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ns.p, k->samp.p, (size_t)k->len * 4, hipMemcpyDeviceToDevice, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(nv);
-        (void)hipFree(ns);
-        return fail(MVS_E_HIP, "growing the staging list: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(MVS_E_HIP, "growing the staging list: %s", hipGetErrorString(e));
     if (k->cap > 0) ++k->growths;
-    sketcher_free_staging(k);
-    k->vals = nv;
-    k->samp = ns;
+    k->vals = std::move(nv);
+    k->samp = std::move(ns);
     k->cap = cap;
     return MVS_OK;
 }
@@ -163,8 +147,7 @@ int counted_build(mvs_ctx* c, const unsigned long long* d_in, const uint32_t* d_
     h->ctx = c;
     h->n = n;
     DevBuf doff, ddist, dsorted, dsortedw, dborders, dwork, dhist;
-    if (hipMalloc((void**)&h->offsets, ((size_t)n + 1) * 8) != hipSuccess ||
-        hipMalloc((void**)&h->sizes, (size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess ||
+    if (h->offsets.alloc(((size_t)n + 1) * 8) != hipSuccess || h->sizes.alloc((size_t)std::max<int64_t>(n, 1) * 4) != hipSuccess ||
         doff.alloc(((size_t)n + 1) * 8) != hipSuccess || ddist.alloc(((size_t)n + 1) * 8) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of the offsets of %lld samples failed", (long long)n);
     HIP_TRY(hipMemcpyAsync(doff.p, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
@@ -225,13 +208,14 @@ int counted_build(mvs_ctx* c, const unsigned long long* d_in, const uint32_t* d_
         rc = tm.add_to(&c->ab_count_ms);
         if (rc) return rc;
         if (flag) return fail(MVS_E_RANGE, "the abundance of a value reaches 2^32");
-        if (hipMalloc((void**)&h->hashes, (size_t)std::max<long long>(totals[1], 1) * 8) != hipSuccess ||
-            hipMalloc((void**)&h->abund, (size_t)std::max<long long>(totals[1], 1) * 4) != hipSuccess)
+        if (h->hashes.alloc((size_t)std::max<long long>(totals[1], 1) * 8) != hipSuccess ||
+            h->abund.alloc((size_t)std::max<long long>(totals[1], 1) * 4) != hipSuccess)
             return fail(MVS_E_NOMEM, "hipMalloc of %lld values and abundances failed", totals[1]);
         StageTimer tf;                      // pass D
         rc = tf.begin(c);
         if (rc) return rc;
-        rc = mvs::ab_fill(c->stream, a, h->hashes, h->abund, h->offsets, (long long*)ddist.p, h->sizes);
+        rc = mvs::ab_fill(c->stream, a, h->hashes.as<unsigned long long>(), h->abund.as<uint32_t>(), h->offsets.as<long long>(),
+                          (long long*)ddist.p, h->sizes.as<int32_t>());
         if (!rc) rc = check_kernel("k_ab_fill");
         if (rc) return rc;
         rc = tf.mark_end();
@@ -240,9 +224,10 @@ int counted_build(mvs_ctx* c, const unsigned long long* d_in, const uint32_t* d_
         rc = tf.add_to(&c->ab_count_ms);
         if (rc) return rc;
     } else {
-        if (hipMalloc((void**)&h->hashes, 8) != hipSuccess || hipMalloc((void**)&h->abund, 4) != hipSuccess)
+        if (h->hashes.alloc(8) != hipSuccess || h->abund.alloc(4) != hipSuccess)
             return fail(MVS_E_NOMEM, "hipMalloc of an empty set failed");
-        int rc = mvs::ab_fill(c->stream, a, h->hashes, h->abund, h->offsets, (long long*)ddist.p, h->sizes);
+        int rc = mvs::ab_fill(c->stream, a, h->hashes.as<unsigned long long>(), h->abund.as<uint32_t>(), h->offsets.as<long long>(),
+                          (long long*)ddist.p, h->sizes.as<int32_t>());
         if (!rc) rc = check_kernel("k_ab_tail");
         if (rc) return rc;
     }
@@ -252,7 +237,7 @@ int counted_build(mvs_ctx* c, const unsigned long long* d_in, const uint32_t* d_
     if (distinct || passed) {
         std::vector<long long> d((size_t)n + 1), p((size_t)n + 1);
         HIP_TRY(hipMemcpyAsync(d.data(), ddist.p, d.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(p.data(), h->offsets, p.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(p.data(), h->offsets.p, p.size() * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (distinct) distinct->resize((size_t)n);
         if (passed) passed->resize((size_t)n);
@@ -317,12 +302,12 @@ int mvs_hash_set_create_counted(mvs_ctx* c, const uint64_t* hashes, int mem_hash
 int mvs_hash_set_abundances(const mvs_hash_set* h, uint32_t* out, int mem_out) {
     if (!h) return fail(MVS_E_INVALID, "NULL hash set");
     if (!mem_ok(mem_out)) return fail(MVS_E_INVALID, "bad argument");
-    if (!h->abund) return fail(MVS_E_INVALID, "the hash set carries no abundances");
+    if (!h->abund.p) return fail(MVS_E_INVALID, "the hash set carries no abundances");
     if (h->total == 0) return MVS_OK;
     if (!out) return fail(MVS_E_INVALID, "out is NULL");
     mvs_ctx* c = h->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(out, h->abund, (size_t)h->total * 4, mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+    HIP_TRY(hipMemcpyAsync(out, h->abund.p, (size_t)h->total * 4, mem_out == MVS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MVS_OK;
@@ -438,7 +423,8 @@ int mvs_kmer_sketcher_add(mvs_kmer_sketcher* k, const uint8_t* bases, int mem_ba
         rc = tm.begin(c);
         if (rc) return rc;
         rc = mvs::launch_kmer_hash(c->stream, d_bases, total_bytes, (const mvs::KmerUnit*)dunits.p, n_units, U, ksize, k->seed, k->max_hash,
-                                   k->vals + k->len, k->samp + k->len, room, d_counters, d_sample_counts, d_sample_valid);
+                                   k->vals.as<unsigned long long>() + k->len, k->samp.as<int32_t>() + k->len, room, d_counters,
+                                   d_sample_counts, d_sample_valid);
         if (rc) return fail(rc, "k_kmer_hash: bad launch geometry");
         rc = check_kernel("k_kmer_hash");
         if (rc) return rc;
@@ -496,8 +482,8 @@ int mvs_kmer_sketcher_finish(mvs_kmer_sketcher* k, uint32_t min_abundance, uint3
         StageTimer tm;
         int rc = tm.begin(c);
         if (rc) return rc;
-        rc = mvs::launch_kmer_scatter(c->stream, k->vals, k->samp, k->len, (const long long*)doff.p, (unsigned long long*)dcur.p,
-                                      (unsigned long long*)dgrouped.p);
+        rc = mvs::launch_kmer_scatter(c->stream, k->vals.as<unsigned long long>(), k->samp.as<int32_t>(), k->len, (const long long*)doff.p,
+                                      (unsigned long long*)dcur.p, (unsigned long long*)dgrouped.p);
         if (rc) return fail(rc, "k_kmer_scatter: bad launch geometry");
         rc = check_kernel("k_kmer_scatter");
         if (rc) return rc;
@@ -508,7 +494,9 @@ int mvs_kmer_sketcher_finish(mvs_kmer_sketcher* k, uint32_t min_abundance, uint3
         if (rc) return rc;
     }
     k->finished = true;                    // the staging list is gone: whatever follows, there is no second finish
-    sketcher_free_staging(k);
+    k->vals.reset();
+    k->samp.reset();
+    k->cap = 0;
     return counted_build(c, (const unsigned long long*)dgrouped.p, nullptr, hoff, n, min_abundance, max_abundance, histogram, &k->distinct,
                          &k->passed, out);
 }
@@ -544,7 +532,6 @@ int mvs_kmer_sketcher_destroy(mvs_kmer_sketcher* k) {
         (void)hipSetDevice(k->ctx->device);
         (void)hipStreamSynchronize(k->ctx->stream);
     }
-    sketcher_free_staging(k);
     delete k;
     return MVS_OK;
 }

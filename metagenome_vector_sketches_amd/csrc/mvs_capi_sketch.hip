@@ -260,17 +260,17 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
     if (rc) return rc;
     size_t n_units = 0;
     thread_local std::vector<RowRange> cut_rows;   // samples of several units: combined with atomics, statistics afterwards
-    rc = plan_project_units(offsets, n_samples, ny, slots, kProjOverhead, balance, (mvs::ProjUnit*)c->pinned,
-                            c->pinned_bytes / sizeof(mvs::ProjUnit), &n_units, &cut_rows);
+    rc = plan_project_units(offsets, n_samples, ny, slots, kProjOverhead, balance, (mvs::ProjUnit*)c->pinned.p,
+                            c->pinned.bytes / sizeof(mvs::ProjUnit), &n_units, &cut_rows);
     if (rc) return rc;
-    if (n_units * sizeof(mvs::ProjUnit) > c->pinned_bytes) {
+    if (n_units * sizeof(mvs::ProjUnit) > c->pinned.bytes) {
         rc = acquire_pinned(c, n_units * sizeof(mvs::ProjUnit));
         if (rc) return rc;
-        rc = plan_project_units(offsets, n_samples, ny, slots, kProjOverhead, balance, (mvs::ProjUnit*)c->pinned,
-                                c->pinned_bytes / sizeof(mvs::ProjUnit), &n_units, &cut_rows);
+        rc = plan_project_units(offsets, n_samples, ny, slots, kProjOverhead, balance, (mvs::ProjUnit*)c->pinned.p,
+                                c->pinned.bytes / sizeof(mvs::ProjUnit), &n_units, &cut_rows);
         if (rc) return rc;
     }
-    mvs::ProjUnit* units = (mvs::ProjUnit*)c->pinned;
+    mvs::ProjUnit* units = (mvs::ProjUnit*)c->pinned.p;
     // many scattered ranges (long samples all over a ragged list) are not worth a memset and a launch each: rows between
     // them may be cleared before and measured again after the projection without changing anything
     c->pj_units = (long long)n_units;
@@ -303,7 +303,7 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
     rc = ensure_scratch(c, std::max<size_t>(ubytes, 256));
     if (rc) return rc;
     if (n_units) {
-        HIP_TRY(hipMemcpyAsync(c->scratch, units, ubytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->scratch.p, units, ubytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipEventRecord(c->pinned_ev, c->stream));
         c->pinned_busy = true;
     }
@@ -316,12 +316,12 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
     const bool fused = sumsq != nullptr;
     if (fused) {
         HIP_TRY(hipMemsetAsync(sumsq, 0, (size_t)n_samples * 8, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 8, c->stream));
+        HIP_TRY(hipMemsetAsync(c->counters(), 0, 8, c->stream));
     }
     if (c->timing) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     if (!pipelined) {
-        mvs::launch_project(c->stream, d_hashes, (const mvs::ProjUnit*)c->scratch, (int64_t)n_units, d, d_out, bpw,
-                            fused ? (unsigned long long*)sumsq : nullptr, fused ? c->d_counter : nullptr);
+        mvs::launch_project(c->stream, d_hashes, (const mvs::ProjUnit*)c->scratch.p, (int64_t)n_units, d, d_out, bpw,
+                            fused ? (unsigned long long*)sumsq : nullptr, fused ? c->counters() : nullptr);
         rc = check_kernel("k_project");
         if (rc) return rc;
     } else {
@@ -335,16 +335,16 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
             const int b = piece & 1;
             const size_t len = std::min(kUploadPiece, total_bytes - off);
             if (piece >= 2) HIP_TRY(hipEventSynchronize(c->up_done[b]));      // staging buffer b is free again
-            parallel_copy(c->up_pinned[b], (const char*)hashes + off, len);
-            HIP_TRY(hipMemcpyAsync((char*)dh.p + off, c->up_pinned[b], len, hipMemcpyHostToDevice, c->up_stream));
+            parallel_copy(c->up_pinned[b].p, (const char*)hashes + off, len);
+            HIP_TRY(hipMemcpyAsync((char*)dh.p + off, c->up_pinned[b].p, len, hipMemcpyHostToDevice, c->up_stream));
             HIP_TRY(hipEventRecord(c->up_done[b], c->up_stream));
             const int64_t covered = (int64_t)((off + len) / 8);
             size_t u_next = u_done;
             while (u_next < n_units && units[u_next].begin + units[u_next].count <= covered) ++u_next;
             if (u_next > u_done) {
                 HIP_TRY(hipStreamWaitEvent(c->stream, c->up_done[b], 0));
-                mvs::launch_project(c->stream, d_hashes, (const mvs::ProjUnit*)c->scratch + u_done, (int64_t)(u_next - u_done), d,
-                                    d_out, bpw, fused ? (unsigned long long*)sumsq : nullptr, fused ? c->d_counter : nullptr);
+                mvs::launch_project(c->stream, d_hashes, (const mvs::ProjUnit*)c->scratch.p + u_done, (int64_t)(u_next - u_done), d,
+                                    d_out, bpw, fused ? (unsigned long long*)sumsq : nullptr, fused ? c->counters() : nullptr);
                 rc = check_kernel("k_project");
                 if (rc) return rc;
                 u_done = u_next;
@@ -358,13 +358,13 @@ int mvs_project_csr_stats(mvs_ctx* c, const uint64_t* hashes, int mem_hashes, co
     }
     if (fused) {
         for (const RowRange& r : cut_rows) {   // their entries are final only now
-            mvs::launch_stats(c->stream, d_out + r.lo * (int64_t)d, r.hi - r.lo, d, sumsq + r.lo, c->d_counter);
+            mvs::launch_stats(c->stream, d_out + r.lo * (int64_t)d, r.hi - r.lo, d, sumsq + r.lo, c->counters());
             rc = check_kernel("k_stats");
             if (rc) return rc;
         }
         unsigned long long m = 0;
         {
-            const int rb_rc = read_back(c, c->stream, {{&m, c->d_counter, 8}});
+            const int rb_rc = read_back(c, c->stream, {{&m, c->counters(), 8}});
             if (rb_rc) return rb_rc;
         }
         *max_abs = (int64_t)m;
@@ -494,15 +494,15 @@ int mvs_sketch_stats(mvs_ctx* c, const int32_t* sketches, int mem_in, int64_t n,
         HIP_TRY(dout.alloc((size_t)n * 8));
         d_out = (int64_t*)dout.p;
     }
-    HIP_TRY(hipMemsetAsync(c->d_counter, 0, 8, c->stream));
-    mvs::launch_stats(c->stream, d_in, n, d, d_out, c->d_counter);
+    HIP_TRY(hipMemsetAsync(c->counters(), 0, 8, c->stream));
+    mvs::launch_stats(c->stream, d_in, n, d, d_out, c->counters());
     int rc = check_kernel("k_stats");
     if (rc) return rc;
     if (mem_out == MVS_MEM_HOST)
         HIP_TRY(hipMemcpyAsync(sumsq, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     unsigned long long m = 0;
     {
-        const int rb_rc = read_back(c, c->stream, {{&m, c->d_counter, 8}});
+        const int rb_rc = read_back(c, c->stream, {{&m, c->counters(), 8}});
         if (rb_rc) return rb_rc;
     }
     *max_abs = (int64_t)m;
@@ -551,18 +551,18 @@ int mvs_sketch_max_abs(mvs_ctx* c, const void* sketches, int elem_bytes, int mem
     HIP_TRY(hipSetDevice(c->device));
     const void* d_in = sketches;
     if (mem == MVS_MEM_HOST) {
-        int rc0 = ensure_buf(c, &c->stage, &c->stage_bytes, (size_t)n_elems * elem_bytes);
+        int rc0 = ensure_buf(c, c->stage, (size_t)n_elems * elem_bytes);
         if (rc0) return rc0;
-        HIP_TRY(hipMemcpyAsync(c->stage, sketches, (size_t)n_elems * elem_bytes, hipMemcpyHostToDevice, c->stream));
-        d_in = c->stage;
+        HIP_TRY(hipMemcpyAsync(c->stage.p, sketches, (size_t)n_elems * elem_bytes, hipMemcpyHostToDevice, c->stream));
+        d_in = c->stage.p;
     }
-    HIP_TRY(hipMemsetAsync(c->d_counter, 0, 8, c->stream));
-    mvs::launch_max_abs(c->stream, d_in, elem_bytes, n_elems, c->d_counter);
+    HIP_TRY(hipMemsetAsync(c->counters(), 0, 8, c->stream));
+    mvs::launch_max_abs(c->stream, d_in, elem_bytes, n_elems, c->counters());
     int rc = check_kernel("k_max_abs");
     if (rc) return rc;
     unsigned long long m = 0;
     {
-        const int rb_rc = read_back(c, c->stream, {{&m, c->d_counter, 8}});
+        const int rb_rc = read_back(c, c->stream, {{&m, c->counters(), 8}});
         if (rb_rc) return rb_rc;
     }
     *max_abs = (int64_t)m;
@@ -599,10 +599,10 @@ int mvs_limb_split(mvs_ctx* c, const void* sketches, int elem_bytes, int mem, in
     HIP_TRY(hipSetDevice(c->device));
     const void* d_in = sketches;
     if (mem == MVS_MEM_HOST) {   // grow-only staging buffer of the context (no allocation per chunk)
-        int rc0 = ensure_buf(c, &c->stage, &c->stage_bytes, (size_t)n_rows * d * elem_bytes);
+        int rc0 = ensure_buf(c, c->stage, (size_t)n_rows * d * elem_bytes);
         if (rc0) return rc0;
-        HIP_TRY(hipMemcpyAsync(c->stage, sketches, (size_t)n_rows * d * elem_bytes, hipMemcpyHostToDevice, c->stream));
-        d_in = c->stage;
+        HIP_TRY(hipMemcpyAsync(c->stage.p, sketches, (size_t)n_rows * d * elem_bytes, hipMemcpyHostToDevice, c->stream));
+        d_in = c->stage.p;
     }
     mvs::launch_limb_split(c->stream, d_in, elem_bytes, n_rows, d, limbs, planes, d_pad, row_offset);
     int rc = check_kernel("k_limb_split");
@@ -640,32 +640,26 @@ int mvs_sketch_set_create(mvs_ctx* c, const void* sketches, int elem_bytes, int 
     int d_pad = 0;
     size_t bytes = 0;
     mvs_limb_geometry(n, d, limbs, &n_alloc, &d_pad, &bytes);
-    mvs_sketch_set* s = new (std::nothrow) mvs_sketch_set();
+    std::unique_ptr<mvs_sketch_set> s(new (std::nothrow) mvs_sketch_set());
     if (!s) return fail(MVS_E_NOMEM, "out of host memory");
-    if (hipMalloc((void**)&s->owned, bytes) != hipSuccess) {
-        delete s;
-        return fail(MVS_E_NOMEM, "hipMalloc of %zu bytes of limb planes failed", bytes);
-    }
+    if (s->owned.alloc(bytes) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %zu bytes of limb planes failed", bytes);
     s->ctx = c;
-    s->planes = s->owned;
+    s->planes = s->owned.as<int8_t>();
     s->n = n;
     s->n_alloc = n_alloc;
     s->d = d;
     s->d_pad = d_pad;
     s->limbs = limbs;
     s->id = ++g_set_ids;
-    hipError_t e = hipMemsetAsync(s->owned, 0, bytes, c->stream);
+    hipError_t e = hipMemsetAsync(s->owned.p, 0, bytes, c->stream);
     if (e == hipSuccess) {
-        rc = mvs_limb_split(c, d_in, elem_bytes, MVS_MEM_DEVICE, n, d, limbs, s->owned, d_pad, 0);
+        rc = mvs_limb_split(c, d_in, elem_bytes, MVS_MEM_DEVICE, n, d, limbs, s->owned.as<int8_t>(), d_pad, 0);
         if (rc == MVS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(MVS_E_HIP, "sync failed");
     } else {
         rc = fail(MVS_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
-    if (rc) {
-        mvs_sketch_set_destroy(s);
-        return rc;
-    }
-    *out = s;
+    if (rc) return rc;
+    *out = s.release();
     return MVS_OK;
 }
 
@@ -704,25 +698,19 @@ int mvs_sketch_set_alloc(mvs_ctx* c, int64_t n, int d, int limbs, mvs_sketch_set
     int d_pad = 0;
     size_t bytes = 0;
     mvs_limb_geometry(n, d, limbs, &n_alloc, &d_pad, &bytes);
-    mvs_sketch_set* s = new (std::nothrow) mvs_sketch_set();
+    std::unique_ptr<mvs_sketch_set> s(new (std::nothrow) mvs_sketch_set());
     if (!s) return fail(MVS_E_NOMEM, "out of host memory");
-    if (hipMalloc((void**)&s->owned, bytes) != hipSuccess) {
-        delete s;
-        return fail(MVS_E_NOMEM, "hipMalloc of %zu bytes of limb planes failed", bytes);
-    }
+    if (s->owned.alloc(bytes) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %zu bytes of limb planes failed", bytes);
     s->ctx = c;
-    s->planes = s->owned;
+    s->planes = s->owned.as<int8_t>();
     s->n = n;
     s->n_alloc = n_alloc;
     s->d = d;
     s->d_pad = d_pad;
     s->limbs = limbs;
     s->id = ++g_set_ids;
-    if (hipMemsetAsync(s->owned, 0, bytes, c->stream) != hipSuccess) {
-        mvs_sketch_set_destroy(s);
-        return fail(MVS_E_HIP, "hipMemsetAsync failed");
-    }
-    *out = s;
+    if (hipMemsetAsync(s->owned.p, 0, bytes, c->stream) != hipSuccess) return fail(MVS_E_HIP, "hipMemsetAsync failed");
+    *out = s.release();
     return MVS_OK;
 }
 
@@ -756,7 +744,7 @@ extern "C" {
 
 int mvs_sketch_set_fill(mvs_sketch_set* s, const void* sketches, int elem_bytes, int mem, int64_t row_offset,
                         int64_t n_rows) {
-    if (!s || !s->owned) return fail(MVS_E_INVALID, "set is NULL or not owned by the library");
+    if (!s || !s->owned.p) return fail(MVS_E_INVALID, "set is NULL or not owned by the library");
     if (row_offset < 0 || n_rows < 0 || row_offset + n_rows > s->n)
         return fail(MVS_E_INVALID, "rows [%lld,%lld) outside the set", (long long)row_offset,
                     (long long)(row_offset + n_rows));
@@ -764,12 +752,12 @@ int mvs_sketch_set_fill(mvs_sketch_set* s, const void* sketches, int elem_bytes,
     if ((elem_bytes != 4 && elem_bytes != 2) || !mem_ok(mem)) return fail(MVS_E_INVALID, "bad argument");
     if (n_rows > 0 && !sketches) return fail(MVS_E_INVALID, "sketches is NULL");
     if (n_rows > 0) note_rows_rewritten(s, row_offset, row_offset + n_rows);
-    return mvs_limb_split(s->ctx, sketches, elem_bytes, mem, n_rows, s->d, s->limbs, s->owned, s->d_pad, row_offset);
+    return mvs_limb_split(s->ctx, sketches, elem_bytes, mem, n_rows, s->d, s->limbs, s->owned.as<int8_t>(), s->d_pad, row_offset);
 }
 
 int mvs_sketch_set_fill_stats(mvs_sketch_set* s, const void* sketches, int elem_bytes, int mem, int64_t row_offset,
                               int64_t n_rows, int64_t* max_abs) {
-    if (!s || !s->owned) return fail(MVS_E_INVALID, "set is NULL or not owned by the library");
+    if (!s || !s->owned.p) return fail(MVS_E_INVALID, "set is NULL or not owned by the library");
     if (!max_abs) return fail(MVS_E_INVALID, "max_abs is NULL");
     *max_abs = 0;
     if ((elem_bytes != 4 && elem_bytes != 2) || !mem_ok(mem)) return fail(MVS_E_INVALID, "bad argument");
@@ -783,22 +771,22 @@ int mvs_sketch_set_fill_stats(mvs_sketch_set* s, const void* sketches, int elem_
     const size_t bytes = (size_t)n_rows * s->d * elem_bytes;
     const void* d_in = sketches;
     if (mem == MVS_MEM_HOST) {   // one upload serves both kernels
-        int rc0 = ensure_buf(c, &c->stage, &c->stage_bytes, bytes);
+        int rc0 = ensure_buf(c, c->stage, bytes);
         if (rc0) return rc0;
-        HIP_TRY(hipMemcpyAsync(c->stage, sketches, bytes, hipMemcpyHostToDevice, c->stream));
-        d_in = c->stage;
+        HIP_TRY(hipMemcpyAsync(c->stage.p, sketches, bytes, hipMemcpyHostToDevice, c->stream));
+        d_in = c->stage.p;
     }
     note_rows_rewritten(s, row_offset, row_offset + n_rows);
-    HIP_TRY(hipMemsetAsync(c->d_counter, 0, 8, c->stream));
-    mvs::launch_max_abs(c->stream, d_in, elem_bytes, n_rows * s->d, c->d_counter);
+    HIP_TRY(hipMemsetAsync(c->counters(), 0, 8, c->stream));
+    mvs::launch_max_abs(c->stream, d_in, elem_bytes, n_rows * s->d, c->counters());
     int rc = check_kernel("k_max_abs");
     if (rc) return rc;
-    mvs::launch_limb_split(c->stream, d_in, elem_bytes, n_rows, s->d, s->limbs, s->owned, s->d_pad, row_offset);
+    mvs::launch_limb_split(c->stream, d_in, elem_bytes, n_rows, s->d, s->limbs, s->owned.as<int8_t>(), s->d_pad, row_offset);
     rc = check_kernel("k_limb_split");
     if (rc) return rc;
     unsigned long long m = 0;
     {
-        const int rb_rc = read_back(c, c->stream, {{&m, c->d_counter, 8}});
+        const int rb_rc = read_back(c, c->stream, {{&m, c->counters(), 8}});
         if (rb_rc) return rb_rc;
     }
     *max_abs = (int64_t)m;
@@ -817,8 +805,8 @@ int mvs_sketch_set_info(const mvs_sketch_set* s, int64_t* n, int* d, int* limbs,
 
 int mvs_sketch_set_planes(mvs_sketch_set* s, int8_t** planes) {
     if (!s || !planes) return fail(MVS_E_INVALID, "NULL argument");
-    if (!s->owned) return fail(MVS_E_INVALID, "the set is a view of a caller-owned buffer");
-    *planes = s->owned;
+    if (!s->owned.p) return fail(MVS_E_INVALID, "the set is a view of a caller-owned buffer");
+    *planes = s->owned.as<int8_t>();
     return MVS_OK;
 }
 
@@ -842,10 +830,9 @@ int mvs_ctx_derived_stats(mvs_ctx* c, int64_t* coarse_builds, int64_t* coarse_ro
 
 int mvs_sketch_set_destroy(mvs_sketch_set* s) {
     if (!s) return MVS_OK;
-    if (s->owned) {
+    if (s->owned.p) {
         (void)hipSetDevice(s->ctx->device);
         (void)hipStreamSynchronize(s->ctx->stream);
-        (void)hipFree(s->owned);
     }
     delete s;
     return MVS_OK;

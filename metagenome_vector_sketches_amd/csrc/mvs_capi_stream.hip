@@ -58,11 +58,10 @@ void hsa_copy_free(void* p) {
     delete h;
 }
 int ensure_hsa_copy(mvs_ctx* c) {
-    if (c->dl_hsa) return static_cast<HsaCopy*>(c->dl_hsa)->ok ? MVS_OK : fail(MVS_E_HIP, "the DMA copy path is not available");
+    if (c->dl_hsa) return static_cast<HsaCopy*>(c->dl_hsa.get())->ok ? MVS_OK : fail(MVS_E_HIP, "the DMA copy path is not available");
     HsaCopy* h = new (std::nothrow) HsaCopy();
     if (!h) return fail(MVS_E_NOMEM, "out of host memory");
-    c->dl_hsa = h;
-    c->dl_hsa_free = hsa_copy_free;
+    c->dl_hsa = {h, hsa_copy_free};
     if (hsa_init() != HSA_STATUS_SUCCESS) return fail(MVS_E_HIP, "hsa_init failed");
     HsaAgents ag;
     if (hsa_iterate_agents(hsa_on_agent, &ag) != HSA_STATUS_SUCCESS || ag.gpus.empty() || !ag.have_cpu) {
@@ -191,7 +190,7 @@ struct StreamOut {
             int status = 0;
             hipError_t e = hipSuccess;
             if (it.dma) {
-                const HsaCopy* h = static_cast<const HsaCopy*>(c->dl_hsa);
+                const HsaCopy* h = static_cast<const HsaCopy*>(c->dl_hsa.get());
                 if (hsa_signal_wait_scacquire(h->sig[it.slot], HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED) != 0)
                     e = hipErrorUnknown;       // (a negative value: the copy failed)
             } else {
@@ -216,7 +215,7 @@ struct StreamOut {
                     b.first_col = it.first_col.data();
                     b.offset = it.offset.data();
                     b.jac_bytes = it.jac_bytes.data();
-                    b.bytes = static_cast<const uint8_t*>(c->dl_pinned[it.slot]);
+                    b.bytes = static_cast<const uint8_t*>(c->dl_pinned[it.slot].p);
                     b.n_bytes = it.n_bytes;
                     try {
                         status = ecb(user, &b);
@@ -229,7 +228,7 @@ struct StreamOut {
                     b.row_end = it.row_end;
                     b.n_cells = it.n_cells;
                     b.row_ptr = it.row_ptr.data();
-                    const char* base = static_cast<const char*>(c->dl_pinned[it.slot]);
+                    const char* base = static_cast<const char*>(c->dl_pinned[it.slot].p);
                     b.col = reinterpret_cast<const int32_t*>(base);
                     const char* qbase = base + (size_t)it.n_cells * 4;
                     b.q = it.wide ? nullptr : reinterpret_cast<const uint8_t*>(qbase);
@@ -291,26 +290,22 @@ struct StreamOut {
 
 int ensure_download_side(mvs_ctx* c) {
     if (!c->dl_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->dl_stream, hipStreamNonBlocking));
+        HIP_TRY(c->dl_stream.create(hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {
-            HIP_TRY(hipEventCreateWithFlags(&c->dl_done[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c->dl_block[i], hipEventDisableTiming));
+            HIP_TRY(c->dl_done[i].create(hipEventDisableTiming));
+            HIP_TRY(c->dl_block[i].create(hipEventDisableTiming));
         }
-        for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&c->dl_ready[i], hipEventDisableTiming));
-        HIP_TRY(hipStreamCreateWithFlags(&c->post_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&c->cmp_done, hipEventDisableTiming));
+        for (int i = 0; i < 2; ++i) HIP_TRY(c->dl_ready[i].create(hipEventDisableTiming));
+        HIP_TRY(c->post_stream.create(hipStreamNonBlocking));
+        HIP_TRY(c->cmp_done.create(hipEventDisableTiming));
     }
     return MVS_OK;
 }
 
 // pinned buffer `slot` holds at least `bytes`; called by the producer while it owns the slot (nobody reads it)
 int ensure_pinned_slot(mvs_ctx* c, int slot, size_t bytes) {
-    if (c->dl_bytes[slot] >= bytes) return MVS_OK;
-    if (c->dl_pinned[slot]) HIP_TRY(hipHostFree(c->dl_pinned[slot]));
-    c->dl_pinned[slot] = nullptr;
-    c->dl_bytes[slot] = 0;
-    HIP_TRY(hipHostMalloc(&c->dl_pinned[slot], bytes, hipHostMallocDefault));
-    c->dl_bytes[slot] = bytes;
+    if (c->dl_pinned[slot].bytes >= bytes) return MVS_OK;
+    HIP_TRY(c->dl_pinned[slot].alloc(bytes));
     return MVS_OK;
 }
 
@@ -327,7 +322,7 @@ struct BlockCsr {
     std::vector<uint32_t> enc_jac, enc_first;
 };
 
-// The CSR arrays of `b` (set b.set) -> the rows' shard records in c->st_enc[b.set], directory on the host; on stream `ps`
+// The CSR arrays of `b` (set b.set) -> the rows' shard records in c->st_enc[b.set].p, directory on the host; on stream `ps`
 // (the context's stream, or the side stream on which a dense block is post-processed beside the next comparison)
 int encode_block(mvs_ctx* c, BlockCsr& b, hipStream_t ps) {
     const int64_t rows = b.re - b.rb;
@@ -339,39 +334,39 @@ int encode_block(mvs_ctx* c, BlockCsr& b, hipStream_t ps) {
         HIP_TRY(hipEventRecord(c->dl_ready[b.set], ps));
         return MVS_OK;
     }
-    int rc = ensure_buf(c, &c->en_size, &c->en_size_bytes, (size_t)(rows + 1) * 8);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_off, &c->en_off_bytes, (size_t)(rows + 1) * 8);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_jac, &c->en_jac_bytes, (size_t)rows * 4);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_first, &c->en_first_bytes, (size_t)rows * 4);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_par, &c->en_par_bytes, (size_t)rows * sizeof(mvs::EncRow));
+    int rc = ensure_buf(c, c->en_size, (size_t)(rows + 1) * 8);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_off, (size_t)(rows + 1) * 8);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_jac, (size_t)rows * 4);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_first, (size_t)rows * 4);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_par, (size_t)rows * sizeof(mvs::EncRow));
     if (rc) return rc;
     const int qb = b.wide ? 2 : 1;
-    HIP_TRY(hipMemsetAsync((char*)c->en_size + (size_t)rows * 8, 0, 8, ps));
+    HIP_TRY(hipMemsetAsync((char*)c->en_size.p + (size_t)rows * 8, 0, 8, ps));
     if (!b.sizes_ready) {                  // (a dense block's fill pass has computed them already)
-        mvs::launch_encode_sizes(ps, (const long long*)c->st_rowptr, (const int32_t*)c->st_col[b.set], c->st_q[b.set], qb, rows,
-                                 (unsigned long long*)c->en_size, (unsigned int*)c->en_jac, (unsigned int*)c->en_first,
-                                 (mvs::EncRow*)c->en_par);
+        mvs::launch_encode_sizes(ps, (const long long*)c->st_rowptr.p, (const int32_t*)c->st_col[b.set].p, c->st_q[b.set].p, qb, rows,
+                                 (unsigned long long*)c->en_size.p, (unsigned int*)c->en_jac.p, (unsigned int*)c->en_first.p,
+                                 (mvs::EncRow*)c->en_par.p);
         rc = check_kernel("k_enc_size");
         if (rc) return rc;
     }
     size_t need = 0;
-    rc = mvs::encode_offsets(ps, (unsigned long long*)c->en_size, (unsigned long long*)c->en_off, rows, nullptr, 0, &need);
+    rc = mvs::encode_offsets(ps, (unsigned long long*)c->en_size.p, (unsigned long long*)c->en_off.p, rows, nullptr, 0, &need);
     if (rc) return fail(rc, "scan sizing failed");
-    rc = ensure_buf(c, &c->pw_sort, &c->pw_sort_bytes, need);
+    rc = ensure_buf(c, c->pw_sort, need);
     if (rc) return rc;
-    rc = mvs::encode_offsets(ps, (unsigned long long*)c->en_size, (unsigned long long*)c->en_off, rows, c->pw_sort,
-                             c->pw_sort_bytes, nullptr);
+    rc = mvs::encode_offsets(ps, (unsigned long long*)c->en_size.p, (unsigned long long*)c->en_off.p, rows, c->pw_sort.p,
+                             c->pw_sort.bytes, nullptr);
     if (rc) return fail(rc, "scan of the record sizes failed");
-    rc = read_back(c, ps, {{b.enc_off.data(), c->en_off, (size_t)(rows + 1) * 8},
-                           {b.enc_jac.data(), c->en_jac, (size_t)rows * 4},
-                           {b.enc_first.data(), c->en_first, (size_t)rows * 4}});
+    rc = read_back(c, ps, {{b.enc_off.data(), c->en_off.p, (size_t)(rows + 1) * 8},
+                           {b.enc_jac.data(), c->en_jac.p, (size_t)rows * 4},
+                           {b.enc_first.data(), c->en_first.p, (size_t)rows * 4}});
     if (rc) return rc;
     const size_t total = (size_t)b.enc_off[(size_t)rows];
-    rc = ensure_buf(c, &c->st_enc[b.set], &c->st_enc_bytes[b.set], std::max<size_t>(total, 8));
+    rc = ensure_buf(c, c->st_enc[b.set], std::max<size_t>(total, 8));
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(c->st_enc[b.set], 0, total, ps));       // the unary parts are OR-ed into zeroed words
-    mvs::launch_encode_fill(ps, (const long long*)c->st_rowptr, (const int32_t*)c->st_col[b.set], c->st_q[b.set], qb, rows,
-                            (const unsigned long long*)c->en_off, (const mvs::EncRow*)c->en_par, (unsigned char*)c->st_enc[b.set],
+    HIP_TRY(hipMemsetAsync(c->st_enc[b.set].p, 0, total, ps));       // the unary parts are OR-ed into zeroed words
+    mvs::launch_encode_fill(ps, (const long long*)c->st_rowptr.p, (const int32_t*)c->st_col[b.set].p, c->st_q[b.set].p, qb, rows,
+                            (const unsigned long long*)c->en_off.p, (const mvs::EncRow*)c->en_par.p, (unsigned char*)c->st_enc[b.set].p,
                             c->opt.encode_stage_words);
     rc = check_kernel("k_enc_fill");
     if (rc) return rc;
@@ -383,12 +378,12 @@ int encode_block(mvs_ctx* c, BlockCsr& b, hipStream_t ps) {
 int claim_csr_set(mvs_ctx* c, int set, int64_t block_index, int64_t n, bool wide, hipStream_t ps) {
     // (with DMA copies the driving thread has waited for the callback thread to see that block's last piece: StreamOut::wait_done)
     if (block_index >= 2 && c->opt.stream_copy == 0) HIP_TRY(hipStreamWaitEvent(ps, c->dl_block[set], 0));
-    int rc = ensure_buf(c, &c->st_col[set], &c->st_col_bytes[set], (size_t)std::max<int64_t>(n, 1) * 4);
+    int rc = ensure_buf(c, c->st_col[set], (size_t)std::max<int64_t>(n, 1) * 4);
     if (rc) return rc;
-    return ensure_buf(c, &c->st_q[set], &c->st_q_bytes[set], (size_t)std::max<int64_t>(n, 1) * (wide ? 2 : 1));
+    return ensure_buf(c, c->st_q[set], (size_t)std::max<int64_t>(n, 1) * (wide ? 2 : 1));
 }
 
-// n packed cells of rows [rb, re) sit in c->st_raw: radix sort on the (row, col) bits, then row_ptr / col / q
+// n packed cells of rows [rb, re) sit in c->st_raw.p: radix sort on the (row, col) bits, then row_ptr / col / q
 int csr_from_packed(mvs_ctx* c, int64_t rb, int64_t re, int64_t n, int shift, int col_bits, int64_t block_index, BlockCsr& out) {
     const int64_t rows = re - rb;
     const int row_bits = bits_for(std::max<int64_t>(rows - 1, 1));
@@ -402,38 +397,38 @@ int csr_from_packed(mvs_ctx* c, int64_t rb, int64_t re, int64_t n, int shift, in
         HIP_TRY(hipEventRecord(c->dl_ready[out.set], c->stream));
         return MVS_OK;
     }
-    int rc = ensure_buf(c, &c->st_rowptr, &c->st_rowptr_bytes, (size_t)(rows + 1) * 8);
+    int rc = ensure_buf(c, c->st_rowptr, (size_t)(rows + 1) * 8);
     if (rc) return rc;
-    rc = ensure_buf(c, &c->st_sorted, &c->st_sorted_bytes, (size_t)n * 8);
+    rc = ensure_buf(c, c->st_sorted, (size_t)n * 8);
     if (rc) return rc;
     size_t need = 0;
-    rc = mvs::sort_packed(c->stream, (unsigned long long*)c->st_raw, (unsigned long long*)c->st_sorted, n, 16, shift + row_bits,
+    rc = mvs::sort_packed(c->stream, (unsigned long long*)c->st_raw.p, (unsigned long long*)c->st_sorted.p, n, 16, shift + row_bits,
                           nullptr, 0, &need);
     if (rc) return fail(rc, "sort sizing failed");
-    rc = ensure_buf(c, &c->pw_sort, &c->pw_sort_bytes, need);
+    rc = ensure_buf(c, c->pw_sort, need);
     if (rc) return rc;
-    rc = mvs::sort_packed(c->stream, (unsigned long long*)c->st_raw, (unsigned long long*)c->st_sorted, n, 16, shift + row_bits,
-                          c->pw_sort, c->pw_sort_bytes, nullptr);
+    rc = mvs::sort_packed(c->stream, (unsigned long long*)c->st_raw.p, (unsigned long long*)c->st_sorted.p, n, 16, shift + row_bits,
+                          c->pw_sort.p, c->pw_sort.bytes, nullptr);
     if (rc) return fail(rc, "sort of the kept cells failed");
     rc = claim_csr_set(c, out.set, block_index, n, false, c->stream);
     if (rc) return rc;
-    unsigned int* d_wide = reinterpret_cast<unsigned int*>(c->d_counter + 3);
+    unsigned int* d_wide = reinterpret_cast<unsigned int*>(c->counters() + 3);
     HIP_TRY(hipMemsetAsync(d_wide, 0, 4, c->stream));
     const unsigned long long col_mask = (1ULL << col_bits) - 1ULL;
-    mvs::launch_packed_csr(c->stream, (const unsigned long long*)c->st_sorted, n, shift, rows, col_mask, (long long*)c->st_rowptr,
-                           (int32_t*)c->st_col[out.set], (uint8_t*)c->st_q[out.set], nullptr, d_wide);
+    mvs::launch_packed_csr(c->stream, (const unsigned long long*)c->st_sorted.p, n, shift, rows, col_mask, (long long*)c->st_rowptr.p,
+                           (int32_t*)c->st_col[out.set].p, (uint8_t*)c->st_q[out.set].p, nullptr, d_wide);
     rc = check_kernel("k_packed_csr");
     if (rc) return rc;
     unsigned int h_wide = 0;
-    HIP_TRY(hipMemcpyAsync(out.row_ptr.data(), c->st_rowptr, (size_t)(rows + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out.row_ptr.data(), c->st_rowptr.p, (size_t)(rows + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&h_wide, d_wide, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (h_wide) {                      // some q needs 16 bits (norms that do not belong to the vectors): redo the q array
         out.wide = true;
-        rc = ensure_buf(c, &c->st_q[out.set], &c->st_q_bytes[out.set], (size_t)n * 2);
+        rc = ensure_buf(c, c->st_q[out.set], (size_t)n * 2);
         if (rc) return rc;
-        mvs::launch_packed_csr(c->stream, (const unsigned long long*)c->st_sorted, n, shift, rows, col_mask, nullptr,
-                               (int32_t*)c->st_col[out.set], nullptr, (uint16_t*)c->st_q[out.set], nullptr);
+        mvs::launch_packed_csr(c->stream, (const unsigned long long*)c->st_sorted.p, n, shift, rows, col_mask, nullptr,
+                               (int32_t*)c->st_col[out.set].p, nullptr, (uint16_t*)c->st_q[out.set].p, nullptr);
         rc = check_kernel("k_packed_csr(16-bit q)");
         if (rc) return rc;
     }
@@ -453,32 +448,32 @@ int csr_from_dense(mvs_ctx* c, int64_t rb, int64_t re, int64_t n_cols, int64_t d
     out.wide = false;
     out.set = (int)(block_index & 1);
     out.row_ptr.assign((size_t)rows + 1, 0);
-    int rc = ensure_buf(c, &c->st_rowptr, &c->st_rowptr_bytes, (size_t)(rows + 1) * 8);
+    int rc = ensure_buf(c, c->st_rowptr, (size_t)(rows + 1) * 8);
     if (rc) return rc;
-    rc = ensure_buf(c, &c->st_counts, &c->st_counts_bytes, (size_t)(rows + 1) * 8);
+    rc = ensure_buf(c, c->st_counts, (size_t)(rows + 1) * 8);
     if (rc) return rc;
     // the active tiles of the block's tile rows, every row's first / last kept column
     int tr0 = 0, n_trows = 0, n_tc = 0;
     mvs::dense_tile_rows(active, rows, n_cols, &tr0, &n_trows, &n_tc);
-    rc = ensure_buf(c, &c->st_tlist, &c->st_tlist_bytes, std::max<size_t>((size_t)n_trows * (size_t)n_tc * 4, 4));
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->st_tlist_n, &c->st_tlist_n_bytes, std::max<size_t>((size_t)n_trows * 4, 4));
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->st_ends, &c->st_ends_bytes, std::max<size_t>((size_t)rows * sizeof(int2), 8));
+    rc = ensure_buf(c, c->st_tlist, std::max<size_t>((size_t)n_trows * (size_t)n_tc * 4, 4));
+    if (rc == MVS_OK) rc = ensure_buf(c, c->st_tlist_n, std::max<size_t>((size_t)n_trows * 4, 4));
+    if (rc == MVS_OK) rc = ensure_buf(c, c->st_ends, std::max<size_t>((size_t)rows * sizeof(int2), 8));
     if (rc) return rc;
-    const uint8_t* first = (const uint8_t*)c->st_dense + (size_t)(rb - dense_row0) * (size_t)ld;
-    HIP_TRY(hipMemsetAsync((char*)c->st_counts + (size_t)rows * 8, 0, 8, ps));
-    mvs::launch_dense_count(ps, first, ld, n_cols, rows, (long long*)c->st_counts, (int2*)c->st_ends, active, (int*)c->st_tlist,
-                            (int*)c->st_tlist_n);
+    const uint8_t* first = (const uint8_t*)c->st_dense.p + (size_t)(rb - dense_row0) * (size_t)ld;
+    HIP_TRY(hipMemsetAsync((char*)c->st_counts.p + (size_t)rows * 8, 0, 8, ps));
+    mvs::launch_dense_count(ps, first, ld, n_cols, rows, (long long*)c->st_counts.p, (int2*)c->st_ends.p, active, (int*)c->st_tlist.p,
+                            (int*)c->st_tlist_n.p);
     rc = check_kernel("k_dense_count");
     if (rc) return rc;
     size_t need = 0;
-    rc = mvs::dense_row_ptr(ps, (long long*)c->st_counts, (long long*)c->st_rowptr, rows, nullptr, 0, &need);
+    rc = mvs::dense_row_ptr(ps, (long long*)c->st_counts.p, (long long*)c->st_rowptr.p, rows, nullptr, 0, &need);
     if (rc) return fail(rc, "scan sizing failed");
-    rc = ensure_buf(c, &c->pw_sort, &c->pw_sort_bytes, need);
+    rc = ensure_buf(c, c->pw_sort, need);
     if (rc) return rc;
-    rc = mvs::dense_row_ptr(ps, (long long*)c->st_counts, (long long*)c->st_rowptr, rows, c->pw_sort, c->pw_sort_bytes, nullptr);
+    rc = mvs::dense_row_ptr(ps, (long long*)c->st_counts.p, (long long*)c->st_rowptr.p, rows, c->pw_sort.p, c->pw_sort.bytes, nullptr);
     if (rc) return fail(rc, "scan of the row counts failed");
     unsigned int h_odd = 0;
-    rc = read_back(c, ps, {{out.row_ptr.data(), c->st_rowptr, (size_t)(rows + 1) * 8}, {&h_odd, c->d_counter + 4, 4}});
+    rc = read_back(c, ps, {{out.row_ptr.data(), c->st_rowptr.p, (size_t)(rows + 1) * 8}, {&h_odd, c->counters() + 4, 4}});
     if (rc) return rc;
     *odd = h_odd != 0;
     if (*odd) return MVS_OK;
@@ -488,17 +483,17 @@ int csr_from_dense(mvs_ctx* c, int64_t rb, int64_t re, int64_t n_cols, int64_t d
     // rows that will be encoded on the device: the record sizes come out of the fill pass (k_enc_size would read the CSR
     // arrays this pass is writing once more)
     if (want_sizes && rows > 0) {
-        rc = ensure_buf(c, &c->en_size, &c->en_size_bytes, (size_t)(rows + 1) * 8);
-        if (rc == MVS_OK) rc = ensure_buf(c, &c->en_jac, &c->en_jac_bytes, (size_t)rows * 4);
-        if (rc == MVS_OK) rc = ensure_buf(c, &c->en_first, &c->en_first_bytes, (size_t)rows * 4);
-        if (rc == MVS_OK) rc = ensure_buf(c, &c->en_par, &c->en_par_bytes, (size_t)rows * sizeof(mvs::EncRow));
+        rc = ensure_buf(c, c->en_size, (size_t)(rows + 1) * 8);
+        if (rc == MVS_OK) rc = ensure_buf(c, c->en_jac, (size_t)rows * 4);
+        if (rc == MVS_OK) rc = ensure_buf(c, c->en_first, (size_t)rows * 4);
+        if (rc == MVS_OK) rc = ensure_buf(c, c->en_par, (size_t)rows * sizeof(mvs::EncRow));
         if (rc) return rc;
     }
     const bool sizes = want_sizes && rows > 0 && out.n > 0;
-    mvs::launch_dense_fill(ps, first, ld, n_cols, rows, (const long long*)c->st_rowptr, (int32_t*)c->st_col[out.set],
-                           (uint8_t*)c->st_q[out.set], active, (const int*)c->st_tlist, (const int*)c->st_tlist_n,
-                           (const int2*)c->st_ends, sizes ? (unsigned long long*)c->en_size : nullptr, (unsigned int*)c->en_jac,
-                           (unsigned int*)c->en_first, (mvs::EncRow*)c->en_par);
+    mvs::launch_dense_fill(ps, first, ld, n_cols, rows, (const long long*)c->st_rowptr.p, (int32_t*)c->st_col[out.set].p,
+                           (uint8_t*)c->st_q[out.set].p, active, (const int*)c->st_tlist.p, (const int*)c->st_tlist_n.p,
+                           (const int2*)c->st_ends.p, sizes ? (unsigned long long*)c->en_size.p : nullptr, (unsigned int*)c->en_jac.p,
+                           (unsigned int*)c->en_first.p, (mvs::EncRow*)c->en_par.p);
     rc = check_kernel("k_dense_fill");
     if (rc) return rc;
     out.sizes_ready = sizes;
@@ -525,48 +520,49 @@ int rows_from_dense_spec(mvs_ctx* c, int64_t rb, int64_t re, int64_t n_cols, int
     out.wide = false;
     out.set = (int)(block_index & 1);
     out.row_ptr.assign((size_t)rows + 1, 0);
-    int rc = ensure_buf(c, &c->st_rowptr, &c->st_rowptr_bytes, (size_t)(rows + 1) * 8);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->st_counts, &c->st_counts_bytes, (size_t)(rows + 1) * 8);
+    int rc = ensure_buf(c, c->st_rowptr, (size_t)(rows + 1) * 8);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->st_counts, (size_t)(rows + 1) * 8);
     if (rc) return rc;
     int tr0 = 0, n_trows = 0, n_tc = 0;
     mvs::dense_tile_rows(active, rows, n_cols, &tr0, &n_trows, &n_tc);
-    rc = ensure_buf(c, &c->st_tlist, &c->st_tlist_bytes, std::max<size_t>((size_t)n_trows * (size_t)n_tc * 4, 4));
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->st_tlist_n, &c->st_tlist_n_bytes, std::max<size_t>((size_t)n_trows * 4, 4));
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->st_ends, &c->st_ends_bytes, std::max<size_t>((size_t)rows * sizeof(int2), 8));
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_size, &c->en_size_bytes, (size_t)(rows + 1) * 8);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_off, &c->en_off_bytes, (size_t)(rows + 1) * 8);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_jac, &c->en_jac_bytes, (size_t)rows * 4);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_first, &c->en_first_bytes, (size_t)rows * 4);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->en_par, &c->en_par_bytes, (size_t)rows * sizeof(mvs::EncRow));
+    rc = ensure_buf(c, c->st_tlist, std::max<size_t>((size_t)n_trows * (size_t)n_tc * 4, 4));
+    if (rc == MVS_OK) rc = ensure_buf(c, c->st_tlist_n, std::max<size_t>((size_t)n_trows * 4, 4));
+    if (rc == MVS_OK) rc = ensure_buf(c, c->st_ends, std::max<size_t>((size_t)rows * sizeof(int2), 8));
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_size, (size_t)(rows + 1) * 8);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_off, (size_t)(rows + 1) * 8);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_jac, (size_t)rows * 4);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_first, (size_t)rows * 4);
+    if (rc == MVS_OK) rc = ensure_buf(c, c->en_par, (size_t)rows * sizeof(mvs::EncRow));
     if (rc == MVS_OK) rc = claim_csr_set(c, out.set, block_index, cap_cells, false, ps);
-    if (rc == MVS_OK) rc = ensure_buf(c, &c->st_enc[out.set], &c->st_enc_bytes[out.set], std::max<size_t>(cap_bytes, 8));
+    if (rc == MVS_OK) rc = ensure_buf(c, c->st_enc[out.set], std::max<size_t>(cap_bytes, 8));
     if (rc) return rc;
     size_t need = 0, need2 = 0;
-    rc = mvs::dense_row_ptr(ps, (long long*)c->st_counts, (long long*)c->st_rowptr, rows, nullptr, 0, &need);
-    if (rc == MVS_OK) rc = mvs::encode_offsets(ps, (unsigned long long*)c->en_size, (unsigned long long*)c->en_off, rows, nullptr, 0, &need2);
+    rc = mvs::dense_row_ptr(ps, (long long*)c->st_counts.p, (long long*)c->st_rowptr.p, rows, nullptr, 0, &need);
+    if (rc == MVS_OK) rc = mvs::encode_offsets(ps, (unsigned long long*)c->en_size.p, (unsigned long long*)c->en_off.p, rows, nullptr, 0, &need2);
     if (rc) return fail(rc, "scan sizing failed");
-    rc = ensure_buf(c, &c->pw_sort, &c->pw_sort_bytes, std::max(need, need2));
+    rc = ensure_buf(c, c->pw_sort, std::max(need, need2));
     if (rc) return rc;
-    const uint8_t* first = (const uint8_t*)c->st_dense + (size_t)(rb - dense_row0) * (size_t)ld;
-    HIP_TRY(hipMemsetAsync((char*)c->st_counts + (size_t)rows * 8, 0, 8, ps));
-    mvs::launch_dense_count(ps, first, ld, n_cols, rows, (long long*)c->st_counts, (int2*)c->st_ends, active, (int*)c->st_tlist,
-                            (int*)c->st_tlist_n);
+    const uint8_t* first = (const uint8_t*)c->st_dense.p + (size_t)(rb - dense_row0) * (size_t)ld;
+    HIP_TRY(hipMemsetAsync((char*)c->st_counts.p + (size_t)rows * 8, 0, 8, ps));
+    mvs::launch_dense_count(ps, first, ld, n_cols, rows, (long long*)c->st_counts.p, (int2*)c->st_ends.p, active, (int*)c->st_tlist.p,
+                            (int*)c->st_tlist_n.p);
     rc = check_kernel("k_dense_count");
     if (rc) return rc;
-    rc = mvs::dense_row_ptr(ps, (long long*)c->st_counts, (long long*)c->st_rowptr, rows, c->pw_sort, c->pw_sort_bytes, nullptr);
+    rc = mvs::dense_row_ptr(ps, (long long*)c->st_counts.p, (long long*)c->st_rowptr.p, rows, c->pw_sort.p, c->pw_sort.bytes, nullptr);
     if (rc) return fail(rc, "scan of the row counts failed");
-    HIP_TRY(hipMemsetAsync((char*)c->en_size + (size_t)rows * 8, 0, 8, ps));
-    mvs::launch_dense_fill(ps, first, ld, n_cols, rows, (const long long*)c->st_rowptr, (int32_t*)c->st_col[out.set],
-                           (uint8_t*)c->st_q[out.set], active, (const int*)c->st_tlist, (const int*)c->st_tlist_n,
-                           (const int2*)c->st_ends, (unsigned long long*)c->en_size, (unsigned int*)c->en_jac, (unsigned int*)c->en_first,
-                           (mvs::EncRow*)c->en_par, (long long)cap_cells);
+    HIP_TRY(hipMemsetAsync((char*)c->en_size.p + (size_t)rows * 8, 0, 8, ps));
+    mvs::launch_dense_fill(ps, first, ld, n_cols, rows, (const long long*)c->st_rowptr.p, (int32_t*)c->st_col[out.set].p,
+                           (uint8_t*)c->st_q[out.set].p, active, (const int*)c->st_tlist.p, (const int*)c->st_tlist_n.p,
+                           (const int2*)c->st_ends.p, (unsigned long long*)c->en_size.p, (unsigned int*)c->en_jac.p, (unsigned int*)c->en_first.p,
+                           (mvs::EncRow*)c->en_par.p, (long long)cap_cells);
     rc = check_kernel("k_dense_fill");
     if (rc) return rc;
-    rc = mvs::encode_offsets(ps, (unsigned long long*)c->en_size, (unsigned long long*)c->en_off, rows, c->pw_sort, c->pw_sort_bytes, nullptr);
+    rc = mvs::encode_offsets(ps, (unsigned long long*)c->en_size.p, (unsigned long long*)c->en_off.p, rows, c->pw_sort.p, c->pw_sort.bytes,
+                             nullptr);
     if (rc) return fail(rc, "scan of the record sizes failed");
-    HIP_TRY(hipMemsetAsync(c->st_enc[out.set], 0, cap_bytes, ps));        // the unary parts are OR-ed into zeroed words
-    mvs::launch_encode_fill(ps, (const long long*)c->st_rowptr, (const int32_t*)c->st_col[out.set], c->st_q[out.set], 1, rows,
-                            (const unsigned long long*)c->en_off, (const mvs::EncRow*)c->en_par, (unsigned char*)c->st_enc[out.set],
+    HIP_TRY(hipMemsetAsync(c->st_enc[out.set].p, 0, cap_bytes, ps));        // the unary parts are OR-ed into zeroed words
+    mvs::launch_encode_fill(ps, (const long long*)c->st_rowptr.p, (const int32_t*)c->st_col[out.set].p, c->st_q[out.set].p, 1, rows,
+                            (const unsigned long long*)c->en_off.p, (const mvs::EncRow*)c->en_par.p, (unsigned char*)c->st_enc[out.set].p,
                             stage_words, (unsigned long long)cap_cells, (unsigned long long)cap_bytes);
     rc = check_kernel("k_enc_fill");
     if (rc) return rc;
@@ -574,11 +570,11 @@ int rows_from_dense_spec(mvs_ctx* c, int64_t rb, int64_t re, int64_t n_cols, int
     out.enc_jac.assign((size_t)rows, 0);
     out.enc_first.assign((size_t)rows, 0);
     unsigned int h_odd = 0;
-    rc = read_back(c, ps, {{out.row_ptr.data(), c->st_rowptr, (size_t)(rows + 1) * 8},
-                           {out.enc_off.data(), c->en_off, (size_t)(rows + 1) * 8},
-                           {out.enc_jac.data(), c->en_jac, (size_t)rows * 4},
-                           {out.enc_first.data(), c->en_first, (size_t)rows * 4},
-                           {&h_odd, c->d_counter + 4, 4}});
+    rc = read_back(c, ps, {{out.row_ptr.data(), c->st_rowptr.p, (size_t)(rows + 1) * 8},
+                           {out.enc_off.data(), c->en_off.p, (size_t)(rows + 1) * 8},
+                           {out.enc_jac.data(), c->en_jac.p, (size_t)rows * 4},
+                           {out.enc_first.data(), c->en_first.p, (size_t)rows * 4},
+                           {&h_odd, c->counters() + 4, 4}});
     if (rc) return rc;
     *odd = h_odd != 0;
     out.n = out.row_ptr[(size_t)rows];
@@ -643,16 +639,16 @@ int feed_block(mvs_ctx* c, StreamOut& out, const BlockCsr& b, size_t piece_bytes
         for (int64_t r = r0; r <= r1; ++r) it.row_ptr[(size_t)(r - r0)] = row_ptr[(size_t)r] - c0;
         it.dma = dma;
         it.last_of_block = dma && r1 == rows;
-        char* dst = static_cast<char*>(c->dl_pinned[sl]);
+        char* dst = static_cast<char*>(c->dl_pinned[sl].p);
         if (dma) {
-            const HsaCopy* h = static_cast<const HsaCopy*>(c->dl_hsa);
+            const HsaCopy* h = static_cast<const HsaCopy*>(c->dl_hsa.get());
             hsa_signal_store_relaxed(h->sig[sl], cells > 0 ? 2 : 0);       // two copies (columns, q) count it down
             hsa_status_t hs = HSA_STATUS_SUCCESS;
             if (cells > 0) {
-                hs = hsa_amd_memory_async_copy(dst, h->cpu, (const char*)c->st_col[b.set] + (size_t)c0 * 4, h->gpu, (size_t)cells * 4, 0, nullptr,
-                                               h->sig[sl]);
+                hs = hsa_amd_memory_async_copy(dst, h->cpu, (const char*)c->st_col[b.set].p + (size_t)c0 * 4, h->gpu, (size_t)cells * 4, 0,
+                                               nullptr, h->sig[sl]);
                 if (hs == HSA_STATUS_SUCCESS)
-                    hs = hsa_amd_memory_async_copy(dst + (size_t)cells * 4, h->cpu, (const char*)c->st_q[b.set] + (size_t)c0 * (wide ? 2 : 1),
+                    hs = hsa_amd_memory_async_copy(dst + (size_t)cells * 4, h->cpu, (const char*)c->st_q[b.set].p + (size_t)c0 * (wide ? 2 : 1),
                                                    h->gpu, (size_t)cells * (wide ? 2 : 1), 0, nullptr, h->sig[sl]);
             }
             if (hs != HSA_STATUS_SUCCESS) {
@@ -668,10 +664,10 @@ int feed_block(mvs_ctx* c, StreamOut& out, const BlockCsr& b, size_t piece_bytes
         }
         hipError_t e = hipStreamWaitEvent(c->dl_stream, c->dl_ready[b.set], 0);
         if (e == hipSuccess && cells > 0) {
-            e = hipMemcpyAsync(dst, (const char*)c->st_col[b.set] + (size_t)c0 * 4, (size_t)cells * 4, hipMemcpyDeviceToHost,
+            e = hipMemcpyAsync(dst, (const char*)c->st_col[b.set].p + (size_t)c0 * 4, (size_t)cells * 4, hipMemcpyDeviceToHost,
                                c->dl_stream);
             if (e == hipSuccess)
-                e = hipMemcpyAsync(dst + (size_t)cells * 4, (const char*)c->st_q[b.set] + (size_t)c0 * (wide ? 2 : 1),
+                e = hipMemcpyAsync(dst + (size_t)cells * 4, (const char*)c->st_q[b.set].p + (size_t)c0 * (wide ? 2 : 1),
                                    (size_t)cells * (wide ? 2 : 1), hipMemcpyDeviceToHost, c->dl_stream);
         }
         if (e == hipSuccess) e = hipEventRecord(c->dl_done[sl], c->dl_stream);
@@ -741,11 +737,11 @@ int feed_encoded(mvs_ctx* c, StreamOut& out, const BlockCsr& b, size_t piece_byt
         it.dma = dma;
         it.last_of_block = dma && r1 == rows;
         if (dma) {
-            const HsaCopy* h = static_cast<const HsaCopy*>(c->dl_hsa);
+            const HsaCopy* h = static_cast<const HsaCopy*>(c->dl_hsa.get());
             hsa_signal_store_relaxed(h->sig[sl], bytes > 0 ? 1 : 0);
-            const hsa_status_t hs = bytes > 0 ? hsa_amd_memory_async_copy(c->dl_pinned[sl], h->cpu, (const char*)c->st_enc[b.set] + o0, h->gpu,
-                                                                          (size_t)bytes, 0, nullptr, h->sig[sl])
-                                              : HSA_STATUS_SUCCESS;
+            const hsa_status_t hs = bytes > 0 ? hsa_amd_memory_async_copy(c->dl_pinned[sl].p, h->cpu, (const char*)c->st_enc[b.set].p + o0,
+                                                                          h->gpu, (size_t)bytes, 0, nullptr,
+                                                                          h->sig[sl]) : HSA_STATUS_SUCCESS;
             if (hs != HSA_STATUS_SUCCESS) {
                 hsa_signal_store_relaxed(h->sig[sl], 0);
                 out.release_slot(sl);
@@ -759,7 +755,7 @@ int feed_encoded(mvs_ctx* c, StreamOut& out, const BlockCsr& b, size_t piece_byt
         }
         hipError_t e = hipStreamWaitEvent(c->dl_stream, c->dl_ready[b.set], 0);
         if (e == hipSuccess && bytes > 0)
-            e = hipMemcpyAsync(c->dl_pinned[sl], (const char*)c->st_enc[b.set] + o0, (size_t)bytes, hipMemcpyDeviceToHost, c->dl_stream);
+            e = hipMemcpyAsync(c->dl_pinned[sl].p, (const char*)c->st_enc[b.set].p + o0, (size_t)bytes, hipMemcpyDeviceToHost, c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(c->dl_done[sl], c->dl_stream);
         if (e != hipSuccess) {
             out.release_slot(sl);
@@ -969,19 +965,19 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
     TwoStage ts;                                                     // M2: the whole pass; M1: the current block's pass
     mvs::DenseActive active{};                                       // flags == NULL: every tile (plan B)
     auto matrix_setup = [&]() -> int {                               // matrix, touch map, list of newly touched tiles
-        const void* before = c->st_dense;
-        int r = ensure_buf(c, &c->st_dense, &c->st_dense_bytes, (size_t)rows_all * (size_t)ld);
+        const void* before = c->st_dense.p;
+        int r = ensure_buf(c, c->st_dense, (size_t)rows_all * (size_t)ld);
         if (r) return r;
-        if (c->st_dense != before) c->st_dense_zero = 0;
+        if (c->st_dense.p != before) c->st_dense_zero = 0;
         const size_t n_tiles = (size_t)n_tr_all * (size_t)n_tc_all;
-        r = ensure_buf(c, &c->pw_ttouch, &c->pw_ttouch_bytes, n_tiles * 4);
+        r = ensure_buf(c, c->pw_ttouch, n_tiles * 4);
         if (r) return r;
-        r = ensure_buf(c, &c->pw_tnew, &c->pw_tnew_bytes, (n_tiles + 1) * 4);
+        r = ensure_buf(c, c->pw_tnew, (n_tiles + 1) * 4);
         if (r) return r;
-        HIP_TRY(hipMemsetAsync(c->pw_ttouch, 0, n_tiles * 4, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_counter + 4, 0, 8, c->stream));      // the "q beyond a byte" flag
+        HIP_TRY(hipMemsetAsync(c->pw_ttouch.p, 0, n_tiles * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(c->counters() + 4, 0, 8, c->stream));      // the "q beyond a byte" flag
         c->st_dense_zero = 0;
-        active.touch = (const unsigned int*)c->pw_ttouch;
+        active.touch = (const unsigned int*)c->pw_ttouch.p;
         active.n_tr = n_tr_all;
         active.n_tc = n_tc_all;
         active.o = tile_o;
@@ -991,28 +987,28 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
     // re-check of t's candidates with the kept cells going into the matrix: a packed list first (the re-check decides
     // which candidates are kept), then mark / clear / scatter (mvs_internal.h: launch_packed_to_dense)
     auto recheck_into_matrix = [&](TwoStage& t) -> int {
-        int r = ensure_buf(c, &c->st_raw, &c->st_raw_bytes, (size_t)(2 * t.n_cand + 64) * 8);
+        int r = ensure_buf(c, c->st_raw, (size_t)(2 * t.n_cand + 64) * 8);
         if (r) return r;
         t.a.dense = nullptr;
-        t.a.packed = (unsigned long long*)c->st_raw;
-        t.a.capacity = c->st_raw_bytes / 8;
+        t.a.packed = (unsigned long long*)c->st_raw.p;
+        t.a.capacity = c->st_raw.bytes / 8;
         t.a.pack_row0 = row_begin;
         t.a.pack_shift = shift;
         r = two_stage_recheck(c, t);
         if (r) return r;
-        HIP_TRY(hipMemsetAsync(c->d_counter + 10, 0, 8, c->stream));     // count of newly touched tiles
-        mvs::launch_packed_to_dense(c->stream, (const unsigned long long*)c->st_raw, c->d_counter, shift,
-                                    (1ULL << col_bits) - 1ULL, (uint8_t*)c->st_dense, ld, rows_all, (unsigned int*)c->pw_ttouch, n_tc_all,
-                                    (int*)c->pw_tnew, reinterpret_cast<unsigned int*>(c->d_counter + 10),
-                                    reinterpret_cast<unsigned int*>(c->d_counter + 4));
+        HIP_TRY(hipMemsetAsync(c->counters() + 10, 0, 8, c->stream));     // count of newly touched tiles
+        mvs::launch_packed_to_dense(c->stream, (const unsigned long long*)c->st_raw.p, c->counters(), shift,
+                                    (1ULL << col_bits) - 1ULL, (uint8_t*)c->st_dense.p, ld, rows_all, (unsigned int*)c->pw_ttouch.p, n_tc_all,
+                                    (int*)c->pw_tnew.p, reinterpret_cast<unsigned int*>(c->counters() + 10),
+                                    reinterpret_cast<unsigned int*>(c->counters() + 4));
         r = check_kernel("k_packed_touch / k_clear_tiles / k_packed_scatter");
         if (r) return r;
         // from here on t.a describes the exact kernel's launches on the flagged tiles: bytes of whole tiles into the matrix
         t.a.packed = nullptr;
-        t.a.dense = (uint8_t*)c->st_dense;
+        t.a.dense = (uint8_t*)c->st_dense.p;
         t.a.dense_row0 = row_begin;
         t.a.dense_ld = ld;
-        t.a.dense_flag = reinterpret_cast<unsigned int*>(c->d_counter + 4);
+        t.a.dense_flag = reinterpret_cast<unsigned int*>(c->counters() + 4);
         return MVS_OK;
     };
     // M1, one block: filter its rows (symmetric square = the whole row range), re-check into the matrix, its flagged tiles
@@ -1022,14 +1018,14 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
         fa.sym_begin = row_begin;
         fa.sym_end = row_end;
         t = TwoStage();
-        t.ext_flags = (unsigned int*)c->pw_tflag + (size_t)((rb - row_begin) / 256) * (size_t)n_tc_all;
+        t.ext_flags = (unsigned int*)c->pw_tflag.p + (size_t)((rb - row_begin) / 256) * (size_t)n_tc_all;
         return two_stage_filter(c, s, d_n2, 0.05, 0, true, 0, fa, t, &lopt);
     };
     if (applies) {
         bool whole_pass = true;
         if (can_matrix && rows_all > 512 && lopt.stream_pipeline != 0) {
             // M1's first block doubles as the probe: one tile row of the filter
-            rc = ensure_buf(c, &c->pw_tflag, &c->pw_tflag_bytes, (size_t)n_tr_all * (size_t)n_tc_all * 4);
+            rc = ensure_buf(c, c->pw_tflag, (size_t)n_tr_all * (size_t)n_tc_all * 4);
             if (rc) return finish(rc);
             if (lopt.filter_variant < 0) lopt.filter_variant = 8;    // what the whole range gets (filter_flags_tiles said so)
             rc = pipeline_filter(row_begin, row_begin + 256, ts);
@@ -1064,20 +1060,20 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
                 // cheaper than counting and filling a matrix of rows x n bytes
                 const bool as_list = list_fits && (bound <= (unsigned long long)lopt.stream_list_cells || !can_matrix || ts.n_flagged == 0);
                 if (as_list) {
-                    rc = ensure_buf(c, &c->st_raw, &c->st_raw_bytes, (size_t)(bound + 64) * 8);
+                    rc = ensure_buf(c, c->st_raw, (size_t)(bound + 64) * 8);
                     if (rc) return finish(rc);
-                    ts.a.packed = (unsigned long long*)c->st_raw;
-                    ts.a.capacity = c->st_raw_bytes / 8;
+                    ts.a.packed = (unsigned long long*)c->st_raw.p;
+                    ts.a.capacity = c->st_raw.bytes / 8;
                     ts.a.pack_row0 = row_begin;
                     ts.a.pack_shift = shift;
                     rc = two_stage_recheck(c, ts);
                     if (rc == MVS_OK) rc = two_stage_tiles(c, ts, 0, ts.n_flagged, true);
                     if (rc) return finish(rc);
                     unsigned long long got = 0;
-                    hipError_t e = hipMemcpyAsync(&got, c->d_counter, 8, hipMemcpyDeviceToHost, c->stream);
+                    hipError_t e = hipMemcpyAsync(&got, c->counters(), 8, hipMemcpyDeviceToHost, c->stream);
                     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
                     if (e != hipSuccess) return finish(fail(MVS_E_HIP, "reading the cell count: %s", hipGetErrorString(e)));
-                    if ((size_t)got * 8 > c->st_raw_bytes) return finish(fail(MVS_E_HIP, "internal: kept cells beyond the sized output"));
+                    if ((size_t)got * 8 > c->st_raw.bytes) return finish(fail(MVS_E_HIP, "internal: kept cells beyond the sized output"));
                     total = (int64_t)got;
                     add_kernel_ms();
                     c->st_blocks = 1;
@@ -1136,11 +1132,11 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
     if (matrix_mode != kNone) {
         rc = matrix_setup();
         if (rc) return finish(rc);
-        active.flags = matrix_mode == kM1 ? (const unsigned int*)c->pw_tflag : (const unsigned int*)ts.a.tile_flag;
+        active.flags = matrix_mode == kM1 ? (const unsigned int*)c->pw_tflag.p : (const unsigned int*)ts.a.tile_flag;
         if (matrix_mode == kM1) {
             // flags of blocks not yet filtered read as "not flagged"; block 0 has been filtered already (the probe)
             const size_t done = (size_t)n_tc_all;
-            HIP_TRY(hipMemsetAsync((unsigned int*)c->pw_tflag + done, 0, ((size_t)n_tr_all * (size_t)n_tc_all - done) * 4, c->stream));
+            HIP_TRY(hipMemsetAsync((unsigned int*)c->pw_tflag.p + done, 0, ((size_t)n_tr_all * (size_t)n_tc_all - done) * 4, c->stream));
         }
         rc = recheck_into_matrix(ts);                                // M2: all candidates; M1: block 0's
         if (rc) return finish(rc);
@@ -1148,12 +1144,12 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
         c->st_two_stage = matrix_mode == kM1 ? 3 : 2;
     } else if (dense) {
         const size_t bytes = (size_t)(whole ? rows_all : std::min(block_rows + 256, rows_all)) * (size_t)ld;
-        const void* before = c->st_dense;
-        rc = ensure_buf(c, &c->st_dense, &c->st_dense_bytes, bytes);
+        const void* before = c->st_dense.p;
+        rc = ensure_buf(c, c->st_dense, bytes);
         if (rc) return finish(rc);
         (void)before;
         c->st_dense_zero = 0;
-        hipError_t e = hipMemsetAsync(c->d_counter + 4, 0, 8, c->stream);      // the "q beyond a byte" flag
+        hipError_t e = hipMemsetAsync(c->counters() + 4, 0, 8, c->stream);      // the "q beyond a byte" flag
         if (e != hipSuccess) return finish(fail(MVS_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e)));
     }
     // M1: which blocks open a filter segment.  Segment 0 is the probe (one tile row); the others end where 4 %, 16 % and 45 %
@@ -1183,14 +1179,14 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
         exact_opt.pairwise_filter = 0;
         int r;
         if (as_dense) {
-            DenseOut dno{(uint8_t*)c->st_dense, whole ? row_begin : rb, ld, whole ? row_begin : rb, whole ? row_end : re,
-                         reinterpret_cast<unsigned int*>(c->d_counter + 4)};
+            DenseOut dno{(uint8_t*)c->st_dense.p, whole ? row_begin : rb, ld, whole ? row_begin : rb, whole ? row_end : re,
+                         reinterpret_cast<unsigned int*>(c->counters() + 4)};
             r = pairwise_launch(c, s, d_n2, keep_mode, rb, re, 0, s->n, true, false, nullptr, 0, 0, &got, 0.05, nullptr, &dno, &exact_opt);
         } else {
             const int64_t worst = (re - rb) * s->n;
-            r = ensure_buf(c, &c->st_raw, &c->st_raw_bytes, (size_t)worst * 8);
+            r = ensure_buf(c, c->st_raw, (size_t)worst * 8);
             if (r == MVS_OK) {
-                PackedOut po{&c->st_raw, &c->st_raw_bytes, rb, shift, false};
+                PackedOut po{&c->st_raw, rb, shift, false};
                 r = pairwise_launch(c, s, d_n2, keep_mode, rb, re, 0, s->n, true, false, nullptr, 0, 0, &got, 0.05, &po, nullptr, &exact_opt);
             }
         }
@@ -1229,7 +1225,7 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
                 // images; the tiles below the diagonal stay what earlier blocks made of them
                 const int t0 = (int)((rb - row_begin) / 256), t1 = (int)((re - row_begin + 255) / 256);
                 for (int t = t0; t < t1; ++t) {
-                    unsigned int* rowf = (unsigned int*)c->pw_tflag + (size_t)t * (size_t)n_tc_all;
+                    unsigned int* rowf = (unsigned int*)c->pw_tflag.p + (size_t)t * (size_t)n_tc_all;
                     hipError_t e = hipSuccess;
                     if (tile_o > 0) e = hipMemsetD32Async((hipDeviceptr_t)rowf, 1, (size_t)tile_o, c->stream);
                     if (e == hipSuccess && t + tile_o < n_tc_all)
@@ -1248,7 +1244,7 @@ int pairwise_stream_impl(mvs_ctx* c, const mvs_sketch_set* s, const double* norm
     };
     auto packed_count = [&](size_t k, int64_t* n) -> int {
         unsigned long long got = 0;
-        hipError_t e = hipMemcpyAsync(&got, c->d_counter, 8, hipMemcpyDeviceToHost, c->stream);
+        hipError_t e = hipMemcpyAsync(&got, c->counters(), 8, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(MVS_E_HIP, "reading the cell count: %s", hipGetErrorString(e));
         if ((int64_t)got > (blocks[k].second - blocks[k].first) * s->n) return fail(MVS_E_HIP, "internal: more kept cells than cells");
@@ -1422,30 +1418,30 @@ int cells_stream_impl(mvs_ctx* c, const mvs_cell* cells, int64_t n, int64_t rb, 
     // the arrays of set 0 may still be on their way out of an earlier call's last block: that call drained its download stream
     // before it returned (finish / below), so nothing is in flight here
     if (n > 0) {
-        rc = ensure_buf(c, &c->st_rowptr, &c->st_rowptr_bytes, (size_t)(rows + 1) * 8);
-        if (rc == MVS_OK) rc = ensure_buf(c, &c->st_counts, &c->st_counts_bytes, (size_t)(rows + 2) * 8);   // index into the list + the "wide q" flag
+        rc = ensure_buf(c, c->st_rowptr, (size_t)(rows + 1) * 8);
+        if (rc == MVS_OK) rc = ensure_buf(c, c->st_counts, (size_t)(rows + 2) * 8);   // index into the list + the "wide q" flag
         if (rc == MVS_OK) rc = claim_csr_set(c, 0, 0, n, false, c->stream);
         if (rc) return rc;
-        unsigned int* d_wide = reinterpret_cast<unsigned int*>((long long*)c->st_counts + rows + 1);
+        unsigned int* d_wide = reinterpret_cast<unsigned int*>((long long*)c->st_counts.p + rows + 1);
         HIP_TRY(hipMemsetAsync(d_wide, 0, 8, c->stream));
-        mvs::launch_cells_rowptr(c->stream, cells, n, rb, rows, (long long*)c->st_counts);
+        mvs::launch_cells_rowptr(c->stream, cells, n, rb, rows, (long long*)c->st_counts.p);
         rc = check_kernel("k_cells_rowptr");
         if (rc) return rc;
-        mvs::launch_cells_split(c->stream, cells, (const long long*)c->st_counts, rows, n, (long long*)c->st_rowptr, (int32_t*)c->st_col[0],
-                                c->st_q[0], 1, d_wide);
+        mvs::launch_cells_split(c->stream, cells, (const long long*)c->st_counts.p, rows, n, (long long*)c->st_rowptr.p, (int32_t*)c->st_col[0].p,
+                                c->st_q[0].p, 1, d_wide);
         rc = check_kernel("k_cells_split");
         if (rc) return rc;
         unsigned int h_wide = 0;
-        rc = read_back(c, c->stream, {{blk.row_ptr.data(), c->st_rowptr, (size_t)(rows + 1) * 8}, {&h_wide, d_wide, 4}});
+        rc = read_back(c, c->stream, {{blk.row_ptr.data(), c->st_rowptr.p, (size_t)(rows + 1) * 8}, {&h_wide, d_wide, 4}});
         if (rc) return rc;
         blk.n = blk.row_ptr[(size_t)rows];
         if (blk.n < 0 || blk.n > n) return fail(MVS_E_INVALID, "the cell list is not ordered by row");
         if (h_wide) {                      // some q needs 16 bits (norms that do not belong to the vectors): the q array again
             blk.wide = true;
-            rc = ensure_buf(c, &c->st_q[0], &c->st_q_bytes[0], (size_t)n * 2);
+            rc = ensure_buf(c, c->st_q[0], (size_t)n * 2);
             if (rc) return rc;
-            mvs::launch_cells_split(c->stream, cells, (const long long*)c->st_counts, rows, n, nullptr, (int32_t*)c->st_col[0], c->st_q[0], 2,
-                                    nullptr);
+            mvs::launch_cells_split(c->stream, cells, (const long long*)c->st_counts.p, rows, n, nullptr, (int32_t*)c->st_col[0].p,
+                                    c->st_q[0].p, 2, nullptr);
             rc = check_kernel("k_cells_split(16-bit q)");
             if (rc) return rc;
         }

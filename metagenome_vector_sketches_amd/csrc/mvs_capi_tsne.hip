@@ -20,24 +20,20 @@ struct mvs_tsne_graph {
     mvs_ctx* ctx = nullptr;
     int64_t n = 0;
     // the fed directed entries (row << 32 | col, value): `count` of them, `dead` of those with the key ~0 (self loops)
-    u64* keys = nullptr;
-    u64* vals = nullptr;
+    DevBuf keys, vals;                       // u64
     int64_t cap = 0, count = 0, dead = 0;
-    u64* counters = nullptr;
+    DevBuf counters;                         // u64
     // the symmetric graph (finish_graph)
     bool built = false;
     int64_t m = 0;
-    long long* row_ptr = nullptr;
-    int32_t* src = nullptr;
-    int32_t* col = nullptr;
-    double* p = nullptr;
+    DevBuf row_ptr;                          // long long
+    DevBuf src, col;                         // int32_t
+    DevBuf p;                                // double
     u64 S = 0;
     // the optimiser's state and its accumulators
-    double* y = nullptr;
-    double* vel = nullptr;
-    double* gain = nullptr;
-    long long* sums = nullptr;               // 5 n + 1 words (mvs::TsneSums)
-    double* beta = nullptr;                  // n
+    DevBuf y, vel, gain;                     // double
+    DevBuf sums;                             // long long, 5 n + 1 words (mvs::TsneSums)
+    DevBuf beta;                             // double, n
 };
 
 namespace {
@@ -45,17 +41,8 @@ namespace {
 constexpr int64_t kMaxN = 1LL << 21;
 constexpr int64_t kTopkCells = 1LL << 24;    // cells of a top-k range kept on the device at a time (256 MiB)
 
-template <typename T>
-void free_dev(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 void drop_graph(mvs_tsne_graph* t) {
-    free_dev(t->row_ptr);
-    free_dev(t->src);
-    free_dev(t->col);
-    free_dev(t->p);
+    for (DevBuf* b : {&t->row_ptr, &t->src, &t->col, &t->p}) b->reset();
     t->built = false;
     t->m = 0;
     t->S = 0;
@@ -63,31 +50,27 @@ void drop_graph(mvs_tsne_graph* t) {
 
 mvs::TsneSums sums_of(const mvs_tsne_graph* t) {
     mvs::TsneSums s;
-    s.z_rows = t->sums;
-    s.rep = t->sums + t->n;
-    s.att = t->sums + 3 * t->n;
-    s.z = t->sums + 5 * t->n;
+    s.z_rows = t->sums.as<long long>();
+    s.rep = t->sums.as<long long>() + t->n;
+    s.att = t->sums.as<long long>() + 3 * t->n;
+    s.z = t->sums.as<long long>() + 5 * t->n;
     return s;
 }
 
 int ensure_room(mvs_tsne_graph* t, int64_t extra) {
     if (t->count + extra <= t->cap) return MVS_OK;
     const int64_t cap = std::max<int64_t>({2 * t->cap, t->count + extra, 1024});
-    u64 *nk = nullptr, *nv = nullptr;
-    if (hipMalloc((void**)&nk, (size_t)cap * 8) != hipSuccess || hipMalloc((void**)&nv, (size_t)cap * 8) != hipSuccess) {
-        free_dev(nk);
+    DevBuf nk, nv;
+    if (nk.alloc((size_t)cap * 8) != hipSuccess || nv.alloc((size_t)cap * 8) != hipSuccess)
         return fail(MVS_E_NOMEM, "hipMalloc of %lld graph entries failed", (long long)cap);
-    }
     mvs_ctx* c = t->ctx;
     if (t->count > 0) {
-        HIP_TRY(hipMemcpyAsync(nk, t->keys, (size_t)t->count * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(nv, t->vals, (size_t)t->count * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(nk.p, t->keys.p, (size_t)t->count * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(nv.p, t->vals.p, (size_t)t->count * 8, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    free_dev(t->keys);
-    free_dev(t->vals);
-    t->keys = nk;
-    t->vals = nv;
+    t->keys = std::move(nk);
+    t->vals = std::move(nv);
     t->cap = cap;
     return MVS_OK;
 }
@@ -99,12 +82,12 @@ bool perplexity_ok(double perplexity) { return perplexity >= 1.0 && perplexity <
 int consume_neighbours(mvs_tsne_graph* t, const mvs_cell* d_cells, int64_t n_cells, int64_t row0, int64_t rows, const double* d_n2, int d,
                        double perplexity, int32_t* d_c, int64_t* beta_zero) {
     mvs_ctx* c = t->ctx;
-    HIP_TRY(hipMemsetAsync(t->counters, 0, mvs::kTsneCounters * 8, c->stream));
-    int rc = mvs::launch_tsne_check_cells(c->stream, d_cells, n_cells, t->n, t->counters);
+    HIP_TRY(hipMemsetAsync(t->counters.as<u64>(), 0, mvs::kTsneCounters * 8, c->stream));
+    int rc = mvs::launch_tsne_check_cells(c->stream, d_cells, n_cells, t->n, t->counters.as<u64>());
     if (!rc) rc = check_kernel("k_tsne_check_cells");
     if (rc) return rc;
     u64 back[3] = {0, 0, 0};
-    rc = read_back(c, c->stream, {{back, t->counters, sizeof(back)}});
+    rc = read_back(c, c->stream, {{back, t->counters.as<u64>(), sizeof(back)}});
     if (rc) return rc;
     if (back[0] != 0)
         return fail(MVS_E_RANGE, "%llu cells name a sample outside [0, %lld) or have row == col: nothing was added", back[0], (long long)t->n);
@@ -115,14 +98,14 @@ int consume_neighbours(mvs_tsne_graph* t, const mvs_cell* d_cells, int64_t n_cel
     StageTimer timer;
     rc = timer.begin(c);
     if (rc) return rc;
-    rc = mvs::launch_tsne_calibrate(c->stream, d_cells, n_cells, row0, rows, d_n2, d, perplexity, t->beta, d_c, t->keys + t->count,
-                                    t->vals + t->count, t->counters);
+    rc = mvs::launch_tsne_calibrate(c->stream, d_cells, n_cells, row0, rows, d_n2, d, perplexity, t->beta.as<double>(), d_c,
+                                    t->keys.as<u64>() + t->count, t->vals.as<u64>() + t->count, t->counters.as<u64>());
     if (rc) return fail(rc, "t-SNE: calibration launch rejected");
     rc = check_kernel("k_tsne_calibrate");
     if (!rc) rc = timer.mark_end();
     if (rc) return rc;
     u64 zero = 0;
-    rc = read_back(c, c->stream, {{&zero, t->counters + 3, 8}});
+    rc = read_back(c, c->stream, {{&zero, t->counters.as<u64>() + 3, 8}});
     if (!rc) rc = timer.add_to(&c->ts.calibrate_ms);
     if (rc) return rc;
     if (beta_zero) *beta_zero += (int64_t)zero;
@@ -137,18 +120,18 @@ int consume_neighbours(mvs_tsne_graph* t, const mvs_cell* d_cells, int64_t n_cel
 int evaluate(mvs_tsne_graph* t, bool timed) {
     mvs_ctx* c = t->ctx;
     const mvs::TsneSums s = sums_of(t);
-    HIP_TRY(hipMemsetAsync(t->sums, 0, (size_t)(5 * t->n + 1) * 8, c->stream));
+    HIP_TRY(hipMemsetAsync(t->sums.as<long long>(), 0, (size_t)(5 * t->n + 1) * 8, c->stream));
     StageTimer tr, ta;
     int rc = timed ? tr.begin(c) : MVS_OK;
     if (rc) return rc;
     int64_t units = 0;
-    rc = mvs::launch_tsne_repulse(c->stream, t->y, t->n, c->tsne_slice_cols, s, &units);
+    rc = mvs::launch_tsne_repulse(c->stream, t->y.as<double>(), t->n, c->tsne_slice_cols, s, &units);
     if (rc) return fail(rc, "t-SNE: %lld samples at slices of %d columns are more units than a launch holds", (long long)t->n, c->tsne_slice_cols);
     rc = check_kernel("k_tsne_repulse");
     if (!rc && timed) rc = tr.mark_end();
     if (!rc && timed) rc = ta.begin(c);
     if (rc) return rc;
-    rc = mvs::launch_tsne_attract(c->stream, t->y, t->n, t->row_ptr, t->col, t->p, s);
+    rc = mvs::launch_tsne_attract(c->stream, t->y.as<double>(), t->n, t->row_ptr.as<long long>(), t->col.as<int32_t>(), t->p.as<double>(), s);
     if (!rc) rc = check_kernel("k_tsne_attract");
     if (!rc && timed) rc = ta.mark_end();
     if (!rc && timed) rc = tr.add_to(&c->ts.repulse_ms);
@@ -180,24 +163,24 @@ int mvs_tsne_create(mvs_ctx* c, int64_t n, mvs_tsne_graph** out) {
     if (n < 1) return fail(MVS_E_INVALID, "n = %lld is below 1", (long long)n);
     if (n > kMaxN) return fail(MVS_E_INVALID, "n = %lld exceeds 2^21: the sum Z of the rows' Z_i >> 20 would leave int64", (long long)n);
     HIP_TRY(hipSetDevice(c->device));
-    mvs_tsne_graph* t = new (std::nothrow) mvs_tsne_graph();
+    std::unique_ptr<mvs_tsne_graph> t(new (std::nothrow) mvs_tsne_graph());
     if (!t) return fail(MVS_E_NOMEM, "out of host memory");
     t->ctx = c;
     t->n = n;
     const size_t nn = (size_t)n;
-    bool ok = hipMalloc((void**)&t->counters, mvs::kTsneCounters * 8) == hipSuccess && hipMalloc((void**)&t->y, nn * 16) == hipSuccess &&
-              hipMalloc((void**)&t->vel, nn * 16) == hipSuccess && hipMalloc((void**)&t->gain, nn * 16) == hipSuccess &&
-              hipMalloc((void**)&t->sums, (5 * nn + 1) * 8) == hipSuccess && hipMalloc((void**)&t->beta, nn * 8) == hipSuccess;
+    bool ok = t->counters.alloc(mvs::kTsneCounters * 8) == hipSuccess && t->y.alloc(nn * 16) == hipSuccess &&
+              t->vel.alloc(nn * 16) == hipSuccess && t->gain.alloc(nn * 16) == hipSuccess &&
+              t->sums.alloc((5 * nn + 1) * 8) == hipSuccess && t->beta.alloc(nn * 8) == hipSuccess;
     if (ok)
-        ok = hipMemsetAsync(t->y, 0, nn * 16, c->stream) == hipSuccess && hipMemsetAsync(t->vel, 0, nn * 16, c->stream) == hipSuccess &&
-             hipMemsetAsync(t->beta, 0, nn * 8, c->stream) == hipSuccess && mvs::launch_tsne_fill(c->stream, t->gain, 2 * n, 1.0) == 0 &&
-             hipStreamSynchronize(c->stream) == hipSuccess;
-    if (!ok) {
-        mvs_tsne_destroy(t);
-        return fail(MVS_E_NOMEM, "hipMalloc of the state of %lld samples failed", (long long)n);
-    }
+        ok = hipMemsetAsync(t->y.as<double>(), 0, nn * 16, c->stream) == hipSuccess && hipMemsetAsync(t->vel.as<double>(), 0, nn * 16,
+                                                                                                      c->stream) == hipSuccess &&
+            hipMemsetAsync(t->beta.as<double>(), 0, nn * 8, c->stream) == hipSuccess && mvs::launch_tsne_fill(c->stream,
+                                                                                                              t->gain.as<double>(), 2 * n,
+                                                                                                              1.0) == 0 &&
+            hipStreamSynchronize(c->stream) == hipSuccess;
+    if (!ok) return fail(MVS_E_NOMEM, "hipMalloc of the state of %lld samples failed", (long long)n);
     c->ts.reset();
-    *out = t;
+    *out = t.release();
     return MVS_OK;
 }
 
@@ -207,15 +190,6 @@ int mvs_tsne_destroy(mvs_tsne_graph* t) {
         (void)hipSetDevice(t->ctx->device);
         (void)hipStreamSynchronize(t->ctx->stream);
     }
-    drop_graph(t);
-    free_dev(t->keys);
-    free_dev(t->vals);
-    free_dev(t->counters);
-    free_dev(t->y);
-    free_dev(t->vel);
-    free_dev(t->gain);
-    free_dev(t->sums);
-    free_dev(t->beta);
     delete t;
     return MVS_OK;
 }
@@ -239,22 +213,23 @@ int mvs_tsne_add_edges(mvs_tsne_graph* t, const int32_t* lo, const int32_t* hi, 
         dhi = p + n_edges;
         ds = p + 2 * n_edges;
     }
-    HIP_TRY(hipMemsetAsync(t->counters, 0, mvs::kTsneCounters * 8, c->stream));
-    int rc = mvs::launch_tsne_check_edges(c->stream, dlo, dhi, ds, n_edges, t->n, t->counters);
+    HIP_TRY(hipMemsetAsync(t->counters.as<u64>(), 0, mvs::kTsneCounters * 8, c->stream));
+    int rc = mvs::launch_tsne_check_edges(c->stream, dlo, dhi, ds, n_edges, t->n, t->counters.as<u64>());
     if (!rc) rc = check_kernel("k_tsne_check_edges");
     if (rc) return rc;
     u64 bad = 0;
-    rc = read_back(c, c->stream, {{&bad, t->counters, 8}});
+    rc = read_back(c, c->stream, {{&bad, t->counters.as<u64>(), 8}});
     if (rc) return rc;
     if (bad != 0)
         return fail(MVS_E_RANGE, "%llu edges name a sample outside [0, %lld) or have a weight below 1: nothing was added", bad, (long long)t->n);
     rc = ensure_room(t, 2 * n_edges);
     if (rc) return rc;
-    rc = mvs::launch_tsne_edges(c->stream, dlo, dhi, ds, n_edges, t->keys + t->count, t->vals + t->count, t->counters);
+    rc = mvs::launch_tsne_edges(c->stream, dlo, dhi, ds, n_edges, t->keys.as<u64>() + t->count, t->vals.as<u64>() + t->count,
+                                t->counters.as<u64>());
     if (!rc) rc = check_kernel("k_tsne_edges");
     if (rc) return rc;
     u64 selfs = 0;
-    rc = read_back(c, c->stream, {{&selfs, t->counters + 1, 8}});     // (also before `stage` is freed)
+    rc = read_back(c, c->stream, {{&selfs, t->counters.as<u64>() + 1, 8}});     // (also before `stage` is freed)
     if (rc) return rc;
     t->count += 2 * n_edges;
     t->dead += 2 * (int64_t)selfs;
@@ -291,7 +266,7 @@ int mvs_tsne_add_neighbours(mvs_tsne_graph* t, const mvs_cell* cells, int64_t n_
         return fail(MVS_E_RANGE, "the cell list's rows %d .. %d leave [0, %lld) or descend: nothing was added", ends[0], ends[1], (long long)t->n);
     rc = consume_neighbours(t, d_cells, n_cells, ends[0], (int64_t)ends[1] - ends[0] + 1, d_n2, d, perplexity, (int32_t*)dc.p, nullptr);
     if (rc) return rc;
-    if (beta_out) HIP_TRY(hipMemcpyAsync(beta_out + ends[0], t->beta + ends[0], (size_t)(ends[1] - ends[0] + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (beta_out) HIP_TRY(hipMemcpyAsync(beta_out + ends[0], t->beta.as<double>() + ends[0], (size_t)(ends[1] - ends[0] + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     if (c_out) HIP_TRY(hipMemcpyAsync(c_out, dc.p, (size_t)n_cells * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MVS_OK;
@@ -312,32 +287,33 @@ int mvs_tsne_finish_graph(mvs_tsne_graph* t) {
         DevBuf tk, tv;
         HIP_TRY(tk.alloc((size_t)t->count * 8));
         HIP_TRY(tv.alloc((size_t)t->count * 8));
-        rc = mvs::comm_sum_by_key(c->stream, t->keys, t->vals, t->count, t->count - t->dead, (u64*)tk.p, (u64*)tv.p, t->counters + 4);
+        rc = mvs::comm_sum_by_key(c->stream, t->keys.as<u64>(), t->vals.as<u64>(), t->count, t->count - t->dead, (u64*)tk.p, (u64*)tv.p,
+                                  t->counters.as<u64>() + 4);
         if (rc) return fail(rc, "t-SNE: summing the entries by key failed");
         u64 left = 0;
-        rc = read_back(c, c->stream, {{&left, t->counters + 4, 8}});
+        rc = read_back(c, c->stream, {{&left, t->counters.as<u64>() + 4, 8}});
         if (rc) return rc;
         m = (int64_t)left;
         t->count = m;                                                   // the list stays: one entry per directed pair now
         t->dead = 0;
     }
     const size_t mm = (size_t)std::max<int64_t>(m, 1);
-    if (hipMalloc((void**)&t->row_ptr, ((size_t)t->n + 1) * 8) != hipSuccess || hipMalloc((void**)&t->src, mm * 4) != hipSuccess ||
-        hipMalloc((void**)&t->col, mm * 4) != hipSuccess || hipMalloc((void**)&t->p, mm * 8) != hipSuccess) {
+    if (t->row_ptr.alloc(((size_t)t->n + 1) * 8) != hipSuccess || t->src.alloc(mm * 4) != hipSuccess ||
+        t->col.alloc(mm * 4) != hipSuccess || t->p.alloc(mm * 8) != hipSuccess) {
         drop_graph(t);
         return fail(MVS_E_NOMEM, "hipMalloc of the graph of %lld entries failed", (long long)m);
     }
-    rc = mvs::launch_comm_csr(c->stream, t->keys, m, t->n, t->row_ptr, t->src, t->col);
+    rc = mvs::launch_comm_csr(c->stream, t->keys.as<u64>(), m, t->n, t->row_ptr.as<long long>(), t->src.as<int32_t>(), t->col.as<int32_t>());
     if (!rc) rc = check_kernel("k_comm_csr");
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(t->counters + 5, 0, 8, c->stream));
-    rc = mvs::launch_tsne_total(c->stream, t->vals, m, t->counters + 5);
+    HIP_TRY(hipMemsetAsync(t->counters.as<u64>() + 5, 0, 8, c->stream));
+    rc = mvs::launch_tsne_total(c->stream, t->vals.as<u64>(), m, t->counters.as<u64>() + 5);
     if (!rc) rc = check_kernel("k_tsne_total");
     if (rc) return rc;
     u64 S = 0;
-    rc = read_back(c, c->stream, {{&S, t->counters + 5, 8}});
+    rc = read_back(c, c->stream, {{&S, t->counters.as<u64>() + 5, 8}});
     if (rc) return rc;
-    rc = mvs::launch_tsne_p(c->stream, t->vals, m, S, t->p);
+    rc = mvs::launch_tsne_p(c->stream, t->vals.as<u64>(), m, S, t->p.as<double>());
     if (!rc) rc = check_kernel("k_tsne_p");
     if (!rc) rc = timer.mark_end();
     if (rc) return rc;
@@ -360,9 +336,9 @@ int mvs_tsne_edges(mvs_tsne_graph* t, int32_t* row, int32_t* col, int64_t* s, in
     if (!row && !col && !s) return MVS_OK;
     if (capacity < t->m) return fail(MVS_E_CAPACITY, "%lld entries, room for %lld", (long long)t->m, (long long)capacity);
     HIP_TRY(hipSetDevice(c->device));
-    int rc = give_out(c, row, t->src, t->m, MVS_MEM_HOST);
-    if (!rc) rc = give_out(c, col, t->col, t->m, MVS_MEM_HOST);
-    if (!rc) rc = give_out(c, s, t->vals, t->m, MVS_MEM_HOST);
+    int rc = give_out(c, row, t->src.as<int32_t>(), t->m, MVS_MEM_HOST);
+    if (!rc) rc = give_out(c, col, t->col.as<int32_t>(), t->m, MVS_MEM_HOST);
+    if (!rc) rc = give_out(c, s, t->vals.as<u64>(), t->m, MVS_MEM_HOST);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MVS_OK;
@@ -373,9 +349,9 @@ int mvs_tsne_set_state(mvs_tsne_graph* t, const double* y, const double* velocit
     mvs_ctx* c = t->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)t->n * 16;
-    if (y) HIP_TRY(hipMemcpyAsync(t->y, y, bytes, hipMemcpyHostToDevice, c->stream));
-    if (velocity) HIP_TRY(hipMemcpyAsync(t->vel, velocity, bytes, hipMemcpyHostToDevice, c->stream));
-    if (gain) HIP_TRY(hipMemcpyAsync(t->gain, gain, bytes, hipMemcpyHostToDevice, c->stream));
+    if (y) HIP_TRY(hipMemcpyAsync(t->y.as<double>(), y, bytes, hipMemcpyHostToDevice, c->stream));
+    if (velocity) HIP_TRY(hipMemcpyAsync(t->vel.as<double>(), velocity, bytes, hipMemcpyHostToDevice, c->stream));
+    if (gain) HIP_TRY(hipMemcpyAsync(t->gain.as<double>(), gain, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MVS_OK;
 }
@@ -384,9 +360,9 @@ int mvs_tsne_get_state(mvs_tsne_graph* t, double* y, double* velocity, double* g
     if (!t) return fail(MVS_E_INVALID, "NULL graph");
     mvs_ctx* c = t->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = give_out(c, y, t->y, 2 * t->n, MVS_MEM_HOST);
-    if (!rc) rc = give_out(c, velocity, t->vel, 2 * t->n, MVS_MEM_HOST);
-    if (!rc) rc = give_out(c, gain, t->gain, 2 * t->n, MVS_MEM_HOST);
+    int rc = give_out(c, y, t->y.as<double>(), 2 * t->n, MVS_MEM_HOST);
+    if (!rc) rc = give_out(c, velocity, t->vel.as<double>(), 2 * t->n, MVS_MEM_HOST);
+    if (!rc) rc = give_out(c, gain, t->gain.as<double>(), 2 * t->n, MVS_MEM_HOST);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MVS_OK;
@@ -403,7 +379,8 @@ int mvs_tsne_gradient(mvs_tsne_graph* t, double exaggeration, double* grad, int6
     DevBuf dg;
     HIP_TRY(dg.alloc((size_t)t->n * 16));
     const mvs::TsneSums s = sums_of(t);
-    rc = mvs::launch_tsne_update(c->stream, t->n, s, exaggeration, 0.0, 0.0, 0, t->y, t->vel, t->gain, (double*)dg.p);
+    rc = mvs::launch_tsne_update(c->stream, t->n, s, exaggeration, 0.0, 0.0, 0, t->y.as<double>(), t->vel.as<double>(),
+                                 t->gain.as<double>(), (double*)dg.p);
     if (!rc) rc = check_kernel("k_tsne_update");
     if (!rc) rc = give_out(c, grad, dg.p, 2 * t->n, MVS_MEM_HOST);
     if (!rc) rc = give_out(c, (long long*)z_rows, s.z_rows, t->n, MVS_MEM_HOST);
@@ -428,7 +405,8 @@ int mvs_tsne_run(mvs_tsne_graph* t, int64_t iterations, double exaggeration, dou
         StageTimer tu;
         rc = tu.begin(c);
         if (rc) return rc;
-        rc = mvs::launch_tsne_update(c->stream, t->n, s, exaggeration, momentum, learning_rate, 1, t->y, t->vel, t->gain, nullptr);
+        rc = mvs::launch_tsne_update(c->stream, t->n, s, exaggeration, momentum, learning_rate, 1, t->y.as<double>(), t->vel.as<double>(),
+                                     t->gain.as<double>(), nullptr);
         if (!rc) rc = check_kernel("k_tsne_update");
         if (!rc) rc = tu.mark_end();
         if (!rc) rc = tu.add_to(&c->ts.update_ms);
@@ -449,7 +427,8 @@ int mvs_tsne_kl(mvs_tsne_graph* t, double* kl) {
     DevBuf dk;
     HIP_TRY(dk.alloc(8));
     HIP_TRY(hipMemsetAsync(dk.p, 0, 8, c->stream));
-    rc = mvs::launch_tsne_kl(c->stream, t->y, t->m, t->src, t->col, t->p, sums_of(t), (double*)dk.p);
+    rc = mvs::launch_tsne_kl(c->stream, t->y.as<double>(), t->m, t->src.as<int32_t>(), t->col.as<int32_t>(), t->p.as<double>(), sums_of(t),
+                             (double*)dk.p);
     if (!rc) rc = check_kernel("k_tsne_kl");
     if (rc) return rc;
     return read_back(c, c->stream, {{kl, dk.p, 8}});
@@ -546,7 +525,7 @@ int mvs_tsne(mvs_ctx* c, const mvs_sketch_set* set, const double* norms_sq, int 
     r.entries = t->m;
     r.S = t->S;
     if (beta) {
-        HIP_TRY(hipMemcpyAsync(beta, t->beta, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(beta, t->beta.as<double>(), (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
 

@@ -180,6 +180,10 @@ def test_reader_and_codec_under_address_sanitizer(toy_index, gold, tmp_path):
     asan = os.path.join(BIN, "asan")
     r = run(os.path.join(asan, "mvs_codec_selftest"))
     assert r.returncode == 0 and "mvs_codec_selftest ok" in r.stdout, r.stderr
+    # the owning types of the C ABI's objects against counting stand-ins for the runtime (no device, no HIP library)
+    r = run(os.path.join(asan, "mvs_owned_selftest"))
+    assert r.returncode == 0 and "all checks passed" in r.stdout, r.stdout + r.stderr
+    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
     # the shard writer's threads under ThreadSanitizer.  GCC 11's runtime aborts ("unexpected memory mapping") where the kernel
     # randomises mmap addresses with more bits than its shadow layout allows: the child runs with randomisation off for itself
     no_aslr = ["setarch", platform.machine(), "-R"]
