@@ -1017,7 +1017,7 @@ int mvs_ctx_kmer_sample_stats(const mvs_ctx* ctx, int64_t n_samples, int64_t* km
  * mvs_hash_set_abundances    the abundances of a counted set, aligned with mvs_hash_set_export's values, where `mem_out` says.
  *                       MVS_E_INVALID for a set that carries none (made by mvs_hash_set_create / _from_sequences).  To
  *                       mvs_intersect_cells, mvs_gather, mvs_hash_set_export and mvs_hash_set_device a counted set is the
- *                       plain set it also is.
+ *                       plain set it also is.  mvs_abund_overlap_cells ("abundance-weighted overlaps" below) reads them.
  * mvs_ctx_abund_stats   the context's last counted build: time of its sorts and of its run-sum passes (0 unless
  *                       mvs_ctx_set_timing is on), values given, distinct values, values that passed, units of the run-sum
  *                       passes, samples sorted device-wide.  Any pointer may be NULL. */
@@ -1038,6 +1038,64 @@ int mvs_hash_set_create_counted(mvs_ctx* ctx, const uint64_t* hashes, int mem_ha
 int mvs_hash_set_abundances(const mvs_hash_set* set, uint32_t* out, int mem_out);
 int mvs_ctx_abund_stats(const mvs_ctx* ctx, double* sort_ms, double* count_ms, int64_t* values_in, int64_t* distinct, int64_t* passed,
                         int64_t* units, int64_t* big_segments);
+
+/* ---- abundance-weighted overlaps for kept pairs -----------------------------------------------------------------------------
+ * The measures people report for metagenomes weigh a shared k-mer by how often it was seen: Bray-Curtis, weighted Jaccard
+ * (Ruzicka), the cosine of the abundance vectors with sourmash's angular similarity of it, abundance-weighted containment.
+ * These calls compute their integer ingredients for a list of cells with the units of work, the searches and the exactness
+ * of mvs_intersect_cells, and state the derived measures once, in host code.  The reference carries no abundances anywhere,
+ * so nothing of it is replaced.
+ *
+ * For a hash set let a_s(h) be the abundance of value h in sample s: the carried uint32 of a counted set, and 1 FOR EVERY
+ * VALUE OF A SET THAT CARRIES NONE -- a metagenome with counts against plain genome sketches is an ordinary call, and a call
+ * on two plain sets reproduces mvs_intersect_cells in every field.  For a cell (row r of hs_rows, column c of hs_cols), with
+ * M = H(r) n H(c):
+ *     inter  = |M|
+ *     w_row  = sum over M of a_r(h)                      w_col = sum over M of a_c(h)
+ *     w_min  = sum over M of min(a_r(h), a_c(h))
+ *     dot_lo = sum over M of (a_r(h) * a_c(h) mod 2^32)  dot_hi = sum over M of floor(a_r(h) * a_c(h) / 2^32)
+ * The dot product of the two abundance vectors is dot_hi * 2^32 + dot_lo.  It is carried as two sums and not as one 64-bit
+ * word so that NO FIELD CAN OVERFLOW: a sample holds fewer than 2^31 values and every term is below 2^32, so every sum is
+ * below 2^63 -- a poly-A k-mer seen 10^7 times in both samples (one term of 10^14) stays an ordinary input, and so do 2^31 - 1
+ * of them.  Exact and deterministic: integer sums do not depend on the unit size, the blocking, the order of the cells or of
+ * the units.  Per-sample totals, with the same split:
+ *     S(s) = sum of a_s(h)      Q_lo(s) = sum of (a_s(h)^2 mod 2^32)      Q_hi(s) = sum of floor(a_s(h)^2 / 2^32)
+ * A cell with row == col on the same set yields w_row = w_col = w_min = S and dot = Q = Q_hi * 2^32 + Q_lo.
+ *
+ * mvs_abund_overlap_cells   the records of n_cells cells.  Arguments, refusals, hs_cols == NULL, repeated cells and device / host
+ *                       memory exactly as for mvs_intersect_cells; `out` holds n_cells records where `mem_out` says.  A cell that
+ *                       names a sample outside its set: MVS_E_RANGE, nothing is written for that cell, every other cell is
+ *                       answered.  Synchronous.  Like mvs_gather it is also "the context's last mvs_intersect_cells" for
+ *                       mvs_ctx_intersect_stats.  How: the plan, the units and the searches of mvs_intersect_cells (option
+ *                       intersect_unit); the lane that finds its key knows the position on both sides, loads the two
+ *                       abundances from global memory -- on a match only, no load at all for a side that carries none --,
+ *                       and the wave adds its six sums to the cell's record with one 64-bit integer atomic per non-zero field.
+ * mvs_hash_set_abundance_totals
+ *                       S, Q_lo and Q_hi of every sample: n_samples uint64 each where `mem_out` says; any pointer may be NULL.
+ *                       A set that carries no abundances: S = Q_lo = the sample's size, Q_hi = 0.  Synchronous.
+ * mvs_abund_similarity  pure host, the library's own statement of the derived measures of one cell, from its record and the
+ *                       totals of its row and column sample.  Every integer is converted to fp64 with round-to-nearest-even, a
+ *                       128-bit value (D = dot, Q_row, Q_col) as a whole; then exactly these operations, 0 / 0 = NaN:
+ *                         out[0] w_contain_row = w_row / S_row
+ *                         out[1] w_contain_col = w_col / S_col
+ *                         out[2] bray_curtis   = (S_row + S_col - 2 w_min) / (S_row + S_col)     the DISsimilarity; numerator and
+ *                                                                                                 denominator formed as integers
+ *                         out[3] ruzicka       = w_min / (S_row + S_col - w_min)                 denominator formed as an integer
+ *                         out[4] cosine        = min(1, D / sqrt(Q_row * Q_col))                 one multiply, one sqrt, one divide
+ *                         out[5] angular       = 1 - 2 acos(cosine) / pi                         sourmash's angular_similarity
+ *                       size_row / size_col (the samples' numbers of values) enter no measure; they are checked with the
+ *                       rest: a NULL pointer, a negative size or inter, inter above a size, w_min above S_row or S_col:
+ *                       MVS_E_INVALID. */
+typedef struct mvs_abund_overlap {
+    int64_t inter;                                   /* never negative in an answered cell */
+    uint64_t w_row, w_col, w_min, dot_lo, dot_hi;
+} mvs_abund_overlap;                                 /* 48 bytes */
+int mvs_abund_overlap_cells(mvs_ctx* ctx, const mvs_hash_set* hs_rows, const mvs_hash_set* hs_cols, const mvs_cell* cells,
+                            int mem_cells, int64_t n_cells, mvs_abund_overlap* out, int mem_out);
+int mvs_hash_set_abundance_totals(const mvs_hash_set* set, uint64_t* sum, uint64_t* sumsq_lo, uint64_t* sumsq_hi, int mem_out);
+int mvs_abund_similarity(const mvs_abund_overlap* overlap, uint64_t sum_row, uint64_t sumsq_lo_row, uint64_t sumsq_hi_row,
+                         int64_t size_row, uint64_t sum_col, uint64_t sumsq_lo_col, uint64_t sumsq_hi_col, int64_t size_col,
+                         double out[6]);
 
 /* ---- gather: the greedy decomposition of a query into samples of a hash set -------------------------------------------------
  * Everything above asks about a PAIR of samples.  This call answers the set question "which DB samples make up my sample, and

@@ -16,6 +16,6 @@ Importing the package does not load the HIP library; the first call that needs i
 loudly if it is missing (there is no CPU fallback).
 """
 from . import _capi  # noqa: F401
-from ._capi import Cluster, ClusterResult, Communities, CommunityGraph, Context, Derep, DerepResult, DeviceArray, GatherResult, HashSet, Hclust, Hdbscan, KmerSketcher, Linkage, LinkageResult, MvsError, Pca, Pcoa, Permanova, Silhouette, Tsne, TsneGraph, community_modularity, hclust_cut, hclust_order, hdbscan_select, kmer_hash, kmer_max_hash, load_library, permutation_labels, silhouette_stats  # noqa: F401
+from ._capi import Cluster, ClusterResult, Communities, CommunityGraph, Context, Derep, DerepResult, DeviceArray, GatherResult, HashSet, Hclust, Hdbscan, KmerSketcher, Linkage, LinkageResult, MvsError, Pca, Pcoa, Permanova, Silhouette, Tsne, TsneGraph, abund_similarity, community_modularity, hclust_cut, hclust_order, hdbscan_select, kmer_hash, kmer_max_hash, load_library, permutation_labels, silhouette_stats  # noqa: F401
 
-__all__ = ["Cluster", "ClusterResult", "Communities", "CommunityGraph", "Context", "Derep", "DerepResult", "DeviceArray", "GatherResult", "HashSet", "Hclust", "Hdbscan", "KmerSketcher", "Linkage", "LinkageResult", "MvsError", "Pca", "Pcoa", "Permanova", "Silhouette", "Tsne", "TsneGraph", "community_modularity", "hclust_cut", "hclust_order", "hdbscan_select", "kmer_hash", "kmer_max_hash", "load_library", "permutation_labels", "silhouette_stats"]
+__all__ = ["Cluster", "ClusterResult", "Communities", "CommunityGraph", "Context", "Derep", "DerepResult", "DeviceArray", "GatherResult", "HashSet", "Hclust", "Hdbscan", "KmerSketcher", "Linkage", "LinkageResult", "MvsError", "Pca", "Pcoa", "Permanova", "Silhouette", "Tsne", "TsneGraph", "abund_similarity", "community_modularity", "hclust_cut", "hclust_order", "hdbscan_select", "kmer_hash", "kmer_max_hash", "load_library", "permutation_labels", "silhouette_stats"]

@@ -31,6 +31,8 @@ HMERGE_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("round", "<i4"), ("size", 
 HCLUST_METHODS = {"average": 0, "complete": 1}
 HCLUST_MAX_TOTAL = 131072
 GATHER_DTYPE = np.dtype([("sample", "<i4"), ("intersect", "<i4"), ("unique", "<i4"), ("remaining", "<i4")])  # mvs_gather_match
+ABUND_OVERLAP_DTYPE = np.dtype([("inter", "<i8"), ("w_row", "<u8"), ("w_col", "<u8"), ("w_min", "<u8"), ("dot_lo", "<u8"),
+                                ("dot_hi", "<u8")])                                                     # mvs_abund_overlap
 
 # every symbol include/mvs_hip.h declares: (name, restype, argtypes)
 _c = ctypes
@@ -253,6 +255,10 @@ SYMBOLS = [
     ("mvs_intersect_cells", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _P, _c.c_int]),
     ("mvs_ctx_intersect_stats", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
                                             _c.POINTER(_c.c_int64)]),
+    ("mvs_abund_overlap_cells", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _P, _c.c_int]),
+    ("mvs_hash_set_abundance_totals", _c.c_int, [_P, _P, _P, _P, _c.c_int]),
+    ("mvs_abund_similarity", _c.c_int, [_P, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64, _c.c_uint64, _c.c_uint64, _c.c_uint64,
+                                         _c.c_int64, _c.POINTER(_c.c_double)]),
     ("mvs_gather", _c.c_int, [_P, _P, _c.c_int64, _P, _P, _c.c_int, _c.c_int64, _c.c_int32, _c.c_int64, _P, _c.c_int,
                                _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32)]),
     ("mvs_ctx_gather_stats", _c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
@@ -401,6 +407,22 @@ class DeviceArray:
 
     def __len__(self):
         return self.count
+
+
+ABUND_MEASURES = ("w_contain_row", "w_contain_col", "bray_curtis", "ruzicka", "cosine", "angular")
+
+
+def abund_similarity(overlap, totals_row, size_row, totals_col, size_col):
+    """mvs_abund_similarity, pure host: the six measures of ABUND_MEASURES, in that order, as a float64 array.  overlap: one
+    ABUND_OVERLAP_DTYPE record or a sequence (inter, w_row, w_col, w_min, dot_lo, dot_hi); totals_*: (sum, sumsq_lo, sumsq_hi)
+    of the row / column sample, size_*: its number of values.  Needs no device."""
+    rec = np.zeros(1, dtype=ABUND_OVERLAP_DTYPE)
+    rec[0] = tuple(int(overlap[f]) for f in ABUND_OVERLAP_DTYPE.names) if hasattr(overlap, "dtype") and overlap.dtype == ABUND_OVERLAP_DTYPE \
+        else tuple(int(v) for v in overlap)
+    out = (_c.c_double * 6)()
+    _check(load_library().mvs_abund_similarity(rec.ctypes.data, *[int(v) for v in totals_row], int(size_row),
+                                               *[int(v) for v in totals_col], int(size_col), out))
+    return np.array(out[:], dtype=np.float64)
 
 
 def kmer_max_hash(scaled):
@@ -1368,6 +1390,16 @@ class HashSet(_Handle):
             return None
         _check(rc)
         return out
+
+    def abundance_totals(self):
+        """-> (sum, sumsq_lo, sumsq_hi), uint64 [n] each: per sample the sum S of the abundances and the sum Q of their squares
+        as Q = sumsq_hi * 2^32 + sumsq_lo (mvs_hash_set_abundance_totals).  A set that carries no abundances counts 1 per
+        value: S = sumsq_lo = the sample's size, sumsq_hi = 0."""
+        if self._h is None:
+            raise ValueError("the hash set is closed")
+        out = [np.zeros(self.n, dtype=np.uint64) for _ in range(3)]
+        _check(self.ctx.lib.mvs_hash_set_abundance_totals(self._h, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, MEM_HOST))
+        return tuple(out)
 
 
 class KmerSketcher(_Handle):
@@ -2675,26 +2707,29 @@ class Context:
         _check(self.lib.mvs_ctx_kmer_sample_stats(self._h, int(n_samples), kmers.ctypes.data, kept.ctypes.data))
         return kmers, kept
 
+    @staticmethod
+    def _cells_arg(cells):
+        """cells as intersect_cells / abund_overlap take them -> (pointer, mem flag, keepalive, number of cells)"""
+        if _is_torch(cells):
+            cp, cm, ck = _buf(cells)
+            return cp, cm, ck, cells.shape[0]
+        a = np.asarray(cells)
+        if a.dtype != CELL_DTYPE:
+            a = np.asarray(a, dtype=np.int32)
+            if a.ndim != 2 or a.shape[1] < 2:
+                raise ValueError("cells must be CELL_DTYPE records or an int32 array [m, >= 2]")
+            full = np.zeros((a.shape[0], 4), dtype=np.int32)
+            full[:, :min(4, a.shape[1])] = a[:, :4]
+            a = full
+        ck = np.ascontiguousarray(a)
+        return ck.ctypes.data, MEM_HOST, ck, ck.shape[0]
+
     def intersect_cells(self, hs, cells, n_cells=None, hs_cols=None, out=None):
         """inter[i] = |H_rows(cells[i].row) n H_cols(cells[i].col)|, exact (mvs_intersect_cells).  cells: numpy structured
         array (CELL_DTYPE) or int32 [m, 4] / [m, 2+] rows of (row, col, ...), or a torch device tensor int32 [m, 4] (the first
         n_cells rows, default all).  hs_cols: the columns' set (default: hs).  Returns int32 counts: a numpy array for host
         cells, a torch device tensor for device cells, or `out`."""
-        if _is_torch(cells):
-            cp, cm, ck = _buf(cells)
-            m = cells.shape[0]
-        else:
-            a = np.asarray(cells)
-            if a.dtype != CELL_DTYPE:
-                a = np.asarray(a, dtype=np.int32)
-                if a.ndim != 2 or a.shape[1] < 2:
-                    raise ValueError("cells must be CELL_DTYPE records or an int32 array [m, >= 2]")
-                full = np.zeros((a.shape[0], 4), dtype=np.int32)
-                full[:, :min(4, a.shape[1])] = a[:, :4]
-                a = full
-            ck = np.ascontiguousarray(a)
-            cp, cm = ck.ctypes.data, MEM_HOST
-            m = ck.shape[0]
+        cp, cm, ck, m = self._cells_arg(cells)
         if n_cells is None:
             n_cells = m
         elif n_cells > m:
@@ -2727,6 +2762,64 @@ class Context:
         fi = inter.astype(np.float64)
         with np.errstate(invalid="ignore", divide="ignore"):
             return inter, fi / (sa + sb - fi), fi / sa, fi / sb
+
+    # ---- abundance-weighted overlaps (include/mvs_hip.h "abundance-weighted overlaps") ----
+    def abund_overlap(self, hs, cells, n_cells=None, hs_cols=None, out=None):
+        """mvs_abund_overlap_cells: per cell inter, w_row, w_col, w_min, dot_lo, dot_hi over the values the two samples share,
+        a value of a set without abundances counting 1; exact.  cells and hs_cols as intersect_cells takes them.  Returns
+        ABUND_OVERLAP_DTYPE records (numpy) for host cells, a torch device tensor int64 [m, 6] (the bits of the unsigned sums)
+        for device cells, or `out`.  Also leaves intersect_stats()."""
+        cp, cm, ck, m = self._cells_arg(cells)
+        if n_cells is None:
+            n_cells = m
+        elif n_cells > m:
+            raise ValueError("n_cells beyond the cell list")
+        if out is None:
+            if cm == MEM_DEVICE:
+                import torch
+                out = torch.empty((max(int(n_cells), 0), 6), dtype=torch.int64, device=cells.device)
+            else:
+                out = np.empty(max(int(n_cells), 0), dtype=ABUND_OVERLAP_DTYPE)
+        if _is_torch(out):
+            if str(out.dtype) != "torch.int64" or out.numel() < 6 * int(n_cells):
+                raise ValueError("out must be an int64 tensor [n_cells, 6]")
+            op, om, ok = _buf(out)
+        else:
+            if len(out) < int(n_cells):
+                raise ValueError("out is shorter than the cell list")
+            op, om, ok = _buf(out, ABUND_OVERLAP_DTYPE, writable=True)
+        _check(self.lib.mvs_abund_overlap_cells(self._h, hs._h, hs_cols._h if hs_cols is not None else None, cp, cm, int(n_cells),
+                                                op, om))
+        return out
+
+    def abundance_similarity(self, hs, cells, hs_cols=None):
+        """The abundance-weighted measures of every cell -> dict of numpy arrays: inter, w_row, w_col, w_min, dot (object array
+        of Python ints: dot_hi * 2^32 + dot_lo), and float64 w_contain_row, w_contain_col, bray_curtis (the dissimilarity),
+        ruzicka, cosine, angular -- each computed by mvs_abund_similarity from the record and the samples' totals, so the
+        rounding is the library's; 0 / 0 is NaN"""
+        rec = self.abund_overlap(hs, cells, hs_cols=hs_cols)
+        if _is_torch(rec):
+            rec = np.ascontiguousarray(rec.cpu().numpy()).view(ABUND_OVERLAP_DTYPE).reshape(-1)
+        if _is_torch(cells):
+            rc = cells[:, :2].cpu().numpy()
+            rows, cols = rc[:, 0], rc[:, 1]
+        else:
+            a = np.asarray(cells)
+            rows, cols = (a["row"], a["col"]) if a.dtype == CELL_DTYPE else (a[:, 0], a[:, 1])
+        cs = hs_cols if hs_cols is not None else hs
+        tr, tc = hs.abundance_totals(), (cs.abundance_totals() if cs is not hs else None)
+        tc = tr if tc is None else tc
+        zr, zc = hs.sizes(), (cs.sizes() if cs is not hs else None)
+        zc = zr if zc is None else zc
+        derived = np.empty((len(rec), 6), dtype=np.float64)
+        for i in range(len(rec)):
+            r, c = int(rows[i]), int(cols[i])
+            derived[i] = abund_similarity(rec[i], (tr[0][r], tr[1][r], tr[2][r]), zr[r], (tc[0][c], tc[1][c], tc[2][c]), zc[c])
+        res = {f: rec[f].copy() for f in ("inter", "w_row", "w_col", "w_min")}
+        res["dot"] = np.array([(int(h) << 32) + int(l) for l, h in zip(rec["dot_lo"], rec["dot_hi"])], dtype=object)
+        for k, f in enumerate(ABUND_MEASURES):
+            res[f] = derived[:, k].copy()
+        return res
 
     def intersect_stats(self):
         """-> dict of this context's last intersect_cells: kernel_ms (timing on), units of work launched, cut_pairs (cells

@@ -507,6 +507,19 @@ int launch_isect_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_ce
                        const unsigned long long* d_hash_r, const long long* d_off_r, const int32_t* d_size_r,
                        const unsigned long long* d_hash_c, const long long* d_off_c, const int32_t* d_size_c, int unit,
                        int32_t* d_inter);
+// abundance-weighted overlaps (mvs_overlap.hip).  The plan is isect_plan's with whole records (every field of a cell in range is
+// zeroed; mark_bad: inter = -1 for the others); launch_overlap_units gives every unit to one wave as launch_isect_units does and
+// adds the unit's count and five sums to the cell's record.  d_ab_r / d_ab_c: uint32 abundances aligned with the hashes, or
+// NULL = 1 for every value of that side.  launch_abund_totals: S, Q mod 2^32 summed, Q / 2^32 summed per sample (any output NULL).
+int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
+               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, mvs_abund_overlap* d_out,
+               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed);
+int launch_overlap_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const long long* d_unit_start, long long n_units,
+                         const unsigned long long* d_hash_r, const long long* d_off_r, const int32_t* d_size_r, const uint32_t* d_ab_r,
+                         const unsigned long long* d_hash_c, const long long* d_off_c, const int32_t* d_size_c, const uint32_t* d_ab_c,
+                         int unit, mvs_abund_overlap* d_out);
+int launch_abund_totals(hipStream_t stream, const uint32_t* d_abund, const long long* d_offsets, int64_t n, unsigned long long* d_sum,
+                        unsigned long long* d_sumsq_lo, unsigned long long* d_sumsq_hi);
 // FracMinHash values of DNA bytes (mvs_kmer.hip).  A unit is npos <= `unit` consecutive k-mer positions of one sample, the first
 // at byte `byte0` of the buffer; launch_kmer_hash gives every unit to one workgroup (kmer_lds_bytes(unit, ksize) of LDS), which
 // appends (value, sample) of the kept positions to a staging list of `cap` entries -- what does not fit is dropped but

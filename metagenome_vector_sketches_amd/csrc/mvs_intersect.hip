@@ -44,12 +44,18 @@ __device__ __forceinline__ void wave_add64(unsigned long long* counter, unsigned
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter, v);
 }
 
+// what the planning launch leaves in a cell's result: the count (0, or -1 for a cell out of range), and for the weighted
+// overlaps (mvs_overlap.hip) the five sums zeroed with it
+__device__ __forceinline__ void set_result(int32_t& r, int v) { r = v; }
+__device__ __forceinline__ void set_result(mvs_abund_overlap& r, int v) { r = mvs_abund_overlap{v, 0, 0, 0, 0, 0}; }
+
 // counters: [0] cells out of range, [1] cells cut into several units, [2] sum of 8 * (|A| + |B|) over the cells in range
 // units[i] for i < n_cells, units[n_cells] = 0 (the exclusive scan then ends with the number of units)
+template <typename R>
 __global__ __launch_bounds__(kIxThreads) void k_isect_count(const mvs_cell* __restrict__ cells, int64_t n_cells,
                                                             const int32_t* __restrict__ size_r, int64_t n_r,
                                                             const int32_t* __restrict__ size_c, int64_t n_c, int unit,
-                                                            long long* __restrict__ units, int32_t* __restrict__ inter,
+                                                            long long* __restrict__ units, R* __restrict__ inter,
                                                             int mark_bad, unsigned long long* __restrict__ counters) {
     const int64_t stride = (int64_t)gridDim.x * kIxThreads;
     const int64_t rounds = (n_cells + 1 + stride - 1) / stride;        // every lane makes every trip: whole-wave sums
@@ -61,14 +67,14 @@ __global__ __launch_bounds__(kIxThreads) void k_isect_count(const mvs_cell* __re
             long long u = 0;
             if (r < 0 || c < 0 || r >= n_r || c >= n_c) {
                 bad = 1;
-                if (mark_bad) inter[i] = -1;                           // (host output: the caller's entry is left alone)
+                if (mark_bad) set_result(inter[i], -1);                // (host output: the caller's entry is left alone)
             } else {
                 const int32_t la = size_r[r], lb = size_c[c];
                 const int32_t m = la < lb ? la : lb;
                 u = ((long long)m + unit - 1) / unit;
                 cut = u > 1;
                 bytes = 8ULL * ((unsigned long long)la + (unsigned long long)lb);
-                inter[i] = 0;
+                set_result(inter[i], 0);
             }
             units[i] = u;
         } else if (i == n_cells) {
@@ -261,20 +267,40 @@ int launch_hs_compact(hipStream_t stream, const unsigned long long* d_sorted, co
     return 0;
 }
 
-// d_units / d_unit_start: n_cells + 1 entries each; scratch as rocprim's scan wants it (d_scratch == NULL: *scratch_needed only)
-int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
-               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, int32_t* d_inter,
-               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed) {
+namespace {
+
+template <typename R>
+int isect_plan_for(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
+                   const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, R* d_inter,
+                   bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed) {
     size_t need = 0;
     hipError_t e = rocprim::exclusive_scan(nullptr, need, d_units, d_unit_start, 0LL, (size_t)n_cells + 1, rocprim::plus<long long>(), stream);
     if (e != hipSuccess) return MVS_E_HIP;
     if (scratch_needed) *scratch_needed = need;
     if (d_scratch == nullptr) return 0;
     if (scratch_bytes < need) return MVS_E_CAPACITY;
-    hipLaunchKernelGGL(k_isect_count, dim3(ix_grid(n_cells + 1, kIxThreads)), dim3(kIxThreads), 0, stream, d_cells, n_cells, d_size_r,
+    hipLaunchKernelGGL(k_isect_count<R>, dim3(ix_grid(n_cells + 1, kIxThreads)), dim3(kIxThreads), 0, stream, d_cells, n_cells, d_size_r,
                        n_r, d_size_c, n_c, unit, d_units, d_inter, mark_bad ? 1 : 0, d_counters);
     e = rocprim::exclusive_scan(d_scratch, need, d_units, d_unit_start, 0LL, (size_t)n_cells + 1, rocprim::plus<long long>(), stream);
     return e == hipSuccess ? 0 : MVS_E_HIP;
+}
+
+}  // namespace
+
+// d_units / d_unit_start: n_cells + 1 entries each; scratch as rocprim's scan wants it (d_scratch == NULL: *scratch_needed only)
+int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
+               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, int32_t* d_inter,
+               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed) {
+    return isect_plan_for(stream, d_cells, n_cells, d_size_r, n_r, d_size_c, n_c, unit, d_units, d_unit_start, d_inter, mark_bad,
+                          d_counters, d_scratch, scratch_bytes, scratch_needed);
+}
+
+// ... the same plan for the weighted overlaps: the whole record of a cell in range is zeroed (mark_bad: inter = -1 for the others)
+int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
+               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, mvs_abund_overlap* d_out,
+               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed) {
+    return isect_plan_for(stream, d_cells, n_cells, d_size_r, n_r, d_size_c, n_c, unit, d_units, d_unit_start, d_out, mark_bad,
+                          d_counters, d_scratch, scratch_bytes, scratch_needed);
 }
 
 int launch_isect_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const long long* d_unit_start, long long n_units,
