@@ -81,6 +81,17 @@ struct HdbscanStats {
     long long ranges = 0, rounds = 0, links = 0, edges = 0;
     void reset() { *this = HdbscanStats(); }
 };
+// what the last mvs_pairwise_stream / mvs_cells_stream did on a context (mvs_ctx_stream_stats): comparison kernels summed over
+// the row blocks (timing enabled), bytes, row blocks, pieces, the two-stage route -- and the route its row blocks took
+// (mvs_ctx_stream_dense_stats): delivered out of the dense byte matrix, row passes queued with buffers sized from the blocks
+// before, of those the ones whose sizes did not hold (done again), dense blocks with a q a byte cannot hold (that block and the
+// rest became lists)
+struct StreamStats {
+    double kernel_ms = 0.0;
+    long long bytes = 0, blocks = 0, pieces = 0, two_stage = 0;
+    long long dense_blocks = 0, spec_blocks = 0, spec_redone = 0, list_fallbacks = 0;
+    void reset() { *this = StreamStats(); }
+};
 // what the last mvs_hclust / mvs_hclust_weights / mvs_hclust_sums did on a context (mvs_ctx_hclust_stats): kernel times of the
 // dots and of the fill summed over the row blocks, of the nearest pass, of the merge (pairs, column and row phase) and of the
 // compactions summed over the rounds (timing enabled); rounds, rows scanned, bytes of the table those scans read, compactions
@@ -171,13 +182,7 @@ struct mvs_ctx {
                                                   // pinning costs ~0.3 ms per MiB, a one-piece result needs only one
     std::unique_ptr<void, void (*)(void*)> dl_hsa{nullptr, nullptr};   // option stream_copy = 1: agents + completion signals of
                                                                        // the DMA copies (mvs_capi_stream.hip owns the type)
-    // what the last mvs_pairwise_stream did (mvs_ctx_stream_stats)
-    double st_kernel_ms = 0.0;                    // comparison kernels, summed over the row blocks (timing enabled)
-    long long st_bytes = 0, st_blocks = 0, st_pieces = 0, st_two_stage = 0;
-    // ... and the route its row blocks took (mvs_ctx_stream_dense_stats): delivered out of the dense byte matrix, row passes
-    // queued with buffers sized from the blocks before, of those the ones whose sizes did not hold (done again), dense
-    // blocks with a q a byte cannot hold (that block and the rest became lists)
-    long long st_dense_blocks = 0, st_spec_blocks = 0, st_spec_redone = 0, st_list_fallbacks = 0;
+    mvs_capi::StreamStats st;                     // what the last mvs_pairwise_stream did
     // tile-granular two-stage comparison: tile flags, flagged tiles per tile row, their row-major list (entry 0 = total),
     // the candidate list without the pairs of flagged tiles
     DevBuf pw_tflag, pw_trow, pw_tlist, pw_cand2;
