@@ -276,43 +276,26 @@ int main(int argc, char* argv[]) {
             if (g.d_norms.alloc(g.ctx, (size_t)n * 8) != MVS_OK ||
                 mvs_device_copy(g.ctx, g.d_norms.p, MVS_MEM_DEVICE, sdb.info.norms_sq.data(), MVS_MEM_HOST, (size_t)n * 8) != MVS_OK)
                 return gpu_fail(kProg, "uploading the norms");
-            // row blocks of the search comparison; a block that keeps more than the buffer holds reports what it needs
-            const int64_t block_rows = std::max<int64_t>(256, std::min<int64_t>(n, (1LL << 28) / std::max<int64_t>(n, 1) / 256 * 256));
-            int64_t capacity = 0;
-            for (int64_t rb = 0; rb < n;) {
-                const int64_t re = std::min(n, rb + block_rows);
-                if (capacity == 0) capacity = kBlockCells;
-                if (!g.d_cells.p && (g.d_cells.alloc(g.ctx, (size_t)capacity * sizeof(mvs_cell)) != MVS_OK ||
-                                     g.d_out.alloc(g.ctx, (size_t)capacity * sizeof(mvs_abund_overlap)) != MVS_OK))
-                    return gpu_fail(kProg, "allocating the cell buffers");
-                int64_t count = 0;
-                const int src = mvs_search_block(g.ctx, g.set, (const double*)g.d_norms.p, o.min_jaccard, rb, re, 0, n, (mvs_cell*)g.d_cells.p,
-                                                 capacity, &count);
+            auto compare = [&](int64_t rb, int64_t re, mvs_cell* d_cells, int64_t capacity, int64_t* count) {
+                const int rc = mvs_search_block(g.ctx, g.set, (const double*)g.d_norms.p, o.min_jaccard, rb, re, 0, n, d_cells, capacity, count);
                 float ms = 0.f;
                 if (mvs_ctx_kernel_ms(g.ctx, 1, &ms) == MVS_OK) compare_ms += ms;
-                if (src == MVS_E_CAPACITY) {
-                    g.d_cells.free();
-                    g.d_out.free();
-                    capacity = count + count / 8 + 1024;
-                    continue;
-                }
-                if (src != MVS_OK) return gpu_fail(kProg, "comparing");
-                if (count > 0) {
-                    if (mvs_abund_overlap_cells(g.ctx, g.hs, nullptr, (const mvs_cell*)g.d_cells.p, MVS_MEM_DEVICE, count,
-                                                (mvs_abund_overlap*)g.d_out.p, MVS_MEM_DEVICE) != MVS_OK)
-                        return gpu_fail(kProg, "computing the overlaps");
-                    add_kernel_time();
-                    cells.resize((size_t)count);
-                    recs.resize((size_t)count);
-                    if (mvs_device_copy(g.ctx, cells.data(), MVS_MEM_HOST, g.d_cells.p, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_cell)) != MVS_OK ||
-                        mvs_device_copy(g.ctx, recs.data(), MVS_MEM_HOST, g.d_out.p, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_abund_overlap)) !=
-                            MVS_OK)
-                        return gpu_fail(kProg, "downloading");
-                    for (int64_t i = 0; i < count; ++i)                // sorted by (row, col) inside a block, blocks ascend
-                        if (cells[(size_t)i].row < cells[(size_t)i].col) pairs.push_back({cells[(size_t)i].row, cells[(size_t)i].col, recs[(size_t)i]});
-                }
-                rb = re;
-            }
+                return rc;
+            };
+            auto weigh = [&](const mvs_cell* d_cells, void* d_out, int64_t count) {
+                if (mvs_abund_overlap_cells(g.ctx, g.hs, nullptr, d_cells, MVS_MEM_DEVICE, count, (mvs_abund_overlap*)d_out, MVS_MEM_DEVICE) != MVS_OK)
+                    return gpu_fail(kProg, "computing the overlaps");
+                add_kernel_time();
+                cells.resize((size_t)count);
+                recs.resize((size_t)count);
+                if (mvs_device_copy(g.ctx, cells.data(), MVS_MEM_HOST, d_cells, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_cell)) != MVS_OK ||
+                    mvs_device_copy(g.ctx, recs.data(), MVS_MEM_HOST, d_out, MVS_MEM_DEVICE, (size_t)count * sizeof(mvs_abund_overlap)) != MVS_OK)
+                    return gpu_fail(kProg, "downloading");
+                for (int64_t i = 0; i < count; ++i)                    // sorted by (row, col) inside a block, blocks ascend
+                    if (cells[(size_t)i].row < cells[(size_t)i].col) pairs.push_back({cells[(size_t)i].row, cells[(size_t)i].col, recs[(size_t)i]});
+                return 0;
+            };
+            if (const int rc = for_kept_cell_blocks(kProg, g.ctx, n, sizeof(mvs_abund_overlap), g.d_cells, g.d_out, compare, weigh)) return rc;
         }
     }
 

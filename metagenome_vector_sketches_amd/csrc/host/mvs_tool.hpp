@@ -4,6 +4,7 @@
 //   - the holders of what a tool keeps on the device (Owned, DeviceMem);
 //   - reporting a device error and writing an output file under <file>.part;
 //   - opening the DB folder and loading vectors.bin into a sketch set;
+//   - the row-block loop of the tools that answer kept cells on the device (for_kept_cell_blocks);
 //   - what the ordination tools share;
 //   - the hash file a DB was sketched from.
 // Header-only; include it after mvs_host.hpp.  Each tool keeps its own flag table, usage text and output format.
@@ -347,6 +348,38 @@ inline int load_sketch_dbs(const char* prog, mvs_ctx* ctx, const std::vector<con
 }
 inline int load_sketch_db(const char* prog, mvs_ctx* ctx, const SketchDb& db, mvs_sketch_set** set) {
     return load_sketch_dbs(prog, ctx, {&db}, set);
+}
+
+// ---- kept cells answered on the device (verify_pairs, abundance_pairs --db, contain_sketches) ----
+// The rows [0, n) in blocks: compare(rb, re, d_cells, capacity, &count) leaves a block's kept cells in device memory and
+// returns the library's code; a block that keeps more than the buffers hold (MVS_E_CAPACITY: count is what it needs) is done
+// again with larger ones.  consume(d_cells, d_results, count) then answers the cells into `results`, result_bytes per cell, and
+// takes both home; it returns the tool's exit code, 0 to go on.  A tool's time accounting goes into its compare, which runs
+// once per attempt.  The two buffers are the tool's (declared after its context, as every DeviceMem).  0, or the exit code
+// after a message on stderr.
+template <class Compare, class Consume>
+int for_kept_cell_blocks(const char* prog, mvs_ctx* ctx, int64_t n, size_t result_bytes, DeviceMem& cells, DeviceMem& results,
+                         Compare&& compare, Consume&& consume) {
+    const int64_t block_rows = std::max<int64_t>(256, std::min<int64_t>(n, (1LL << 28) / std::max<int64_t>(n, 1) / 256 * 256));
+    int64_t capacity = 1 << 20;
+    for (int64_t rb = 0; rb < n;) {
+        const int64_t re = std::min(n, rb + block_rows);
+        if (!cells.p && (cells.alloc(ctx, (size_t)capacity * sizeof(mvs_cell)) != MVS_OK || results.alloc(ctx, (size_t)capacity * result_bytes) != MVS_OK))
+            return gpu_fail(prog, "allocating the cell buffers");
+        int64_t count = 0;
+        const int rc = compare(rb, re, (mvs_cell*)cells.p, capacity, &count);
+        if (rc == MVS_E_CAPACITY) {
+            cells.free();
+            results.free();
+            capacity = count + count / 8 + 1024;
+            continue;
+        }
+        if (rc != MVS_OK) return gpu_fail(prog, "comparing");
+        if (count > 0)
+            if (const int exit_code = consume((const mvs_cell*)cells.p, results.p, count)) return exit_code;
+        rb = re;
+    }
+    return 0;
 }
 
 // ---- what the ordination tools share (pca_sketches, pcoa_sketches; permanova_sketches for the norms and its report) ----

@@ -1,6 +1,6 @@
 // mvs_capi_gather.hip -- C ABI of the greedy decomposition of a query into samples of a hash set: mvs_gather,
 // mvs_ctx_gather_stats and mvs_ctx_gather_round_bytes (include/mvs_hip.h "gather").  Three phases: the original overlaps of all
-// candidates through mvs_intersect_cells as it is, the bit rows of the survivors (k_gather_mark over the units isect_plan lays
+// candidates through mvs_intersect_cells as it is, the bit rows of the survivors (k_gather_mark over the units plan_units lays
 // out), then the rounds, queued option gather_batch at a time with one read-back of the walk's state per batch.  The kernels
 // are in mvs_gather.hip.
 #include "mvs_capi_internal.h"
@@ -113,28 +113,12 @@ int mvs_gather(mvs_ctx* c, const mvs_hash_set* hs_query, int64_t query, const mv
 
     // ---- phase 1: the survivors' bit rows over the positions of Q, in the units of the intersection ----
     const int unit = std::max(64, c->opt.intersect_unit & ~63);        // a word of a row belongs to one unit
-    const size_t arr = (((size_t)ns + 1) * 8 + 255) & ~(size_t)255;
-    size_t need = 0;
-    rc = mvs::isect_plan(c->stream, d_cells, ns, hs_query->sizes.as<int32_t>(), hs_query->n, hs_db->sizes.as<int32_t>(), hs_db->n, unit,
-                         nullptr, nullptr, d_count, false, nullptr, nullptr, 0, &need);
-    if (rc) return fail(rc, "gather: scan sizing failed");
-    rc = ensure_buf(c, c->ix_work, 256 + 2 * arr + need);
-    if (rc) return rc;
-    unsigned long long* d_counters = (unsigned long long*)c->ix_work.p;
-    long long* d_units = (long long*)((char*)c->ix_work.p + 256);
-    long long* d_start = (long long*)((char*)c->ix_work.p + 256 + arr);
-    void* d_scan = (char*)c->ix_work.p + 256 + 2 * arr;
-    HIP_TRY(hipMemsetAsync(d_counters, 0, 32, c->stream));
-    rc = mvs::isect_plan(c->stream, d_cells, ns, hs_query->sizes.as<int32_t>(), hs_query->n, hs_db->sizes.as<int32_t>(), hs_db->n, unit,
-                         d_units, d_start, d_count, false, d_counters, d_scan, need, nullptr);
-    if (rc) return fail(rc, "gather: planning the units failed");
-    if ((rc = check_kernel("k_isect_count"))) return rc;
-    long long n_units = 0;
-    if ((rc = read_back(c, c->stream, {{&n_units, d_start + ns, 8}}))) return rc;
+    PlannedUnits plan;
+    if ((rc = plan_units(c, "gather", d_cells, ns, hs_query, hs_db, unit, d_count, false, nullptr, false, plan))) return rc;
     StageTimer t_mark, t_rounds;
     if ((rc = t_mark.begin(c))) return rc;
     HIP_TRY(hipMemsetAsync(d_rows, 0, row_bytes, c->stream));
-    rc = mvs::launch_gather_mark(c->stream, d_cells, ns, d_start, n_units, hs_query->hashes.as<unsigned long long>(),
+    rc = mvs::launch_gather_mark(c->stream, d_cells, ns, plan.d_start, plan.n_units, hs_query->hashes.as<unsigned long long>(),
                                  hs_query->offsets.as<long long>(), hs_query->sizes.as<int32_t>(), hs_db->hashes.as<unsigned long long>(),
                                  hs_db->offsets.as<long long>(), hs_db->sizes.as<int32_t>(), unit, d_rows, W);
     if (!rc) rc = check_kernel("k_gather_mark");

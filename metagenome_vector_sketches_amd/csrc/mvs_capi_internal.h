@@ -1,5 +1,6 @@
 // mvs_capi_internal.h -- what the translation units of the C ABI (mvs_capi*.hip) share: the context and sketch-set objects, the
-// buffer / read-back helpers, and the stages of the comparison that the streamed output and the block plans drive themselves.
+// buffer / read-back helpers, the stages of the comparison that the streamed output and the block plans drive themselves, and
+// the bodies that families of entry points share (consumers of kept cells, of dense dots, of units over sorted hash lists).
 // Not installed.
 #ifndef MVS_CAPI_INTERNAL_H
 #define MVS_CAPI_INTERNAL_H
@@ -529,6 +530,123 @@ struct DotsBlocks {
         return MVS_OK;
     }
 };
+// ---- what the consumers of units over two sorted hash lists share (mvs_intersect_cells, mvs_abund_overlap_cells, mvs_gather) ----
+// The units of n_cells device cells over two sets, planned in the context's work space: c->ix_work is grown and carved into
+// counters (256 bytes) | units per cell | their scan (n_cells + 1 entries each, rounded up to 256 bytes) | the scan's scratch,
+// isect_plan<R> fills it -- d_result as it leaves it: zero for a cell in range, mark_bad: -1 for the others -- and the figures
+// come back with ONE synchronisation of the stream.  `noun` names the caller in the messages.  ev (or NULL): two events that
+// exist when timing is on, recorded around the planning launches then.  counters = false: only n_units is read back.
+struct PlannedUnits {
+    const long long* d_start = nullptr;               // where every cell's units start, n_cells + 1 entries; valid until ix_work grows
+    long long n_units = 0;
+    unsigned long long back[3] = {0, 0, 0};           // cells out of range, cells cut into several units, sum of 8 (|A| + |B|)
+};
+template <typename R>
+int plan_units(mvs_ctx* c, const char* noun, const mvs_cell* d_cells, int64_t n_cells, const mvs_hash_set* hs_rows,
+               const mvs_hash_set* hs_cols, int unit, R* d_result, bool mark_bad, Event* ev, bool counters, PlannedUnits& plan) {
+    const size_t arr = (((size_t)n_cells + 1) * 8 + 255) & ~(size_t)255;
+    size_t need = 0;
+    int rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes.as<int32_t>(), hs_rows->n, hs_cols->sizes.as<int32_t>(),
+                             hs_cols->n, unit, nullptr, nullptr, d_result, false, nullptr, nullptr, 0, &need);
+    if (rc) return fail(rc, "%s: scan sizing failed", noun);
+    rc = ensure_buf(c, c->ix_work, 256 + 2 * arr + need);
+    if (rc) return rc;
+    unsigned long long* d_counters = (unsigned long long*)c->ix_work.p;
+    long long* d_units = (long long*)((char*)c->ix_work.p + 256);
+    long long* d_start = (long long*)((char*)c->ix_work.p + 256 + arr);
+    void* d_scan = (char*)c->ix_work.p + 256 + 2 * arr;
+    const bool timed = ev && c->timing;
+    if (timed) HIP_TRY(hipEventRecord(ev[0], c->stream));
+    HIP_TRY(hipMemsetAsync(d_counters, 0, 32, c->stream));
+    rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes.as<int32_t>(), hs_rows->n, hs_cols->sizes.as<int32_t>(), hs_cols->n,
+                         unit, d_units, d_start, d_result, mark_bad, d_counters, d_scan, need, nullptr);
+    if (rc) return fail(rc, "%s: planning the units failed", noun);
+    rc = check_kernel("k_isect_count");
+    if (rc) return rc;
+    if (timed) HIP_TRY(hipEventRecord(ev[1], c->stream));
+    plan.d_start = d_start;
+    return read_back(c, c->stream, {{plan.back, d_counters, counters ? sizeof(plan.back) : 0}, {&plan.n_units, d_start + n_cells, 8}});
+}
+
+// The body of mvs_intersect_cells (R = int32_t) and mvs_abund_overlap_cells (R = mvs_abund_overlap): the checks, cells and results
+// staged on the device where they are the host's, the plan, launch(d_cells, plan, d_out) -- the caller's units kernel --, the
+// download, which leaves the entries of cells out of range what the caller had there, and the statistics of
+// mvs_ctx_intersect_stats.
+struct CellsTexts {
+    const char *entry, *noun, *results, *out_name, *kernel;   // "mvs_intersect_cells", "intersect", "counts", "inter", "k_isect_units"
+};
+inline bool answered(int32_t r) { return r >= 0; }
+inline bool answered(const mvs_abund_overlap& r) { return r.inter >= 0; }
+template <typename R, typename Launch>
+int cells_over_units(mvs_ctx* c, const CellsTexts& txt, const mvs_hash_set* hs_rows, const mvs_hash_set* hs_cols, const mvs_cell* cells,
+                     int mem_cells, int64_t n_cells, R* out, int mem_out, Launch&& launch) {
+    if (!c || !hs_rows) return fail(MVS_E_INVALID, "NULL argument");
+    if (!hs_cols) hs_cols = hs_rows;
+    if (!mem_ok(mem_cells) || !mem_ok(mem_out)) return fail(MVS_E_INVALID, "bad argument");
+    if (n_cells < 0) return fail(MVS_E_INVALID, "n_cells = %lld is negative", (long long)n_cells);
+    if (n_cells >= (1LL << 40)) return fail(MVS_E_RANGE, "n_cells too large");
+    if (hs_rows->ctx != c || hs_cols->ctx != c) return fail(MVS_E_INVALID, "a hash set belongs to another context");
+    c->ix_kernel_ms = 0.0;
+    c->ix_units = c->ix_cut = c->ix_bytes = 0;
+    if (n_cells == 0) return MVS_OK;
+    if (!cells || !out) return fail(MVS_E_INVALID, "cells or %s is NULL", txt.out_name);
+    HIP_TRY(hipSetDevice(c->device));
+    const Range range(c, txt.entry);
+
+    DevBuf dcells, dout;
+    const mvs_cell* d_cells = cells;
+    if (mem_cells == MVS_MEM_HOST) {
+        if (dcells.alloc((size_t)n_cells * sizeof(mvs_cell)) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %lld cells failed", (long long)n_cells);
+        HIP_TRY(hipMemcpyAsync(dcells.p, cells, (size_t)n_cells * sizeof(mvs_cell), hipMemcpyHostToDevice, c->stream));
+        d_cells = (const mvs_cell*)dcells.p;
+    }
+    R* d_out = out;
+    if (mem_out == MVS_MEM_HOST) {
+        if (dout.alloc((size_t)n_cells * sizeof(R)) != hipSuccess)
+            return fail(MVS_E_NOMEM, "hipMalloc of %lld %s failed", (long long)n_cells, txt.results);
+        d_out = (R*)dout.p;
+    }
+    Event ev[4];                                      // around the plan, around the units
+    if (c->timing)
+        for (Event& x : ev) HIP_TRY(x.create());
+    PlannedUnits plan;
+    int rc = plan_units(c, txt.noun, d_cells, n_cells, hs_rows, hs_cols, c->opt.intersect_unit, d_out, mem_out == MVS_MEM_HOST, ev, true, plan);
+    if (rc) return rc;
+    if (c->timing) HIP_TRY(hipEventRecord(ev[2], c->stream));
+    rc = launch(d_cells, plan, d_out);
+    if (!rc) rc = check_kernel(txt.kernel);
+    if (rc) return rc;
+    if (c->timing) HIP_TRY(hipEventRecord(ev[3], c->stream));
+    if (mem_out == MVS_MEM_HOST) {
+        if (plan.back[0] == 0) {
+            HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n_cells * sizeof(R), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        } else {
+            // the entries of the cells out of range (count -1 on the device) stay what the caller had there
+            std::vector<R> tmp((size_t)n_cells);
+            HIP_TRY(hipMemcpyAsync(tmp.data(), d_out, (size_t)n_cells * sizeof(R), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (int64_t i = 0; i < n_cells; ++i)
+                if (answered(tmp[(size_t)i])) out[i] = tmp[(size_t)i];
+        }
+    } else {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (c->timing) {
+        float a = 0.f, b = 0.f;
+        HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+        HIP_TRY(hipEventElapsedTime(&b, ev[2], ev[3]));
+        c->ix_kernel_ms = (double)a + (double)b;
+    }
+    c->ix_units = plan.n_units;
+    c->ix_cut = (long long)plan.back[1];
+    c->ix_bytes = (long long)plan.back[2];
+    if (plan.back[0] != 0)
+        return fail(MVS_E_RANGE, "%llu cells name a sample outside the sets (%lld rows, %lld columns): they were not answered", plan.back[0],
+                    (long long)hs_rows->n, (long long)hs_cols->n);
+    return MVS_OK;
+}
+
 // the body of mvs_ctx_topk_stats / _contain_stats / _levels_stats
 int dots_stats_out(const mvs_ctx* c, DotsStats mvs_ctx::*which, double* dots_ms, double* work_ms, int64_t* row_blocks, int64_t* block_rows);
 // ---- mvs_capi_pca.hip: the eigensolver the ordinations share (mvs_pca_fit, mvs_pcoa_fit) ----

@@ -1,7 +1,8 @@
 // mvs_capi_intersect.hip -- C ABI of the exact hash-set intersections: mvs_hash_set_create / _info / _sizes / _destroy (a
 // resident, per-sample sorted and de-duplicated copy of hash lists), mvs_intersect_cells (|H(row) n H(col)| for every cell of a
 // list, whoever produced it) and mvs_ctx_intersect_stats.  The kernels and the layout of the units of work are in
-// mvs_intersect.hip.  With device cells and device counts nothing but a few counters crosses the link.
+// mvs_intersect.hip; the body of the cell-list call is cells_over_units (mvs_capi_internal.h), which mvs_abund_overlap_cells
+// shares.  With device cells and device counts nothing but a few counters crosses the link.
 #include "mvs_capi_internal.h"
 
 #include <hip/hip_runtime.h>
@@ -176,95 +177,15 @@ int mvs_hash_set_destroy(mvs_hash_set* h) {
 
 int mvs_intersect_cells(mvs_ctx* c, const mvs_hash_set* hs_rows, const mvs_hash_set* hs_cols, const mvs_cell* cells, int mem_cells,
                         int64_t n_cells, int32_t* inter, int mem_out) {
-    if (!c || !hs_rows) return fail(MVS_E_INVALID, "NULL argument");
-    if (!hs_cols) hs_cols = hs_rows;
-    if (!mem_ok(mem_cells) || !mem_ok(mem_out)) return fail(MVS_E_INVALID, "bad argument");
-    if (n_cells < 0) return fail(MVS_E_INVALID, "n_cells = %lld is negative", (long long)n_cells);
-    if (n_cells >= (1LL << 40)) return fail(MVS_E_RANGE, "n_cells too large");
-    if (hs_rows->ctx != c || hs_cols->ctx != c) return fail(MVS_E_INVALID, "a hash set belongs to another context");
-    c->ix_kernel_ms = 0.0;
-    c->ix_units = c->ix_cut = c->ix_bytes = 0;
-    if (n_cells == 0) return MVS_OK;
-    if (!cells || !inter) return fail(MVS_E_INVALID, "cells or inter is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    const Range range(c, "mvs_intersect_cells");
-
-    DevBuf dcells, dinter;
-    const mvs_cell* d_cells = cells;
-    if (mem_cells == MVS_MEM_HOST) {
-        if (dcells.alloc((size_t)n_cells * sizeof(mvs_cell)) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %lld cells failed", (long long)n_cells);
-        HIP_TRY(hipMemcpyAsync(dcells.p, cells, (size_t)n_cells * sizeof(mvs_cell), hipMemcpyHostToDevice, c->stream));
-        d_cells = (const mvs_cell*)dcells.p;
-    }
-    int32_t* d_inter = inter;
-    if (mem_out == MVS_MEM_HOST) {
-        if (dinter.alloc((size_t)n_cells * 4) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %lld counts failed", (long long)n_cells);
-        d_inter = (int32_t*)dinter.p;
-    }
-    // work space: counters | units per cell | their scan | the scan's scratch
-    const size_t arr = (((size_t)n_cells + 1) * 8 + 255) & ~(size_t)255;
-    size_t need = 0;
-    int rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes.as<int32_t>(), hs_rows->n, hs_cols->sizes.as<int32_t>(),
-                             hs_cols->n, c->opt.intersect_unit, nullptr, nullptr, d_inter, false, nullptr, nullptr, 0, &need);
-    if (rc) return fail(rc, "intersect: scan sizing failed");
-    rc = ensure_buf(c, c->ix_work, 256 + 2 * arr + need);
-    if (rc) return rc;
-    unsigned long long* d_counters = (unsigned long long*)c->ix_work.p;
-    long long* d_units = (long long*)((char*)c->ix_work.p + 256);
-    long long* d_start = (long long*)((char*)c->ix_work.p + 256 + arr);
-    void* d_scan = (char*)c->ix_work.p + 256 + 2 * arr;
-
-    Event ev[4];
-    if (c->timing) {
-        for (Event& x : ev) HIP_TRY(x.create());
-        HIP_TRY(hipEventRecord(ev[0], c->stream));
-    }
-    HIP_TRY(hipMemsetAsync(d_counters, 0, 32, c->stream));
-    rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes.as<int32_t>(), hs_rows->n, hs_cols->sizes.as<int32_t>(), hs_cols->n,
-                         c->opt.intersect_unit, d_units, d_start, d_inter, mem_out == MVS_MEM_HOST, d_counters, d_scan, need, nullptr);
-    if (rc) return fail(rc, "intersect: planning the units failed");
-    rc = check_kernel("k_isect_count");
-    if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev[1], c->stream));
-    unsigned long long back[3] = {0, 0, 0};
-    long long n_units = 0;
-    rc = read_back(c, c->stream, {{back, d_counters, sizeof(back)}, {&n_units, d_start + n_cells, 8}});
-    if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev[2], c->stream));
-    rc = mvs::launch_isect_units(c->stream, d_cells, n_cells, d_start, n_units, hs_rows->hashes.as<unsigned long long>(),
-                                 hs_rows->offsets.as<long long>(), hs_rows->sizes.as<int32_t>(), hs_cols->hashes.as<unsigned long long>(),
-                                 hs_cols->offsets.as<long long>(), hs_cols->sizes.as<int32_t>(), c->opt.intersect_unit, d_inter);
-    if (!rc) rc = check_kernel("k_isect_units");
-    if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev[3], c->stream));
-    if (mem_out == MVS_MEM_HOST) {
-        if (back[0] == 0) {
-            HIP_TRY(hipMemcpyAsync(inter, d_inter, (size_t)n_cells * 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        } else {
-            // the entries of the cells out of range (marked -1 on the device) stay what the caller had there
-            std::vector<int32_t> tmp((size_t)n_cells);
-            HIP_TRY(hipMemcpyAsync(tmp.data(), d_inter, (size_t)n_cells * 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            for (int64_t i = 0; i < n_cells; ++i)
-                if (tmp[(size_t)i] >= 0) inter[i] = tmp[(size_t)i];
-        }
-    } else {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    if (c->timing) {
-        float a = 0.f, b = 0.f;
-        HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&b, ev[2], ev[3]));
-        c->ix_kernel_ms = (double)a + (double)b;
-    }
-    c->ix_units = n_units;
-    c->ix_cut = (long long)back[1];
-    c->ix_bytes = (long long)back[2];
-    if (back[0] != 0)
-        return fail(MVS_E_RANGE, "%llu cells name a sample outside the sets (%lld rows, %lld columns): they were not answered", back[0],
-                    (long long)hs_rows->n, (long long)hs_cols->n);
-    return MVS_OK;
+    const mvs_hash_set* hc = hs_cols ? hs_cols : hs_rows;
+    return cells_over_units(c, {"mvs_intersect_cells", "intersect", "counts", "inter", "k_isect_units"}, hs_rows, hs_cols, cells, mem_cells,
+                            n_cells, inter, mem_out, [&](const mvs_cell* d_cells, const PlannedUnits& plan, int32_t* d_inter) {
+                                return mvs::launch_isect_units(c->stream, d_cells, n_cells, plan.d_start, plan.n_units,
+                                                               hs_rows->hashes.as<unsigned long long>(), hs_rows->offsets.as<long long>(),
+                                                               hs_rows->sizes.as<int32_t>(), hc->hashes.as<unsigned long long>(),
+                                                               hc->offsets.as<long long>(), hc->sizes.as<int32_t>(),
+                                                               c->opt.intersect_unit, d_inter);
+                            });
 }
 
 int mvs_ctx_intersect_stats(const mvs_ctx* c, double* kernel_ms, int64_t* units, int64_t* cut_pairs, int64_t* bytes) {

@@ -1,7 +1,7 @@
 // mvs_capi_overlap.hip -- C ABI of the abundance-weighted overlaps: mvs_abund_overlap_cells (the six integer sums of every cell
 // of a list), mvs_hash_set_abundance_totals (the per-sample totals they are set against) and mvs_abund_similarity (pure host:
-// the derived measures, one rounding per line).  The kernels are in mvs_overlap.hip; the plan of the units of work and the
-// context's work space are those of mvs_intersect_cells (mvs_capi_intersect.hip), whose statistics this call also leaves.
+// the derived measures, one rounding per line).  The kernels are in mvs_overlap.hip; the body of the cell-list call is the one
+// mvs_intersect_cells has (cells_over_units, mvs_capi_internal.h), so it leaves that call's statistics too.
 #include "mvs_capi_internal.h"
 
 #include <cmath>
@@ -16,97 +16,16 @@ extern "C" {
 
 int mvs_abund_overlap_cells(mvs_ctx* c, const mvs_hash_set* hs_rows, const mvs_hash_set* hs_cols, const mvs_cell* cells, int mem_cells,
                             int64_t n_cells, mvs_abund_overlap* out, int mem_out) {
-    if (!c || !hs_rows) return fail(MVS_E_INVALID, "NULL argument");
-    if (!hs_cols) hs_cols = hs_rows;
-    if (!mem_ok(mem_cells) || !mem_ok(mem_out)) return fail(MVS_E_INVALID, "bad argument");
-    if (n_cells < 0) return fail(MVS_E_INVALID, "n_cells = %lld is negative", (long long)n_cells);
-    if (n_cells >= (1LL << 40)) return fail(MVS_E_RANGE, "n_cells too large");
-    if (hs_rows->ctx != c || hs_cols->ctx != c) return fail(MVS_E_INVALID, "a hash set belongs to another context");
-    c->ix_kernel_ms = 0.0;
-    c->ix_units = c->ix_cut = c->ix_bytes = 0;
-    if (n_cells == 0) return MVS_OK;
-    if (!cells || !out) return fail(MVS_E_INVALID, "cells or out is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    const Range range(c, "mvs_abund_overlap_cells");
-
-    DevBuf dcells, dout;
-    const mvs_cell* d_cells = cells;
-    if (mem_cells == MVS_MEM_HOST) {
-        if (dcells.alloc((size_t)n_cells * sizeof(mvs_cell)) != hipSuccess) return fail(MVS_E_NOMEM, "hipMalloc of %lld cells failed", (long long)n_cells);
-        HIP_TRY(hipMemcpyAsync(dcells.p, cells, (size_t)n_cells * sizeof(mvs_cell), hipMemcpyHostToDevice, c->stream));
-        d_cells = (const mvs_cell*)dcells.p;
-    }
-    mvs_abund_overlap* d_out = out;
-    if (mem_out == MVS_MEM_HOST) {
-        if (dout.alloc((size_t)n_cells * sizeof(mvs_abund_overlap)) != hipSuccess)
-            return fail(MVS_E_NOMEM, "hipMalloc of %lld records failed", (long long)n_cells);
-        d_out = (mvs_abund_overlap*)dout.p;
-    }
-    // work space: counters | units per cell | their scan | the scan's scratch
-    const size_t arr = (((size_t)n_cells + 1) * 8 + 255) & ~(size_t)255;
-    size_t need = 0;
-    int rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes.as<int32_t>(), hs_rows->n, hs_cols->sizes.as<int32_t>(),
-                             hs_cols->n, c->opt.intersect_unit, nullptr, nullptr, d_out, false, nullptr, nullptr, 0, &need);
-    if (rc) return fail(rc, "overlap: scan sizing failed");
-    rc = ensure_buf(c, c->ix_work, 256 + 2 * arr + need);
-    if (rc) return rc;
-    unsigned long long* d_counters = (unsigned long long*)c->ix_work.p;
-    long long* d_units = (long long*)((char*)c->ix_work.p + 256);
-    long long* d_start = (long long*)((char*)c->ix_work.p + 256 + arr);
-    void* d_scan = (char*)c->ix_work.p + 256 + 2 * arr;
-
-    Event ev[4];
-    if (c->timing) {
-        for (Event& x : ev) HIP_TRY(x.create());
-        HIP_TRY(hipEventRecord(ev[0], c->stream));
-    }
-    HIP_TRY(hipMemsetAsync(d_counters, 0, 32, c->stream));
-    rc = mvs::isect_plan(c->stream, d_cells, n_cells, hs_rows->sizes.as<int32_t>(), hs_rows->n, hs_cols->sizes.as<int32_t>(), hs_cols->n,
-                         c->opt.intersect_unit, d_units, d_start, d_out, mem_out == MVS_MEM_HOST, d_counters, d_scan, need, nullptr);
-    if (rc) return fail(rc, "overlap: planning the units failed");
-    rc = check_kernel("k_isect_count");
-    if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev[1], c->stream));
-    unsigned long long back[3] = {0, 0, 0};
-    long long n_units = 0;
-    rc = read_back(c, c->stream, {{back, d_counters, sizeof(back)}, {&n_units, d_start + n_cells, 8}});
-    if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev[2], c->stream));
-    rc = mvs::launch_overlap_units(c->stream, d_cells, n_cells, d_start, n_units, hs_rows->hashes.as<unsigned long long>(),
-                                   hs_rows->offsets.as<long long>(), hs_rows->sizes.as<int32_t>(), hs_rows->abund.as<uint32_t>(),
-                                   hs_cols->hashes.as<unsigned long long>(), hs_cols->offsets.as<long long>(),
-                                   hs_cols->sizes.as<int32_t>(), hs_cols->abund.as<uint32_t>(), c->opt.intersect_unit, d_out);
-    if (!rc) rc = check_kernel("k_overlap_units");
-    if (rc) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(ev[3], c->stream));
-    if (mem_out == MVS_MEM_HOST) {
-        if (back[0] == 0) {
-            HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n_cells * sizeof(mvs_abund_overlap), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        } else {
-            // the records of the cells out of range (inter = -1 on the device) stay what the caller had there
-            std::vector<mvs_abund_overlap> tmp((size_t)n_cells);
-            HIP_TRY(hipMemcpyAsync(tmp.data(), d_out, (size_t)n_cells * sizeof(mvs_abund_overlap), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            for (int64_t i = 0; i < n_cells; ++i)
-                if (tmp[(size_t)i].inter >= 0) out[i] = tmp[(size_t)i];
-        }
-    } else {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    if (c->timing) {
-        float a = 0.f, b = 0.f;
-        HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&b, ev[2], ev[3]));
-        c->ix_kernel_ms = (double)a + (double)b;
-    }
-    c->ix_units = n_units;
-    c->ix_cut = (long long)back[1];
-    c->ix_bytes = (long long)back[2];
-    if (back[0] != 0)
-        return fail(MVS_E_RANGE, "%llu cells name a sample outside the sets (%lld rows, %lld columns): they were not answered", back[0],
-                    (long long)hs_rows->n, (long long)hs_cols->n);
-    return MVS_OK;
+    const mvs_hash_set* hc = hs_cols ? hs_cols : hs_rows;
+    return cells_over_units(c, {"mvs_abund_overlap_cells", "overlap", "records", "out", "k_overlap_units"}, hs_rows, hs_cols, cells, mem_cells,
+                            n_cells, out, mem_out, [&](const mvs_cell* d_cells, const PlannedUnits& plan, mvs_abund_overlap* d_out) {
+                                return mvs::launch_overlap_units(c->stream, d_cells, n_cells, plan.d_start, plan.n_units,
+                                                                 hs_rows->hashes.as<unsigned long long>(), hs_rows->offsets.as<long long>(),
+                                                                 hs_rows->sizes.as<int32_t>(), hs_rows->abund.as<uint32_t>(),
+                                                                 hc->hashes.as<unsigned long long>(), hc->offsets.as<long long>(),
+                                                                 hc->sizes.as<int32_t>(), hc->abund.as<uint32_t>(), c->opt.intersect_unit,
+                                                                 d_out);
+                            });
 }
 
 int mvs_hash_set_abundance_totals(const mvs_hash_set* h, uint64_t* sum, uint64_t* sumsq_lo, uint64_t* sumsq_hi, int mem_out) {

@@ -6,9 +6,8 @@
 //
 //   k_gather_mark   once, for every surviving candidate s (those whose overlap with the whole query reaches min_hashes: the
 //                   intersection kernel of mvs_intersect.hip counted it): a bit row over the query's positions, W = ceil(|Q| / 64)
-//                   words, bit p set iff Q[p] is in H(s).  The units of work are those of mvs_intersect.hip -- a chunk of the
-//                   shorter list against the window of the longer one it can match, one wave each, the window staged in LDS
-//                   tile by tile or, when it is more than kSkew times the chunk, searched where it lies -- and a match sets a
+//                   words, bit p set iff Q[p] is in H(s).  The units of work are those of mvs_intersect.hip and so is the walk
+//                   (unit_of and walk_unit<true> of mvs_intersect_dev.h: every lane reaches the sink on every trip); a match sets a
 //                   bit instead of adding one.  Where the query is the chunked side the 64 lanes cover 64 consecutive
 //                   positions of a word that belongs to this unit alone (the unit size is a multiple of 64): the ballot is
 //                   the word, lane 0 ORs it in with a plain load and store.  Where the candidate is the chunked side every
@@ -38,11 +37,6 @@ constexpr int kGaThreads = 256;
 constexpr int kGaWaves = kGaThreads / 64;
 constexpr int kGaSlice = 2048;                 // words of a row that one wave counts (16 KiB: 32 loads per lane)
 
-unsigned ga_grid(int64_t items, int per_block) {
-    const int64_t blocks = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, 1 << 20));
-}
-
 // alive: ones for the positions [0, q_size); retired: nobody; counts: zero; state: nothing found yet
 __global__ __launch_bounds__(kGaThreads) void k_gather_init(unsigned long long* __restrict__ alive, int64_t W, int32_t q_size,
                                                            int32_t* __restrict__ retired, int32_t* __restrict__ count, int64_t ns,
@@ -67,15 +61,15 @@ __global__ __launch_bounds__(kGaThreads) void k_gather_init(unsigned long long* 
     }
 }
 
-// positions [base, base + 64) of the query when it is the chunked side (lane = position - base, the word is this unit's alone),
-// else the position `pos` this lane found for its element
-__device__ __forceinline__ void mark_hits(unsigned long long* __restrict__ row, bool q_chunked, bool hit, int32_t base, int32_t pos,
-                                          int lane) {
+// what the walk found for position x of the chunked list, which the value shares with position y of the other one if hit.  The
+// query chunked: the lanes of a trip stand at 64 consecutive positions of it, lane 0 at a multiple of 64 -- the ballot is the word,
+// which is this unit's alone.  Else y is the bit.
+__device__ __forceinline__ void mark_hits(unsigned long long* __restrict__ row, bool q_chunked, bool hit, int32_t x, int32_t y, int lane) {
     if (q_chunked) {
         const unsigned long long m = __ballot(hit);
-        if (lane == 0 && m) row[base >> 6] |= m;
+        if (lane == 0 && m) row[x >> 6] |= m;
     } else if (hit) {
-        atomicOr(row + (pos >> 6), 1ULL << (pos & 63));
+        atomicOr(row + (y >> 6), 1ULL << (y & 63));
     }
 }
 
@@ -93,66 +87,10 @@ __global__ __launch_bounds__(kIxThreads) void k_gather_mark(const mvs_cell* __re
     unsigned long long* tile = tiles[wave];
     const long long n_waves = (long long)gridDim.x * kIxWaves;
     for (long long u = (long long)blockIdx.x * kIxWaves + wave; u < n_units; u += n_waves) {
-        const int64_t cell = wave_bound<long long, int64_t>(unit_start, 0, n_cells + 1, u, true, lane) - 1;
-        const int32_t q = cells[cell].row, c = cells[cell].col;
-        const int32_t lq = size_q[q], lc = size_d[c];
-        const bool q_chunked = lq <= lc;                               // the rule of k_isect_count: the shorter list is cut
-        const unsigned long long* A = q_chunked ? hash_q + off_q[q] : hash_d + off_d[c];
-        const unsigned long long* B = q_chunked ? hash_d + off_d[c] : hash_q + off_q[q];
-        const int32_t la = q_chunked ? lq : lc, lb = q_chunked ? lc : lq;
-        unsigned long long* row = rows + cell * W;
-        const long long chunk = u - unit_start[cell];
-        const int32_t a0 = (int32_t)(chunk * unit);                    // a multiple of 64
-        const int32_t a1 = (int32_t)(((long long)a0 + unit < la) ? (long long)a0 + unit : la);   // a0 < a1 <= la
-        const int32_t w0 = wave_bound<unsigned long long, int32_t>(B, 0, lb, A[a0], false, lane);
-        const int32_t w1 = wave_bound<unsigned long long, int32_t>(B, w0, lb, A[a1 - 1], true, lane);
-        if ((long long)(w1 - w0) > (long long)kSkew * (a1 - a0)) {
-            // a long window for a few elements: search it where it lies
-            for (int32_t base = a0; base < a1; base += 64) {           // (every lane makes every trip: the ballot is whole)
-                const int32_t a = base + lane;
-                bool hit = false;
-                int32_t l = w0;
-                if (a < a1) {
-                    const unsigned long long key = A[a];
-                    int32_t h = w1;
-                    while (l < h) {
-                        const int32_t mid = l + ((h - l) >> 1);
-                        if (B[mid] < key) l = mid + 1;
-                        else h = mid;
-                    }
-                    hit = l < w1 && B[l] == key;
-                }
-                mark_hits(row, q_chunked, hit, base, q_chunked ? a : l, lane);
-            }
-        } else {
-            int32_t a = a0;                                            // elements of the chunk before a are settled
-            for (int32_t t0 = w0; t0 < w1 && a < a1; t0 += kTile) {
-                const int tn = (w1 - t0 < kTile) ? (w1 - t0) : kTile;
-                for (int j = lane; j < tn; j += 64) tile[j] = B[t0 + j];
-                wave_lds_sync();
-                // the chunk's elements up to the tile's last one can only match inside this tile
-                const int32_t ae = wave_bound<unsigned long long, int32_t>(A, a, a1, tile[tn - 1], true, lane);
-                // groups of 64 on the grid of a0: a group that straddles two tiles is visited by both, each with its own elements
-                for (int32_t base = a0 + ((a - a0) & ~63); base < ae; base += 64) {
-                    const int32_t x = base + lane;
-                    bool hit = false;
-                    int l = 0;
-                    if (x >= a && x < ae) {
-                        const unsigned long long key = A[x];
-                        int h = tn;
-                        while (l < h) {
-                            const int mid = (l + h) >> 1;
-                            if (tile[mid] < key) l = mid + 1;
-                            else h = mid;
-                        }
-                        hit = l < tn && tile[l] == key;
-                    }
-                    mark_hits(row, q_chunked, hit, base, q_chunked ? x : t0 + l, lane);
-                }
-                a = ae;
-                wave_lds_sync();                                       // the next tile overwrites what the lanes just read
-            }
-        }
+        // the query is the row of every cell: where it is the shorter list it is the chunked side (a0 is a multiple of 64)
+        const IxUnit n = unit_of(cells, n_cells, unit_start, u, hash_q, off_q, size_q, hash_d, off_d, size_d, unit, lane);
+        unsigned long long* row = rows + n.cell * W;
+        walk_unit<true>(n, tile, lane, [&](int32_t x, int32_t y, bool hit) { mark_hits(row, n.row_short, hit, x, y, lane); });
     }
 }
 
@@ -176,7 +114,7 @@ __global__ __launch_bounds__(kGaThreads) void k_gather_count(const unsigned long
         int sum = 0;
 #pragma unroll 4
         for (int64_t w = w0 + lane; w < w1; w += 64) sum += __popcll(row[w] & alive[w]);
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        sum = wave_sum(sum);
         if (lane == 0 && sum) atomicAdd(count + s, sum);
     }
 }
@@ -249,7 +187,7 @@ __global__ __launch_bounds__(kGaThreads) void k_gather_pick(const unsigned long 
 
 int launch_gather_init(hipStream_t stream, unsigned long long* d_alive, int64_t W, int32_t q_size, int32_t* d_retired, int32_t* d_count,
                        int64_t ns, GatherState* d_state) {
-    hipLaunchKernelGGL(k_gather_init, dim3(ga_grid(std::max(W, ns), kGaThreads)), dim3(kGaThreads), 0, stream, d_alive, W, q_size,
+    hipLaunchKernelGGL(k_gather_init, dim3(ix_grid(std::max(W, ns), kGaThreads)), dim3(kGaThreads), 0, stream, d_alive, W, q_size,
                        d_retired, d_count, ns, d_state);
     return 0;
 }
@@ -259,7 +197,7 @@ int launch_gather_mark(hipStream_t stream, const mvs_cell* d_cells, int64_t n_ce
                        const unsigned long long* d_hash_d, const long long* d_off_d, const int32_t* d_size_d, int unit,
                        unsigned long long* d_rows, int64_t W) {
     if (n_units <= 0) return 0;
-    hipLaunchKernelGGL(k_gather_mark, dim3(ga_grid(n_units, kIxWaves)), dim3(kIxThreads), 0, stream, d_cells, n_cells, d_unit_start,
+    hipLaunchKernelGGL(k_gather_mark, dim3(ix_grid(n_units, kIxWaves)), dim3(kIxThreads), 0, stream, d_cells, n_cells, d_unit_start,
                        n_units, d_hash_q, d_off_q, d_size_q, d_hash_d, d_off_d, d_size_d, unit, d_rows, W);
     return 0;
 }
@@ -268,11 +206,11 @@ int launch_gather_round(hipStream_t stream, const unsigned long long* d_rows, in
                         int32_t* d_retired, int32_t min_hashes, int32_t* d_count, const int32_t* d_surv_sample,
                         const int32_t* d_surv_orig, mvs_gather_match* d_rec, int64_t max_matches, GatherState* d_state, int parity) {
     const int64_t n_slices = (W + kGaSlice - 1) / kGaSlice;
-    hipLaunchKernelGGL(k_gather_count, dim3(ga_grid(ns * n_slices, kGaWaves)), dim3(kGaThreads), 0, stream, d_rows, W, ns, n_slices,
+    hipLaunchKernelGGL(k_gather_count, dim3(ix_grid(ns * n_slices, kGaWaves)), dim3(kGaThreads), 0, stream, d_rows, W, ns, n_slices,
                        d_alive, d_retired, d_count, d_state);
-    hipLaunchKernelGGL(k_gather_bid, dim3(ga_grid(ns, kGaThreads)), dim3(kGaThreads), 0, stream, ns, d_retired, min_hashes, d_count,
+    hipLaunchKernelGGL(k_gather_bid, dim3(ix_grid(ns, kGaThreads)), dim3(kGaThreads), 0, stream, ns, d_retired, min_hashes, d_count,
                        d_state, parity);
-    hipLaunchKernelGGL(k_gather_pick, dim3(ga_grid(W, 4 * kGaThreads)), dim3(kGaThreads), 0, stream, d_rows, W, d_alive, d_retired,
+    hipLaunchKernelGGL(k_gather_pick, dim3(ix_grid(W, 4 * kGaThreads)), dim3(kGaThreads), 0, stream, d_rows, W, d_alive, d_retired,
                        d_surv_sample, d_surv_orig, d_rec, max_matches, d_state, parity);
     return 0;
 }

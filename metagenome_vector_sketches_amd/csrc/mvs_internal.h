@@ -489,9 +489,11 @@ int launch_plan_verdict(hipStream_t stream, unsigned long long* d_counter, unsig
                         int tile_cap, bool tiles_skipped);
 // exact hash-set intersections (mvs_intersect.hip).  Building a set: is every sample's list strictly increasing (*d_flag = 1
 // if not), a segmented sort of up to 2^32 - 1 keys (offsets relative to d_in), distinct values per sample of sorted lists, and
-// their compaction.  Intersecting: isect_plan zeroes inter[] for the cells in range (mark_bad: writes -1 for the others),
-// counts the units of every cell and scans them (d_units, d_unit_start: n_cells + 1 entries; d_counters: [0] cells out of
-// range, [1] cells cut into several units, [2] sum of 8 (|A| + |B|)); launch_isect_units gives every unit to one wave.
+// their compaction.  Intersecting: isect_plan<R> zeroes the result of every cell in range (R = int32_t: the count; R =
+// mvs_abund_overlap: the whole record; mark_bad: the count of the others becomes -1), counts the units of every cell and scans
+// them (d_units, d_unit_start: n_cells + 1 entries; d_counters: [0] cells out of range, [1] cells cut into several units, [2] sum
+// of 8 (|A| + |B|)); d_scratch == NULL: *scratch_needed only.  launch_isect_units gives every unit to one wave, which decodes it
+// and walks it with the code of mvs_intersect_dev.h, as the units kernels of mvs_overlap.hip and mvs_gather.hip do.
 int launch_hs_check(hipStream_t stream, const unsigned long long* d_hashes, const long long* d_offsets, int64_t n,
                     unsigned int* d_flag);
 int hs_sort_segments(hipStream_t stream, const unsigned long long* d_in, unsigned long long* d_out, unsigned int count,
@@ -500,20 +502,18 @@ int hs_sort_segments(hipStream_t stream, const unsigned long long* d_in, unsigne
 int launch_hs_count(hipStream_t stream, const unsigned long long* d_sorted, const long long* d_offsets, int64_t n, int32_t* d_sizes);
 int launch_hs_compact(hipStream_t stream, const unsigned long long* d_sorted, const long long* d_offsets, const long long* d_new_offsets,
                       int64_t n, unsigned long long* d_out);
+template <typename R>
 int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
-               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, int32_t* d_inter,
+               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, R* d_inter,
                bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed);
 int launch_isect_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const long long* d_unit_start, long long n_units,
                        const unsigned long long* d_hash_r, const long long* d_off_r, const int32_t* d_size_r,
                        const unsigned long long* d_hash_c, const long long* d_off_c, const int32_t* d_size_c, int unit,
                        int32_t* d_inter);
-// abundance-weighted overlaps (mvs_overlap.hip).  The plan is isect_plan's with whole records (every field of a cell in range is
-// zeroed; mark_bad: inter = -1 for the others); launch_overlap_units gives every unit to one wave as launch_isect_units does and
-// adds the unit's count and five sums to the cell's record.  d_ab_r / d_ab_c: uint32 abundances aligned with the hashes, or
-// NULL = 1 for every value of that side.  launch_abund_totals: S, Q mod 2^32 summed, Q / 2^32 summed per sample (any output NULL).
-int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
-               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, mvs_abund_overlap* d_out,
-               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed);
+// abundance-weighted overlaps (mvs_overlap.hip).  The plan is isect_plan<mvs_abund_overlap>; launch_overlap_units gives every unit
+// to one wave as launch_isect_units does and adds the unit's count and five sums to the cell's record.  d_ab_r / d_ab_c: uint32
+// abundances aligned with the hashes, or NULL = 1 for every value of that side.  launch_abund_totals: S, Q mod 2^32 summed,
+// Q / 2^32 summed per sample (any output NULL).
 int launch_overlap_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const long long* d_unit_start, long long n_units,
                          const unsigned long long* d_hash_r, const long long* d_off_r, const int32_t* d_size_r, const uint32_t* d_ab_r,
                          const unsigned long long* d_hash_c, const long long* d_off_c, const int32_t* d_size_c, const uint32_t* d_ab_c,

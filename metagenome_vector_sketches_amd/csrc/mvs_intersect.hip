@@ -14,7 +14,9 @@
 // the two lists and B the longer, a unit is (cell, chunk c of A): elements [c * U, min(|A|, (c + 1) * U)) of A against all of
 // B (U = option intersect_unit).  k_isect_count writes ceil(|A| / U) per cell (0 for an empty list or a cell out of range),
 // an exclusive scan of those numbers lays the units of all cells out in cell order -- so consecutive units share the row's
-// list while it is in the L2 / Infinity Cache -- and k_isect_units gives every unit to ONE wave:
+// list while it is in the L2 / Infinity Cache -- and k_isect_units gives every unit to ONE wave.  Steps 1 and 2 are unit_of and
+// step 3 is walk_unit of mvs_intersect_dev.h, which k_overlap_units (mvs_overlap.hip) and k_gather_mark (mvs_gather.hip) call
+// too; step 4 is this kernel's own:
 //   1. the unit's cell: upper bound of the unit index in the scanned array, as a 64-ary search (each lane probes one of 64
 //      splitters and a ballot picks the interval: 3 rounds for 2^18 entries instead of 18 dependent loads);
 //   2. B's window for the chunk: lower bound of the chunk's first element, upper bound of its last, the same search;
@@ -30,7 +32,7 @@
 // inter[] is zeroed by k_isect_count, a launch of its own in front of k_isect_units, for every cell in range; a cell out of
 // range is never written.
 #include "mvs_internal.h"
-#include "mvs_intersect_dev.h"   // unit geometry (kIxThreads, kTile, kSkew) and wave_bound, shared with mvs_gather.hip
+#include "mvs_intersect_dev.h"   // unit geometry (kIxThreads, kTile, kSkew), unit_of, walk_unit, wave_sum, ix_grid
 
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -40,7 +42,7 @@ namespace mvs {
 namespace {
 
 __device__ __forceinline__ void wave_add64(unsigned long long* counter, unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter, v);
 }
 
@@ -98,63 +100,11 @@ __global__ __launch_bounds__(kIxThreads) void k_isect_units(const mvs_cell* __re
     unsigned long long* tile = tiles[wave];
     const long long n_waves = (long long)gridDim.x * kIxWaves;
     for (long long u = (long long)blockIdx.x * kIxWaves + wave; u < n_units; u += n_waves) {
-        // the unit's cell: the last one whose first unit is <= u (cells without units share their successor's start)
-        const int64_t cell = wave_bound<long long, int64_t>(unit_start, 0, n_cells + 1, u, true, lane) - 1;
-        const int32_t r = cells[cell].row, c = cells[cell].col;
-        const int32_t lr = size_r[r], lc = size_c[c];
-        const bool row_short = lr <= lc;
-        const unsigned long long* A = row_short ? hash_r + off_r[r] : hash_c + off_c[c];
-        const unsigned long long* B = row_short ? hash_c + off_c[c] : hash_r + off_r[r];
-        const int32_t la = row_short ? lr : lc, lb = row_short ? lc : lr;
-        const long long chunk = u - unit_start[cell];
-        const int32_t a0 = (int32_t)(chunk * unit);
-        const int32_t a1 = (int32_t)(((long long)a0 + unit < la) ? (long long)a0 + unit : la);   // a0 < a1 <= la
-        // B's window: everything that can equal an element of the chunk
-        const int32_t w0 = wave_bound<unsigned long long, int32_t>(B, 0, lb, A[a0], false, lane);
-        const int32_t w1 = wave_bound<unsigned long long, int32_t>(B, w0, lb, A[a1 - 1], true, lane);
+        const IxUnit n = unit_of(cells, n_cells, unit_start, u, hash_r, off_r, size_r, hash_c, off_c, size_c, unit, lane);
         int found = 0;
-        if ((long long)(w1 - w0) > (long long)kSkew * (a1 - a0)) {
-            // a long window for a few elements: search it where it lies
-            for (int32_t a = a0 + lane; a < a1; a += 64) {
-                const unsigned long long key = A[a];
-                int32_t l = w0, h = w1;
-                while (l < h) {
-                    const int32_t mid = l + ((h - l) >> 1);
-                    if (B[mid] < key) l = mid + 1;
-                    else h = mid;
-                }
-                found += (l < w1 && B[l] == key) ? 1 : 0;
-            }
-        } else {
-            int32_t a = a0;                                            // elements of the chunk before a are settled
-            for (int32_t t0 = w0; t0 < w1 && a < a1; t0 += kTile) {
-                const int tn = (w1 - t0 < kTile) ? (w1 - t0) : kTile;
-                for (int j = lane; j < tn; j += 64) tile[j] = B[t0 + j];
-                // (the tile belongs to this wave alone; its lanes run in lockstep, the compiler orders LDS stores and loads)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                // the chunk's elements up to the tile's last one can only match inside this tile (B's earlier tiles are
-                // below the elements from a on: those were not <= the previous tile's last element)
-                const int32_t ae = wave_bound<unsigned long long, int32_t>(A, a, a1, tile[tn - 1], true, lane);
-                for (int32_t x = a + lane; x < ae; x += 64) {
-                    const unsigned long long key = A[x];
-                    int l = 0, h = tn;
-                    while (l < h) {
-                        const int mid = (l + h) >> 1;
-                        if (tile[mid] < key) l = mid + 1;
-                        else h = mid;
-                    }
-                    found += (l < tn && tile[l] == key) ? 1 : 0;
-                }
-                a = ae;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();                       // the next tile overwrites what the lanes just read
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) found += __shfl_xor(found, o);
-        if (lane == 0 && found) atomicAdd(inter + cell, found);
+        walk_unit<false>(n, tile, lane, [&](int32_t, int32_t, bool) { found += 1; });
+        found = wave_sum(found);
+        if (lane == 0 && found) atomicAdd(inter + n.cell, found);
     }
 }
 
@@ -180,7 +130,7 @@ __global__ __launch_bounds__(kIxThreads) void k_hs_count(const unsigned long lon
         const long long b = offsets[s], e = offsets[s + 1];
         int mine = 0;
         for (long long i = b + threadIdx.x; i < e; i += kIxThreads) mine += (i == b || sorted[i] != sorted[i - 1]) ? 1 : 0;
-        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+        mine = wave_sum(mine);
         if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -225,11 +175,6 @@ __global__ __launch_bounds__(kIxThreads) void k_hs_compact(const unsigned long l
     }
 }
 
-unsigned ix_grid(int64_t items, int per_block) {
-    const int64_t blocks = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, 1 << 20));
-}
-
 }  // namespace
 
 int launch_hs_check(hipStream_t stream, const unsigned long long* d_hashes, const long long* d_offsets, int64_t n,
@@ -267,12 +212,11 @@ int launch_hs_compact(hipStream_t stream, const unsigned long long* d_sorted, co
     return 0;
 }
 
-namespace {
-
+// d_units / d_unit_start: n_cells + 1 entries each; scratch as rocprim's scan wants it (d_scratch == NULL: *scratch_needed only)
 template <typename R>
-int isect_plan_for(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
-                   const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, R* d_inter,
-                   bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed) {
+int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
+               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, R* d_inter,
+               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed) {
     size_t need = 0;
     hipError_t e = rocprim::exclusive_scan(nullptr, need, d_units, d_unit_start, 0LL, (size_t)n_cells + 1, rocprim::plus<long long>(), stream);
     if (e != hipSuccess) return MVS_E_HIP;
@@ -284,24 +228,11 @@ int isect_plan_for(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells,
     e = rocprim::exclusive_scan(d_scratch, need, d_units, d_unit_start, 0LL, (size_t)n_cells + 1, rocprim::plus<long long>(), stream);
     return e == hipSuccess ? 0 : MVS_E_HIP;
 }
-
-}  // namespace
-
-// d_units / d_unit_start: n_cells + 1 entries each; scratch as rocprim's scan wants it (d_scratch == NULL: *scratch_needed only)
-int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
-               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, int32_t* d_inter,
-               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed) {
-    return isect_plan_for(stream, d_cells, n_cells, d_size_r, n_r, d_size_c, n_c, unit, d_units, d_unit_start, d_inter, mark_bad,
-                          d_counters, d_scratch, scratch_bytes, scratch_needed);
-}
-
-// ... the same plan for the weighted overlaps: the whole record of a cell in range is zeroed (mark_bad: inter = -1 for the others)
-int isect_plan(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const int32_t* d_size_r, int64_t n_r,
-               const int32_t* d_size_c, int64_t n_c, int unit, long long* d_units, long long* d_unit_start, mvs_abund_overlap* d_out,
-               bool mark_bad, unsigned long long* d_counters, void* d_scratch, size_t scratch_bytes, size_t* scratch_needed) {
-    return isect_plan_for(stream, d_cells, n_cells, d_size_r, n_r, d_size_c, n_c, unit, d_units, d_unit_start, d_out, mark_bad,
-                          d_counters, d_scratch, scratch_bytes, scratch_needed);
-}
+// the two results a plan is made for: counts, and the records of the weighted overlaps (mvs_overlap.hip)
+template int isect_plan<int32_t>(hipStream_t, const mvs_cell*, int64_t, const int32_t*, int64_t, const int32_t*, int64_t, int, long long*,
+                                 long long*, int32_t*, bool, unsigned long long*, void*, size_t, size_t*);
+template int isect_plan<mvs_abund_overlap>(hipStream_t, const mvs_cell*, int64_t, const int32_t*, int64_t, const int32_t*, int64_t, int,
+                                           long long*, long long*, mvs_abund_overlap*, bool, unsigned long long*, void*, size_t, size_t*);
 
 int launch_isect_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const long long* d_unit_start, long long n_units,
                        const unsigned long long* d_hash_r, const long long* d_off_r, const int32_t* d_size_r,

@@ -2,19 +2,18 @@
 // totals of the abundances (mvs_hash_set_abundance_totals); the contract is in include/mvs_hip.h, "abundance-weighted overlaps".
 //
 // The work is that of mvs_intersect.hip and is laid out the same way: isect_plan cuts every cell into units of `unit` elements
-// of its shorter list A and zeroes the cell's record, and k_overlap_units gives every unit to one wave, which finds B's window
-// for the chunk with the 64-ary wave_bound searches and then either stages the window in LDS tile by tile or, for a window more
-// than kSkew times the chunk, searches it where it lies.  What is new happens where a lane finds its key: it then knows the
-// position on both sides -- x in A, t0 + l (or l) in B -- and loads the two abundances from global memory.  B's abundances are
-// NOT staged beside the tile: a load happens on a match only, at most one per element of the chunk, and a side that carries no
-// abundances (template argument) costs no load at all: its abundance is the constant 1.
+// of its shorter list A and zeroes the cell's record, and k_overlap_units gives every unit to one wave, which decodes it and walks
+// it with unit_of and walk_unit of mvs_intersect_dev.h.  What is its own happens in the sink, where a lane has found its key: it
+// hears the position on both sides and loads the two abundances from global memory.  B's abundances are NOT staged beside the
+// tile: a load happens on a match only, at most one per element of the chunk, and a side that carries no abundances (template
+// argument) costs no load at all: its abundance is the constant 1.
 //
 // A lane accumulates the count and five 64-bit sums; the sums of a wave are reduced once per unit and lane 0 adds each non-zero
 // one to the cell's record with a 64-bit integer atomic.  The lists hold no duplicates, so a value of A matches at most one of
 // B and the chunks of a cell partition A: the sums over a cell's units are the contract's.  No sum can overflow (fewer than 2^31
 // terms below 2^32 each) and integer addition commutes: nothing depends on the unit size or on any order.
 #include "mvs_internal.h"
-#include "mvs_intersect_dev.h"   // unit geometry (kIxThreads, kTile, kSkew), wave_bound, wave_lds_sync
+#include "mvs_intersect_dev.h"   // unit geometry (kIxThreads), unit_of, walk_unit, wave_sum, ix_grid
 
 namespace mvs {
 
@@ -35,11 +34,6 @@ struct Sums {
     }
 };
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __device__ __forceinline__ void add_field(unsigned long long* field, unsigned long long v) {
     if (v) atomicAdd(field, v);
 }
@@ -59,62 +53,15 @@ __global__ __launch_bounds__(kIxThreads) void k_overlap_units(const mvs_cell* __
     unsigned long long* tile = tiles[wave];
     const long long n_waves = (long long)gridDim.x * kIxWaves;
     for (long long u = (long long)blockIdx.x * kIxWaves + wave; u < n_units; u += n_waves) {
-        // the unit's cell: the last one whose first unit is <= u (cells without units share their successor's start)
-        const int64_t cell = wave_bound<long long, int64_t>(unit_start, 0, n_cells + 1, u, true, lane) - 1;
-        const int32_t r = cells[cell].row, c = cells[cell].col;
-        const int32_t lr = size_r[r], lc = size_c[c];
-        const bool row_short = lr <= lc;
-        const long long at_r = off_r[r], at_c = off_c[c];
-        const unsigned long long* A = row_short ? hash_r + at_r : hash_c + at_c;
-        const unsigned long long* B = row_short ? hash_c + at_c : hash_r + at_r;
+        const IxUnit n = unit_of(cells, n_cells, unit_start, u, hash_r, off_r, size_r, hash_c, off_c, size_c, unit, lane);
+        const bool row_short = n.row_short;
         // the abundances aligned with A and B; NULL: 1 throughout (known when the kernel is compiled if neither side carries any)
-        const uint32_t* wr = kAbundR ? ab_r + at_r : nullptr;
-        const uint32_t* wc = kAbundC ? ab_c + at_c : nullptr;
+        const uint32_t* wr = kAbundR ? ab_r + (row_short ? n.at_a : n.at_b) : nullptr;
+        const uint32_t* wc = kAbundC ? ab_c + (row_short ? n.at_b : n.at_a) : nullptr;
         const uint32_t* WA = row_short ? wr : wc;
         const uint32_t* WB = row_short ? wc : wr;
-        const int32_t la = row_short ? lr : lc, lb = row_short ? lc : lr;
-        const long long chunk = u - unit_start[cell];
-        const int32_t a0 = (int32_t)(chunk * unit);
-        const int32_t a1 = (int32_t)(((long long)a0 + unit < la) ? (long long)a0 + unit : la);   // a0 < a1 <= la
-        // B's window: everything that can equal an element of the chunk
-        const int32_t w0 = wave_bound<unsigned long long, int32_t>(B, 0, lb, A[a0], false, lane);
-        const int32_t w1 = wave_bound<unsigned long long, int32_t>(B, w0, lb, A[a1 - 1], true, lane);
         Sums s;
-        if ((long long)(w1 - w0) > (long long)kSkew * (a1 - a0)) {
-            // a long window for a few elements: search it where it lies
-            for (int32_t a = a0 + lane; a < a1; a += 64) {
-                const unsigned long long key = A[a];
-                int32_t l = w0, h = w1;
-                while (l < h) {
-                    const int32_t mid = l + ((h - l) >> 1);
-                    if (B[mid] < key) l = mid + 1;
-                    else h = mid;
-                }
-                if (l < w1 && B[l] == key) s.add(WA ? WA[a] : 1u, WB ? WB[l] : 1u);
-            }
-        } else {
-            int32_t a = a0;                                            // elements of the chunk before a are settled
-            for (int32_t t0 = w0; t0 < w1 && a < a1; t0 += kTile) {
-                const int tn = (w1 - t0 < kTile) ? (w1 - t0) : kTile;
-                for (int j = lane; j < tn; j += 64) tile[j] = B[t0 + j];
-                wave_lds_sync();
-                // the chunk's elements up to the tile's last one can only match inside this tile (B's earlier tiles are
-                // below the elements from a on: those were not <= the previous tile's last element)
-                const int32_t ae = wave_bound<unsigned long long, int32_t>(A, a, a1, tile[tn - 1], true, lane);
-                for (int32_t x = a + lane; x < ae; x += 64) {
-                    const unsigned long long key = A[x];
-                    int l = 0, h = tn;
-                    while (l < h) {
-                        const int mid = (l + h) >> 1;
-                        if (tile[mid] < key) l = mid + 1;
-                        else h = mid;
-                    }
-                    if (l < tn && tile[l] == key) s.add(WA ? WA[x] : 1u, WB ? WB[t0 + l] : 1u);
-                }
-                a = ae;
-                wave_lds_sync();                                       // the next tile overwrites what the lanes just read
-            }
-        }
+        walk_unit<false>(n, tile, lane, [&](int32_t x, int32_t y, bool) { s.add(WA ? WA[x] : 1u, WB ? WB[y] : 1u); });
         s.n = wave_sum(s.n);
         if (s.n == 0) continue;                                        // (the same for every lane) no match: every sum is 0
         s.wa = wave_sum(s.wa);
@@ -123,7 +70,7 @@ __global__ __launch_bounds__(kIxThreads) void k_overlap_units(const mvs_cell* __
         s.dlo = wave_sum(s.dlo);
         s.dhi = wave_sum(s.dhi);
         if (lane == 0) {
-            mvs_abund_overlap* o = out + cell;
+            mvs_abund_overlap* o = out + n.cell;
             atomicAdd((unsigned long long*)&o->inter, s.n);
             add_field((unsigned long long*)&o->w_row, row_short ? s.wa : s.wb);
             add_field((unsigned long long*)&o->w_col, row_short ? s.wb : s.wa);
@@ -170,11 +117,6 @@ __global__ __launch_bounds__(kIxThreads) void k_abund_totals(const uint32_t* __r
     }
 }
 
-unsigned overlap_grid(int64_t items, int per_block) {
-    const int64_t blocks = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, 1 << 20));
-}
-
 }  // namespace
 
 int launch_overlap_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_cells, const long long* d_unit_start, long long n_units,
@@ -182,7 +124,7 @@ int launch_overlap_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_
                          const unsigned long long* d_hash_c, const long long* d_off_c, const int32_t* d_size_c, const uint32_t* d_ab_c,
                          int unit, mvs_abund_overlap* d_out) {
     if (n_units <= 0) return 0;
-    const dim3 grid(overlap_grid(n_units, kIxWaves)), block(kIxThreads);
+    const dim3 grid(ix_grid(n_units, kIxWaves)), block(kIxThreads);
 #define MVS_OVERLAP_LAUNCH(R, C)                                                                                              \
     hipLaunchKernelGGL((k_overlap_units<R, C>), grid, block, 0, stream, d_cells, n_cells, d_unit_start, n_units, d_hash_r, d_off_r, \
                        d_size_r, d_ab_r, d_hash_c, d_off_c, d_size_c, d_ab_c, unit, d_out)
@@ -197,7 +139,7 @@ int launch_overlap_units(hipStream_t stream, const mvs_cell* d_cells, int64_t n_
 int launch_abund_totals(hipStream_t stream, const uint32_t* d_abund, const long long* d_offsets, int64_t n, unsigned long long* d_sum,
                         unsigned long long* d_sumsq_lo, unsigned long long* d_sumsq_hi) {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_abund_totals, dim3(overlap_grid(n, 1)), dim3(kIxThreads), 0, stream, d_abund, d_offsets, n, d_sum, d_sumsq_lo,
+    hipLaunchKernelGGL(k_abund_totals, dim3(ix_grid(n, 1)), dim3(kIxThreads), 0, stream, d_abund, d_offsets, n, d_sum, d_sumsq_lo,
                        d_sumsq_hi);
     return 0;
 }
