@@ -917,8 +917,9 @@ int mvs_ctx_intersect_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* unit
  *     the string order); ksize > 32 is refused.
  *   max_hash(scaled) = (uint64)(2^64 / (double)scaled) for scaled >= 2 and 2^64 - 1 for scaled = 1 (keep everything): 1000 gives
  *     18446744073709552, 2000 gives 9223372036854776.
- * Exact and deterministic whatever the options, the units of work or where the bytes lie.  Not offered: ksize > 32, protein /
- * dayhoff / hp alphabets, abundances, sourmash .sig JSON, adding bases to a sample over several calls, several GPUs.
+ * Exact and deterministic whatever the options, the units of work or where the bytes lie.  Not offered: ksize > 32,
+ * abundances, sourmash .sig JSON, adding bases to a sample over several calls, several GPUs.  (Protein, dayhoff and hp
+ * alphabets: "protein sketches" below.)
  *
  * mvs_kmer_max_hash     the formula above.  Pure host.  scaled < 1: MVS_E_INVALID.
  * mvs_kmer_hash         the per-k-mer rule for the ksize bytes at `kmer`: *h and *valid = 1, or *valid = 0 (and *h = 0) if one
@@ -956,6 +957,65 @@ int mvs_hash_set_device(const mvs_hash_set* set, const uint64_t** d_hashes);
 int mvs_ctx_kmer_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* bases, int64_t* kmers, int64_t* kept, int64_t* units,
                        int64_t* second_trips);
 int mvs_ctx_kmer_sample_stats(const mvs_ctx* ctx, int64_t n_samples, int64_t* kmers, int64_t* kept);
+
+/* ---- protein sketches: FracMinHash values of residues, from proteins or from DNA in six frames ----------------------------------
+ * DNA k-mers at ksize 31 see nothing below roughly 80 % identity; relations at the level of a family show in protein k-mers, in
+ * the amino acids themselves or in reduced alphabets.  These calls make such sketches, as a mvs_hash_set like the one above:
+ * every consumer takes it unchanged.
+ *
+ * A SAMPLE is a byte string.  Its sketch for (input kind, alphabet, ksize, seed, max_hash) is the ascending list of the distinct
+ * kept values h below.
+ *   Residues: the 20 letters A C D E F G H I K L M N P Q R S T V W Y in either case (lower case counting as upper case) and
+ *     '*', the stop, are residues; every other byte (X B Z J U O - '\n' 0 255 ...) is a break.  No k-mer contains a break; a
+ *     caller joins the records of one sample with one '\n'.
+ *   Alphabets: what the hash reads, one byte per residue.
+ *     MVS_AA_PROTEIN  the upper-case letter;
+ *     MVS_AA_DAYHOFF  C -> a;  A G P S T -> b;  D E N Q -> c;  H K R -> d;  I L M V -> e;  F W Y -> f;
+ *     MVS_AA_HP       A F G I L M P V W Y -> h;  C D E H K N Q R S T -> p;
+ *     '*' stays '*' in all three.
+ *   Hash: h = the FIRST 64-bit word of MurmurHash3_x64_128(the ksize encoded bytes, seed), kept iff h <= max_hash
+ *     (mvs_kmer_max_hash, unchanged).  There is no canonical form: a protein has one direction.  1 <= ksize <= 64 residues.
+ *     Customary: seed 42, scaled 200, ksize 10 / 16 / 42 for protein / dayhoff / hp.
+ *   MVS_SEQ_PROTEIN: the bytes are residues; every window of ksize residues gives one h.
+ *   MVS_SEQ_TRANSLATE: the bytes are DNA, bases and breaks exactly as in "sketches from sequences".  The genetic code is the
+ *     standard one: codon xyz with T, C, A, G = 0, 1, 2, 3 indexes
+ *         FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG       at 16x + 4y + z.
+ *     The sketch is the union over all six reading frames: for every maximal run of bases, the run and its reverse complement,
+ *     each at offsets 0, 1 and 2, translated codon by codon (a trailing partial codon is dropped); every window of ksize
+ *     residues gives one h.  Equivalently: every window of 3 * ksize bases gives two values, one of its codons read forward,
+ *     one of the codons of its reverse complement.
+ *   Statistics: `kmers` counts hashed k-mers (two per window with MVS_SEQ_TRANSLATE), `kept` the values <= max_hash, duplicates
+ *     included.
+ * An unknown residue or codon is a break here (sourmash hashes it as X); byte-compatibility with sourmash's signatures is not
+ * claimed.  Not offered: translated read sets with abundances, other genetic codes, .sig JSON, several GPUs.
+ *
+ * mvs_translate_codon   the residue of the three bytes at `codon3`: *aa (an upper-case letter or '*') and *valid = 1, or *valid =
+ *                       0 (and *aa = 0) if one of them is no base.  Pure host.
+ * mvs_aa_hash           the hash of the ksize residues at `kmer` in `alphabet`: *h and *valid = 1, or *valid = 0 (and *h = 0) if
+ *                       one of them is a break.  Pure host, and shares no code with the kernel.
+ * mvs_hash_set_from_residues
+ *                       the sketches of n_samples samples -> a new hash set.  Samples, offsets, `mem_bytes`, limits and
+ *                       synchrony as for mvs_hash_set_from_sequences.  NULL pointers, an input kind or alphabet that is none
+ *                       of the constants, ksize outside 1 .. 64, decreasing offsets: MVS_E_INVALID, nothing is allocated.
+ *                       How: the frame of mvs_hash_set_from_sequences with its options kmer_unit and kmer_capacity (the
+ *                       staging list expects two values per window with MVS_SEQ_TRANSLATE), and k_aa_hash as the hashing
+ *                       pass.  Its planes of residues cost LDS, so a unit holds at most 18432 positions with
+ *                       MVS_SEQ_PROTEIN and 12032 with MVS_SEQ_TRANSLATE whatever kmer_unit says.
+ * mvs_ctx_aa_stats, mvs_ctx_aa_sample_stats
+ *                       the context's last mvs_hash_set_from_residues, shaped like mvs_ctx_kmer_stats and
+ *                       mvs_ctx_kmer_sample_stats (which keep what the last mvs_hash_set_from_sequences left). */
+#define MVS_SEQ_PROTEIN   0
+#define MVS_SEQ_TRANSLATE 1
+#define MVS_AA_PROTEIN 0
+#define MVS_AA_DAYHOFF 1
+#define MVS_AA_HP      2
+int mvs_translate_codon(const char* codon3, char* aa, int* valid);
+int mvs_aa_hash(const char* kmer, int ksize, int alphabet, uint32_t seed, uint64_t* h, int* valid);
+int mvs_hash_set_from_residues(mvs_ctx* ctx, const uint8_t* bytes, int mem_bytes, const int64_t* offsets, int64_t n_samples,
+                               int input_kind, int alphabet, int ksize, uint32_t seed, uint64_t max_hash, mvs_hash_set** set);
+int mvs_ctx_aa_stats(const mvs_ctx* ctx, double* kernel_ms, int64_t* bytes, int64_t* kmers, int64_t* kept, int64_t* units,
+                     int64_t* second_trips);
+int mvs_ctx_aa_sample_stats(const mvs_ctx* ctx, int64_t n_samples, int64_t* kmers, int64_t* kept);
 
 /* ---- abundances: read sets, k-mer counts, a minimum count ----------------------------------------------------------------------
  * A metagenome sample is a read set, and in raw reads most distinct k-mers are sequencing errors seen once.  These calls count

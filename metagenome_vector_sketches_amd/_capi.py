@@ -243,6 +243,11 @@ SYMBOLS = [
     ("mvs_hash_set_device", _c.c_int, [_P, _c.POINTER(_P)]),
     ("mvs_ctx_kmer_stats", _c.c_int, [_P, _c.POINTER(_c.c_double)] + [_c.POINTER(_c.c_int64)] * 5),
     ("mvs_ctx_kmer_sample_stats", _c.c_int, [_P, _c.c_int64, _P, _P]),
+    ("mvs_translate_codon", _c.c_int, [_c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
+    ("mvs_aa_hash", _c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_uint32, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
+    ("mvs_hash_set_from_residues", _c.c_int, [_P, _P, _c.c_int, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_uint32, _c.c_uint64, _c.POINTER(_P)]),
+    ("mvs_ctx_aa_stats", _c.c_int, [_P, _c.POINTER(_c.c_double)] + [_c.POINTER(_c.c_int64)] * 5),
+    ("mvs_ctx_aa_sample_stats", _c.c_int, [_P, _c.c_int64, _P, _P]),
     ("mvs_kmer_sketcher_create", _c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_uint32, _c.c_uint64, _c.POINTER(_P)]),
     ("mvs_kmer_sketcher_add", _c.c_int, [_P, _P, _c.c_int, _P, _P, _c.c_int64]),
     ("mvs_kmer_sketcher_finish", _c.c_int, [_P, _c.c_uint32, _c.c_uint32, _P, _c.POINTER(_P)]),
@@ -441,6 +446,41 @@ def kmer_hash(kmer, seed=42):
     h, valid = _c.c_uint64(), _c.c_int()
     _check(load_library().mvs_kmer_hash(kmer, len(kmer), int(seed) & 0xFFFFFFFF, ctypes.byref(h), ctypes.byref(valid)))
     return h.value if valid.value else None
+
+
+SEQ_PROTEIN, SEQ_TRANSLATE = 0, 1                                      # MVS_SEQ_*
+AA_ALPHABETS = {"protein": 0, "dayhoff": 1, "hp": 2}                   # MVS_AA_*
+AA_KSIZE = {"protein": 10, "dayhoff": 16, "hp": 42}                    # the customary ksize of each alphabet
+
+
+def _alphabet(alphabet):
+    if alphabet not in AA_ALPHABETS:
+        raise ValueError("alphabet must be one of %s" % ", ".join(AA_ALPHABETS))
+    return AA_ALPHABETS[alphabet]
+
+
+def aa_hash(kmer, alphabet="protein", seed=42):
+    """mvs_aa_hash: the hash of one protein k-mer (bytes or str, 1 .. 64 residues) in `alphabet` ("protein", "dayhoff", "hp") --
+    MurmurHash3_x64_128's first word of the encoded residues --, or None if one of its bytes is not a residue"""
+    if isinstance(kmer, str):
+        kmer = kmer.encode("latin-1")
+    kmer = bytes(kmer)
+    h, valid = _c.c_uint64(), _c.c_int()
+    _check(load_library().mvs_aa_hash(kmer, len(kmer), _alphabet(alphabet), int(seed) & 0xFFFFFFFF, ctypes.byref(h), ctypes.byref(valid)))
+    return h.value if valid.value else None
+
+
+def translate_codon(codon):
+    """mvs_translate_codon: the residue (a one-letter str, '*' for a stop) of a codon of three bases (bytes or str) under the
+    standard genetic code, or None if one of its bytes is not a base"""
+    if isinstance(codon, str):
+        codon = codon.encode("latin-1")
+    codon = bytes(codon)
+    if len(codon) != 3:
+        raise ValueError("a codon is three bytes")
+    aa, valid = _c.create_string_buffer(1), _c.c_int()
+    _check(load_library().mvs_translate_codon(codon, aa, ctypes.byref(valid)))
+    return aa.raw.decode("latin-1") if valid.value else None
 
 
 def _norms(norms_sq):
@@ -2617,12 +2657,9 @@ class Context:
         _check(self.lib.mvs_hash_set_create(self._h, hp, hm, offsets.ctypes.data, n, ctypes.byref(h)))
         return HashSet(self, h)
 
-    # ---- sketches from sequences (include/mvs_hip.h "sketches from sequences") ----
-    def sketch_sequences(self, seqs, ksize=31, scaled=1000, seed=42, max_hash=None):
-        """mvs_hash_set_from_sequences: the FracMinHash sketches of DNA samples -> HashSet.  seqs: a list of bytes / str, one
-        sample each (join the records of a sample with one non-base byte such as b"\\n"), or a pair (bases, offsets) with bases
-        a uint8 numpy array or torch tensor (host or device) and offsets host int64 [n + 1].  A value is kept iff it is
-        <= max_hash (default: kmer_max_hash(scaled))."""
+    @staticmethod
+    def _sample_bytes(seqs):
+        """seqs as sketch_sequences / sketch_proteins take them -> (pointer, mem flag, keepalive, offsets int64 [n + 1])"""
         if isinstance(seqs, tuple) and len(seqs) == 2 and not isinstance(seqs[0], (bytes, bytearray, str)):
             bases, offsets = seqs
             offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -2640,12 +2677,53 @@ class Context:
             bp, bm, bk = _buf(np.frombuffer(b"".join(parts), dtype=np.uint8), np.uint8)
         if offsets.ndim != 1 or len(offsets) < 1:
             raise ValueError("offsets must hold n + 1 entries")
+        return bp, bm, bk, offsets
+
+    # ---- sketches from sequences (include/mvs_hip.h "sketches from sequences") ----
+    def sketch_sequences(self, seqs, ksize=31, scaled=1000, seed=42, max_hash=None):
+        """mvs_hash_set_from_sequences: the FracMinHash sketches of DNA samples -> HashSet.  seqs: a list of bytes / str, one
+        sample each (join the records of a sample with one non-base byte such as b"\\n"), or a pair (bases, offsets) with bases
+        a uint8 numpy array or torch tensor (host or device) and offsets host int64 [n + 1].  A value is kept iff it is
+        <= max_hash (default: kmer_max_hash(scaled))."""
+        bp, bm, bk, offsets = self._sample_bytes(seqs)
         if max_hash is None:
             max_hash = kmer_max_hash(scaled)
         h = _P()
         _check(self.lib.mvs_hash_set_from_sequences(self._h, bp, bm, offsets.ctypes.data, len(offsets) - 1, int(ksize),
                                                      int(seed) & 0xFFFFFFFF, int(max_hash), ctypes.byref(h)))
         return HashSet(self, h)
+
+    # ---- protein sketches (include/mvs_hip.h "protein sketches") ----
+    def sketch_proteins(self, seqs, ksize=None, scaled=200, alphabet="protein", translate=False, seed=42, max_hash=None):
+        """mvs_hash_set_from_residues: the FracMinHash sketches of protein samples, or with translate=True of DNA samples in all
+        six reading frames, in `alphabet` ("protein", "dayhoff", "hp") -> HashSet.  seqs as sketch_sequences takes them.  ksize
+        counts residues, 1 .. 64 (default 10 / 16 / 42 by alphabet).  A value is kept iff it is <= max_hash (default:
+        kmer_max_hash(scaled))."""
+        alpha = _alphabet(alphabet)
+        if ksize is None:
+            ksize = AA_KSIZE[alphabet]
+        bp, bm, bk, offsets = self._sample_bytes(seqs)
+        if max_hash is None:
+            max_hash = kmer_max_hash(scaled)
+        h = _P()
+        _check(self.lib.mvs_hash_set_from_residues(self._h, bp, bm, offsets.ctypes.data, len(offsets) - 1,
+                                                    SEQ_TRANSLATE if translate else SEQ_PROTEIN, alpha, int(ksize),
+                                                    int(seed) & 0xFFFFFFFF, int(max_hash), ctypes.byref(h)))
+        return HashSet(self, h)
+
+    def aa_stats(self):
+        """-> dict of this context's last sketch_proteins: kernel_ms (timing on), bytes, kmers (hashed k-mers: two per window
+        with translate), kept (values <= max_hash before the unique compaction), units of work, second_trips"""
+        ms = _c.c_double()
+        v = [_c.c_int64() for _ in range(5)]
+        _check(self.lib.mvs_ctx_aa_stats(self._h, ctypes.byref(ms), *[ctypes.byref(x) for x in v]))
+        return dict(zip(("kernel_ms", "bytes", "kmers", "kept", "units", "second_trips"), [ms.value] + [x.value for x in v]))
+
+    def aa_sample_stats(self, n_samples):
+        """-> (kmers, kept): int64 [n_samples] each, per sample of this context's last sketch_proteins"""
+        kmers, kept = np.empty(n_samples, dtype=np.int64), np.empty(n_samples, dtype=np.int64)
+        _check(self.lib.mvs_ctx_aa_sample_stats(self._h, int(n_samples), kmers.ctypes.data, kept.ctypes.data))
+        return kmers, kept
 
     # ---- abundances (include/mvs_hip.h "abundances") ----
     def kmer_sketcher(self, n_samples, ksize=31, scaled=1000, seed=42, max_hash=None):

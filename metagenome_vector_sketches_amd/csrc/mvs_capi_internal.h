@@ -120,6 +120,14 @@ struct TsneStats {
     long long iterations = 0, edges = 0, units = 0, blocks = 0;
     void reset() { *this = TsneStats(); }
 };
+// what the last sketching call of one kind did on a context (mvs_ctx_kmer_stats, mvs_ctx_aa_stats): time of the hashing passes
+// and the scatter (timing enabled), bytes read, hashed k-mers, kept values before the unique compaction, units of work, hashing
+// passes repeated because the staging list was too short; hashed k-mers and kept values per sample
+struct SeqStats {
+    double kernel_ms = 0.0;
+    long long bases = 0, kmers = 0, kept = 0, units = 0, second_trips = 0;
+    std::vector<long long> sample_kmers, sample_kept;
+};
 }  // namespace mvs_capi
 
 struct mvs_ctx {
@@ -267,12 +275,8 @@ struct mvs_ctx {
     // walk's state), bytes of the bit rows; kernel times of the three phases (timing enabled)
     long long ga_survivors = 0, ga_rounds = 0, ga_batches = 0, ga_row_bytes = 0, ga_round_bytes = 0;
     double ga_overlap_ms = 0.0, ga_mark_ms = 0.0, ga_rounds_ms = 0.0;
-    // what the last mvs_hash_set_from_sequences did (mvs_ctx_kmer_stats): time of the hashing passes and the scatter (timing
-    // enabled), bytes read, valid positions, kept values before the unique compaction, units of work, hashing passes repeated
-    // because the staging list was too short
-    double km_kernel_ms = 0.0;
-    long long km_bases = 0, km_kmers = 0, km_kept = 0, km_units = 0, km_second_trips = 0;
-    std::vector<long long> km_sample_kmers, km_sample_kept;   // ... and per sample (mvs_ctx_kmer_sample_stats)
+    // what the last mvs_hash_set_from_sequences (mvs_ctx_kmer_stats) and the last mvs_hash_set_from_residues (mvs_ctx_aa_stats) did
+    mvs_capi::SeqStats km, aa;
     // what the last counted set build did (mvs_ctx_abund_stats): time of the sorts and of the run-sum passes (timing enabled),
     // values given, distinct values, values that passed the filter, units of the run-sum passes, samples sorted device-wide
     double ab_sort_ms = 0.0, ab_count_ms = 0.0;
@@ -374,6 +378,19 @@ constexpr size_t kUploadPiece = 32u << 20;    // bytes per staging buffer (pinni
 int ensure_upload_pipeline(mvs_ctx* c);
 int check_kernel(const char* what);
 void plan_state_free(mvs_ctx* c);      // mvs_capi_plan.hip
+
+// ---- mvs_capi_kmer.hip: bytes -> hash set, for any hashing kernel of the k_kmer_hash frame ----
+// The units of work (up to `unit` window positions of one sample, a window `window` bytes long), the upload, the staging list
+// with its second trip at the exact size, the counts per sample, k_kmer_scatter and mvs_hash_set_create.  `launch` queues the
+// hashing kernel (named `kernel` in messages) over the units; it hashes `per_window` k-mers per position.  The arguments are
+// checked by the caller (check_sample_bytes: the offsets and the bytes of n samples); *st is reset and filled.
+int check_sample_bytes(const uint8_t* bytes, const int64_t* offsets, int64_t n);
+using HashLauncher = std::function<int(const uint8_t* d_bytes, long long total_bytes, const mvs::KmerUnit* d_units, long long n_units,
+                                       unsigned long long* d_vals, int32_t* d_sample, unsigned long long cap, unsigned long long* d_counters,
+                                       unsigned long long* d_sample_counts, unsigned long long* d_sample_valid)>;
+int hash_set_from_bytes(mvs_ctx* c, const char* call, const char* kernel, const uint8_t* bytes, int mem_bytes, const int64_t* offsets,
+                        int64_t n, int window, int per_window, int unit, uint64_t max_hash, SeqStats* st, const HashLauncher& launch,
+                        mvs_hash_set** out);
 
 // ---- mvs_capi_reads.hip: the counted set build (mvs_hash_set_create_counted, mvs_kmer_sketcher_finish) ----
 // d_in (and d_w, or NULL: weight 1) hold the samples' values on the device, sample s at [off[s], off[s + 1]) with off[0] = 0,

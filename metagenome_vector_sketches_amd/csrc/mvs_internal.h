@@ -538,6 +538,24 @@ int launch_kmer_hash(hipStream_t stream, const uint8_t* d_bases, long long total
                      unsigned long long* d_sample_valid);
 int launch_kmer_scatter(hipStream_t stream, const unsigned long long* d_vals, const int32_t* d_sample, long long n,
                         const long long* d_offsets, unsigned long long* d_cursors, unsigned long long* d_out);
+// FracMinHash values of residues (mvs_protein.hip).  The units, the staging list and the counters are launch_kmer_hash's; a
+// unit's positions are window starts (a window is ksize bytes, or 3 * ksize bases with translate, which hashes two k-mers per
+// window: d_sample_valid counts hashed k-mers).  aa_fill_tables makes the look-up tables of the kernel's classification pass
+// for an alphabet (0 protein, 1 dayhoff, 2 hp).  The planes of residues make a unit cost more LDS than k_kmer_hash's: a unit
+// holds at most aa_unit_max positions, which keeps a workgroup under a third of a CU's 160 KiB.
+struct AaTables {
+    uint8_t byte_map[256];     // protein: byte -> encoded residue, 0 for a break; translate: byte -> T C A G = 0 1 2 3, 0x80 for a break
+    uint8_t codon_fw[64];      // translate: 16x + 4y + z -> the encoded residue of codon xyz
+    uint8_t codon_rv[64];      // ... of its reverse complement
+};
+constexpr int kAaUnitProtein = 18432, kAaUnitTranslate = 12032;
+int aa_unit_max(bool translate);
+size_t aa_lds_bytes(int unit, int ksize, bool translate);
+int aa_fill_tables(bool translate, int alphabet, AaTables* out);
+int launch_aa_hash(hipStream_t stream, const uint8_t* d_bytes, long long total_bytes, const KmerUnit* d_units, long long n_units, int unit,
+                   bool translate, const AaTables& tables, int ksize, uint32_t seed, uint64_t max_hash, unsigned long long* d_vals,
+                   int32_t* d_sample, unsigned long long cap, unsigned long long* d_counters, unsigned long long* d_sample_counts,
+                   unsigned long long* d_sample_valid);
 // the counted set build (mvs_abund.hip).  ab_sort_segments / ab_sort_whole: the segmented sort of hs_sort_segments, or a
 // device-wide radix sort of ONE sample, with the weights travelling along where d_win is not NULL.  launch_ab_borders sets
 // bit off[s] of the (zeroed) bit map for every sample that starts in front of `total`.  ab_count queues passes A, B, C and the

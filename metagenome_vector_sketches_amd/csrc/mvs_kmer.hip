@@ -15,7 +15,7 @@
 //      selector bytes (two shift-or-mask steps) -> one v_perm_b32 into the word "ACGT".  The hash runs for every lane, valid or
 //      not (no divergence), in the instantiation for the shape of its input (whole blocks, tail words: six cover ksize
 //      1 .. 32), so the loop holds no branch on ksize; its 64-bit multiplies by constants are one v_mad_u64_u32 with the
-//      cross terms in the addend (mad64 / mul64_mad, the idiom of mvs_project.hip in this unit's own copy);
+//      cross terms in the addend (mad64 / mul64_mad of mvs_murmur_dev.h, shared with mvs_protein.hip);
 //   4. kept values leave per wave: ballot, the lane's rank among the kept, the value into the wave's own LDS buffer of 512
 //      entries; a buffer that cannot take the next ballot's values, and every buffer at the end, is flushed with ONE atomic on
 //      the cursor of the staging list and coalesced stores of (value, sample) where cursor + i is below the list's capacity.
@@ -27,6 +27,7 @@
 // host), again with one atomic per wave and sample.  Arrival order is arbitrary; the segmented sort and unique compaction of
 // mvs_hash_set_create make the result deterministic.
 #include "mvs_internal.h"
+#include "mvs_murmur_dev.h"
 
 namespace mvs {
 
@@ -35,37 +36,6 @@ namespace {
 constexpr int kKmThreads = 256;
 constexpr int kWaveBuf = 512;                                   // kept values a wave collects in LDS between two flushes
 constexpr int kKmBufBytes = kKmThreads / 64 * kWaveBuf * 8;     // ... of the four waves: 16 KiB
-
-constexpr uint64_t kMurC1 = 0x87c37b91114253d5ULL, kMurC2 = 0x4cf5ad432745937fULL;
-constexpr uint64_t kFmix1 = 0xff51afd7ed558ccdULL, kFmix2 = 0xc4ceb9fe1a85ec53ULL;
-
-// a * b + c as one v_mad_u64_u32 (b a constant in an SGPR; the carry out goes to an SGPR pair nobody reads)
-__device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) {
-    uint64_t r, carry;
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry) : "v"(a), "s"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ uint32_t mul_lo(uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_mul_lo_u32 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
-    return r;
-}
-// z * C (mod 2^64) for a constant C: lo * C.lo + ((lo * C.hi + hi * C.lo) << 32), the cross terms in the mad's addend
-__device__ __forceinline__ uint64_t mul64_mad(uint64_t z, uint64_t C) {
-    const uint32_t zl = (uint32_t)z, zh = (uint32_t)(z >> 32);
-    const uint32_t cross = mul_lo(zl, (uint32_t)(C >> 32)) + mul_lo(zh, (uint32_t)C);
-    return mad64(zl, (uint32_t)C, (uint64_t)cross << 32);
-}
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {
-    k ^= k >> 33;
-    k = mul64_mad(k, kFmix1);
-    k ^= k >> 33;
-    k = mul64_mad(k, kFmix2);
-    return k ^ (k >> 33);
-}
-__device__ __forceinline__ uint64_t mur_k1(uint64_t k1) { return mul64_mad(rotl64(mul64_mad(k1, kMurC1), 31), kMurC2); }
-__device__ __forceinline__ uint64_t mur_k2(uint64_t k2) { return mul64_mad(rotl64(mul64_mad(k2, kMurC2), 33), kMurC1); }
 
 // four bases (2 bits each, the first in the lowest bits) -> their four ASCII bytes, the first in the lowest byte
 __device__ __forceinline__ uint32_t ascii4(uint32_t x) {
@@ -82,14 +52,6 @@ __device__ __forceinline__ uint64_t ascii8(uint64_t lsb_first, int w) {
 // MurmurHash3_x64_128, first word, of the ksize ASCII bytes of the k-mer `lsb_first`.  The shape of the input is a template
 // parameter, so that a kernel's loop holds no branch on it: BLOCKS whole 16-byte blocks (0 .. 2), then TAIL = 0 nothing, 1 a
 // k1 word of 1 .. 8 bytes, 2 a full k1 word and a k2 word of 1 .. 7 bytes.  last_mask keeps the tail's last word's bytes.
-__device__ __forceinline__ void murmur_block(uint64_t& h1, uint64_t& h2, uint64_t k1, uint64_t k2) {
-    h1 ^= mur_k1(k1);
-    h1 = rotl64(h1, 27) + h2;
-    h1 = h1 * 5 + 0x52dce729u;
-    h2 ^= mur_k2(k2);
-    h2 = rotl64(h2, 31) + h1;
-    h2 = h2 * 5 + 0x38495ab5u;
-}
 template <int BLOCKS, int TAIL>
 __device__ __forceinline__ uint64_t murmur_kmer(uint64_t lsb_first, int ksize, uint32_t seed, uint64_t last_mask) {
     uint64_t h1 = seed, h2 = seed;
