@@ -153,19 +153,7 @@ int main(int argc, char* argv[]) {
     std::vector<int64_t> offsets;
     const bool counted = !o.abund_file.empty();
     if (!counted) {
-        bool parsed = load_csr_cache(o.hash_file, sets);
-        if (!parsed) {
-            try {
-                parsed = read_hash_file(o.hash_file, true, sets);
-            } catch (const std::exception& e) {
-                std::cerr << kProg << ": reading " << o.hash_file << ": " << e.what() << std::endl;
-                return 1;
-            }
-        }
-        if (!parsed) {
-            std::cerr << "Error opening " << o.hash_file << " for reading." << std::endl;
-            return 1;
-        }
+        if (const int rc = load_hash_sets(kProg, o.hash_file, true, sets)) return rc;
         names = sets.names;
     } else {
         TokenText ht, at;

@@ -48,24 +48,6 @@ struct Gpu {
     OwnedHashSet hs_db, hs_q;
 };
 
-// a hash file: its .csr cache when `cached` and valid, else the text; 0, or 1 after a message on stderr
-int load_hashes(const std::string& file, bool cached, HashSets& sets) {
-    bool parsed = cached && load_csr_cache(file, sets);
-    if (!parsed) {
-        try {
-            parsed = read_hash_file(file, true, sets);
-        } catch (const std::exception& e) {
-            std::cerr << kProg << ": reading " << file << ": " << e.what() << std::endl;
-            return 1;
-        }
-    }
-    if (!parsed) {
-        std::cerr << "Error opening " << file << " for reading." << std::endl;
-        return 1;
-    }
-    return 0;
-}
-
 std::string ratio9(double num, double den) { return den == 0.0 ? "nan" : fmt9(num / den); }
 
 }  // namespace
@@ -84,8 +66,8 @@ int main(int argc, char* argv[]) {
     const Args args = parse_flags(argc, argv, flags);
     if (const int rc = args.exit_code(kProg, print_usage, argv[0]); rc >= 0) return rc;
     HashSets db, queries;
-    if (const int rc = load_hashes(o.hash_file, true, db)) return rc;
-    if (const int rc = load_hashes(o.query_file, false, queries)) return rc;
+    if (const int rc = load_hash_sets(kProg, o.hash_file, true, db)) return rc;
+    if (const int rc = load_hash_sets(kProg, o.query_file, false, queries)) return rc;
     const int64_t n = (int64_t)db.names.size(), nq = (int64_t)queries.names.size();
 
     std::string text = "query\trank\tmatch\tintersect\tunique\tf_orig_query\tf_match\tf_unique_to_query\tremaining\n";

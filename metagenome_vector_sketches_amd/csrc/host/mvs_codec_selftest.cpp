@@ -43,6 +43,16 @@ static int dump_parse(const char* path, bool with_names) {
     return 0;
 }
 
+static std::string slurp_file(const std::string& f) {
+    std::ifstream in(f, std::ios::binary);
+    return std::string((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+}
+
+static bool same_sets(const mvs_host::HashSets& a, const mvs_host::HashSets& b) {
+    return a.names == b.names && a.offsets == b.offsets && a.hashes.size() == b.hashes.size() &&
+           std::equal(a.hashes.data(), a.hashes.data() + a.hashes.size(), b.hashes.data());
+}
+
 int main(int argc, char* argv[]) {
     if (argc == 4 && std::string(argv[1]) == "--parse") return dump_parse(argv[2], std::string(argv[3]) == "names");
     std::mt19937_64 rng(12345);
@@ -268,7 +278,34 @@ int main(int argc, char* argv[]) {
             }
         }
     }
+    {   // index files that cannot be written (a directory stands where row_index.bin goes): write_shard says so
+        std::filesystem::create_directories(dir + "blocked/row_index.bin");
+        const mvs_cell one{3, 5, 0, 200};
+        bool threw = false;
+        try {
+            mvs_host::write_shard(dir + "blocked/", &one, 1);
+        } catch (const std::runtime_error& e) {
+            threw = std::string(e.what()).find("writing the index files") != std::string::npos;
+        }
+        CHECK(threw);
+    }
     std::filesystem::remove_all(dir);
+    // run_threads: what a body throws reaches the caller, the lowest-numbered thrower's if there are several, and every
+    // thread has been joined by then (the counts are plain ints: ThreadSanitizer would report a thread still running)
+    for (int throwers = 1; throwers <= 2; ++throwers) {
+        int ran[4] = {0, 0, 0, 0};
+        std::string caught;
+        try {
+            mvs_host::run_threads(4, [&](unsigned t) {
+                ran[t] = 1;
+                if (t == 2 || (throwers == 2 && t == 1)) throw std::runtime_error("thread " + std::to_string(t));
+            });
+        } catch (const std::runtime_error& e) {
+            caught = e.what();
+        }
+        CHECK(ran[0] + ran[1] + ran[2] + ran[3] == 4);
+        CHECK(caught == (throwers == 2 ? "thread 1" : "thread 2"));
+    }
     // hash text parsing: dedup, stop at the first bad token, lines without ':' skipped
     {
         const std::string p = "/tmp/mvs_codec_selftest_hashes.txt";
@@ -517,6 +554,107 @@ int main(int argc, char* argv[]) {
                 std::remove(mvs_host::csr_cache_path(p).c_str());
             }
         }
+        std::remove(p.c_str());
+    }
+    // the line table across slices (one per 4 MiB of text): a text of more than 16 MiB in which one line is longer than a
+    // slice, so that a slice holds no newline at all, lines straddle every slice border and the last line has no
+    // newline -- on one thread (one slice), on five (four slices), and with the cache written behind the parsers
+    {
+        const std::string p = "/tmp/mvs_codec_selftest_hashes4.txt";
+        std::string text;
+        size_t lines = 0;
+        std::string values;                                                               // ascending, 16 bytes each
+        for (size_t j = 0; j < ((size_t)6 << 20) / 16; ++j) values += " " + std::to_string(100000000000000ULL + j * 977);
+        auto add_line = [&](size_t count, bool newline) {
+            text += "s" + std::to_string(lines++) + ":";
+            text.append(values, 0, count * 16);
+            if (newline) text += "\n";
+        };
+        while (text.size() < (size_t)7 << 19) add_line(2000 + lines % 7, true);          // 3.5 MiB of 32 KiB lines
+        add_line(values.size() / 16, true);                                               // 6 MiB in one line
+        while (text.size() < ((size_t)16 << 20) + 4096) add_line(2000 + lines % 7, true);
+        add_line(5, false);
+        const size_t slice = text.size() / 4;
+        CHECK(text.size() >> 22 == 4 && text.find('\n', slice) >= 2 * slice);             // slice 1 of 4 has no newline
+        for (size_t border = slice; border < text.size(); border += slice) CHECK(text[border - 1] != '\n');
+        {
+            std::ofstream f(p, std::ios::binary);
+            f << text;
+        }
+        mvs_host::HashSets one, five, behind, loaded;
+        CHECK(mvs_host::read_hash_file(p, true, one, 1));
+        CHECK(mvs_host::read_hash_file(p, true, five, 5));
+        CHECK(mvs_host::read_hash_file(p, true, behind, 5, p));
+        CHECK(mvs_host::load_csr_cache(p, loaded));
+        CHECK(one.names.size() == lines && one.names[lines - 1] == "s" + std::to_string(lines - 1));
+        CHECK(one.offsets[lines] - one.offsets[lines - 1] == 5 && one.hashes[one.hashes.size() - 1] == 100000000000000ULL + 4 * 977);
+        for (const mvs_host::HashSets* o : {&five, &behind, &loaded}) CHECK(same_sets(*o, one));
+        std::remove(mvs_host::csr_cache_path(p).c_str());
+        std::remove(p.c_str());
+    }
+    // the cache's bytes: for a text without gaps (no duplicate, no bad token) the file written behind the parsers is byte
+    // for byte the one write_csr_cache() writes from the returned sets, with a thread handed back and without
+    {
+        const std::string p = "/tmp/mvs_codec_selftest_hashes5.txt";
+        std::mt19937_64 rng(9);
+        {
+            std::string text;
+            for (int i = 0; i < 300; ++i) {
+                text += "sample" + std::to_string(i) + (i % 4 ? "" : " x") + ":";
+                std::vector<uint64_t> vals(400 + (size_t)i);
+                uint64_t v = rng() % 1000;
+                for (auto& x : vals) x = v += 1 + rng() % 40000000000000ULL;
+                if (i % 2 == 0) std::reverse(vals.begin(), vals.end());            // odd lines in order, even ones descending
+                for (const uint64_t x : vals) text += " " + std::to_string(x);
+                text += "\n";
+            }
+            std::ofstream f(p, std::ios::binary);
+            f << text;
+        }
+        std::string behind[2];
+        mvs_host::HashSets sets[2];
+        for (int handed = 0; handed < 2; ++handed) {
+            std::thread writer;
+            CHECK(mvs_host::read_hash_file(p, true, sets[handed], 4, p, handed ? &writer : nullptr));
+            CHECK(writer.joinable() == (handed == 1));
+            if (handed) writer.join();
+            behind[handed] = slurp_file(mvs_host::csr_cache_path(p));
+            std::remove(mvs_host::csr_cache_path(p).c_str());
+        }
+        CHECK(mvs_host::write_csr_cache(p, sets[0], 3));
+        const std::string from_sets = slurp_file(mvs_host::csr_cache_path(p));
+        CHECK(from_sets.size() > sets[0].hashes.size() * 8 && behind[0] == from_sets && behind[1] == from_sets);
+        std::remove(mvs_host::csr_cache_path(p).c_str());
+        std::remove(p.c_str());
+    }
+    // load_hash_sets: the cache if asked for and valid, else the text; 1 for what cannot be read
+    {
+        const std::string p = "/tmp/mvs_codec_selftest_hashes6.txt";
+        {
+            std::ofstream f(p);
+            f << "a: 1 2 3\nb: 9 8\n";
+        }
+        mvs_host::HashSets text, other, got;
+        CHECK(mvs_host::read_hash_file(p, true, text, 1));
+        {   // a valid cache of this text that holds other values
+            std::ofstream f(p + ".other");
+            f << "a: 4 5 6\nb: 7 10\n";
+        }
+        CHECK(mvs_host::read_hash_file(p + ".other", true, other, 1));
+        std::remove((p + ".other").c_str());
+        CHECK(mvs_host::write_csr_cache(p, other));
+        CHECK(mvs_host::load_hash_sets("selftest", p, true, got) == 0 && same_sets(got, other));
+        CHECK(mvs_host::load_hash_sets("selftest", p, false, got) == 0 && same_sets(got, text));
+        {
+            std::ofstream f(p, std::ios::app);
+            f << "c: 11\n";
+        }
+        mvs_host::HashSets longer;
+        CHECK(mvs_host::read_hash_file(p, true, longer, 1) && longer.names.size() == 3);
+        for (const bool use_cache : {true, false}) CHECK(mvs_host::load_hash_sets("selftest", p, use_cache, got) == 0 && same_sets(got, longer));
+        CHECK(mvs_host::load_hash_sets("selftest", p + ".missing", true, got) == 1);
+        CHECK(mvs_host::load_hash_sets("selftest", "/tmp", true, got) == 1);
+        std::remove(mvs_host::csr_cache_path(p).c_str());
         std::remove(p.c_str());
     }
     CHECK(mvs_host::format_g(56.46254) == "56.4625" && mvs_host::format_g(1234567.0) == "1.23457e+06");

@@ -419,19 +419,7 @@ inline std::string scores_text(const std::vector<std::string>& names, const std:
 // is valid, else the text.  The file's sample names must be the DB's names in the DB's order.  0, or 1 after a message on
 // stderr; no device is needed.
 inline int load_db_hashes(const char* prog, const std::string& hash_file, const SketchDb& db, HashSets& sets) {
-    bool parsed = load_csr_cache(hash_file, sets);
-    if (!parsed) {
-        try {
-            parsed = read_hash_file(hash_file, true, sets);
-        } catch (const std::exception& e) {
-            std::cerr << prog << ": reading " << hash_file << ": " << e.what() << std::endl;
-            return 1;
-        }
-    }
-    if (!parsed) {
-        std::cerr << "Error opening " << hash_file << " for reading." << std::endl;
-        return 1;
-    }
+    if (const int rc = load_hash_sets(prog, hash_file, true, sets)) return rc;
     const std::vector<std::string>& names = db.info.names;
     if ((int64_t)sets.names.size() != db.n || !std::equal(sets.names.begin(), sets.names.end(), names.begin())) {
         size_t at = 0;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Regenerate tests/golden/ref_parser.json (dev container only): what the REFERENCE binaries make of malformed hash text.
 
-The text parser of this repository (csrc/host/mvs_host.hpp: parse_u64_raw_scalar and its AVX2 fast path) restates
+The text parser of this repository (csrc/host/mvs_hash_text.hpp: parse_u64_raw_scalar and its AVX2 fast path) restates
 `while (iss >> hash)` of src/project_everything.cpp:264-281 and src/standalone_projection.cpp:28-36.  The reference
 never prints the sets it parsed, so each case records what it DOES print / write: `sketch` -> "Loaded <N> hash sets",
 the names and norms of vector_norms.txt and vectors.bin at d = 128; `standalone_projection` -> its stdout.  A sketch at
